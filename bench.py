@@ -803,7 +803,13 @@ def main():
     ap.add_argument("--mode", default="sample", choices=["sample", "train", "rollout", "agent"],
                     help="sample (default, BASELINE metric): 10-step DDIM chunks at B=128; train: configs[2]/[3] score-matching steps "
                          "(fwd+bwd+AdamW, DP all-reduce); rollout: configs[4], B=32 environments, router pre-cached per noise level")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="sample / rollout: write the action chunk the LAST timed step returned to DIR/actions.npy "
+                    "(float32, rank 0), so that two builds can be compared output for output on the same seeded inputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode not in ("sample", "rollout"):
+        ap.error("--dump-outputs is implemented for --mode sample and rollout")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -877,6 +883,10 @@ def main():
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "actions.npy"), out.detach().float().cpu().numpy())
 
     n_gpus = world
     denoise_steps = n_gpus * args.steps * N_SAMPLING_STEPS

@@ -447,3 +447,14 @@ def test_training_side_api_surface():
         os.environ.pop("MODE_TRUST_CKPT", None)
         with pytest.raises(RuntimeError, match="trust_pickle=True"):
             rollout._read_checkpoint_file(path)
+
+
+@pytest.mark.parametrize("args,msg", [(["--steps", "0"], "--steps must be at least 1"),
+                                      (["--mode", "train", "--dump-outputs", "d"], "--dump-outputs is implemented for --mode sample and rollout")])
+def test_bench_rejects_arguments_it_cannot_honour(args, msg):
+    """bench.py refuses, before touching a device, a run with no timed step (ms_per_step would be undefined) and an output dump in a mode
+    that has none."""
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *args], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 2 and msg in p.stderr, p.stderr[-2000:]

@@ -373,6 +373,30 @@ def test_bench_main_world2_end_to_end_through_torch_distributed_run(tmp_path):
     assert r["fused_expert_step"] is False and "train_twopass_ms_per_step" not in r     # (N = 1 only: the fused-epilogue step and its two-pass anchor)
 
 
+def test_bench_dump_outputs_reproducible_across_step_counts(tmp_path):
+    """``bench.py --dump-outputs DIR``: the last timed step's action chunk lands in DIR/actions.npy (float32, [B, 10, 7]); the seeded inputs make it
+    identical for any --steps / --warmup, and the JSON line reports the --steps it was given (1-layer dry-run model: plumbing, not a measurement)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, MODE_BENCH_DRYRUN_LAYERS="1")
+    outs = []
+    for steps, warmup, d in ((2, 1, "a"), (5, 2, "b")):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--no-extras",
+               "--no-cpu-baseline", "--dump-outputs", str(tmp_path / d)]
+        p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        r = json.loads(lines[0])
+        assert r["steps"] == steps and r["ms_per_step"] > 0
+        a = np.load(tmp_path / d / "actions.npy")
+        assert a.dtype == np.float32 and a.shape == (128, 10, 7) and np.isfinite(a).all()
+        outs.append(a)
+    assert np.array_equal(outs[0], outs[1])
+
+
 # ---------------------------------------------------------------------------------------------- cond_router=False: token routing in TRAINING
 def _tok_model(dtype, **over):
     import dataclasses
