@@ -249,8 +249,8 @@ int mode_rmsnorm_cond_fwd(const float* x, const float* g, const float* cond, int
  * mode_attn_block_fwd — per (sample, head): qk-RMSNorm over head_dim (learned gains, eps), causal softmax(QK^T/sqrt(hd)) V.
  * Replaces Attention.forward minus the four Linears (modedit.py:125-127, 145-165; SDPA is_causal=True at :149).
  * qkv is the packed [B*T, 3*D] output of the fused QKV GEMM ([q | k | v] along columns); y is [B*T, D] (heads merged).
- * T <= 16 (the path's sequence is 14 tokens), head_dim % 16 == 0 and <= 128 for bf16.  p_drop > 0 (training only) drops
- * probabilities after the softmax exactly where SDPA does.
+ * T <= 64 (the default sequence is 14 tokens; T <= 16 and 16 < T <= 64 run different kernels), head_dim % 16 == 0 and <= 128 for
+ * bf16, head_dim <= 128 for fp32 when T > 16.  p_drop > 0 (training only) drops probabilities after the softmax exactly where SDPA does.
  * ------------------------------------------------------------------------------------------------------------------ */
 int mode_attn_block_fwd(const void* qkv, const float* q_gain, const float* k_gain, void* y, int dtype,
                         int B, int T, int H, int head_dim, float eps, uint32_t seed, float p_drop, void* stream);
@@ -276,7 +276,7 @@ int mode_qkv_attn_fwd(const ModeQkvAttnDesc* desc, void* stream);
 
 /* backward of the above (training): dy [B*T, D] -> dqkv [B*T, 3D]; dgq_partial / dgk_partial [B*H, head_dim] are per-(sample, head)
  * partial gradients of the qk-norm gains (reduce with mode_colsum).  Attention dropout (SDPA dropout_p, modedit.py:149) is a
- * counter-based hash mask keyed by (seed, sample, head, query, key), regenerated here. */
+ * counter-based hash mask keyed by (seed, sample, head, query, key), regenerated here.  T <= 64, head_dim <= 128 (% 8 == 0 bf16, % 4 == 0 fp32). */
 int mode_attn_block_bwd(const void* qkv, const float* q_gain, const float* k_gain, const void* dy, void* dqkv,
                         float* dgq_partial, float* dgk_partial, int dtype, int B, int T, int H, int head_dim, float eps,
                         uint32_t seed, float p_drop, void* stream);

@@ -415,6 +415,14 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_kernel(const T2* __restrict__
 
 }  // namespace mode
 
+namespace mode {
+// attn_long.hip: the kernels for 16 < T <= 64 (taken by both entry points below when T > 16)
+int attn_long_fwd_launch(const void* qkv, const float* qg, const float* kg, void* y, int dtype, int B, int T, int H, int HD, float eps, uint32_t seed,
+                         uint32_t thresh, float inv_keep, hipStream_t s);
+int attn_long_bwd_launch(const void* qkv, const float* qg, const float* kg, const void* dy, void* dqkv, float* dgq_partial, float* dgk_partial, int dtype,
+                         int B, int T, int H, int HD, float eps, uint32_t seed, uint32_t thresh, float inv_keep, float* dbias_partial, hipStream_t s);
+}  // namespace mode
+
 using namespace mode;
 
 static inline uint32_t attn_thresh(float p) { return p <= 0.f ? 0u : (uint32_t)((double)p * 4294967296.0); }
@@ -426,6 +434,7 @@ extern "C" int mode_attn_block_fwd(const void* qkv, const float* q_gain, const f
   if (p_drop < 0.f || p_drop >= 1.f) return MODE_ERR_BAD_ARG;
   const uint32_t th = attn_thresh(p_drop); const float ik = 1.0f / (1.0f - p_drop);
   hipStream_t s = (hipStream_t)stream;
+  if (T > 16) return attn_long_fwd_launch(qkv, q_gain, k_gain, y, dtype, B, T, H, head_dim, eps, seed, th, ik, s);
   if (dtype == MODE_BF16) {
     if (T > 16 || head_dim % 16 != 0 || head_dim > 128) return MODE_ERR_UNSUPPORTED;
     const dim3 grid((B * H + 3) / 4), blk(256);
@@ -455,6 +464,9 @@ int attn_block_bwd_launch(const void* qkv, const float* q_gain, const float* k_g
   if (!qkv || !q_gain || !k_gain || !dy || !dqkv || !dgq_partial || !dgk_partial || B < 0 || T <= 0 || H <= 0) return MODE_ERR_BAD_ARG;
   if (p_drop < 0.f || p_drop >= 1.f) return MODE_ERR_BAD_ARG;
   if (B == 0) return MODE_OK;
+  if (T > 16)
+    return attn_long_bwd_launch(qkv, q_gain, k_gain, dy, dqkv, dgq_partial, dgk_partial, dtype, B, T, H, head_dim, eps, seed, attn_thresh(p_drop),
+                                1.0f / (1.0f - p_drop), dbias_partial, (hipStream_t)stream);
   const bool mf = head_dim % 16 == 0 && g_attn_bwd_mfma;
   const size_t tiles = mf ? 3 : 4;                             // 16 x 16 coefficient tiles (the MFMA form needs no transposed copy of the dropped probabilities)
   const size_t lds = dtype == MODE_BF16 ? ((size_t)4 * T * (head_dim + 1) + 4 + tiles * 256 + 2 * T + 4 + 2 * head_dim) * 4 + (size_t)2 * T * (head_dim + 8) * 2

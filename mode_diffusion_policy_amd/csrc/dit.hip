@@ -85,7 +85,7 @@ static int check_dims(const ModeDims* d) {
   if (!d) return MODE_ERR_BAD_ARG;
   if (d->D <= 0 || d->H <= 0 || d->D % d->H || d->L <= 0 || d->E <= 0 || d->k <= 0 || d->k > d->E) return MODE_ERR_BAD_ARG;
   if (d->T != (d->use_noise_token ? 1 : 0) + 1 + d->n_img + d->A_len) return MODE_ERR_UNSUPPORTED;
-  if (d->D % 4 || d->A_dim > 8 || d->T > 16) return MODE_ERR_UNSUPPORTED;
+  if (d->D % 4 || d->A_dim > kMaxActionDim || d->T > kMaxTokens) return MODE_ERR_UNSUPPORTED;
   return MODE_OK;
 }
 

@@ -49,6 +49,10 @@ __device__ __forceinline__ bool drop_keep(uint32_t seed, uint64_t idx, uint32_t 
   return hash_u32(hash_u32((uint32_t)idx ^ seed) + (uint32_t)(idx >> 32) * 0x9e3779b9U) >= thresh;
 }
 
+// ---- model-size limits of the HIP path: tokens per sample (attention: attn.hip for T <= 16, attn_long.hip above) and action width (rowops.hip)
+constexpr int kMaxTokens = 64;
+constexpr int kMaxActionDim = 32;
+
 // ---- wave64 reductions via cross-lane shuffles ----------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

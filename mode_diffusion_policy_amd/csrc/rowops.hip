@@ -272,7 +272,7 @@ __global__ __launch_bounds__(256) void combine_norm_row_kernel(const float* u, c
 }
 
 // --------------------------------------------------------------------------------------------------------------- embed
-template <bool LP_BF16, int NCH>
+template <bool LP_BF16, int NCH, int AMAX>   // AMAX: widest action (8 or 32)
 __global__ __launch_bounds__(256) void embed_tokens_kernel(const ModeEmbedDesc e) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -284,11 +284,11 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(const ModeEmbedDesc e
   const int t0 = e.use_noise_token ? 1 : 0;            // first goal position
   const int t_img = t0 + 1, t_act = t_img + e.n_img;   // goal_seq_len == 1 on this path
   const float cin = e.c_in ? e.c_in[(long)b * e.c_in_stride] : 1.0f;
-  float a[8];
+  float a[AMAX];
   const int ai = t - t_act;
   if (ai >= 0) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) a[j] = (j < e.A_dim) ? e.actions[((long)b * e.A_len + ai) * e.A_dim + j] * cin : 0.f;
+    for (int j = 0; j < AMAX; ++j) a[j] = (j < e.A_dim) ? e.actions[((long)b * e.A_len + ai) * e.A_dim + j] * cin : 0.f;
   }
   float ssq = 0.f;
   for_chunks<NCH>(D, lane, [&](int d) {
@@ -328,7 +328,7 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(const ModeEmbedDesc e
           const float* wr = e.w_act + (long)(d + c) * e.A_dim;
           float s_ = 0.f;
 #pragma unroll
-          for (int j = 0; j < 8; ++j) if (j < e.A_dim) s_ = fmaf(a[j], wr[j], s_);
+          for (int j = 0; j < AMAX; ++j) if (j < e.A_dim) s_ = fmaf(a[j], wr[j], s_);
           o[c] = s_;
         }
       }
@@ -344,7 +344,7 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(const ModeEmbedDesc e
 }
 
 // ---------------------------------------------------------------------------------------------------------------- head
-template <int NCH>   // NCH > 0: D == 256*NCH, chunk loops fully unrolled (all loads of a phase in flight together)
+template <int NCH, int AMAX>   // NCH > 0: D == 256*NCH, chunk loops fully unrolled (all loads of a phase in flight together); AMAX: widest action (8 or 32)
 __global__ __launch_bounds__(256) void head_ddim_kernel(const ModeHeadDesc h) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -398,18 +398,18 @@ __global__ __launch_bounds__(256) void head_ddim_kernel(const ModeHeadDesc h) {
     *reinterpret_cast<float4*>(cache + d) = v;
     ssq += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
   });
-  float accv[8];
+  float accv[AMAX];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) accv[j] = 0.f;
-  if constexpr (NCH > 0) {
+  for (int j = 0; j < AMAX; ++j) accv[j] = 0.f;
+  if constexpr (NCH > 0 && AMAX <= 8) {
     // final-norm gain and the 7 head rows for all chunks are requested BEFORE the row reduction (their round trip overlaps it)
-    float4 gq[NCH], wq[NCH][8];
+    float4 gq[NCH], wq[NCH][AMAX];
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       const int d = lane * 4 + c * 256;
       gq[c] = *reinterpret_cast<const float4*>(h.g + d);
 #pragma unroll
-      for (int j = 0; j < 8; ++j)
+      for (int j = 0; j < AMAX; ++j)
         wq[c][j] = j < h.A_dim ? *reinterpret_cast<const float4*>(h.w_out + (long)j * D + d) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     ssq = wave_sum(ssq);
@@ -420,7 +420,7 @@ __global__ __launch_bounds__(256) void head_ddim_kernel(const ModeHeadDesc h) {
       const float4 v = *reinterpret_cast<const float4*>(cache + lane * 4 + c * 256);
       const float4 n = make_float4(v.x * rnrm * gq[c].x, v.y * rnrm * gq[c].y, v.z * rnrm * gq[c].z, v.w * rnrm * gq[c].w);
 #pragma unroll
-      for (int j = 0; j < 8; ++j)
+      for (int j = 0; j < AMAX; ++j)
         if (j < h.A_dim) accv[j] += n.x * wq[c][j].x + n.y * wq[c][j].y + n.z * wq[c][j].z + n.w * wq[c][j].w;
     }
   } else {
@@ -432,7 +432,7 @@ __global__ __launch_bounds__(256) void head_ddim_kernel(const ModeHeadDesc h) {
       const float4 gg = *reinterpret_cast<const float4*>(h.g + d);
       const float4 n = make_float4(v.x * rnrm * gg.x, v.y * rnrm * gg.y, v.z * rnrm * gg.z, v.w * rnrm * gg.w);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
+      for (int j = 0; j < AMAX; ++j) {
         if (j < h.A_dim) {
           const float4 w = *reinterpret_cast<const float4*>(h.w_out + (long)j * D + d);
           accv[j] += n.x * w.x + n.y * w.y + n.z * w.z + n.w * w.w;
@@ -441,11 +441,11 @@ __global__ __launch_bounds__(256) void head_ddim_kernel(const ModeHeadDesc h) {
     }
   }
 #pragma unroll
-  for (int j = 0; j < 8; ++j) accv[j] = wave_sum(accv[j]);
+  for (int j = 0; j < AMAX; ++j) accv[j] = wave_sum(accv[j]);
   if (act_lane) {
     float F = 0.f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) if (lane == j) F = accv[j];
+    for (int j = 0; j < AMAX; ++j) if (lane == j) F = accv[j];
     F += bo;
     if (h.F) h.F[oidx] = F;
     if (scp) {
@@ -595,7 +595,7 @@ namespace mode {
 // One workgroup per token row (the form of the combine / head row kernels).  The token kind is uniform per workgroup: it selects a source row
 // and a positional row by POINTER (dummy = the positional table, masked by selects), so the row's loads are unconditional; only the action
 // rows' Linear(A_dim, D) sits behind a (scalar) branch.
-template <bool LP_BF16, int NC>
+template <bool LP_BF16, int NC, int AMAX>   // AMAX: widest action (8 or 32; the instantiation for 8 is the original kernel)
 __global__ __launch_bounds__(256) void embed_tokens_row_kernel(const ModeEmbedDesc e) {
   __shared__ float red[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -611,13 +611,13 @@ __global__ __launch_bounds__(256) void embed_tokens_row_kernel(const ModeEmbedDe
   const float* pp = is_act ? e.pos + (long)(1 + ai) * D : is_goal ? e.pos : e.pos + D;   // both image tokens share pos row 1; the noise token has none
   const bool has_src = !is_act, has_pos = !is_noise;
   const float cin = (e.c_in ? e.c_in : e.pos)[e.c_in ? (long)b * e.c_in_stride : 0];
-  float a[8];
+  float a[AMAX];
   {
     const long abase = ((long)b * e.A_len + (is_act ? ai : 0)) * e.A_dim;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) a[j] = e.actions[abase + (j < e.A_dim ? j : 0)];
+    for (int j = 0; j < AMAX; ++j) a[j] = e.actions[abase + (j < e.A_dim ? j : 0)];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) a[j] = j < e.A_dim ? a[j] * (e.c_in ? cin : 1.0f) : 0.f;
+    for (int j = 0; j < AMAX; ++j) a[j] = j < e.A_dim ? a[j] * (e.c_in ? cin : 1.0f) : 0.f;
   }
   const float* cr = e.cond ? e.cond + (long)b * e.cond_row_stride : e.pos;
   float4 v[NC], gq[NC], cq[NC];
@@ -648,16 +648,16 @@ __global__ __launch_bounds__(256) void embed_tokens_row_kernel(const ModeEmbedDe
           o[cc] = s_;
         }
       } else {
-        float wr[4][8];
+        float wr[4][AMAX];
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc)
 #pragma unroll
-          for (int j = 0; j < 8; ++j) wr[cc][j] = e.w_act[(long)(dc + cc) * e.A_dim + (j < e.A_dim ? j : 0)];
+          for (int j = 0; j < AMAX; ++j) wr[cc][j] = e.w_act[(long)(dc + cc) * e.A_dim + (j < e.A_dim ? j : 0)];
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc) {
           float s_ = 0.f;
 #pragma unroll
-          for (int j = 0; j < 8; ++j) s_ = j < e.A_dim ? fmaf(a[j], wr[cc][j], s_) : s_;
+          for (int j = 0; j < AMAX; ++j) s_ = j < e.A_dim ? fmaf(a[j], wr[cc][j], s_) : s_;
           o[cc] = s_;
         }
       }
@@ -692,13 +692,15 @@ __global__ __launch_bounds__(256) void embed_tokens_row_kernel(const ModeEmbedDe
 extern "C" int mode_embed_tokens_fwd(const ModeEmbedDesc* d, void* stream) {
   if (!d || !d->goal_e || !d->img_e || !d->actions || !d->w_act || !d->pos || !d->g || !d->x || !d->h) return MODE_ERR_BAD_ARG;
   if (d->use_noise_token && !d->emb_t) return MODE_ERR_BAD_ARG;
-  if ((d->D & 3) || d->A_dim > 8 || d->T != (d->use_noise_token ? 1 : 0) + 1 + d->n_img + d->A_len) return MODE_ERR_UNSUPPORTED;
+  if ((d->D & 3) || d->A_dim > kMaxActionDim || d->T != (d->use_noise_token ? 1 : 0) + 1 + d->n_img + d->A_len) return MODE_ERR_UNSUPPORTED;
   const int rows = d->B * d->T;
   if (rows == 0) return MODE_OK;
+  const bool wide = d->A_dim > 8;                                     // AMAX = 32 instantiations
   if (d->D <= 4096 && d->A_dim >= 1) {                               // one workgroup per row
     const hipStream_t st = (hipStream_t)stream;
     const int nc = (d->D + 1023) / 1024;
-#define MODE_EK(LP, NC) hipLaunchKernelGGL((embed_tokens_row_kernel<LP, NC>), dim3(rows), dim3(256), 0, st, *d)
+#define MODE_EK(LP, NC) do { if (wide) hipLaunchKernelGGL((embed_tokens_row_kernel<LP, NC, 32>), dim3(rows), dim3(256), 0, st, *d); \
+                             else hipLaunchKernelGGL((embed_tokens_row_kernel<LP, NC, 8>), dim3(rows), dim3(256), 0, st, *d); } while (0)
 #define MODE_EK_NC(LP) do { if (nc == 1) MODE_EK(LP, 1); else if (nc == 2) MODE_EK(LP, 2); else MODE_EK(LP, 4); } while (0)
     if (d->h_dtype == MODE_BF16) MODE_EK_NC(true); else MODE_EK_NC(false);
 #undef MODE_EK_NC
@@ -708,13 +710,15 @@ extern "C" int mode_embed_tokens_fwd(const ModeEmbedDesc* d, void* stream) {
   }
   const dim3 grid((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
   const size_t lds = (size_t)ROWS_PER_BLOCK * d->D * 4;
+  const hipStream_t st = (hipStream_t)stream;
+#define MODE_EKF(LP, NCH) do { if (wide) hipLaunchKernelGGL((embed_tokens_kernel<LP, NCH, 32>), grid, dim3(256), lds, st, *d); \
+                               else hipLaunchKernelGGL((embed_tokens_kernel<LP, NCH, 8>), grid, dim3(256), lds, st, *d); } while (0)
   if (d->D == 1024) {
-    if (d->h_dtype == MODE_BF16) hipLaunchKernelGGL((embed_tokens_kernel<true, 4>), grid, dim3(256), lds, (hipStream_t)stream, *d);
-    else hipLaunchKernelGGL((embed_tokens_kernel<false, 4>), grid, dim3(256), lds, (hipStream_t)stream, *d);
+    if (d->h_dtype == MODE_BF16) MODE_EKF(true, 4); else MODE_EKF(false, 4);
   } else {
-    if (d->h_dtype == MODE_BF16) hipLaunchKernelGGL((embed_tokens_kernel<true, 0>), grid, dim3(256), lds, (hipStream_t)stream, *d);
-    else hipLaunchKernelGGL((embed_tokens_kernel<false, 0>), grid, dim3(256), lds, (hipStream_t)stream, *d);
+    if (d->h_dtype == MODE_BF16) MODE_EKF(true, 0); else MODE_EKF(false, 0);
   }
+#undef MODE_EKF
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }
@@ -724,10 +728,10 @@ namespace mode {
 // partials and gain, k x slabs expert rows, final-norm gain, the A_dim head rows, bias, EDM scalings, noisy action - is unconditional (clamped
 // indices + selects, dtype / slab bound / top-k as template parameters) and requested before the first reduction.  The one-wave-per-row kernel
 // above had compiled into ~40 dependent branch + load + wait rounds: 18 us per denoise step whatever the batch.
-template <int KK, bool FUSED, bool YBF, int YS, int NC>
+template <int KK, bool FUSED, bool YBF, int YS, int NC, int AMAX>   // AMAX: widest action (8 or 32; the instantiation for 8 is the original kernel)
 __global__ __launch_bounds__(256) void head_ddim_row_kernel(const ModeHeadDesc h) {
   __shared__ float red[4];
-  __shared__ float racc[4][8];
+  __shared__ float racc[4][AMAX];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ar = blockIdx.x;                                       // action-row index in [0, B*A_len)
   const int b = ar / h.A_len, ai = ar % h.A_len, D = h.D;
@@ -746,7 +750,8 @@ __global__ __launch_bounds__(256) void head_ddim_row_kernel(const ModeHeadDesc h
   const float* scp = has_sc ? h.scal + (long)b * h.scal_stride : h.b_out;   // (never used when !has_sc)
   const float sc0 = scp[0], sc1 = has_sc ? scp[1] : 0.f, sc2 = has_sc ? scp[2] : 0.f, sc3 = (has_sc && h.den_prev) ? scp[3] : 0.f;
   const float xa = (has_sc ? h.x_a : h.b_out)[has_sc ? oidx : 0];
-  float4 v[NC], gq[NC], wq[NC][8];
+  constexpr int WQ = AMAX <= 8 ? AMAX : 1;                        // AMAX 8: the head rows are requested with the row's loads; 32: read where used
+  float4 v[NC], gq[NC], wq[NC][WQ];
   float ssq = 0.f;
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
@@ -755,8 +760,10 @@ __global__ __launch_bounds__(256) void head_ddim_row_kernel(const ModeHeadDesc h
     const int dc = in ? d : 0;
     float4 uu = *reinterpret_cast<const float4*>(h.u + row * D + dc);
     gq[c] = *reinterpret_cast<const float4*>(h.g + dc);
+    if constexpr (AMAX <= 8) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) wq[c][j] = *reinterpret_cast<const float4*>(h.w_out + (long)(j < h.A_dim ? j : 0) * D + dc);
+      for (int j = 0; j < AMAX; ++j) wq[c][j] = *reinterpret_cast<const float4*>(h.w_out + (long)(j < h.A_dim ? j : 0) * D + dc);
+    }
     float4 gg = make_float4(1.f, 1.f, 1.f, 1.f);
     if constexpr (FUSED) gg = *reinterpret_cast<const float4*>(h.u_gain + dc);
     float4 ys[KK][YS];
@@ -794,20 +801,25 @@ __global__ __launch_bounds__(256) void head_ddim_row_kernel(const ModeHeadDesc h
   __syncthreads();
   ssq = ((red[0] + red[1]) + red[2]) + red[3];
   const float rnrm = __frcp_rn(fmaxf(sqrtf(ssq) * rsqrtf((float)D), h.eps));
-  float accv[8];
+  float accv[AMAX];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) accv[j] = 0.f;
+  for (int j = 0; j < AMAX; ++j) accv[j] = 0.f;
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     const float4 n = make_float4(v[c].x * rnrm * gq[c].x, v[c].y * rnrm * gq[c].y, v[c].z * rnrm * gq[c].z, v[c].w * rnrm * gq[c].w);   // v = 0 past D
 #pragma unroll
-    for (int j = 0; j < 8; ++j) accv[j] += n.x * wq[c][j].x + n.y * wq[c][j].y + n.z * wq[c][j].z + n.w * wq[c][j].w;
+    for (int j = 0; j < AMAX; ++j) {
+      float4 w;
+      if constexpr (AMAX <= 8) w = wq[c][j];
+      else w = *reinterpret_cast<const float4*>(h.w_out + (long)(j < h.A_dim ? j : 0) * D + (tid * 4 + c * 1024 < D ? tid * 4 + c * 1024 : 0));
+      accv[j] += n.x * w.x + n.y * w.y + n.z * w.z + n.w * w.w;
+    }
   }
 #pragma unroll
-  for (int j = 0; j < 8; ++j) accv[j] = wave_sum(accv[j]);
+  for (int j = 0; j < AMAX; ++j) accv[j] = wave_sum(accv[j]);
   if (lane == 0) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) racc[wave][j] = accv[j];
+    for (int j = 0; j < AMAX; ++j) racc[wave][j] = accv[j];
   }
   __syncthreads();
   if (tid < h.A_dim) {
@@ -837,14 +849,16 @@ extern "C" int mode_head_ddim_fwd(const ModeHeadDesc* d, void* stream) {
   if (!d || !d->u || !d->Y || !d->pos || !d->posw || !d->g || !d->w_out || !d->b_out) return MODE_ERR_BAD_ARG;
   if (d->scal && !d->x_a) return MODE_ERR_BAD_ARG;
   if (d->u_ss && (!d->u_gain || d->u_ss_n <= 0)) return MODE_ERR_BAD_ARG;
-  if ((d->D & 3) || d->A_dim > 8) return MODE_ERR_UNSUPPORTED;
+  if ((d->D & 3) || d->A_dim > kMaxActionDim) return MODE_ERR_UNSUPPORTED;
   const int rows = d->B * d->A_len;
+  const bool wide = d->A_dim > 8;                                     // AMAX = 32 instantiations
   if (rows == 0) return MODE_OK;
   if (d->D <= 4096 && d->y_splits <= 8 && (d->k == 1 || d->k == 2) && d->A_dim >= 1) {   // one workgroup per row
     const hipStream_t st = (hipStream_t)stream;
     const int nc = (d->D + 1023) / 1024, ys = d->y_splits <= 1 ? 1 : d->y_splits <= 2 ? 2 : d->y_splits <= 4 ? 4 : 8;
     const bool ybf = d->y_dtype == MODE_BF16, fu = d->u_ss != nullptr;
-#define MODE_HK(KK, F, YB, YS, NC) hipLaunchKernelGGL((head_ddim_row_kernel<KK, F, YB, YS, NC>), dim3(rows), dim3(256), 0, st, *d)
+#define MODE_HK(KK, F, YB, YS, NC) do { if (wide) hipLaunchKernelGGL((head_ddim_row_kernel<KK, F, YB, YS, NC, 32>), dim3(rows), dim3(256), 0, st, *d); \
+                                        else hipLaunchKernelGGL((head_ddim_row_kernel<KK, F, YB, YS, NC, 8>), dim3(rows), dim3(256), 0, st, *d); } while (0)
 #define MODE_HK_NC(KK, F, YB, YS) do { if (nc == 1) MODE_HK(KK, F, YB, YS, 1); else if (nc == 2) MODE_HK(KK, F, YB, YS, 2); else MODE_HK(KK, F, YB, YS, 4); } while (0)
 #define MODE_HK_YS(KK, F, YB) do { if (ys == 1) MODE_HK_NC(KK, F, YB, 1); else if (ys == 2) MODE_HK_NC(KK, F, YB, 2); else if (ys == 4) MODE_HK_NC(KK, F, YB, 4); else MODE_HK_NC(KK, F, YB, 8); } while (0)
 #define MODE_HK_YB(KK, F) do { if (ybf) MODE_HK_YS(KK, F, true); else MODE_HK_YS(KK, F, false); } while (0)
@@ -860,8 +874,9 @@ extern "C" int mode_head_ddim_fwd(const ModeHeadDesc* d, void* stream) {
   }
   const dim3 grid((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
   const size_t lds = (size_t)ROWS_PER_BLOCK * d->D * 4;
-  if (d->D == 1024) hipLaunchKernelGGL(head_ddim_kernel<4>, grid, dim3(256), lds, (hipStream_t)stream, *d);
-  else hipLaunchKernelGGL(head_ddim_kernel<0>, grid, dim3(256), lds, (hipStream_t)stream, *d);
+  const hipStream_t st = (hipStream_t)stream;
+  if (d->D == 1024) { if (wide) hipLaunchKernelGGL((head_ddim_kernel<4, 32>), grid, dim3(256), lds, st, *d); else hipLaunchKernelGGL((head_ddim_kernel<4, 8>), grid, dim3(256), lds, st, *d); }
+  else { if (wide) hipLaunchKernelGGL((head_ddim_kernel<0, 32>), grid, dim3(256), lds, st, *d); else hipLaunchKernelGGL((head_ddim_kernel<0, 8>), grid, dim3(256), lds, st, *d); }
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }

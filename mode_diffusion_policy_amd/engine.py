@@ -156,7 +156,9 @@ class DitEngine:
     def workspace_bytes(self, B: int, R: int) -> int:
         need = self.lib.mode_dit_workspace_bytes(C.byref(self.dims), B, R, self.dt)
         if need == 0:
-            raise RuntimeError("unsupported MoDeDiT dimensions for the HIP path")
+            d = self.dims
+            raise RuntimeError(f"unsupported MoDeDiT dimensions for the HIP path (T = {d.T} tokens per sample, action_dim = {d.A_dim}): "
+                               f"the HIP path takes T <= 64 and action_dim <= 32")
         return need
 
     def workspace(self, B: int, R: int) -> Tuple[int, int]:
