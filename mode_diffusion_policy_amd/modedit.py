@@ -317,7 +317,8 @@ class MoDeDiT(nn.Module):
             eng.forward(B, emb_t, 0 if R == 1 else D, cond, 0 if Rr == 1 else D, None, 0, goal_e, img_e, x, c_in=c_in, c_in_stride=0 if R == 1 else 1,
                         scal_ptr=scal.data_ptr(), scal_stride=0 if R == 1 else 4, denoised=den, topk_out=idx)
             self._last_topk = idx
-            self._account_token_usage(idx, N)
+            if _account:
+                self._account_token_usage(idx, N)
             return den
         idx, w, _, _ = eng.route(cond)
         meta = eng.dispatch(idx, w, self.num_layers, Rr, N if Rr == 1 else T, N)
@@ -334,9 +335,8 @@ class MoDeDiT(nn.Module):
         """``denoise`` for a batch that shares ONE noise level (a 0-dim / 1-element sigma, device or host), replayed as a hipGraph: sigma embedding,
         fp32 router + dispatch of all layers, EDM scalings, observation embeddings and the denoiser forward are captured once per batch size with
         sigma as a DEVICE scalar, so the same graph serves every noise level of every sampler (euler, heun, dpm-solver++ ...: gc_sampling.py:165-994)
-        - no per-step host work beyond three small input copies.  Returns None when routing depends on the sample (goal / token routing)."""
-        if self.use_goal_in_routing or not self.cond_router:
-            return None
+        - no per-step host work beyond three small input copies.  Goal routing: the graph also forms cond = emb + goal_emb(goal) and routes
+        and dispatches those B rows; token routing: the forward routes every token itself.  Returns None with MODE_HIP_GRAPH=0."""
         import os
         eng = self.engine
         dev, B = eng.device, action.shape[0]
@@ -344,7 +344,7 @@ class MoDeDiT(nn.Module):
             return None
         x = action.detach().to(device=dev, dtype=torch.float32).contiguous()
         sig = torch.as_tensor(sigma, dtype=torch.float32).detach().reshape(-1)[:1]
-        key = (B, eng.compute_dtype, eng._structs_for, str(dev), float(sigma_data))
+        key = (B, eng.compute_dtype, eng._structs_for, str(dev), float(sigma_data), self._routing_mode())
         cache = self._route_cache.setdefault("denoise_graphs", {})
         ent = cache.get(key)
         # The observations are the same tensors for every denoiser call of a sampler run (gc_sampling.py's loops pass `state` / `goal` through
@@ -364,7 +364,7 @@ class MoDeDiT(nn.Module):
             ent = dict(img=img.clone(), goals=gl.clone(), x=x.clone(), sig=torch.empty(1, device=dev),
                        img_e=torch.empty(B * self.n_img_tokens, self.embed_dim, device=dev), goal_e=torch.empty(B, self.embed_dim, device=dev))
             ent["sig"].copy_(sig)
-            ent["ws"] = torch.empty(max(eng.workspace_bytes(B, 0), eng.workspace_bytes(0, 1)), dtype=torch.uint8, device=dev)
+            ent["ws"] = self._chunk_ws(eng, B, 1)
             run = lambda: self.denoise(None, ent["x"], None, ent["sig"], sigma_data, _account=False, _obs_emb=(ent["img_e"], ent["goal_e"]))
             with eng.pinned_workspace(ent["ws"]):
                 side = torch.cuda.Stream(device=dev)
@@ -376,7 +376,8 @@ class MoDeDiT(nn.Module):
                 g = torch.cuda.CUDAGraph()
                 with capture_graph(g):
                     ent["out"] = run()
-                    ent["meta"] = self._last_meta
+                    ent["topk"] = self._last_topk
+                    ent["meta"] = self._last_meta if self.cond_router else None
             ent["graph"] = g
             cache[key] = ent
         if fresh:
@@ -387,7 +388,13 @@ class MoDeDiT(nn.Module):
             ent["obs_ref"], ent["obs_key"] = (src if keep else None), okey
         ent["x"].copy_(x); ent["sig"].copy_(sig, non_blocking=True)
         ent["graph"].replay()
-        self._account_usage(ent["meta"], eng.meta_layout(B * self.seq_len), B * self.seq_len)
+        if not self.cond_router:
+            self._last_topk = ent["topk"]
+            self._account_token_usage(ent["topk"], B * self.seq_len)
+        else:
+            if self.use_goal_in_routing:
+                self._last_topk = ent["topk"]
+            self._account_usage(ent["meta"], eng.meta_layout(B * self.seq_len), B * self.seq_len)
         return ent["out"].clone()
 
     def _schedule_state(self, eng, sig, B, sigma_data: float, out=None, solver: str = "ddim", lin=None):
@@ -410,6 +417,16 @@ class MoDeDiT(nn.Module):
         st = dict(c_in=(1.0 / s2.sqrt()).contiguous(),
                   scal=torch.stack([sigma_data ** 2 / s2, s * sigma_data / s2.sqrt(), nxt / s, ms], 1).contiguous(),
                   emb_all=eng.sigma_embed(s))                            # [n, D]: one conditioning row per step
+        if self._routes_per_chunk():
+            # goal / token routing depends on the observations: it is resolved inside the captured chunk (_chunk_routing), not here - and a
+            # routing cache filled by precompute_experts_for_inference for ONE goal never stands in for the others
+            if lin is not None:
+                st["lin"] = lin.to(device=eng.device, dtype=torch.float32).contiguous()
+            if out is None:
+                return st
+            for k_ in st:
+                out[k_].copy_(st[k_])
+            return out
         cached = None
         if all(blk.fused_experts for blk in self.blocks) and getattr(self, "_fused_for", None) == eng._wkey:
             keys = [float(v) for v in s.tolist()]                        # (host sync: only when the schedule state is (re)built)
@@ -444,19 +461,59 @@ class MoDeDiT(nn.Module):
             ms[1:] = torch.where(nxt[1:] > 0, 1.0 / (2.0 * r), torch.zeros_like(r))
         return ms
 
-    def _ddim_steps(self, eng, img, goals, x, sched, n: int, den=None):
-        """The observation-dependent launch chain of a DDIM run: embeddings of the observations + n denoiser forwards with the fused EDM / DDIM
-        update; pure launches, no host sync -> capturable.  Reads the schedule state by pointer."""
+    def _routing_mode(self):
+        """Part of every captured chunk's key: the chain a graph holds depends on how the model routes."""
+        return bool(self.use_goal_in_routing), bool(self.cond_router)
+
+    def _routes_per_chunk(self) -> bool:
+        """Goal routing (router input emb_t + goal_emb(goal): one row per sample) or token routing (cond_router=False: one decision per token
+        inside the chain): the routing of a sampler run depends on the observations, so the captured chunk resolves it itself."""
+        return self.use_goal_in_routing or not self.cond_router
+
+    def _chunk_routing(self, eng, sched, goal_e, n: int, B: int, ml, tok=None):
+        """Routing state of a captured chunk of n denoiser evaluations, issued right after the observation embeddings; returns (args of
+        evaluation j -> dict, route output or None, dispatch records or None).  Goal routing: the conditioning rows of every level,
+        cond[j·B + b] = emb_all[j] + goal_e[b] ([n·B, D]), one router launch over all of them and one dispatch launch; the router output
+        [L, n·B, k] is, contiguously, [(L·n), B, k], so level j's records sit at meta + j·words with layer stride n·words - the layout of the
+        schedule-only routing.  Token routing (``tok``: int32 [n, L, B·T, k]): every forward routes its tokens itself and writes its
+        decisions to tok[j].  The default (conditioning-row routing on sigma only) reads the schedule state's records, as before."""
+        D, T = self.embed_dim, self.seq_len
+        emb_all = sched["emb_all"]
+        cond = idx = None
+        meta = sched.get("meta")
+        if self.use_goal_in_routing:
+            cond = (emb_all[:, None, :] + goal_e[None, :, :]).reshape(n * B, D)
+            if self.cond_router:
+                idx, w, _, _ = eng.route(cond)
+                meta = eng.dispatch(idx, w, self.num_layers * n, B, T, B * T)
+
+        def at(j):
+            c, cs = (emb_all[j], 0) if cond is None else (cond[j * B:(j + 1) * B], D)
+            if tok is not None:
+                return dict(cond=c, cond_stride=cs, meta_ptr=None, meta_stride=0, uniform=False, topk_out=tok[j])
+            return dict(cond=c, cond_stride=cs, meta_ptr=meta.data_ptr() + 4 * j * ml.total_words, meta_stride=n * ml.total_words,
+                        uniform=cond is None, topk_out=None)
+        return at, idx, meta
+
+    def _ddim_steps(self, eng, img, goals, x, sched, n: int, den=None, tok=None, route_out=None):
+        """The observation-dependent launch chain of a DDIM run: embeddings of the observations (+ the routing of goal-routed models) + n denoiser
+        forwards with the fused EDM / DDIM update; pure launches, no host sync -> capturable.  Reads the schedule state by pointer.
+        ``route_out``: a dict that receives the chunk's routing output (``_chunk_routing``)."""
         B, T = x.shape[0], self.seq_len
         img_e, goal_e = eng.embed_obs(img, goals)                        # step-invariant, hoisted (modedit.py:760,765)
         ml = eng.meta_layout(B * T)
-        emb_all, meta, c_in, scal = sched["emb_all"], sched["meta"], sched["c_in"], sched["scal"]
+        emb_all, c_in, scal = sched["emb_all"], sched["c_in"], sched["scal"]
+        at, idx, meta = self._chunk_routing(eng, sched, goal_e, n, B, ml, tok)
+        if route_out is not None:
+            route_out.update(idx=idx, meta=meta)
         for s in range(n):
             e = emb_all[s]
+            r = at(s)
             # `den` ([2, B, A_len, A_dim]; two-point multistep solvers): the head also writes this step's denoised prediction and reads the previous one
             mk = {} if den is None else dict(denoised=den[s & 1], den_prev=den[(s - 1) & 1] if s > 0 else None)
-            eng.forward(B, e, 0, e, 0, meta.data_ptr() + 4 * s * ml.total_words, n * ml.total_words, goal_e, img_e, x,
-                        c_in=c_in.data_ptr() + 4 * s, c_in_stride=0, scal_ptr=scal.data_ptr() + 16 * s, scal_stride=0, x_next=x, uniform=True, **mk)
+            eng.forward(B, e, 0, r["cond"], r["cond_stride"], r["meta_ptr"], r["meta_stride"], goal_e, img_e, x,
+                        c_in=c_in.data_ptr() + 4 * s, c_in_stride=0, scal_ptr=scal.data_ptr() + 16 * s, scal_stride=0, x_next=x, uniform=r["uniform"],
+                        topk_out=r["topk_out"], **mk)
         return ml
 
     # ---- two-stage solvers on the fused chain (Heun, DPM-Solver-2, DPM-Solver++(2S)) -------------------------------------------------------
@@ -497,20 +554,25 @@ class MoDeDiT(nn.Module):
                 raise ValueError(solver)
         return plan
 
-    def _plan_steps(self, eng, img, goals, bufs, sched, plan):
+    def _plan_steps(self, eng, img, goals, bufs, sched, plan, tok=None, route_out=None):
         """The launch chain of a two-stage solve: one denoiser forward per plan entry, the head applying the entry's linear update between the three
-        [B, A_len, A_dim] buffers `bufs`; pure launches -> capturable.  Coefficients, scalings, embeddings and routing are read by pointer."""
+        [B, A_len, A_dim] buffers `bufs`; pure launches -> capturable.  Coefficients, scalings, embeddings and routing are read by pointer
+        (goal / token routing: resolved in the chain, ``_chunk_routing``)."""
         B, T = bufs[0].shape[0], self.seq_len
         img_e, goal_e = eng.embed_obs(img, goals)
         ml = eng.meta_layout(B * T)
-        emb_all, meta, c_in, scal, lin = sched["emb_all"], sched["meta"], sched["c_in"], sched["scal"], sched["lin"]
+        emb_all, c_in, scal, lin = sched["emb_all"], sched["c_in"], sched["scal"], sched["lin"]
         m = len(plan)
+        at, idx, meta = self._chunk_routing(eng, sched, goal_e, m, B, ml, tok)
+        if route_out is not None:
+            route_out.update(idx=idx, meta=meta)
         for j, (_, xin, xout, _, a1, a2, dout) in enumerate(plan):
             e = emb_all[j]
-            eng.forward(B, e, 0, e, 0, meta.data_ptr() + 4 * j * ml.total_words, m * ml.total_words, goal_e, img_e, bufs[xin],
-                        c_in=c_in.data_ptr() + 4 * j, c_in_stride=0, scal_ptr=scal.data_ptr() + 16 * j, scal_stride=0, x_next=bufs[xout], uniform=True,
+            r = at(j)
+            eng.forward(B, e, 0, r["cond"], r["cond_stride"], r["meta_ptr"], r["meta_stride"], goal_e, img_e, bufs[xin],
+                        c_in=c_in.data_ptr() + 4 * j, c_in_stride=0, scal_ptr=scal.data_ptr() + 16 * j, scal_stride=0, x_next=bufs[xout], uniform=r["uniform"],
                         denoised=None if dout is None else bufs[dout], lin_ptr=lin.data_ptr() + 16 * j,
-                        aux1=None if a1 is None else bufs[a1], aux2=None if a2 is None else bufs[a2])
+                        aux1=None if a1 is None else bufs[a1], aux2=None if a2 is None else bufs[a2], topk_out=r["topk_out"])
         return ml
 
     @torch.no_grad()
@@ -523,7 +585,7 @@ class MoDeDiT(nn.Module):
         assert solver in ("heun", "dpm_2", "dpmpp_2s"), solver
         eng = self.engine
         dev, B = eng.device, action.shape[0]
-        if (B == 0 or self.use_goal_in_routing or not self.cond_router or os.environ.get("MODE_HIP_GRAPH", "1") == "0" or sigmas.numel() < 2):
+        if B == 0 or os.environ.get("MODE_HIP_GRAPH", "1") == "0" or sigmas.numel() < 2:
             return None
         img, goals = self._prep_obs(eng, states, goals)
         sig = sigmas.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -534,7 +596,7 @@ class MoDeDiT(nn.Module):
             tag = None
         sid = ("tag", tag) if tag is not None else ("obj", id(sigmas), sigmas._version)
         sched_key = (sid, eng._wkey, getattr(self, "_fused_gen", 0))
-        key = (B, sig.numel(), eng.compute_dtype, eng._structs_for, str(dev), float(sigma_data))
+        key = (B, sig.numel(), eng.compute_dtype, eng._structs_for, str(dev), float(sigma_data), self._routing_mode())
         gkey = "graph:" + solver
         ent = self._route_cache.get(gkey)
         fresh = ent is None or ent["key"] != key
@@ -558,26 +620,52 @@ class MoDeDiT(nn.Module):
             m = len(plan)
             st = dict(key=key, img=img.clone(), goals=goals.clone(), sig=sig.clone(), plan=plan,
                       bufs=[torch.zeros_like(x0).contiguous() for _ in range(3)])
-            st["ws"] = torch.empty(max(eng.workspace_bytes(B, 0), eng.workspace_bytes(0, m)), dtype=torch.uint8, device=dev)
+            st["ws"] = self._chunk_ws(eng, B, m)
+            st["tok"], st["route"] = self._chunk_topk_buffer(eng, m, B), {}
             ev = torch.tensor([e[0] for e in plan], dtype=torch.float32, device=dev)
             with eng.pinned_workspace(st["ws"]):
                 st["sched"] = self._schedule_state(eng, ev, B, sigma_data, lin=torch.tensor([e[3] for e in plan], dtype=torch.float32))
                 side = torch.cuda.Stream(device=dev)
                 side.wait_stream(torch.cuda.current_stream(dev))
                 with torch.cuda.stream(side):                            # warm-up: loads code objects
-                    self._plan_steps(eng, st["img"], st["goals"], st["bufs"], st["sched"], plan)
+                    self._plan_steps(eng, st["img"], st["goals"], st["bufs"], st["sched"], plan, tok=st["tok"])
                 torch.cuda.current_stream(dev).wait_stream(side)
                 g = torch.cuda.CUDAGraph()
                 with capture_graph(g):
-                    st["ml"] = self._plan_steps(eng, st["img"], st["goals"], st["bufs"], st["sched"], plan)
+                    st["ml"] = self._plan_steps(eng, st["img"], st["goals"], st["bufs"], st["sched"], plan, tok=st["tok"], route_out=st["route"])
             st["graph"], st["sched_key"] = g, sched_key
             st["sig_ref"] = sigmas if tag is None else None
             self._route_cache[gkey] = ent = st
         ent["img"].copy_(img); ent["goals"].copy_(goals); ent["bufs"][0].copy_(x0)
         ent["graph"].replay()
-        self._last_topk = ent["sched"]["idx"]
-        self._account_ddim_usage(ent["sched"], ent["ml"], len(ent["plan"]), B * self.seq_len)
+        self._account_chunk(ent, ent["ml"], len(ent["plan"]), B)
         return ent["bufs"][0].clone()
+
+    def _chunk_ws(self, eng, B: int, n: int) -> torch.Tensor:
+        """The workspace a captured chunk of n evaluations owns: the forward's, or the schedule's sigma embedding / the router's over n rows
+        (n·B conditioning rows with goal routing), whichever is larger."""
+        rows = n * B if self.use_goal_in_routing else n
+        return torch.empty(max(eng.workspace_bytes(B, 0), eng.workspace_bytes(0, rows)), dtype=torch.uint8, device=eng.device)
+
+    def _chunk_topk_buffer(self, eng, n: int, B: int):
+        """Token routing: int32 [n, L, B·T, k] that the n forwards of a captured chunk write their decisions to; None otherwise."""
+        if self.cond_router:
+            return None
+        return torch.empty(n, self.num_layers, B * self.seq_len, self.top_k, dtype=torch.int32, device=eng.device)
+
+    def _account_chunk(self, ent, ml, n: int, B: int) -> None:
+        """After a replay of a captured chunk of n evaluations: ``_last_topk`` (level j of every layer at [:, j]) and the expert-usage counters,
+        with device ops only - token routing: ONE histogram of the chunk's decisions; otherwise the dispatch records' per-expert counts."""
+        N = B * self.seq_len
+        if ent.get("tok") is not None:
+            self._last_topk = ent["tok"].transpose(0, 1)                 # [L, n, N, k]
+            self._account_token_usage(self._last_topk, N * n)
+        elif self.use_goal_in_routing:
+            self._last_topk = ent["route"]["idx"].view(self.num_layers, n, B, self.top_k)
+            self._account_ddim_usage(ent["route"], ml, n, N)
+        else:
+            self._last_topk = ent["sched"]["idx"]
+            self._account_ddim_usage(ent["sched"], ml, n, N)
 
     def _account_ddim_usage(self, sched, ml, n, n_tokens):
         """Expert-usage counters of a whole DDIM run (modedit.py:568-572, 594): one device-side add per chunk, outside the graph."""
@@ -607,7 +695,8 @@ class MoDeDiT(nn.Module):
         x0 = action.detach().to(device=dev, dtype=torch.float32)
         self._check_batch(B, img, goals, x0)
         n = sig.numel() - 1
-        if self.use_goal_in_routing or not self.cond_router:             # routing depends on the sample / the tokens: per-step generic path
+        use_graph = os.environ.get("MODE_HIP_GRAPH", "1") != "0"
+        if self._routes_per_chunk() and not use_graph:                 # goal / token routing without graphs: the per-step generic path
             x = x0.clone()
             prev = None
             for i in range(n):
@@ -620,7 +709,6 @@ class MoDeDiT(nn.Module):
                 x = r * x + (1.0 - r) * dd
                 prev = den
             return x
-        use_graph = os.environ.get("MODE_HIP_GRAPH", "1") != "0"
         multi = solver != "ddim"
         if not use_graph:
             x = x0.clone().contiguous()
@@ -629,7 +717,7 @@ class MoDeDiT(nn.Module):
             self._last_topk = sched["idx"]
             self._account_ddim_usage(sched, ml, n, B * self.seq_len)
             return x
-        key = (B, sig.numel(), eng.compute_dtype, eng._structs_for, str(dev), float(sigma_data))   # arena pointers are static: weight updates keep graphs valid
+        key = (B, sig.numel(), eng.compute_dtype, eng._structs_for, str(dev), float(sigma_data), self._routing_mode())   # arena pointers are static: weight updates keep graphs valid
         gkey = "graph" if not multi else "graph:" + solver                  # one captured chain per solver
         ent = self._route_cache.get(gkey)
         # identity of the schedule: a host-side tag of its VALUES when the tensor came from a get_sigmas_* / get_noise_schedule generator (the
@@ -647,18 +735,19 @@ class MoDeDiT(nn.Module):
             st = dict(key=key, img=img.clone(), goals=goals.clone(), x=x0.clone().contiguous(), sig=sig.clone())
             # the graph owns its workspace: the engine's shared scratch buffer is re-allocated whenever a larger chain (a training step, a
             # bigger batch) asks for more, and a replay would then read freed memory
-            st["ws"] = torch.empty(max(eng.workspace_bytes(B, 0), eng.workspace_bytes(0, n)), dtype=torch.uint8, device=dev)
+            st["ws"] = self._chunk_ws(eng, B, n)
             st["den"] = torch.zeros((2,) + tuple(x0.shape), dtype=torch.float32, device=dev) if multi else None
+            st["tok"], st["route"] = self._chunk_topk_buffer(eng, n, B), {}
             with eng.pinned_workspace(st["ws"]):
                 st["sched"] = self._schedule_state(eng, st["sig"], B, sigma_data, solver=solver)
                 side = torch.cuda.Stream(device=dev)
                 side.wait_stream(torch.cuda.current_stream(dev))
                 with torch.cuda.stream(side):                            # warm-up: loads code objects
-                    self._ddim_steps(eng, st["img"], st["goals"], st["x"], st["sched"], n, den=st["den"])
+                    self._ddim_steps(eng, st["img"], st["goals"], st["x"], st["sched"], n, den=st["den"], tok=st["tok"])
                 torch.cuda.current_stream(dev).wait_stream(side)
                 g = torch.cuda.CUDAGraph()
                 with capture_graph(g):
-                    st["ml"] = self._ddim_steps(eng, st["img"], st["goals"], st["x"], st["sched"], n, den=st["den"])
+                    st["ml"] = self._ddim_steps(eng, st["img"], st["goals"], st["x"], st["sched"], n, den=st["den"], tok=st["tok"], route_out=st["route"])
             st["graph"], st["sched_key"] = g, sched_key
             st["sig_ref"] = sigmas if tag is None else None
             self._route_cache[gkey] = ent = st
@@ -674,8 +763,7 @@ class MoDeDiT(nn.Module):
             ent["sched_key"] = sched_key
         ent["img"].copy_(img); ent["goals"].copy_(goals); ent["x"].copy_(x0)
         ent["graph"].replay()
-        self._last_topk = ent["sched"]["idx"]
-        self._account_ddim_usage(ent["sched"], ent["ml"], n, B * self.seq_len)
+        self._account_chunk(ent, ent["ml"], n, B)
         return ent["x"].clone()
 
     def _account_token_usage(self, idx, n_tokens):

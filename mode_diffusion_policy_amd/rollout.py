@@ -81,7 +81,9 @@ class ChunkedRolloutPolicy:
     ``step(perceptual_emb, latent_goal)``: ``perceptual_emb = {'state_images': (B, 2, obs_dim)}`` (the encoders' output), ``latent_goal``
     (B, G) or (B, 1, G); returns the actions of this control step, (B, action_dim).  With the default DDIM sampler a replanning call is one
     hipGraph replay; the routing decisions of every noise level are resolved once (``precompute_experts_for_inference``) like the agent does
-    on its first inference call.
+    on its first inference call.  Goal-routed (``use_goal_in_routing``) and token-routed (``cond_router=False``) denoisers replan in one replay
+    as well: their routing depends on the observations and is resolved inside the graph for every sample, so the cache the agent fills from
+    the FIRST environment's goal (``latent_goal[:1]``) never routes the others.
 
     With ``static_resnet`` / ``gripper_resnet`` (the agent's perceptual encoders, mode_agent.py:132-160) ``step`` also takes the environment's
     observation as the agent does - ``{'rgb_obs': {'rgb_static': (B, T, 3, H, W), 'rgb_gripper': ...}}`` - and embeds it on replanning steps
@@ -148,30 +150,31 @@ class ChunkedRolloutPolicy:
         """The whole sampler call (every denoiser call, every update of the recurrence, the samplers' own noise draws) as ONE hipGraph replay - what the
         fused DDIM path does for ``ddim`` and ``euler``, for the samplers whose control flow does not depend on the data (heun, dpm-solver(++) ...: the step
         loop only branches on which levels of the SCHEDULE are zero).  Captured once per (sampler, batch, weights storage); the ancestral samplers' noise
-        comes from torch's default generator, which hipGraph capture advances per replay.  None = not applicable (goal / token routing, training mode,
-        MODE_HIP_GRAPH=0): the caller takes the step-by-step path."""
+        comes from torch's default generator, which hipGraph capture advances per replay.  Goal and token routing are captured too: every denoiser call
+        of the chunk routes its own samples / tokens inside the graph.  None = not applicable (training mode, MODE_HIP_GRAPH=0): the caller takes the
+        step-by-step path."""
         import os
         from . import samplers as S
         from .engine import capture_graph
         from .modedit import MoDeDiT
         den = self.model
         inner = getattr(den, "inner_model", None)
-        if (not isinstance(inner, MoDeDiT) or inner.training or inner.use_goal_in_routing or not inner.cond_router or len(x) == 0
-                or os.environ.get("MODE_HIP_GRAPH", "1") == "0"):
+        if not isinstance(inner, MoDeDiT) or inner.training or len(x) == 0 or os.environ.get("MODE_HIP_GRAPH", "1") == "0":
             return None
         eng = inner.engine
         dev, B = eng.device, x.shape[0]
         img, gl = inner._prep_obs(eng, perceptual_emb, latent_goal)
         inner._check_batch(B, img, gl, x)
         cache = self.__dict__.setdefault("_chunk_graphs", {})
-        key = (self.sampler_type, B, eng.compute_dtype, eng._structs_for, str(dev), id(sigmas), sigmas._version, float(den.sigma_data))
+        key = (self.sampler_type, B, eng.compute_dtype, eng._structs_for, str(dev), id(sigmas), sigmas._version, float(den.sigma_data),
+               inner._routing_mode())
         ent = cache.get(key)
         if ent is None:
             if len(cache) >= 4:
                 cache.pop(next(iter(cache)))
             ent = dict(x=x.clone(), img=img.clone(), goals=gl.clone(), sig=sigmas,
                        img_e=torch.empty(B * inner.n_img_tokens, inner.embed_dim, device=dev), goal_e=torch.empty(B, inner.embed_dim, device=dev))
-            ent["ws"] = torch.empty(max(eng.workspace_bytes(B, 0), eng.workspace_bytes(0, 1)), dtype=torch.uint8, device=dev)
+            ent["ws"] = inner._chunk_ws(eng, B, 1)
             state = {"state_images": ent["img"].view(B, inner.n_img_tokens, -1)}
             goal3 = ent["goals"].view(B, 1, -1)
 
@@ -198,8 +201,11 @@ class ChunkedRolloutPolicy:
         ent["x"].copy_(x); ent["img"].copy_(img); ent["goals"].copy_(gl)
         ent["graph"].replay()
         ml = eng.meta_layout(B * inner.seq_len)
-        for meta in ent["metas"]:                                             # expert-usage counters, as the step-by-step path keeps them
-            inner._account_usage(meta, ml, B * inner.seq_len)
+        if not inner.cond_router:                                             # token routing: one histogram of every call's decisions
+            inner._account_token_usage(torch.stack(ent["metas"], 1), B * inner.seq_len * len(ent["metas"]))
+        else:
+            for meta in ent["metas"]:                                         # expert-usage counters, as the step-by-step path keeps them
+                inner._account_usage(meta, ml, B * inner.seq_len)
         return ent["out"].clone()
 
     @torch.no_grad()

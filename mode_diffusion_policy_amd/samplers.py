@@ -146,7 +146,7 @@ def _zero_levels(sigmas):
 
 
 # Set by rollout.ChunkedRolloutPolicy while it captures a whole sampler call in ONE hipGraph: {"inner": MoDeDiT, "sigma_data": float, "obs_emb":
-# (img_e, goal_e), "metas": []}.  A hipGraph cannot be replayed inside a capture, so _Run.denoise then issues the eager launch chain of
+# (img_e, goal_e), "metas": []} (per denoiser call its dispatch records, or under token routing its expert decisions).  A hipGraph cannot be replayed inside a capture, so _Run.denoise then issues the eager launch chain of
 # MoDeDiT.denoise (device-scalar sigma, observation embeddings computed once at the top of the captured chunk) instead of denoise_graphed's replay.
 # Per THREAD (hipGraph stream capture is a per-thread state too: one capture per thread at a time; the policy sets and clears it around its own call),
 # so two policies capturing on two threads do not see each other's hook.
@@ -175,7 +175,7 @@ class _Run:
         if cc is not None and not self.kw and torch.is_tensor(sigma) and sigma.numel() == 1:
             inner = cc["inner"]
             out = inner.denoise(None, x, None, sigma.reshape(1), cc["sigma_data"], _account=False, _obs_emb=cc["obs_emb"])
-            cc["metas"].append(inner._last_meta)
+            cc["metas"].append(inner._last_meta if inner.cond_router else inner._last_topk)     # token routing: the call's decisions [L, N, k]
             return out
         fast = getattr(self.model, "denoise_uniform", None)              # GCDenoiser over the HIP MoDeDiT: one hipGraph replay per call
         if fast is not None and not self.kw and torch.is_tensor(sigma) and sigma.numel() == 1:
