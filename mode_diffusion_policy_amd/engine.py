@@ -52,6 +52,21 @@ def capture_graph(graph: "torch.cuda.CUDAGraph"):
             gc.enable()
 
 
+def warm_and_capture(fn, device, warmups: int = 1):
+    """``warmups`` calls of ``fn`` on a side stream (code-object loads, library algorithm searches: nothing of that may happen inside a capture),
+    then one more call captured into a new hipGraph; returns (graph, the captured call's result).  Callers pin their own workspace around it."""
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):
+        for _ in range(warmups):
+            fn()
+    torch.cuda.current_stream(device).wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with capture_graph(graph):
+        out = fn()
+    return graph, out
+
+
 class DitEngine:
     def __init__(self, model, compute_dtype: str = "bf16"):
         if compute_dtype not in _DT:

@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .engine import DitEngine, capture_graph
+from .engine import DitEngine, warm_and_capture
 
 logger = logging.getLogger(__name__)
 
@@ -237,44 +237,44 @@ class MoDeDiT(nn.Module):
         B = actions.shape[0]
         if B == 0:                                                       # empty batch: empty prediction, no launches
             return torch.empty(0, self.action_seq_len, self.action_dim, dtype=torch.float32, device=dev)
-        T, D = self.seq_len, self.embed_dim
         f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        img = f(states["state_images"])
-        if img.dim() != 3 or img.shape[1] != self.n_img_tokens or img.shape[2] != self.obs_dim:
-            raise ValueError(f"state_images must be (B, {self.n_img_tokens}, {self.obs_dim}), got {tuple(img.shape)}")
-        goals = f(self.preprocess_goals(goals, 1, uncond=bool(uncond)))
+        img, goals = self._prep_obs(eng, states, goals, uncond)
         acts = f(actions)
         self._check_batch(B, img, goals, acts)
         sig = f(sigma).reshape(-1)
         if sig.numel() not in (1, B):
             raise ValueError("sigma must be a scalar or have one entry per sample")
-        R = sig.numel()
         emb_t = eng.sigma_embed(sig)
         img_e, goal_e = eng.embed_obs(img, goals)
-        cond = emb_t
-        if self.use_goal_in_routing:                                       # modedit.py:801-802
-            cond = (emb_t.expand(B, D) + goal_e).contiguous()
-            R = B
-        N = B * T
         F = torch.empty(B, self.action_seq_len, self.action_dim, dtype=torch.float32, device=dev)
-        if not self.cond_router:                                          # token routing inside the chain
-            idx = torch.empty(self.num_layers, N, self.top_k, dtype=torch.int32, device=dev)
-            eng.forward(B, emb_t, 0 if emb_t.shape[0] == 1 else D, cond, 0 if cond.shape[0] == 1 else D, None, 0, goal_e, img_e, acts, F=F, topk_out=idx)
-            self._last_topk = idx
-            self._account_token_usage(idx, N)
-            self.logits_per_layer = [None] * self.num_layers
-            self.probs_per_layer = [None] * self.num_layers
-            return F
-        idx, w, _, _ = eng.route(cond)
-        meta = eng.dispatch(idx, w, self.num_layers, R, N if R == 1 else T, N)
-        ml = eng.meta_layout(N)
-        eng.forward(B, emb_t, 0 if emb_t.shape[0] == 1 else D, cond, 0 if cond.shape[0] == 1 else D,
-                    meta.data_ptr(), ml.total_words, goal_e, img_e, acts, F=F, uniform=R == 1)
-        self._last_topk = idx
-        self._account_usage(meta, ml, N)
+        self._routed_forward(eng, B, emb_t, goal_e, img_e, acts, F=F)
         self.logits_per_layer = [None] * self.num_layers                   # only populated in training (modedit.py:584-593)
         self.probs_per_layer = [None] * self.num_layers
         return F
+
+    def _routed_forward(self, eng, B, emb_t, goal_e, img_e, x, account: bool = True, **head) -> None:
+        """One denoiser forward with its routing.  The conditioning rows are emb_t ([1, D] for the whole batch or [B, D]), or with goal routing
+        emb_t + goal_e, one row per sample (modedit.py:801-802).  Token routing: every block routes its tokens inside the chain, no dispatch
+        records; otherwise router + dispatch of the conditioning rows.  ``head``: the output head's arguments of ``DitEngine.forward``."""
+        D, T = self.embed_dim, self.seq_len
+        N = B * T
+        cond = (emb_t.expand(B, D) + goal_e).contiguous() if self.use_goal_in_routing else emb_t
+        R = cond.shape[0]
+        es, cs = 0 if emb_t.shape[0] == 1 else D, 0 if R == 1 else D
+        if not self.cond_router:
+            idx = torch.empty(self.num_layers, N, self.top_k, dtype=torch.int32, device=eng.device)
+            eng.forward(B, emb_t, es, cond, cs, None, 0, goal_e, img_e, x, topk_out=idx, **head)
+            self._last_topk = idx
+            if account:
+                self._account_token_usage(idx, N)
+            return
+        idx, w, _, _ = eng.route(cond)
+        meta = eng.dispatch(idx, w, self.num_layers, R, N if R == 1 else T, N)
+        ml = eng.meta_layout(N)
+        eng.forward(B, emb_t, es, cond, cs, meta.data_ptr(), ml.total_words, goal_e, img_e, x, uniform=R == 1, **head)
+        self._last_topk, self._last_meta = idx, meta
+        if account:
+            self._account_usage(meta, ml, N)
 
     # ------------------------------------------------------------------ fused EDM forward / DDIM sampler
     def _prep_obs(self, eng, states, goals, uncond=False):
@@ -283,14 +283,14 @@ class MoDeDiT(nn.Module):
         if img.dim() != 3 or img.shape[1] != self.n_img_tokens or img.shape[2] != self.obs_dim:
             raise ValueError(f"state_images must be (B, {self.n_img_tokens}, {self.obs_dim}), got {tuple(img.shape)}")
         goals = f(self.preprocess_goals(goals, 1, uncond=bool(uncond)))
-        return img, goals.reshape(img.shape[0], -1).contiguous()
+        return img, goals.reshape(goals.shape[0], -1)                    # (B, 1, G) after preprocess_goals: a view, still contiguous
 
     @torch.no_grad()
     def denoise(self, states, action, goals, sigma, sigma_data: float, _account: bool = True, _obs_emb=None):
         """GCDenoiser.forward (score_wrappers.py:65-80) with c_in / c_out / c_skip fused into the HIP chain.  ``_obs_emb``: (img_e, goal_e) already
         computed for these observations (denoise_graphed keeps them across the calls of one sampler run)."""
         eng = self.engine
-        dev, B, T, D = eng.device, action.shape[0], self.seq_len, self.embed_dim
+        dev, B = eng.device, action.shape[0]
         if B == 0:
             return action.detach().to(device=dev, dtype=torch.float32).clone()
         x = action.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -306,28 +306,9 @@ class MoDeDiT(nn.Module):
         scal = torch.stack([sigma_data ** 2 / s2, sig * sigma_data / s2.sqrt(), torch.zeros_like(sig), torch.zeros_like(sig)], 1).contiguous()
         emb_t = eng.sigma_embed(sig)
         img_e, goal_e = _obs_emb if _obs_emb is not None else eng.embed_obs(img, goals)
-        cond = emb_t
-        if self.use_goal_in_routing:
-            cond = (emb_t.expand(B, D) + goal_e).contiguous()
-        Rr = cond.shape[0]
-        N = B * T
         den = torch.empty_like(x)
-        if not self.cond_router:                                          # token routing inside the chain
-            idx = torch.empty(self.num_layers, N, self.top_k, dtype=torch.int32, device=dev)
-            eng.forward(B, emb_t, 0 if R == 1 else D, cond, 0 if Rr == 1 else D, None, 0, goal_e, img_e, x, c_in=c_in, c_in_stride=0 if R == 1 else 1,
-                        scal_ptr=scal.data_ptr(), scal_stride=0 if R == 1 else 4, denoised=den, topk_out=idx)
-            self._last_topk = idx
-            if _account:
-                self._account_token_usage(idx, N)
-            return den
-        idx, w, _, _ = eng.route(cond)
-        meta = eng.dispatch(idx, w, self.num_layers, Rr, N if Rr == 1 else T, N)
-        ml = eng.meta_layout(N)
-        eng.forward(B, emb_t, 0 if R == 1 else D, cond, 0 if Rr == 1 else D, meta.data_ptr(), ml.total_words, goal_e, img_e, x,
-                    c_in=c_in, c_in_stride=0 if R == 1 else 1, scal_ptr=scal.data_ptr(), scal_stride=0 if R == 1 else 4, denoised=den, uniform=Rr == 1)
-        self._last_topk, self._last_meta = idx, meta
-        if _account:
-            self._account_usage(meta, ml, N)
+        self._routed_forward(eng, B, emb_t, goal_e, img_e, x, account=_account, c_in=c_in, c_in_stride=0 if R == 1 else 1,
+                             scal_ptr=scal.data_ptr(), scal_stride=0 if R == 1 else 4, denoised=den)
         return den
 
     @torch.no_grad()
@@ -365,20 +346,14 @@ class MoDeDiT(nn.Module):
                        img_e=torch.empty(B * self.n_img_tokens, self.embed_dim, device=dev), goal_e=torch.empty(B, self.embed_dim, device=dev))
             ent["sig"].copy_(sig)
             ent["ws"] = self._chunk_ws(eng, B, 1)
-            run = lambda: self.denoise(None, ent["x"], None, ent["sig"], sigma_data, _account=False, _obs_emb=(ent["img_e"], ent["goal_e"]))
+
+            def run():
+                out = self.denoise(None, ent["x"], None, ent["sig"], sigma_data, _account=False, _obs_emb=(ent["img_e"], ent["goal_e"]))
+                return out, self._last_topk, self._last_meta if self.cond_router else None
             with eng.pinned_workspace(ent["ws"]):
-                side = torch.cuda.Stream(device=dev)
-                side.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(side):                            # warm-up outside the capture: loads code objects
-                    eng.embed_obs(ent["img"], ent["goals"], out=(ent["img_e"], ent["goal_e"]))
-                    run()
-                torch.cuda.current_stream(dev).wait_stream(side)
-                g = torch.cuda.CUDAGraph()
-                with capture_graph(g):
-                    ent["out"] = run()
-                    ent["topk"] = self._last_topk
-                    ent["meta"] = self._last_meta if self.cond_router else None
-            ent["graph"] = g
+                # the warm-up and the capture route on these embeddings: routing on uninitialised memory can yield out-of-range expert ids
+                eng.embed_obs(ent["img"], ent["goals"], out=(ent["img_e"], ent["goal_e"]))
+                ent["graph"], (ent["out"], ent["topk"], ent["meta"]) = warm_and_capture(run, dev)
             cache[key] = ent
         if fresh:
             ent["img"].copy_(img); ent["goals"].copy_(gl)
@@ -495,26 +470,33 @@ class MoDeDiT(nn.Module):
                         uniform=cond is None, topk_out=None)
         return at, idx, meta
 
-    def _ddim_steps(self, eng, img, goals, x, sched, n: int, den=None, tok=None, route_out=None):
-        """The observation-dependent launch chain of a DDIM run: embeddings of the observations (+ the routing of goal-routed models) + n denoiser
-        forwards with the fused EDM / DDIM update; pure launches, no host sync -> capturable.  Reads the schedule state by pointer.
-        ``route_out``: a dict that receives the chunk's routing output (``_chunk_routing``)."""
-        B, T = x.shape[0], self.seq_len
+    def _chunk_steps(self, eng, img, goals, bufs, sched, evals, tok=None):
+        """The observation-dependent launch chain of a fused sampler run: embeddings of the observations (+ the routing of goal-routed models)
+        + one denoiser forward per entry of ``evals``; pure launches, no host sync -> capturable.  Reads the schedule state by pointer.
+        An entry is (x_in, x_out, denoised, den_prev, aux1, aux2, lin): ids into the [B, A_len, A_dim] buffers ``bufs`` (None = not passed) and
+        whether the head applies the schedule's linear update ``sched["lin"][j]`` (two-stage solvers, ModeHeadDesc.lin) instead of DDIM's
+        (scal[2], with scal[3] weighing ``den_prev`` for two-point multistep solvers, ModeHeadDesc.den_prev).  Returns the meta layout and
+        the chunk's routing output {idx, meta} (``_chunk_routing``)."""
+        B, T = bufs[0].shape[0], self.seq_len
         img_e, goal_e = eng.embed_obs(img, goals)                        # step-invariant, hoisted (modedit.py:760,765)
         ml = eng.meta_layout(B * T)
         emb_all, c_in, scal = sched["emb_all"], sched["c_in"], sched["scal"]
-        at, idx, meta = self._chunk_routing(eng, sched, goal_e, n, B, ml, tok)
-        if route_out is not None:
-            route_out.update(idx=idx, meta=meta)
-        for s in range(n):
-            e = emb_all[s]
-            r = at(s)
-            # `den` ([2, B, A_len, A_dim]; two-point multistep solvers): the head also writes this step's denoised prediction and reads the previous one
-            mk = {} if den is None else dict(denoised=den[s & 1], den_prev=den[(s - 1) & 1] if s > 0 else None)
-            eng.forward(B, e, 0, r["cond"], r["cond_stride"], r["meta_ptr"], r["meta_stride"], goal_e, img_e, x,
-                        c_in=c_in.data_ptr() + 4 * s, c_in_stride=0, scal_ptr=scal.data_ptr() + 16 * s, scal_stride=0, x_next=x, uniform=r["uniform"],
-                        topk_out=r["topk_out"], **mk)
-        return ml
+        at, idx, meta = self._chunk_routing(eng, sched, goal_e, len(evals), B, ml, tok)
+        buf = lambda i: None if i is None else bufs[i]
+        for j, (xin, xout, dout, dprev, a1, a2, lin) in enumerate(evals):
+            r = at(j)
+            eng.forward(B, emb_all[j], 0, r["cond"], r["cond_stride"], r["meta_ptr"], r["meta_stride"], goal_e, img_e, bufs[xin],
+                        c_in=c_in.data_ptr() + 4 * j, c_in_stride=0, scal_ptr=scal.data_ptr() + 16 * j, scal_stride=0, x_next=bufs[xout],
+                        uniform=r["uniform"], denoised=buf(dout), den_prev=buf(dprev), lin_ptr=sched["lin"].data_ptr() + 16 * j if lin else None,
+                        aux1=buf(a1), aux2=buf(a2), topk_out=r["topk_out"])
+        return ml, dict(idx=idx, meta=meta)
+
+    @staticmethod
+    def _ddim_evals(n: int, multistep: bool):
+        """``_chunk_steps`` entries of an n-step DDIM run: the state (buffer 0) is updated in place.  ``multistep`` (DPM-Solver++(2M)): the head
+        also writes each step's denoised prediction to buffer 1 / 2 alternately and reads the previous step's from the other one."""
+        den = lambda s: 1 + (s & 1) if multistep and s >= 0 else None
+        return [(0, 0, den(s), den(s - 1), None, None, False) for s in range(n)]
 
     # ---- two-stage solvers on the fused chain (Heun, DPM-Solver-2, DPM-Solver++(2S)) -------------------------------------------------------
     @staticmethod
@@ -554,27 +536,6 @@ class MoDeDiT(nn.Module):
                 raise ValueError(solver)
         return plan
 
-    def _plan_steps(self, eng, img, goals, bufs, sched, plan, tok=None, route_out=None):
-        """The launch chain of a two-stage solve: one denoiser forward per plan entry, the head applying the entry's linear update between the three
-        [B, A_len, A_dim] buffers `bufs`; pure launches -> capturable.  Coefficients, scalings, embeddings and routing are read by pointer
-        (goal / token routing: resolved in the chain, ``_chunk_routing``)."""
-        B, T = bufs[0].shape[0], self.seq_len
-        img_e, goal_e = eng.embed_obs(img, goals)
-        ml = eng.meta_layout(B * T)
-        emb_all, c_in, scal, lin = sched["emb_all"], sched["c_in"], sched["scal"], sched["lin"]
-        m = len(plan)
-        at, idx, meta = self._chunk_routing(eng, sched, goal_e, m, B, ml, tok)
-        if route_out is not None:
-            route_out.update(idx=idx, meta=meta)
-        for j, (_, xin, xout, _, a1, a2, dout) in enumerate(plan):
-            e = emb_all[j]
-            r = at(j)
-            eng.forward(B, e, 0, r["cond"], r["cond_stride"], r["meta_ptr"], r["meta_stride"], goal_e, img_e, bufs[xin],
-                        c_in=c_in.data_ptr() + 4 * j, c_in_stride=0, scal_ptr=scal.data_ptr() + 16 * j, scal_stride=0, x_next=bufs[xout], uniform=r["uniform"],
-                        denoised=None if dout is None else bufs[dout], lin_ptr=lin.data_ptr() + 16 * j,
-                        aux1=None if a1 is None else bufs[a1], aux2=None if a2 is None else bufs[a2], topk_out=r["topk_out"])
-        return ml
-
     @torch.no_grad()
     def sample_two_stage_fused(self, states, action, goals, sigmas, sigma_data: float, solver: str):
         """sample_heun / sample_dpm_2 / sample_dpmpp_2s (deterministic: no churn, no clipping, no callback) as ONE hipGraph replay of the fused chain:
@@ -584,61 +545,111 @@ class MoDeDiT(nn.Module):
         import os
         assert solver in ("heun", "dpm_2", "dpmpp_2s"), solver
         eng = self.engine
-        dev, B = eng.device, action.shape[0]
-        if B == 0 or os.environ.get("MODE_HIP_GRAPH", "1") == "0" or sigmas.numel() < 2:
+        if action.shape[0] == 0 or os.environ.get("MODE_HIP_GRAPH", "1") == "0" or sigmas.numel() < 2:
             return None
+
+        def plan(sig):
+            p = self._two_stage_plan(solver, [float(v) for v in sig.tolist()])          # (host sync: only when the schedule changed)
+            evals = [(xin, xout, dout, None, a1, a2, True) for _, xin, xout, _, a1, a2, dout in p]
+            ev = torch.tensor([e[0] for e in p], dtype=torch.float32, device=eng.device)
+            return evals, ev, dict(lin=torch.tensor([e[3] for e in p], dtype=torch.float32))
+        return self._sample_chunk(eng, "graph:" + solver, states, action, goals, sigmas, sigma_data, plan)
+
+    @torch.no_grad()
+    def sample_ddim_fused(self, states, action, goals, sigmas, sigma_data: float, solver: str = "ddim"):
+        """sample_ddim (gc_sampling.py:922-951) o GCDenoiser o MoDeDiT as one hipGraph replay.  The graph holds only what depends on the
+        observations (embeddings + the denoiser forwards); sigma embeddings, routing, dispatch and the EDM scalings of the schedule live in a
+        schedule state that is rebuilt only when the sigma VALUES, the weights or the batch size change.
+        ``solver="dpmpp_2m"``: sample_dpmpp_2m (gc_sampling.py:700-734) on the same chain - its step is DDIM's exponential-integrator step applied to a
+        two-point extrapolation of the denoised prediction, which the head kernel forms from the previous step's prediction (ModeHeadDesc.den_prev)."""
+        assert solver in ("ddim", "dpmpp_2m"), solver
+        import os
+        eng = self.engine
+        dev, B = eng.device, action.shape[0]
+        if B == 0:                                                       # empty batch: nothing to denoise
+            return action.detach().to(device=dev, dtype=torch.float32).clone()
+        n, multi = sigmas.numel() - 1, solver != "ddim"
+        if os.environ.get("MODE_HIP_GRAPH", "1") != "0":               # one captured chain per solver; its buffer pattern is fixed by n
+            return self._sample_chunk(eng, "graph:" + solver if multi else "graph", states, action, goals, sigmas, sigma_data,
+                                      lambda sig: (self._ddim_evals(n, multi), sig, dict(solver=solver)))
         img, goals = self._prep_obs(eng, states, goals)
         sig = sigmas.detach().to(device=dev, dtype=torch.float32).contiguous()
         x0 = action.detach().to(device=dev, dtype=torch.float32)
         self._check_batch(B, img, goals, x0)
+        if self._routes_per_chunk():                                    # goal / token routing without graphs: the per-step generic path
+            x = x0.clone()
+            prev = None
+            for i in range(n):
+                den = self.denoise({"state_images": img}, x, goals, sig[i].reshape(1), sigma_data)
+                r = sig[i + 1] / sig[i]
+                dd = den
+                if solver == "dpmpp_2m" and prev is not None and float(sig[i + 1]) > 0:
+                    c = 1.0 / (2.0 * ((sig[i - 1].log() - sig[i].log()) / (sig[i].log() - sig[i + 1].log())))
+                    dd = (1.0 + c) * den - c * prev
+                x = r * x + (1.0 - r) * dd
+                prev = den
+            return x
+        bufs = [x0.clone(memory_format=torch.contiguous_format)] + [torch.empty(x0.shape, dtype=torch.float32, device=dev) for _ in range(2)]
+        sched = self._schedule_state(eng, sig, B, sigma_data, solver=solver)
+        self._account_chunk(dict(sched=sched), self._chunk_steps(eng, img, goals, bufs, sched, self._ddim_evals(n, multi))[0], n, B)
+        return bufs[0]
+
+    def _sample_chunk(self, eng, gkey, states, action, goals, sigmas, sigma_data: float, plan):
+        """The fused samplers' hipGraph path: the launch chain of ``_chunk_steps`` captured once per ``_route_cache[gkey]`` entry (one per solver)
+        and replayed per call.  ``plan(sig) -> (evaluations, sigma of the schedule state, its keyword arguments)`` is asked for when the entry is
+        made and when the schedule changes; a new schedule is then written into the schedule state in place (the graph has its pointers baked
+        in), unless its evaluations take another pattern of buffers, which needs another chain."""
+        dev, B = eng.device, action.shape[0]
+        img, goals = self._prep_obs(eng, states, goals)
+        sig = sigmas.detach().to(device=dev, dtype=torch.float32).contiguous()
+        x0 = action.detach().to(device=dev, dtype=torch.float32)
+        self._check_batch(B, img, goals, x0)
+        key = (B, sig.numel(), eng.compute_dtype, eng._structs_for, str(dev), float(sigma_data), self._routing_mode())   # arena pointers are static: weight updates keep graphs valid
+        # identity of the schedule: a host-side tag of its VALUES when the tensor came from a get_sigmas_* / get_noise_schedule generator (the
+        # agent builds a fresh tensor per chunk, mode_agent.py:752) - else the caller's tensor OBJECT (kept alive below, so neither its id nor its
+        # storage can be recycled while the key is live) -, the weights, and the routing cache generation.  No device read on either path.
+        # A tag only vouches for the values the generator wrote: once the tensor has been edited in place (its version moved past the one recorded in
+        # the tag) two tagged tensors with different edits would share (tag, version) - such a tensor is identified as an object, with the device
+        # compare below as the fallback, like any untagged tensor.
         tag = getattr(sigmas, "_mode_sched", None)
         if tag is not None and sigmas._version != tag[3]:
             tag = None
         sid = ("tag", tag) if tag is not None else ("obj", id(sigmas), sigmas._version)
         sched_key = (sid, eng._wkey, getattr(self, "_fused_gen", 0))
-        key = (B, sig.numel(), eng.compute_dtype, eng._structs_for, str(dev), float(sigma_data), self._routing_mode())
-        gkey = "graph:" + solver
         ent = self._route_cache.get(gkey)
-        fresh = ent is None or ent["key"] != key
+        fresh, planned = ent is None or ent["key"] != key, None
         if not fresh and ent["sched_key"] != sched_key:
+            # an UNTAGGED foreign tensor object that may carry the same values: one small device compare (host sync) - the rare path; tagged
+            # schedules and a reused tensor object never get here with an unchanged schedule
             same_values = (tag is None and ent["sched_key"][1:] == sched_key[1:] and bool(torch.equal(sig, ent["sig"])))
             ent["sig_ref"] = sigmas if tag is None else None
-            if same_values:
-                ent["sched_key"] = sched_key
-            else:
-                plan = self._two_stage_plan(solver, [float(v) for v in sig.tolist()])          # (host sync: only when the schedule changed)
-                if [e[1:3] + e[4:] for e in plan] != [e[1:3] + e[4:] for e in ent["plan"]]:
-                    fresh = True                                                              # another zero pattern: another chain
+            if not same_values:
+                planned = plan(sig)
+                if planned[0] != ent["evals"]:
+                    fresh = True                                         # another zero pattern: another chain
                 else:
-                    ent["sig"].copy_(sig); ent["plan"] = plan
-                    ev = torch.tensor([e[0] for e in plan], dtype=torch.float32, device=dev)
+                    ent["sig"].copy_(sig)
                     with eng.pinned_workspace(ent["ws"]):
-                        self._schedule_state(eng, ev, B, sigma_data, out=ent["sched"], lin=torch.tensor([e[3] for e in plan], dtype=torch.float32))
-                    ent["sched_key"] = sched_key
+                        self._schedule_state(eng, planned[1], B, sigma_data, out=ent["sched"], **planned[2])
+            ent["sched_key"] = sched_key
         if fresh:
-            plan = self._two_stage_plan(solver, [float(v) for v in sig.tolist()])
-            m = len(plan)
-            st = dict(key=key, img=img.clone(), goals=goals.clone(), sig=sig.clone(), plan=plan,
-                      bufs=[torch.zeros_like(x0).contiguous() for _ in range(3)])
-            st["ws"] = self._chunk_ws(eng, B, m)
-            st["tok"], st["route"] = self._chunk_topk_buffer(eng, m, B), {}
-            ev = torch.tensor([e[0] for e in plan], dtype=torch.float32, device=dev)
-            with eng.pinned_workspace(st["ws"]):
-                st["sched"] = self._schedule_state(eng, ev, B, sigma_data, lin=torch.tensor([e[3] for e in plan], dtype=torch.float32))
-                side = torch.cuda.Stream(device=dev)
-                side.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(side):                            # warm-up: loads code objects
-                    self._plan_steps(eng, st["img"], st["goals"], st["bufs"], st["sched"], plan, tok=st["tok"])
-                torch.cuda.current_stream(dev).wait_stream(side)
-                g = torch.cuda.CUDAGraph()
-                with capture_graph(g):
-                    st["ml"] = self._plan_steps(eng, st["img"], st["goals"], st["bufs"], st["sched"], plan, tok=st["tok"], route_out=st["route"])
-            st["graph"], st["sched_key"] = g, sched_key
-            st["sig_ref"] = sigmas if tag is None else None
-            self._route_cache[gkey] = ent = st
+            evals, s_sig, s_kw = planned if planned is not None else plan(sig)
+            n = len(evals)
+            ent = dict(key=key, img=img.clone(), goals=goals.clone(), sig=sig.clone(), evals=evals, sched_key=sched_key,
+                       sig_ref=sigmas if tag is None else None,
+                       bufs=[x0.clone(memory_format=torch.contiguous_format)] + [torch.zeros(x0.shape, dtype=torch.float32, device=dev) for _ in range(2)])
+            # the graph owns its workspace: the engine's shared scratch buffer is re-allocated whenever a larger chain (a training step, a
+            # bigger batch) asks for more, and a replay would then read freed memory
+            ent["ws"] = self._chunk_ws(eng, B, n)
+            ent["tok"] = self._chunk_topk_buffer(eng, n, B)
+            with eng.pinned_workspace(ent["ws"]):
+                ent["sched"] = self._schedule_state(eng, s_sig, B, sigma_data, **s_kw)
+                ent["graph"], (ent["ml"], ent["route"]) = warm_and_capture(
+                    lambda: self._chunk_steps(eng, ent["img"], ent["goals"], ent["bufs"], ent["sched"], evals, tok=ent["tok"]), dev)
+            self._route_cache[gkey] = ent
         ent["img"].copy_(img); ent["goals"].copy_(goals); ent["bufs"][0].copy_(x0)
         ent["graph"].replay()
-        self._account_chunk(ent, ent["ml"], len(ent["plan"]), B)
+        self._account_chunk(ent, ent["ml"], len(ent["evals"]), B)
         return ent["bufs"][0].clone()
 
     def _chunk_ws(self, eng, B: int, n: int) -> torch.Tensor:
@@ -654,137 +665,38 @@ class MoDeDiT(nn.Module):
         return torch.empty(n, self.num_layers, B * self.seq_len, self.top_k, dtype=torch.int32, device=eng.device)
 
     def _account_chunk(self, ent, ml, n: int, B: int) -> None:
-        """After a replay of a captured chunk of n evaluations: ``_last_topk`` (level j of every layer at [:, j]) and the expert-usage counters,
-        with device ops only - token routing: ONE histogram of the chunk's decisions; otherwise the dispatch records' per-expert counts."""
+        """After a run of a chunk of n evaluations: ``_last_topk`` (level j of every layer at [:, j]) and the expert-usage counters, with device
+        ops only - token routing: ONE histogram of the chunk's decisions; otherwise the dispatch records' per-expert counts."""
         N = B * self.seq_len
         if ent.get("tok") is not None:
             self._last_topk = ent["tok"].transpose(0, 1)                 # [L, n, N, k]
             self._account_token_usage(self._last_topk, N * n)
         elif self.use_goal_in_routing:
             self._last_topk = ent["route"]["idx"].view(self.num_layers, n, B, self.top_k)
-            self._account_ddim_usage(ent["route"], ml, n, N)
+            self._account_usage(ent["route"]["meta"], ml, N, n)
         else:
             self._last_topk = ent["sched"]["idx"]
-            self._account_ddim_usage(ent["sched"], ml, n, N)
+            self._account_usage(ent["sched"]["meta"], ml, N, n)
 
-    def _account_ddim_usage(self, sched, ml, n, n_tokens):
-        """Expert-usage counters of a whole DDIM run (modedit.py:568-572, 594): one device-side add per chunk, outside the graph."""
-        Ly, E = self.num_layers, self.num_experts
-        counts = sched["meta"][:, ml.counts: ml.counts + E].view(Ly, n, E).sum(1)
-        if getattr(self, "_usage_dev", None) is None or self._usage_dev.device != counts.device:
-            self._usage_dev = torch.zeros(Ly, E, dtype=torch.int64, device=counts.device)
-        self._usage_dev += counts
-        for blk in self.blocks:
-            blk.total_tokens_processed += n_tokens * n
-
-    @torch.no_grad()
-    def sample_ddim_fused(self, states, action, goals, sigmas, sigma_data: float, solver: str = "ddim"):
-        """sample_ddim (gc_sampling.py:922-951) o GCDenoiser o MoDeDiT as one hipGraph replay.  The graph holds only what depends on the
-        observations (embeddings + the denoiser forwards); sigma embeddings, routing, dispatch and the EDM scalings of the schedule live in a
-        schedule state that is rebuilt only when the sigma VALUES, the weights or the batch size change.
-        ``solver="dpmpp_2m"``: sample_dpmpp_2m (gc_sampling.py:700-734) on the same chain - its step is DDIM's exponential-integrator step applied to a
-        two-point extrapolation of the denoised prediction, which the head kernel forms from the previous step's prediction (ModeHeadDesc.den_prev)."""
-        assert solver in ("ddim", "dpmpp_2m"), solver
-        import os
-        eng = self.engine
-        dev, B = eng.device, action.shape[0]
-        if B == 0:                                                       # empty batch: nothing to denoise
-            return action.detach().to(device=dev, dtype=torch.float32).clone()
-        img, goals = self._prep_obs(eng, states, goals)
-        sig = sigmas.detach().to(device=dev, dtype=torch.float32).contiguous()
-        x0 = action.detach().to(device=dev, dtype=torch.float32)
-        self._check_batch(B, img, goals, x0)
-        n = sig.numel() - 1
-        use_graph = os.environ.get("MODE_HIP_GRAPH", "1") != "0"
-        if self._routes_per_chunk() and not use_graph:                 # goal / token routing without graphs: the per-step generic path
-            x = x0.clone()
-            prev = None
-            for i in range(n):
-                den = self.denoise({"state_images": img}, x, goals, sig[i].reshape(1), sigma_data)
-                r = sig[i + 1] / sig[i]
-                dd = den
-                if solver == "dpmpp_2m" and prev is not None and float(sig[i + 1]) > 0:
-                    c = 1.0 / (2.0 * ((sig[i - 1].log() - sig[i].log()) / (sig[i].log() - sig[i + 1].log())))
-                    dd = (1.0 + c) * den - c * prev
-                x = r * x + (1.0 - r) * dd
-                prev = den
-            return x
-        multi = solver != "ddim"
-        if not use_graph:
-            x = x0.clone().contiguous()
-            sched = self._schedule_state(eng, sig, B, sigma_data, solver=solver)
-            ml = self._ddim_steps(eng, img, goals, x, sched, n, den=torch.empty((2,) + tuple(x.shape), dtype=torch.float32, device=dev) if multi else None)
-            self._last_topk = sched["idx"]
-            self._account_ddim_usage(sched, ml, n, B * self.seq_len)
-            return x
-        key = (B, sig.numel(), eng.compute_dtype, eng._structs_for, str(dev), float(sigma_data), self._routing_mode())   # arena pointers are static: weight updates keep graphs valid
-        gkey = "graph" if not multi else "graph:" + solver                  # one captured chain per solver
-        ent = self._route_cache.get(gkey)
-        # identity of the schedule: a host-side tag of its VALUES when the tensor came from a get_sigmas_* / get_noise_schedule generator (the
-        # agent builds a fresh tensor per chunk, mode_agent.py:752) - else the caller's tensor OBJECT (kept alive below, so neither its id nor its
-        # storage can be recycled while the key is live) -, the weights, and the routing cache generation.  No device read on either path.
-        # A tag only vouches for the values the generator wrote: once the tensor has been edited in place (its version moved past the one recorded in
-        # the tag) two tagged tensors with different edits would share (tag, version) - such a tensor is identified as an object, with the device
-        # compare below as the fallback, like any untagged tensor.
-        tag = getattr(sigmas, "_mode_sched", None)
-        if tag is not None and sigmas._version != tag[3]:
-            tag = None
-        sid = ("tag", tag) if tag is not None else ("obj", id(sigmas), sigmas._version)
-        sched_key = (sid, eng._wkey, getattr(self, "_fused_gen", 0))
-        if ent is None or ent["key"] != key:
-            st = dict(key=key, img=img.clone(), goals=goals.clone(), x=x0.clone().contiguous(), sig=sig.clone())
-            # the graph owns its workspace: the engine's shared scratch buffer is re-allocated whenever a larger chain (a training step, a
-            # bigger batch) asks for more, and a replay would then read freed memory
-            st["ws"] = self._chunk_ws(eng, B, n)
-            st["den"] = torch.zeros((2,) + tuple(x0.shape), dtype=torch.float32, device=dev) if multi else None
-            st["tok"], st["route"] = self._chunk_topk_buffer(eng, n, B), {}
-            with eng.pinned_workspace(st["ws"]):
-                st["sched"] = self._schedule_state(eng, st["sig"], B, sigma_data, solver=solver)
-                side = torch.cuda.Stream(device=dev)
-                side.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(side):                            # warm-up: loads code objects
-                    self._ddim_steps(eng, st["img"], st["goals"], st["x"], st["sched"], n, den=st["den"], tok=st["tok"])
-                torch.cuda.current_stream(dev).wait_stream(side)
-                g = torch.cuda.CUDAGraph()
-                with capture_graph(g):
-                    st["ml"] = self._ddim_steps(eng, st["img"], st["goals"], st["x"], st["sched"], n, den=st["den"], tok=st["tok"], route_out=st["route"])
-            st["graph"], st["sched_key"] = g, sched_key
-            st["sig_ref"] = sigmas if tag is None else None
-            self._route_cache[gkey] = ent = st
-        elif ent["sched_key"] != sched_key:
-            # an UNTAGGED foreign tensor object that may carry the same values: one small device compare (host sync) - the rare path; tagged
-            # schedules and a reused tensor object never get here with an unchanged schedule
-            same_values = (tag is None and ent["sched_key"][1:] == sched_key[1:] and bool(torch.equal(sig, ent["sig"])))
-            ent["sig_ref"] = sigmas if tag is None else None
-            if not same_values:
-                ent["sig"].copy_(sig)
-                with eng.pinned_workspace(ent["ws"]):
-                    self._schedule_state(eng, ent["sig"], B, sigma_data, out=ent["sched"], solver=solver)
-            ent["sched_key"] = sched_key
-        ent["img"].copy_(img); ent["goals"].copy_(goals); ent["x"].copy_(x0)
-        ent["graph"].replay()
-        self._account_chunk(ent, ent["ml"], n, B)
-        return ent["x"].clone()
-
-    def _account_token_usage(self, idx, n_tokens):
-        """Expert-usage counters under token routing: idx int32 [L, N, k] -> per-layer histogram, kept on the device like ``_account_usage``."""
-        Ly, E = self.num_layers, self.num_experts
-        counts = torch.zeros(Ly, E, dtype=torch.int64, device=idx.device).scatter_add_(1, idx.reshape(Ly, -1).long(), torch.ones(Ly, idx[0].numel(), dtype=torch.int64, device=idx.device))
-        if getattr(self, "_usage_dev", None) is None or self._usage_dev.device != counts.device:
-            self._usage_dev = torch.zeros(Ly, E, dtype=torch.int64, device=counts.device)
-        self._usage_dev += counts
-        for blk in self.blocks:
-            blk.total_tokens_processed += n_tokens
-
-    def _account_usage(self, meta, ml, n_tokens):
-        """Expert-usage counters (modedit.py:568-572, 594) kept on-device; no host sync on the hot path."""
-        counts = meta[:, ml.counts: ml.counts + self.num_experts]
+    def _add_usage(self, counts, n_tokens: int) -> None:
+        """Expert-usage counters (modedit.py:568-572, 594): ``counts`` [L, E] added on the device - no host sync on the hot path - and
+        ``n_tokens`` to every block's token count."""
         if getattr(self, "_usage_dev", None) is None or self._usage_dev.device != counts.device:
             self._usage_dev = torch.zeros(self.num_layers, self.num_experts, dtype=torch.int64, device=counts.device)
         self._usage_dev += counts
         for blk in self.blocks:
             blk.total_tokens_processed += n_tokens
 
+    def _account_usage(self, meta, ml, n_tokens: int, n: int = 1) -> None:
+        """Usage counters from dispatch records: ``meta`` [L·n, words], n forwards of n_tokens tokens each per layer (layer-major)."""
+        counts = meta[:, ml.counts: ml.counts + self.num_experts]
+        self._add_usage(counts if n == 1 else counts.reshape(self.num_layers, n, -1).sum(1), n_tokens * n)
+
+    def _account_token_usage(self, idx, n_tokens: int) -> None:
+        """Usage counters under token routing: idx int32 [L, ..., k] (every token's experts) -> per-layer histogram."""
+        Ly, E = self.num_layers, self.num_experts
+        self._add_usage(torch.zeros(Ly, E, dtype=torch.int64, device=idx.device).scatter_add_(
+            1, idx.reshape(Ly, -1).long(), torch.ones(Ly, idx[0].numel(), dtype=torch.int64, device=idx.device)), n_tokens)
     def sync_expert_usage(self):
         """Fold the device-side counters into the per-block host tensors the agent's heat-map reads (mode_agent.py:466-511)."""
         if getattr(self, "_usage_dev", None) is not None:

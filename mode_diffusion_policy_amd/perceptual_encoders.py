@@ -1146,7 +1146,7 @@ class GraphedVisualEncoder:
     @torch.no_grad()
     def __call__(self, rgb_static: torch.Tensor, rgb_gripper: torch.Tensor, latent_goal: Optional[torch.Tensor] = None):
         import os
-        from .engine import capture_graph
+        from .engine import warm_and_capture
         if self.static_resnet.training or self.gripper_resnet.training or rgb_static.device.type != "cuda" or os.environ.get("MODE_HIP_GRAPH", "1") == "0":
             return {"state_images": self._eager(rgb_static, rgb_gripper, latent_goal)}       # batch statistics / no device: nothing to replay
         wdt = self.autocast_dtype if self.autocast_dtype is not None else rgb_static.dtype
@@ -1157,25 +1157,15 @@ class GraphedVisualEncoder:
             if len(self._graphs) >= self.max_graphs:
                 self._graphs.pop(next(iter(self._graphs)))
             ent = dict(s=rgb_static.clone(), g=rgb_gripper.clone(), c=None if latent_goal is None else latent_goal.clone())
-            dev = rgb_static.device
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
             global _W_OVERRIDE
             saved, _W_OVERRIDE = _W_OVERRIDE, self._weights(wdt)
             saved_sink, _TABLES.sink = _TABLES.sink, []                          # every index table the warm-up / capture touches: pinned next to the graph
             ent["tables"] = _TABLES.sink
-            try:
-                with torch.cuda.stream(side):                                    # outside the capture: MIOpen's algorithm search, code-object loads
-                    for _ in range(2):
-                        self._eager(ent["s"], ent["g"], ent["c"])
-                torch.cuda.current_stream(dev).wait_stream(side)
-                graph = torch.cuda.CUDAGraph()
-                with capture_graph(graph):
-                    ent["out"] = self._eager(ent["s"], ent["g"], ent["c"])
+            try:                                                                 # two warm-ups: MIOpen's algorithm search, code-object loads
+                ent["graph"], ent["out"] = warm_and_capture(lambda: self._eager(ent["s"], ent["g"], ent["c"]), rgb_static.device, warmups=2)
             finally:
                 _W_OVERRIDE = saved
                 _TABLES.sink = saved_sink
-            ent["graph"] = graph
             self._graphs[key] = ent
         self._weights(wdt)                                                       # weights whose version moved since the last call: re-cast in place
         ent["s"].copy_(rgb_static); ent["g"].copy_(rgb_gripper)

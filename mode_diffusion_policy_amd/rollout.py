@@ -139,8 +139,7 @@ class ChunkedRolloutPolicy:
             self.need_precompute_experts_for_inference = False
         sigmas = self._schedule(dev)
         x = torch.randn((len(latent_goal), self.act_window_size, self.action_dim), device=dev, generator=self.generator) * self.sigma_max
-        graphable = _GRAPHABLE_SAMPLERS + (("heun", "dpm", "dpmpp_2s") if os.environ.get("MODE_TWO_STAGE_FUSED", "1") == "0" else ())
-        if self.sampler_type in graphable and not extra_args:
+        if self.sampler_type in _GRAPHABLE_SAMPLERS and not extra_args:
             out = self._sample_graphed(sigmas, x, perceptual_emb, latent_goal)
             if out is not None:
                 return out
@@ -153,9 +152,8 @@ class ChunkedRolloutPolicy:
         comes from torch's default generator, which hipGraph capture advances per replay.  Goal and token routing are captured too: every denoiser call
         of the chunk routes its own samples / tokens inside the graph.  None = not applicable (training mode, MODE_HIP_GRAPH=0): the caller takes the
         step-by-step path."""
-        import os
         from . import samplers as S
-        from .engine import capture_graph
+        from .engine import warm_and_capture
         from .modedit import MoDeDiT
         den = self.model
         inner = getattr(den, "inner_model", None)
@@ -187,25 +185,17 @@ class ChunkedRolloutPolicy:
                     return out, cc["metas"]
                 finally:
                     S._set_chunk_capture(None)
-            with eng.pinned_workspace(ent["ws"]):
-                side = torch.cuda.Stream(device=dev)
-                side.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(side):                                # warm-up outside the capture (code objects, the schedule's host-side reads)
-                    chunk()
-                torch.cuda.current_stream(dev).wait_stream(side)
-                graph = torch.cuda.CUDAGraph()
-                with capture_graph(graph):
-                    ent["out"], ent["metas"] = chunk()
-            ent["graph"] = graph
+            with eng.pinned_workspace(ent["ws"]):                            # (the warm-up also does the schedule's host-side reads)
+                ent["graph"], (ent["out"], ent["metas"]) = warm_and_capture(chunk, dev)
             cache[key] = ent
         ent["x"].copy_(x); ent["img"].copy_(img); ent["goals"].copy_(gl)
         ent["graph"].replay()
-        ml = eng.meta_layout(B * inner.seq_len)
-        if not inner.cond_router:                                             # token routing: one histogram of every call's decisions
-            inner._account_token_usage(torch.stack(ent["metas"], 1), B * inner.seq_len * len(ent["metas"]))
+        # expert-usage counters of every denoiser call, as the step-by-step path keeps them: [L, calls, ...]
+        N, calls, rec = B * inner.seq_len, len(ent["metas"]), torch.stack(ent["metas"], 1)
+        if not inner.cond_router:
+            inner._account_token_usage(rec, N * calls)                        # token routing: one histogram of every call's decisions
         else:
-            for meta in ent["metas"]:                                         # expert-usage counters, as the step-by-step path keeps them
-                inner._account_usage(meta, ml, B * inner.seq_len)
+            inner._account_usage(rec.flatten(0, 1), eng.meta_layout(N), N, calls)
         return ent["out"].clone()
 
     @torch.no_grad()

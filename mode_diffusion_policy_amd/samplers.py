@@ -238,9 +238,6 @@ def sample_euler_ancestral(model, state, action, goal, sigmas, scaler=None, extr
 def _two_stage_fused(model, state, action, goal, sigmas, solver, draws: bool):
     """The fused route of the deterministic two-stage solvers (GCDenoiser.two_stage_fused); ``draws``: the reference draws ``eps = randn_like(action)``
     on every step of this sampler, churn or not - made and discarded here too, so the generator leaves the call as the reference leaves it."""
-    import os
-    if os.environ.get("MODE_TWO_STAGE_FUSED", "1") == "0":               # A/B runs: the step loop (captured whole by the rollout policy, as before)
-        return None
     fused = getattr(model, "two_stage_fused", None)
     out = fused(state, action, goal, sigmas, solver) if fused is not None else None
     if out is not None and draws:

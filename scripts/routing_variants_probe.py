@@ -45,10 +45,9 @@ def captured_chain(den, img, goal, x0, sig):
     m = den.inner_model
     ent = m._route_cache["graph"]
     eng = m.engine
-    n = sig.numel() - 1
-    x = ent["x"].clone()
+    bufs = [ent["bufs"][0].clone()] + ent["bufs"][1:]                # (plain DDIM never touches buffers 1 and 2)
     with eng.pinned_workspace(ent["ws"]):
-        m._ddim_steps(eng, ent["img"], ent["goals"], x, ent["sched"], n, tok=ent["tok"], route_out={})
+        m._chunk_steps(eng, ent["img"], ent["goals"], bufs, ent["sched"], ent["evals"], tok=ent["tok"])
 
 
 def main():
