@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MODE_HIP_ABI_VERSION 12
+#define MODE_HIP_ABI_VERSION 13
 
 typedef enum ModeStatus {
   MODE_OK = 0,
@@ -785,6 +785,58 @@ int mode_stem_conv_wgrad(const ModeStemConvDesc* d, void* stream);
  * order, no atomics). */
 int mode_maxpool_nhwc_fwd(const void* x, int dtype, int N, int H, int W, int C, int k, int s, int pad, void* y, uint8_t* argmax, void* stream);
 int mode_maxpool_nhwc_bwd(const void* dy, const uint8_t* argmax, int dtype, int N, int H, int W, int C, int k, int s, int pad, void* dx, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * (ABI 13) Per-environment replanning of a vectorised rollout (csrc/env_pool.hip; rollout.VectorEnvPolicy).  A pool of num_envs environments
+ * keeps, per environment b, a plan [W, A] (W = act_window_size planned actions of width A), the index of the plan row it emits next
+ * (counter[b]) and the draw index of its own noise stream (draws[b]).  On a control step the m environments that replan run ONE sampler
+ * chunk at a bucket batch of m_b >= m rows; the rows of the chunk are listed by environment index, padded to m_b by repeating the last real
+ * environment.
+ *
+ * Noise stream.  The initial latent of an environment's replan with stream seed s and draw index d is, for element e of the row-major [W, A]
+ * chunk (lowbias32 = hash_u32 of csrc/mode_common.h, k = mode_stream_seed(s, d) of the same file):
+ *   u1 = ((lowbias32(k ^ 2e) >> 8) + 1) * 2^-24                     in (0, 1]
+ *   u2 = (lowbias32(k ^ (2e + 1)) >> 8) * 2^-24                     in [0, 1)
+ *   z  = sqrt(-2 ln u1) * cos(2 pi u2)                              (Box-Muller; the cosine is evaluated as cospi(2 u2), fp32)
+ *   x0[e] = sigma_max * z
+ * A function of (s, d, e) only: an environment's noise does not depend on which others replan with it or on the bucket size.
+ *
+ * Control block (int32 words, device), written once per replanning step and read by both entry points:
+ *   [0] m       real rows: the first m entries of `rows` are distinct environments
+ *   [1]         reserved (0)
+ *   [2], [3]    device address of this step's [num_envs, A] fp32 action output, low word first
+ *   [4, 4 + NW)                 active bitmask, NW = ceil(num_envs / 32): bit b % 32 of word b / 32 = environment b is active
+ *   [4 + NW, 4 + NW + num_envs) rows
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define MODE_ENV_MAX 1024
+
+/* Gather + initial noise of a chunk (one launch): for j < m_b, r = rows[j] (entries outside [0, num_envs) leave row j untouched):
+ *   img_out[j]  = state_images[r]   (img_floats fp32 each; skipped when state_images or img_out is NULL)
+ *   goal_out[j] = goals[r]          (goal_floats fp32 each; skipped when goals or goal_out is NULL)
+ *   x0[j][e]    = sigma_max * z(seeds[r], draws[r], e), e < noise_floats (= W * A)
+ * seeds / draws [num_envs] uint32.  Reads nothing of the environments that are not listed. */
+int mode_env_gather_noise(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
+                          const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
+                          float* img_out, float* goal_out, float* x0, int noise_floats, float sigma_max, void* stream);
+
+typedef struct ModeEnvPoolDesc {
+  int32_t num_envs;                      /* 1..MODE_ENV_MAX */
+  int32_t W, A;                          /* planned rows per environment and action width; W * A <= 4096 */
+  int32_t multistep;                     /* 1..W: a plan serves this many active steps */
+  const int32_t* ctrl;                   /* the control block above, or NULL: a step without replans, described by `out` and `active` */
+  const float* chunk;                    /* [m_b, W, A] the chunk's result (ctrl != NULL), row j planned for environment rows[j] */
+  float* plan;                           /* [num_envs, W, A] */
+  int32_t* counter;                      /* [num_envs] */
+  uint32_t* draws;                       /* [num_envs] */
+  float* out;                            /* ctrl == NULL: [num_envs, A] action output */
+  uint32_t active[MODE_ENV_MAX / 32];    /* ctrl == NULL: active bitmask, as in the control block */
+} ModeEnvPoolDesc;
+
+/* Commit + emit of a control step (one launch): for j < m the planned rows chunk[j] become plan[rows[j]], that environment's counter is set
+ * to 0 and its draw index advances by one; then every active environment b writes out[b] = plan[b][counter[b]] and advances
+ * counter[b] = (counter[b] + 1) % multistep, every inactive one writes a zero row and keeps its counter.  With ctrl == NULL (m = 0) this
+ * is the whole control step of the environments that do not replan. */
+int mode_env_commit_emit(const ModeEnvPoolDesc* d, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("MODE_HIP_LIB", os.path.join(_HERE, "libmode_hip.so"))
 
 MODE_BF16, MODE_F32 = 0, 1
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_RESIDUAL, EPI_SWIGLU, EPI_RESIDUAL_NORM = 0, 1, 2, 3, 4, 5
-ABI_VERSION = 12
+ABI_VERSION = 13
 GEMM_SKINNY_OK, GEMM_W_KN, GEMM_A_KM, GEMM_UNIFORM_GROUPS, GEMM_SMALL_ROWS, GEMM_IDENTITY_ROWS = 1, 2, 4, 8, 16, 32
 
 c_i32, c_i64, c_f32, c_vp, c_sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
@@ -152,6 +152,15 @@ class ModeStemConvDesc(C.Structure):
                 ("dw_part", c_vp)]
 
 
+MODE_ENV_MAX = 1024
+
+
+class ModeEnvPoolDesc(C.Structure):
+    """Commit + emit of a vectorised rollout's control step (include/mode_hip.h, ABI 13)."""
+    _fields_ = [("num_envs", c_i32), ("W", c_i32), ("A", c_i32), ("multistep", c_i32), ("ctrl", c_vp), ("chunk", c_vp), ("plan", c_vp),
+                ("counter", c_vp), ("draws", c_vp), ("out", c_vp), ("active", c_u32 * (MODE_ENV_MAX // 32))]
+
+
 P = C.POINTER
 # name -> (restype, argtypes): every symbol include/mode_hip.h declares
 PROTOTYPES = {
@@ -235,6 +244,8 @@ PROTOTYPES = {
     "mode_stem_conv_wgrad": (C.c_int, [P(ModeStemConvDesc), c_vp]),
     "mode_maxpool_nhwc_fwd": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mode_maxpool_nhwc_bwd": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "mode_env_gather_noise": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp]),
+    "mode_env_commit_emit": (C.c_int, [P(ModeEnvPoolDesc), c_vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,0 +1,105 @@
+// Per-environment replanning of a vectorised rollout (include/mode_hip.h, ABI 13; rollout.VectorEnvPolicy): the gather of the replanning
+// environments' observations with their initial noise into a chunk's input buffers, and the commit of the chunk's plans + the emission of one
+// action per active environment.  Both move a few hundred KB at most: one launch each, plain coalesced loops, no LDS.
+#include "mode_common.h"
+
+namespace mode {
+
+// Box-Muller sample of the environment noise stream (the formula of include/mode_hip.h): element e of the draw keyed by k = mode_stream_seed(seed, draw)
+__device__ __forceinline__ float env_normal(uint32_t k, uint32_t e) {
+  const float u1 = (float)((hash_u32(k ^ (2u * e)) >> 8) + 1u) * 0x1p-24f;      // (0, 1]: exact in fp32
+  const float u2 = (float)(hash_u32(k ^ (2u * e + 1u)) >> 8) * 0x1p-24f;        // [0, 1)
+  return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);                            // cospi: no rounding of 2 pi u2 before the cosine
+}
+
+__global__ __launch_bounds__(256) void env_gather_noise_kernel(const int32_t* __restrict__ rows, int num_envs, const uint32_t* __restrict__ seeds,
+                                                               const uint32_t* __restrict__ draws, const float* __restrict__ img, long img_floats,
+                                                               const float* __restrict__ goals, long goal_floats, float* __restrict__ img_out,
+                                                               float* __restrict__ goal_out, float* __restrict__ x0, int noise_floats, float sigma_max) {
+  const int j = blockIdx.x;
+  const int r = rows[j];
+  if (r < 0 || r >= num_envs) return;
+  if (img && img_out) {
+    const float* src = img + (long)r * img_floats;
+    float* dst = img_out + (long)j * img_floats;
+    for (long i = threadIdx.x; i < img_floats; i += 256) dst[i] = src[i];
+  }
+  if (goals && goal_out) {
+    const float* src = goals + (long)r * goal_floats;
+    float* dst = goal_out + (long)j * goal_floats;
+    for (long i = threadIdx.x; i < goal_floats; i += 256) dst[i] = src[i];
+  }
+  const uint32_t k = mode_stream_seed(seeds[r], draws[r]);
+  float* dst = x0 + (long)j * noise_floats;
+  for (int e = threadIdx.x; e < noise_floats; e += 256) dst[e] = sigma_max * env_normal(k, (uint32_t)e);
+}
+
+// One wave per environment b: find b among the chunk's m real rows (rows are distinct), commit that row, then emit.  The emitted row of a
+// just-committed plan is read from the chunk itself (counter 0), so no thread reads plan memory another thread of this launch wrote.
+__global__ __launch_bounds__(64) void env_commit_emit_kernel(ModeEnvPoolDesc d) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int NW = (d.num_envs + 31) >> 5;
+  const int32_t* ctrl = d.ctrl;
+  int m = 0;
+  uint32_t act_word;
+  float* out;
+  if (ctrl) {
+    m = min(max(ctrl[0], 0), d.num_envs);
+    out = reinterpret_cast<float*>((uint64_t)(uint32_t)ctrl[2] | ((uint64_t)(uint32_t)ctrl[3] << 32));
+    act_word = (uint32_t)ctrl[4 + (b >> 5)];
+  } else {
+    out = d.out;
+    act_word = d.active[b >> 5];
+  }
+  const bool active = (act_word >> (b & 31)) & 1u;
+  const int32_t* rows = ctrl ? ctrl + 4 + NW : nullptr;
+  int j = -1;
+  for (int i = lane; i < m; i += 64)
+    if (rows[i] == b) j = i;
+  // every lane learns the (unique) row: the largest index found by any lane
+  for (int o = 32; o > 0; o >>= 1) j = max(j, __shfl_xor(j, o, 64));
+  const int WA = d.W * d.A;
+  float* plan = d.plan + (long)b * WA;
+  int c;
+  if (j >= 0) {
+    const float* src = d.chunk + (long)j * WA;
+    for (int i = lane; i < WA; i += 64) plan[i] = src[i];
+    c = 0;
+  } else {
+    c = min(max(d.counter[b], 0), d.W - 1);
+  }
+  if (lane < d.A) {
+    float v = 0.f;
+    if (active) v = j >= 0 ? d.chunk[(long)j * WA + lane] : plan[(long)c * d.A + lane];
+    out[(long)b * d.A + lane] = v;
+  }
+  if (lane == 0) {
+    if (j >= 0) d.draws[b] += 1u;
+    if (active) d.counter[b] = (c + 1) % d.multistep;
+    else if (j >= 0) d.counter[b] = 0;
+  }
+}
+
+}  // namespace mode
+
+using namespace mode;
+
+extern "C" int mode_env_gather_noise(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
+                                     const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
+                                     float* img_out, float* goal_out, float* x0, int noise_floats, float sigma_max, void* stream) {
+  if (!rows || !seeds || !draws || !x0 || m_b <= 0 || num_envs <= 0 || noise_floats <= 0 || img_floats < 0 || goal_floats < 0) return MODE_ERR_BAD_ARG;
+  hipLaunchKernelGGL(env_gather_noise_kernel, dim3(m_b), dim3(256), 0, (hipStream_t)stream, rows, num_envs, seeds, draws, state_images, (long)img_floats,
+                     goals, (long)goal_floats, img_out, goal_out, x0, noise_floats, sigma_max);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
+extern "C" int mode_env_commit_emit(const ModeEnvPoolDesc* d, void* stream) {
+  if (!d || d->num_envs <= 0 || d->num_envs > MODE_ENV_MAX || d->W <= 0 || d->A <= 0 || d->A > 64 || d->W * d->A > 4096 || d->multistep <= 0 ||
+      d->multistep > d->W || !d->plan || !d->counter || !d->draws)
+    return MODE_ERR_BAD_ARG;
+  if (d->ctrl ? !d->chunk : !d->out) return MODE_ERR_BAD_ARG;
+  hipLaunchKernelGGL(env_commit_emit_kernel, dim3(d->num_envs), dim3(64), 0, (hipStream_t)stream, *d);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}

@@ -547,13 +547,21 @@ class MoDeDiT(nn.Module):
         eng = self.engine
         if action.shape[0] == 0 or os.environ.get("MODE_HIP_GRAPH", "1") == "0" or sigmas.numel() < 2:
             return None
+        return self._sample_chunk(eng, *self._chunk_plan(eng, solver, sigmas.numel() - 1), states, action, goals, sigmas, sigma_data)
+
+    def _chunk_plan(self, eng, solver: str, n: int):
+        """(graph key, plan) of a fused sampler over an n-step schedule for ``_sample_chunk``: "ddim" / "dpmpp_2m" (the one-evaluation-per-step
+        chain) or "heun" / "dpm_2" / "dpmpp_2s" (two-stage solvers)."""
+        if solver in ("ddim", "dpmpp_2m"):
+            multi = solver != "ddim"
+            return ("graph:" + solver if multi else "graph"), (lambda sig: (self._ddim_evals(n, multi), sig, dict(solver=solver)))
 
         def plan(sig):
             p = self._two_stage_plan(solver, [float(v) for v in sig.tolist()])          # (host sync: only when the schedule changed)
             evals = [(xin, xout, dout, None, a1, a2, True) for _, xin, xout, _, a1, a2, dout in p]
             ev = torch.tensor([e[0] for e in p], dtype=torch.float32, device=eng.device)
             return evals, ev, dict(lin=torch.tensor([e[3] for e in p], dtype=torch.float32))
-        return self._sample_chunk(eng, "graph:" + solver, states, action, goals, sigmas, sigma_data, plan)
+        return "graph:" + solver, plan
 
     @torch.no_grad()
     def sample_ddim_fused(self, states, action, goals, sigmas, sigma_data: float, solver: str = "ddim"):
@@ -570,8 +578,7 @@ class MoDeDiT(nn.Module):
             return action.detach().to(device=dev, dtype=torch.float32).clone()
         n, multi = sigmas.numel() - 1, solver != "ddim"
         if os.environ.get("MODE_HIP_GRAPH", "1") != "0":               # one captured chain per solver; its buffer pattern is fixed by n
-            return self._sample_chunk(eng, "graph:" + solver if multi else "graph", states, action, goals, sigmas, sigma_data,
-                                      lambda sig: (self._ddim_evals(n, multi), sig, dict(solver=solver)))
+            return self._sample_chunk(eng, *self._chunk_plan(eng, solver, n), states, action, goals, sigmas, sigma_data)
         img, goals = self._prep_obs(eng, states, goals)
         sig = sigmas.detach().to(device=dev, dtype=torch.float32).contiguous()
         x0 = action.detach().to(device=dev, dtype=torch.float32)
@@ -594,11 +601,17 @@ class MoDeDiT(nn.Module):
         self._account_chunk(dict(sched=sched), self._chunk_steps(eng, img, goals, bufs, sched, self._ddim_evals(n, multi))[0], n, B)
         return bufs[0]
 
-    def _sample_chunk(self, eng, gkey, states, action, goals, sigmas, sigma_data: float, plan):
+    def _sample_chunk(self, eng, gkey, plan, states, action, goals, sigmas, sigma_data: float, hooks=None, rows: Optional[int] = None):
         """The fused samplers' hipGraph path: the launch chain of ``_chunk_steps`` captured once per ``_route_cache[gkey]`` entry (one per solver)
         and replayed per call.  ``plan(sig) -> (evaluations, sigma of the schedule state, its keyword arguments)`` is asked for when the entry is
         made and when the schedule changes; a new schedule is then written into the schedule state in place (the graph has its pointers baked
-        in), unless its evaluations take another pattern of buffers, which needs another chain."""
+        in), unless its evaluations take another pattern of buffers, which needs another chain.
+
+        ``hooks`` (rollout.VectorEnvPolicy): the caller's own store and device-side stages instead of the input copies and the returned clone -
+        entries live in ``hooks.store[(gkey, B)]``, one per batch size; ``hooks.prologue(ent)`` writes the entry's inputs (img, goals, bufs[0])
+        before every replay (and once before the capture's warm-up, which must route valid data); ``hooks.epilogue(ent, capturing)`` is
+        captured at the end of the chain and reads its result, bufs[0].  The inputs then only give the shapes; returns None.  ``rows``: the
+        first ``rows`` samples are real, the rest padding - the expert-usage counters count the real ones only."""
         dev, B = eng.device, action.shape[0]
         img, goals = self._prep_obs(eng, states, goals)
         sig = sigmas.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -616,7 +629,8 @@ class MoDeDiT(nn.Module):
             tag = None
         sid = ("tag", tag) if tag is not None else ("obj", id(sigmas), sigmas._version)
         sched_key = (sid, eng._wkey, getattr(self, "_fused_gen", 0))
-        ent = self._route_cache.get(gkey)
+        cache, ckey = (self._route_cache, gkey) if hooks is None else (hooks.store, (gkey, B))
+        ent = cache.get(ckey)
         fresh, planned = ent is None or ent["key"] != key, None
         if not fresh and ent["sched_key"] != sched_key:
             # an UNTAGGED foreign tensor object that may carry the same values: one small device compare (host sync) - the rare path; tagged
@@ -642,15 +656,25 @@ class MoDeDiT(nn.Module):
             # bigger batch) asks for more, and a replay would then read freed memory
             ent["ws"] = self._chunk_ws(eng, B, n)
             ent["tok"] = self._chunk_topk_buffer(eng, n, B)
+
+            def chain():
+                out = self._chunk_steps(eng, ent["img"], ent["goals"], ent["bufs"], ent["sched"], evals, tok=ent["tok"])
+                if hooks is not None:
+                    hooks.epilogue(ent, torch.cuda.is_current_stream_capturing())
+                return out
             with eng.pinned_workspace(ent["ws"]):
                 ent["sched"] = self._schedule_state(eng, s_sig, B, sigma_data, **s_kw)
-                ent["graph"], (ent["ml"], ent["route"]) = warm_and_capture(
-                    lambda: self._chunk_steps(eng, ent["img"], ent["goals"], ent["bufs"], ent["sched"], evals, tok=ent["tok"]), dev)
-            self._route_cache[gkey] = ent
-        ent["img"].copy_(img); ent["goals"].copy_(goals); ent["bufs"][0].copy_(x0)
+                if hooks is not None:
+                    hooks.prologue(ent)
+                ent["graph"], (ent["ml"], ent["route"]) = warm_and_capture(chain, dev)
+            cache[ckey] = ent
+        if hooks is None:
+            ent["img"].copy_(img); ent["goals"].copy_(goals); ent["bufs"][0].copy_(x0)
+        else:
+            hooks.prologue(ent)
         ent["graph"].replay()
-        self._account_chunk(ent, ent["ml"], len(ent["evals"]), B)
-        return ent["bufs"][0].clone()
+        self._account_chunk(ent, ent["ml"], len(ent["evals"]), B, rows)
+        return ent["bufs"][0].clone() if hooks is None else None
 
     def _chunk_ws(self, eng, B: int, n: int) -> torch.Tensor:
         """The workspace a captured chunk of n evaluations owns: the forward's, or the schedule's sigma embedding / the router's over n rows
@@ -664,19 +688,25 @@ class MoDeDiT(nn.Module):
             return None
         return torch.empty(n, self.num_layers, B * self.seq_len, self.top_k, dtype=torch.int32, device=eng.device)
 
-    def _account_chunk(self, ent, ml, n: int, B: int) -> None:
+    def _account_chunk(self, ent, ml, n: int, B: int, rows: Optional[int] = None) -> None:
         """After a run of a chunk of n evaluations: ``_last_topk`` (level j of every layer at [:, j]) and the expert-usage counters, with device
-        ops only - token routing: ONE histogram of the chunk's decisions; otherwise the dispatch records' per-expert counts."""
-        N = B * self.seq_len
+        ops only - token routing: ONE histogram of the chunk's decisions; otherwise the dispatch records' per-expert counts.  ``rows`` < B: only
+        the first ``rows`` samples are counted - token / goal routing: a histogram of their decisions (a goal-routed decision stands for the
+        sample's T tokens); noise-level routing sends every sample to the same experts, so the counts scale by rows / B exactly."""
+        T = self.seq_len
+        N, r = B * T, B if rows is None else rows
         if ent.get("tok") is not None:
             self._last_topk = ent["tok"].transpose(0, 1)                 # [L, n, N, k]
-            self._account_token_usage(self._last_topk, N * n)
+            self._account_token_usage(self._last_topk if r == B else self._last_topk[:, :, :r * T], r * T * n)
         elif self.use_goal_in_routing:
             self._last_topk = ent["route"]["idx"].view(self.num_layers, n, B, self.top_k)
-            self._account_usage(ent["route"]["meta"], ml, N, n)
+            if r == B:
+                self._account_usage(ent["route"]["meta"], ml, N, n)
+            else:
+                self._account_token_usage(self._last_topk[:, :, :r], r * T * n, weight=T)
         else:
             self._last_topk = ent["sched"]["idx"]
-            self._account_usage(ent["sched"]["meta"], ml, N, n)
+            self._account_usage(ent["sched"]["meta"], ml, N, n, rows=None if r == B else (r, B))
 
     def _add_usage(self, counts, n_tokens: int) -> None:
         """Expert-usage counters (modedit.py:568-572, 594): ``counts`` [L, E] added on the device - no host sync on the hot path - and
@@ -687,16 +717,20 @@ class MoDeDiT(nn.Module):
         for blk in self.blocks:
             blk.total_tokens_processed += n_tokens
 
-    def _account_usage(self, meta, ml, n_tokens: int, n: int = 1) -> None:
-        """Usage counters from dispatch records: ``meta`` [L·n, words], n forwards of n_tokens tokens each per layer (layer-major)."""
+    def _account_usage(self, meta, ml, n_tokens: int, n: int = 1, rows=None) -> None:
+        """Usage counters from dispatch records: ``meta`` [L·n, words], n forwards of n_tokens tokens each per layer (layer-major).  ``rows`` =
+        (r, B): count r of the records' B samples (records of one routing row for the whole batch: every count is a multiple of B)."""
         counts = meta[:, ml.counts: ml.counts + self.num_experts]
-        self._add_usage(counts if n == 1 else counts.reshape(self.num_layers, n, -1).sum(1), n_tokens * n)
+        counts = counts if n == 1 else counts.reshape(self.num_layers, n, -1).sum(1)
+        if rows is not None:
+            counts, n_tokens = counts.long() * rows[0] // rows[1], n_tokens * rows[0] // rows[1]
+        self._add_usage(counts, n_tokens * n)
 
-    def _account_token_usage(self, idx, n_tokens: int) -> None:
-        """Usage counters under token routing: idx int32 [L, ..., k] (every token's experts) -> per-layer histogram."""
+    def _account_token_usage(self, idx, n_tokens: int, weight: int = 1) -> None:
+        """Usage counters under token routing: idx int32 [L, ..., k] (every token's experts) -> per-layer histogram; ``weight``: tokens per decision."""
         Ly, E = self.num_layers, self.num_experts
         self._add_usage(torch.zeros(Ly, E, dtype=torch.int64, device=idx.device).scatter_add_(
-            1, idx.reshape(Ly, -1).long(), torch.ones(Ly, idx[0].numel(), dtype=torch.int64, device=idx.device)), n_tokens)
+            1, idx.reshape(Ly, -1).long(), torch.full((Ly, idx[0].numel()), weight, dtype=torch.int64, device=idx.device)), n_tokens)
     def sync_expert_usage(self):
         """Fold the device-side counters into the per-block host tensors the agent's heat-map reads (mode_agent.py:466-511)."""
         if getattr(self, "_usage_dev", None) is not None:

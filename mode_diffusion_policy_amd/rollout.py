@@ -7,9 +7,12 @@ those producers are out of scope here, so this harness starts at their outputs a
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
+from types import SimpleNamespace
 from typing import Dict, Optional
 
+import numpy as np
 import torch
 
 from . import gc_sampling as gs
@@ -219,6 +222,288 @@ class ChunkedRolloutPolicy:
         if self.rollout_step_counter == self.multistep:
             self.rollout_step_counter = 0
         return current
+
+
+# VectorEnvPolicy's samplers: the deterministic ones whose whole call is one captured chunk of MoDeDiT._sample_chunk (sampler_type -> its solver there;
+# "euler" without churn is the DDIM update, see samplers.sample_euler).  The others draw in-loop noise from torch's global generator, which would tie an
+# environment's actions to which other environments replan with it.
+_VECTOR_SAMPLERS = {"ddim": "ddim", "euler": "ddim", "dpmpp_2m": "dpmpp_2m", "heun": "heun", "dpm": "dpm_2", "dpmpp_2s": "dpmpp_2s"}
+
+
+def _u32_as_i32(values) -> torch.Tensor:
+    """Host int32 tensor holding the uint32 bit patterns of ``values`` (each taken modulo 2^32)."""
+    return torch.from_numpy(np.asarray([int(v) & 0xFFFFFFFF for v in values], dtype=np.uint32).view(np.int32).copy())
+
+
+def _buckets(num_envs: int):
+    """Batch sizes a replanning chunk runs at: the powers of two up to ``num_envs``, and ``num_envs``."""
+    return sorted({1 << i for i in range(num_envs.bit_length()) if 1 << i <= num_envs} | {num_envs})
+
+
+@torch.no_grad()
+def env_noise(seeds, draws, act_window_size: int, action_dim: int, sigma_max: float, device="cuda") -> torch.Tensor:
+    """The initial latents ``VectorEnvPolicy`` plans from: row i = draw ``draws[i]`` of the noise stream with seed ``seeds[i]`` times ``sigma_max``,
+    (len(seeds), act_window_size, action_dim) fp32 on ``device``.  The stream is counter-based (formula: include/mode_hip.h, ABI 13), so any
+    environment's replan can be reproduced from its seed and draw index alone."""
+    from . import _lib as L
+    from .engine import _stream
+    seeds, draws = list(seeds), list(draws)
+    if not seeds or len(seeds) != len(draws):
+        raise ValueError("env_noise: one draw index per seed, at least one")
+    dev, n = torch.device(device), len(seeds)
+    s, d = _u32_as_i32(seeds).to(dev), _u32_as_i32(draws).to(dev)
+    rows = torch.arange(n, dtype=torch.int32, device=dev)
+    x = torch.empty(n, act_window_size, action_dim, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().mode_env_gather_noise(rows.data_ptr(), n, n, s.data_ptr(), d.data_ptr(), None, 0, None, 0, None, None, x.data_ptr(),
+                                               act_window_size * action_dim, float(sigma_max), _stream()), "env_gather_noise")
+    return x
+
+
+class VectorEnvPolicy(ChunkedRolloutPolicy):
+    """``MoDEAgent.reset`` / ``step`` (mode_agent.py:584-637) for each of ``num_envs`` environments of a batch on its own: every environment keeps
+    its own plan, its own position in it and its own noise stream, so a batch behaves like ``num_envs`` independent agents whose episodes start,
+    end and pause at different steps.  The schedule, the sampler keywords and the routing pre-cache are ``ChunkedRolloutPolicy``'s.
+
+    ``reset(envs=None, seeds=None)``: the listed environments (None = all, a sequence of indices or a host bool mask (num_envs,)) drop their
+    plans and replan at their next active step; ``seeds`` (one int per listed environment) re-keys their noise streams and rewinds them to draw
+    0, else the streams run on.  Environment b starts with seed ``seed + b``.
+
+    ``step(perceptual_emb, latent_goal, active=None) -> (num_envs, action_dim)`` device tensor: ``perceptual_emb = {'state_images': (num_envs,
+    n_img, obs_dim)}``, ``latent_goal`` (num_envs, G) or (num_envs, 1, G), ``active`` a HOST bool mask (None = all).  An active environment whose
+    counter is 0 replans from its own observation and goal with the next draw of its stream; every active environment emits
+    ``plan[b, counter]`` and advances ``counter = (counter + 1) % multistep``; inactive ones do neither and get a zero row.  Rows of the inputs of
+    environments that do not replan are not read.  ``replanned``: the environments that replanned at the last step (host list).
+
+    The m replanning environments run one chunk at the smallest bucket batch >= m (``_buckets``), padded by repeating the last one; one hipGraph
+    per (sampler, bucket) holds the chain and the commit of the plans + the emission of the step's actions (csrc/env_pool.hip).  A replanning
+    step is one H2D copy of the control block, one gather launch and one replay; any other step is one launch.  Neither synchronises with the
+    host.  ``warmup`` captures every bucket ahead of a control loop.  Samplers: ``_VECTOR_SAMPLERS``."""
+
+    def __init__(self, denoiser, num_envs: int, seed: int = 0, extra_args: Optional[dict] = None, **kw):
+        from . import _lib as L
+        from .modedit import MoDeDiT
+        sampler = kw.get("sampler_type", "ddim")
+        if sampler not in _VECTOR_SAMPLERS or extra_args:
+            raise ValueError(f"VectorEnvPolicy supports the deterministic fused samplers {sorted(_VECTOR_SAMPLERS)} without extra_args; got "
+                             f"sampler_type={sampler!r}, extra_args={extra_args!r}")
+        if kw.get("generator") is not None:
+            raise ValueError("VectorEnvPolicy draws its noise from per-environment streams: give seed= / reset(seeds=) instead of a generator")
+        if not isinstance(getattr(denoiser, "inner_model", None), MoDeDiT):
+            raise ValueError("VectorEnvPolicy needs a GCDenoiser over the HIP MoDeDiT")
+        if not 1 <= int(num_envs) <= L.MODE_ENV_MAX:
+            raise ValueError(f"num_envs must be in [1, {L.MODE_ENV_MAX}], got {num_envs}")
+        self.num_envs = int(num_envs)
+        self._counter = np.zeros(self.num_envs, dtype=np.int64)              # host mirror of the device counters: decides who replans
+        super().__init__(denoiser, **kw)
+        inner = denoiser.inner_model
+        W, A = self.act_window_size, self.action_dim
+        if (inner.action_seq_len, inner.action_dim) != (W, A):
+            raise ValueError(f"act_window_size / action_dim ({W}, {A}) must be the model's action_seq_len / action_dim "
+                             f"({inner.action_seq_len}, {inner.action_dim})")
+        dev = next(inner.parameters()).device
+        if dev.type != "cuda":
+            raise ValueError("VectorEnvPolicy runs on a ROCm device: move the denoiser there first")
+        self._solver = _VECTOR_SAMPLERS[sampler]
+        n, self._nw = self.num_envs, (self.num_envs + 31) // 32
+        self._plan = torch.zeros(n, W, A, dtype=torch.float32, device=dev)
+        self._counter_dev = torch.zeros(n, dtype=torch.int32, device=dev)
+        self._draws = torch.zeros(n, dtype=torch.int32, device=dev)          # uint32 bit patterns
+        self._seeds = _u32_as_i32(range(seed, seed + n)).to(dev)
+        nctrl = 4 + self._nw + n                                             # control block: include/mode_hip.h (ABI 13)
+        self._ctrl = torch.zeros(nctrl, dtype=torch.int32, device=dev)
+        # pinned staging of the control block, a ring: a slot is rewritten only after the copy that read it has run (its event)
+        self._ring = [torch.zeros(nctrl, dtype=torch.int32, pin_memory=True) for _ in range(4)]
+        self._ring_ev = [torch.cuda.Event() for _ in self._ring]
+        self._slot = 0
+        self._scratch_out = torch.zeros(n, A, dtype=torch.float32, device=dev)
+        self._desc = L.ModeEnvPoolDesc(num_envs=n, W=W, A=A, multistep=self.multistep, plan=self._plan.data_ptr(),
+                                       counter=self._counter_dev.data_ptr(), draws=self._draws.data_ptr())
+        self._lib = L.load()
+        self._buckets = _buckets(n)
+        self._templates = {}
+        self._hooks = SimpleNamespace(store={}, prologue=self._gather, epilogue=self._commit)
+        self._inputs = None
+        self.replanned = []
+
+    # ---------------------------------------------------------------------------------------------------------------- host-side bookkeeping
+    def _env_index(self, envs) -> np.ndarray:
+        n = self.num_envs
+        if envs is None:
+            return np.arange(n)
+        if torch.is_tensor(envs):
+            if envs.device.type != "cpu":
+                raise ValueError("envs must be host indices or a host mask")
+            envs = envs.numpy()
+        a = np.asarray(envs)
+        if a.dtype == np.bool_:
+            if a.shape != (n,):
+                raise ValueError(f"an environment mask must have shape ({n},), got {a.shape}")
+            return np.flatnonzero(a)
+        a = a.astype(np.int64).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() >= n or len(np.unique(a)) != a.size):
+            raise ValueError(f"environment indices must be distinct and in [0, {n}), got {a.tolist()}")
+        return a
+
+    def _active_mask(self, active) -> np.ndarray:
+        n = self.num_envs
+        if active is None:
+            return np.ones(n, dtype=np.bool_)
+        if torch.is_tensor(active):
+            if active.device.type != "cpu":
+                raise ValueError("active must be a HOST mask (numpy / list / CPU tensor): a device mask would need a host sync per step")
+            active = active.numpy()
+        a = np.asarray(active)
+        if a.dtype != np.bool_ or a.shape != (n,):
+            raise ValueError(f"active must be a bool mask of shape ({n},), got {a.dtype} {a.shape}")
+        return a
+
+    def _active_words(self, act: np.ndarray) -> np.ndarray:
+        bits = np.packbits(act, bitorder="little")
+        return np.pad(bits, (0, 4 * self._nw - bits.size)).view("<u4")
+
+    def reset(self, envs=None, seeds=None) -> None:
+        """Start a new episode in the listed environments (see the class docstring)."""
+        idx = self._env_index(envs)
+        self._counter[idx] = 0
+        if seeds is None:
+            return
+        seeds = list(seeds)
+        if len(seeds) != len(idx):
+            raise ValueError(f"one seed per listed environment: {len(idx)} environments, {len(seeds)} seeds")
+        if len(idx):
+            dev = self._seeds.device
+            i = torch.from_numpy(idx).pin_memory().to(dev, non_blocking=True)
+            self._seeds[i] = _u32_as_i32(seeds).pin_memory().to(dev, non_blocking=True)
+            self._draws[i] = 0
+
+    @property
+    def plans(self) -> torch.Tensor:
+        """[num_envs, act_window_size, action_dim] every environment's current plan (device)."""
+        return self._plan
+
+    @property
+    def draws(self) -> torch.Tensor:
+        """[num_envs] int32 (uint32 bit patterns): the draw index each environment's next replan takes (device)."""
+        return self._draws
+
+    def _check_inputs(self, perceptual_emb: Dict, latent_goal: torch.Tensor):
+        """Shape / device contract of the inputs: host metadata only (the rows are read by the gather launch, and only those that replan)."""
+        inner = self.model.inner_model
+        n = self.num_envs
+        if "state_images" not in perceptual_emb:
+            raise ValueError("VectorEnvPolicy.step takes embedded observations {'state_images': (num_envs, n_img, obs_dim)}: embed raw camera "
+                             "frames first (policy.embed(obs, latent_goal) with the policy's perceptual encoders)")
+        img = perceptual_emb["state_images"]
+        want = (n, inner.n_img_tokens, inner.obs_dim)
+        if not torch.is_tensor(img) or tuple(img.shape) != want:
+            raise ValueError(f"state_images must be {want} (one row per environment), got {tuple(getattr(img, 'shape', ()))}")
+        gl = latent_goal
+        if not torch.is_tensor(gl) or gl.shape[0] != n or gl.reshape(n, -1).shape[1] != inner.goal_dim or gl.dim() not in (2, 3):
+            raise ValueError(f"latent_goal must be ({n}, {inner.goal_dim}) or ({n}, 1, {inner.goal_dim}), got {tuple(getattr(gl, 'shape', ()))}")
+        dev = self._plan.device
+        if img.device != dev or gl.device != dev:
+            raise ValueError(f"state_images and latent_goal must be on {dev}")
+        return img, gl
+
+    # ---------------------------------------------------------------------------------------------------------------- device side
+    def _stage(self, m: int, rows: np.ndarray, act: np.ndarray, out_ptr: int) -> None:
+        """Fill the next pinned slot with the control block and copy it to the device block the gather and the graphs read."""
+        i = self._slot
+        self._slot = (i + 1) % len(self._ring)
+        self._ring_ev[i].synchronize()            # the copy that last read this slot: done long ago unless the host ran 4 replans ahead
+        buf = self._ring[i].numpy()
+        nw = self._nw
+        buf[0], buf[1] = m, 0
+        buf[2:4] = np.array([out_ptr], dtype="<u8").view("<i4")
+        buf[4:4 + nw] = self._active_words(act).view("<i4")
+        buf[4 + nw:4 + nw + len(rows)] = rows
+        self._ctrl.copy_(self._ring[i], non_blocking=True)
+        self._ring_ev[i].record()
+
+    def _gather(self, ent) -> None:
+        """Chunk prologue: the listed environments' observations, goals and initial noise into the entry's input buffers (one launch)."""
+        from . import _lib as L
+        from .engine import _stream
+        img, gl = self._inputs
+        inner = self.model.inner_model
+        x = ent["bufs"][0]
+        L.check(self._lib.mode_env_gather_noise(self._ctrl.data_ptr() + 4 * (4 + self._nw), x.shape[0], self.num_envs, self._seeds.data_ptr(),
+                                                self._draws.data_ptr(), img.data_ptr(), inner.n_img_tokens * inner.obs_dim, gl.data_ptr(),
+                                                inner.goal_dim, ent["img"].data_ptr(), ent["goals"].data_ptr(), x.data_ptr(),
+                                                self.act_window_size * self.action_dim, float(self.sigma_max), _stream()), "env_gather_noise")
+
+    def _commit(self, ent, capturing: bool) -> None:
+        """Chunk epilogue: commit + emit reading the device control block.  Outside a capture (the warm-up run) the same kernel runs with no
+        replan and no active environment into a scratch row block: it loads the code object and changes nothing."""
+        d = type(self._desc).from_buffer_copy(self._desc)
+        d.chunk = ent["bufs"][0].data_ptr()
+        if capturing:
+            d.ctrl = self._ctrl.data_ptr()
+        else:
+            d.out = self._scratch_out.data_ptr()
+        self._launch(d)
+
+    def _launch(self, d) -> None:
+        from . import _lib as L
+        from .engine import _stream
+        L.check(self._lib.mode_env_commit_emit(C.byref(d), _stream()), "env_commit_emit")
+
+    def _run_chunk(self, mb: int, m: int) -> None:
+        """One replanning chunk at bucket ``mb`` with ``m`` real rows (the control block is staged): gather launch + one replay."""
+        inner = self.model.inner_model
+        eng = inner.engine
+        if self.need_precompute_experts_for_inference:
+            if not inner._routes_per_chunk():                               # goal / token routing resolve their routing inside the chunk
+                self.precompute_expert_for_inference()
+            self.need_precompute_experts_for_inference = False
+        sig = self._schedule(eng.device)
+        tpl = self._templates.get(mb)
+        if tpl is None:
+            dev = eng.device
+            tpl = self._templates[mb] = ({"state_images": torch.zeros(mb, inner.n_img_tokens, inner.obs_dim, device=dev)},
+                                         torch.zeros(mb, self.act_window_size, self.action_dim, device=dev), torch.zeros(mb, inner.goal_dim, device=dev))
+        gkey, plan = inner._chunk_plan(eng, self._solver, sig.numel() - 1)
+        inner._sample_chunk(eng, gkey, plan, tpl[0], tpl[1], tpl[2], sig, float(self.model.sigma_data), hooks=self._hooks, rows=m)
+
+    @torch.no_grad()
+    def warmup(self, perceptual_emb: Dict, latent_goal: torch.Tensor) -> None:
+        """Capture the chunk of every bucket now (the inputs give valid rows for the capture runs); the policy's state does not change."""
+        self.model.eval()
+        self._inputs = self._check_inputs(perceptual_emb, latent_goal)
+        self._inputs = (self._inputs[0].to(torch.float32).contiguous(), self._inputs[1].to(torch.float32).contiguous())
+        none = np.zeros(self.num_envs, dtype=np.bool_)
+        for mb in self._buckets:
+            self._stage(0, np.zeros(mb, dtype=np.int32), none, self._scratch_out.data_ptr())
+            self._run_chunk(mb, 0)
+        self._inputs = None
+
+    @torch.no_grad()
+    def step(self, perceptual_emb: Dict, latent_goal: torch.Tensor, active=None) -> torch.Tensor:
+        if self.model.training or self.model.inner_model.training:       # (eval() walks every submodule: not on every step)
+            self.model.eval()
+        img, gl = self._check_inputs(perceptual_emb, latent_goal)
+        act = self._active_mask(active)
+        rows = np.flatnonzero(act & (self._counter == 0)).astype(np.int32)
+        m = len(rows)
+        out = torch.empty(self.num_envs, self.action_dim, dtype=torch.float32, device=self._plan.device)
+        if m:
+            mb = next(b for b in self._buckets if b >= m)
+            self._stage(m, np.concatenate([rows, np.full(mb - m, rows[-1], dtype=np.int32)]), act, out.data_ptr())
+            self._inputs = (img.to(torch.float32).contiguous(), gl.to(torch.float32).contiguous())
+            try:
+                self._run_chunk(mb, m)
+            finally:
+                self._inputs = None
+        else:
+            d = type(self._desc).from_buffer_copy(self._desc)
+            d.out = out.data_ptr()
+            words = self._active_words(act)
+            C.memmove(d.active, words.ctypes.data, 4 * self._nw)
+            self._launch(d)
+        self._counter[act] = (self._counter[act] + 1) % self.multistep
+        self.replanned = rows.tolist()
+        return out
 
 
 def _read_checkpoint_file(path: str, trust_pickle: bool = False) -> Dict[str, torch.Tensor]:
