@@ -819,6 +819,28 @@ int mode_env_gather_noise(const int32_t* rows, int m_b, int num_envs, const uint
                           const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
                           float* img_out, float* goal_out, float* x0, int noise_floats, float sigma_max, void* stream);
 
+/* Gather of the replanning environments' camera frames into the perceptual encoders' input (one launch, both cameras; rollout.VectorEnvPolicy
+ * with raw observations).  For j < m_b, r = rows[j] (the control block's rows; entries outside [0, num_envs) leave row j untouched) and each
+ * camera k with src and dst set:
+ *   dst_k[j * row_elems .. (j + 1) * row_elems) = src_k[r * src_stride .. r * src_stride + row_elems)
+ * i.e. with row_elems = T * C * H * W the [m_b * T, C, H, W] contiguous input the stem reads, from frames [num_envs, T, C, H, W] whose rows are
+ * contiguous and src_stride elements apart (src_stride >= row_elems).  Element types: fp32 -> fp32, bf16 -> bf16, or fp32 -> bf16 rounded to
+ * nearest-even with NaN kept NaN (= Tensor.to(torch.bfloat16), the rounding the stem applies to an fp32 image).  16-byte loads and stores where
+ * a row's source and destination are 16-byte aligned, element loads otherwise.  Reads nothing of the environments that are not listed. */
+typedef struct ModeEnvFramesCam {
+  const void* src;                       /* [num_envs] rows of row_elems elements, src_stride elements apart; NULL (with dst) = camera skipped */
+  int64_t src_stride, row_elems;
+  void* dst;                             /* [m_b, row_elems] */
+  int32_t src_dtype, dst_dtype;          /* MODE_F32 | MODE_BF16 */
+} ModeEnvFramesCam;
+typedef struct ModeEnvFramesDesc {
+  const int32_t* rows;                   /* [m_b] device */
+  int32_t m_b;                           /* 1..65535 */
+  int32_t num_envs;
+  ModeEnvFramesCam cam[2];               /* static, gripper */
+} ModeEnvFramesDesc;
+int mode_env_gather_frames(const ModeEnvFramesDesc* d, void* stream);
+
 typedef struct ModeEnvPoolDesc {
   int32_t num_envs;                      /* 1..MODE_ENV_MAX */
   int32_t W, A;                          /* planned rows per environment and action width; W * A <= 4096 */

@@ -161,6 +161,16 @@ class ModeEnvPoolDesc(C.Structure):
                 ("counter", c_vp), ("draws", c_vp), ("out", c_vp), ("active", c_u32 * (MODE_ENV_MAX // 32))]
 
 
+class ModeEnvFramesCam(C.Structure):
+    """One camera of mode_env_gather_frames (include/mode_hip.h, ABI 13)."""
+    _fields_ = [("src", c_vp), ("src_stride", c_i64), ("row_elems", c_i64), ("dst", c_vp), ("src_dtype", c_i32), ("dst_dtype", c_i32)]
+
+
+class ModeEnvFramesDesc(C.Structure):
+    """Gather of the replanning environments' camera frames into the encoders' input (include/mode_hip.h, ABI 13)."""
+    _fields_ = [("rows", c_vp), ("m_b", c_i32), ("num_envs", c_i32), ("cam", ModeEnvFramesCam * 2)]
+
+
 P = C.POINTER
 # name -> (restype, argtypes): every symbol include/mode_hip.h declares
 PROTOTYPES = {
@@ -246,6 +256,7 @@ PROTOTYPES = {
     "mode_maxpool_nhwc_bwd": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mode_env_gather_noise": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp]),
     "mode_env_commit_emit": (C.c_int, [P(ModeEnvPoolDesc), c_vp]),
+    "mode_env_gather_frames": (C.c_int, [P(ModeEnvFramesDesc), c_vp]),
 }
 
 _lib: Optional[C.CDLL] = None

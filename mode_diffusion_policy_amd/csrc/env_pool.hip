@@ -1,6 +1,8 @@
 // Per-environment replanning of a vectorised rollout (include/mode_hip.h, ABI 13; rollout.VectorEnvPolicy): the gather of the replanning
 // environments' observations with their initial noise into a chunk's input buffers, and the commit of the chunk's plans + the emission of one
-// action per active environment.  Both move a few hundred KB at most: one launch each, plain coalesced loops, no LDS.
+// action per active environment.  Both move a few hundred KB at most: one launch each, plain coalesced loops, no LDS.  The gather of the
+// replanning environments' camera frames into the encoders' input (mode_env_gather_frames) moves ~1.2 MB per fp32 row at 224 x 224: HBM-bound,
+// 16-byte loads and stores.
 #include "mode_common.h"
 
 namespace mode {
@@ -32,6 +34,60 @@ __global__ __launch_bounds__(256) void env_gather_noise_kernel(const int32_t* __
   const uint32_t k = mode_stream_seed(seeds[r], draws[r]);
   float* dst = x0 + (long)j * noise_floats;
   for (int e = threadIdx.x; e < noise_floats; e += 256) dst[e] = sigma_max * env_normal(k, (uint32_t)e);
+}
+
+// Frames of the replanning environments -> the encoders' input [m_b * T, C, H, W].  grid (x blocks per row, m_b, 2 cameras), 256 threads; each
+// thread moves 8 elements per iteration: fp32 -> fp32 two 16-byte loads + two stores, fp32 -> bf16 two loads + one store (RNE, the rounding the
+// stem applies to an fp32 image), bf16 -> bf16 one load + one store.  A row whose source or destination is not 16-byte aligned (an odd row pitch,
+// odd H * W) takes the element loop; so does the tail of a row that is not a multiple of 8 elements.
+__device__ __forceinline__ void frames_copy_row(const ModeEnvFramesCam& c, const int r, const int j) {
+  const long n = c.row_elems;
+  const int so = c.src_dtype == MODE_F32 ? 4 : 2, dso = c.dst_dtype == MODE_F32 ? 4 : 2;
+  const char* src = static_cast<const char*>(c.src) + (long)r * c.src_stride * so;
+  char* dst = static_cast<char*>(c.dst) + (long)j * n * dso;
+  const long nthr = (long)gridDim.x * 256, t = (long)blockIdx.x * 256 + threadIdx.x;
+  long done = 0;
+  if ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
+    const long nv = n >> 3;                                    // 8-element groups
+    if (c.src_dtype == MODE_BF16) {
+      const uint4* s4 = reinterpret_cast<const uint4*>(src);
+      uint4* d4 = reinterpret_cast<uint4*>(dst);
+      for (long v = t; v < nv; v += nthr) d4[v] = s4[v];
+    } else if (c.dst_dtype == MODE_F32) {
+      const float4* s4 = reinterpret_cast<const float4*>(src);
+      float4* d4 = reinterpret_cast<float4*>(dst);
+      for (long v = t; v < nv; v += nthr) {
+        const float4 a = s4[2 * v], b = s4[2 * v + 1];
+        d4[2 * v] = a; d4[2 * v + 1] = b;
+      }
+    } else {
+      const float4* s4 = reinterpret_cast<const float4*>(src);
+      uint4* d4 = reinterpret_cast<uint4*>(dst);
+      for (long v = t; v < nv; v += nthr) {
+        const float4 a = s4[2 * v], b = s4[2 * v + 1];
+        d4[v] = make_uint4(pack_bf16x2(a.x, a.y), pack_bf16x2(a.z, a.w), pack_bf16x2(b.x, b.y), pack_bf16x2(b.z, b.w));
+      }
+    }
+    done = nv << 3;
+  }
+  for (long i = done + t; i < n; i += nthr) {
+    if (c.src_dtype == MODE_BF16) {
+      reinterpret_cast<uint16_t*>(dst)[i] = reinterpret_cast<const uint16_t*>(src)[i];
+    } else {
+      const float f = reinterpret_cast<const float*>(src)[i];
+      if (c.dst_dtype == MODE_F32) reinterpret_cast<float*>(dst)[i] = f;
+      else reinterpret_cast<uint16_t*>(dst)[i] = f32_to_bf16_bits(f);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void env_gather_frames_kernel(ModeEnvFramesDesc d) {
+  const int j = blockIdx.y;
+  const int r = d.rows[j];
+  if (r < 0 || r >= d.num_envs) return;
+  const ModeEnvFramesCam c = blockIdx.z == 0 ? d.cam[0] : d.cam[1];   // (no dynamic index into the argument block)
+  if (!c.src || !c.dst) return;
+  frames_copy_row(c, r, j);
 }
 
 // One wave per environment b: find b among the chunk's m real rows (rows are distinct), commit that row, then emit.  The emitted row of a
@@ -100,6 +156,28 @@ extern "C" int mode_env_commit_emit(const ModeEnvPoolDesc* d, void* stream) {
     return MODE_ERR_BAD_ARG;
   if (d->ctrl ? !d->chunk : !d->out) return MODE_ERR_BAD_ARG;
   hipLaunchKernelGGL(env_commit_emit_kernel, dim3(d->num_envs), dim3(64), 0, (hipStream_t)stream, *d);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
+extern "C" int mode_env_gather_frames(const ModeEnvFramesDesc* d, void* stream) {
+  if (!d || !d->rows || d->m_b <= 0 || d->m_b > 65535 || d->num_envs <= 0) return MODE_ERR_BAD_ARG;
+  long most = 0;
+  for (int k = 0; k < 2; ++k) {
+    const ModeEnvFramesCam& c = d->cam[k];
+    if (!c.src && !c.dst) continue;
+    if (!c.src || !c.dst || c.row_elems <= 0 || c.src_stride < c.row_elems) return MODE_ERR_BAD_ARG;
+    const bool ok = (c.src_dtype == MODE_F32 && (c.dst_dtype == MODE_F32 || c.dst_dtype == MODE_BF16)) ||
+                    (c.src_dtype == MODE_BF16 && c.dst_dtype == MODE_BF16);
+    if (!ok) return MODE_ERR_UNSUPPORTED;
+    const int so = c.src_dtype == MODE_F32 ? 4 : 2, dso = c.dst_dtype == MODE_F32 ? 4 : 2;
+    if (((uintptr_t)c.src % so) || ((uintptr_t)c.dst % dso)) return MODE_ERR_BAD_ARG;
+    most = c.row_elems > most ? c.row_elems : most;
+  }
+  if (most == 0) return MODE_ERR_BAD_ARG;
+  // up to 4 iterations of 8 elements per thread: ~74 workgroups per 224 x 224 fp32 frame row and camera
+  const long bx = (most + 8L * 256 * 4 - 1) / (8L * 256 * 4);
+  hipLaunchKernelGGL(env_gather_frames_kernel, dim3((unsigned)bx, d->m_b, 2), dim3(256), 0, (hipStream_t)stream, *d);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }

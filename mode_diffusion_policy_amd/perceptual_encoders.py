@@ -333,16 +333,25 @@ class _TableCache:
         return t
 
     def put(self, key, t):
-        if TWO_TOWER_STREAMS and t.is_cuda and not torch.cuda.is_current_stream_capturing():
-            # the other tower's stream may use the table right away: built before it is published.  (Under hipGraph capture a host synchronize is illegal - and
-            # not needed: both towers' launches are captured in fork / join order behind the build.)
+        capturing = t.is_cuda and torch.cuda.is_current_stream_capturing()
+        if self.sink is not None:
+            self.sink.append(t)
+            if capturing:
+                # built inside a capture, on ONE tower's branch of the graph: the other branch has no edge to the build, so the table is not published -
+                # it lives in the graph's sink only, and the other tower builds (or finds from the warm-up) its own
+                return t
+        if TWO_TOWER_STREAMS and t.is_cuda and not capturing:
+            # the other tower's stream may use the table right away: built before it is published
             torch.cuda.current_stream(t.device).synchronize()
         self.d[key] = t
         self.bytes += t.numel() * t.element_size()
-        if self.sink is not None:
-            self.sink.append(t)
-        while self.bytes > self.limit and len(self.d) > 1:
-            _, old = self.d.popitem(last=False)
+        # the tables a warm-up / capture in progress touched (the sink) are not evicted: its capture must find what its warm-up built instead of
+        # rebuilding it inside the graph.  The bound holds again after the capture, at the next put
+        pinned = {id(x) for x in self.sink} if self.sink is not None else ()
+        for k in [k for k in self.d if id(self.d[k]) not in pinned]:
+            if self.bytes <= self.limit or len(self.d) <= 1:
+                break
+            old = self.d.pop(k)
             self.bytes -= old.numel() * old.element_size()
         return t
 
@@ -1143,10 +1152,25 @@ class GraphedVisualEncoder:
         encoders): a re-allocated interior tensor (``p.data = ...``, ``.to()``, ``.half()``) must re-capture, not replay against freed memory."""
         return hash(tuple(t.data_ptr() for m in (self.static_resnet, self.gripper_resnet) for t in list(m.parameters()) + list(m.buffers())))
 
+    def capture(self, fn, device, wdt: torch.dtype):
+        """(graph, fn's result, the index tables it reads) of ``fn`` - a call of the encoders - captured with the compute-dtype weight copies of
+        :meth:`_weights` and every index table the warm-up / capture touches pinned next to the graph.  Also the per-bucket encoder graphs of
+        ``rollout.VectorEnvPolicy``, which keeps them in its own store."""
+        from .engine import warm_and_capture
+        global _W_OVERRIDE
+        saved, _W_OVERRIDE = _W_OVERRIDE, self._weights(wdt)
+        saved_sink, _TABLES.sink = _TABLES.sink, []
+        tables = _TABLES.sink
+        try:                                                                     # two warm-ups: MIOpen's algorithm search, code-object loads
+            graph, out = warm_and_capture(fn, device, warmups=2)
+        finally:
+            _W_OVERRIDE = saved
+            _TABLES.sink = saved_sink
+        return graph, out, tables
+
     @torch.no_grad()
     def __call__(self, rgb_static: torch.Tensor, rgb_gripper: torch.Tensor, latent_goal: Optional[torch.Tensor] = None):
         import os
-        from .engine import warm_and_capture
         if self.static_resnet.training or self.gripper_resnet.training or rgb_static.device.type != "cuda" or os.environ.get("MODE_HIP_GRAPH", "1") == "0":
             return {"state_images": self._eager(rgb_static, rgb_gripper, latent_goal)}       # batch statistics / no device: nothing to replay
         wdt = self.autocast_dtype if self.autocast_dtype is not None else rgb_static.dtype
@@ -1157,15 +1181,7 @@ class GraphedVisualEncoder:
             if len(self._graphs) >= self.max_graphs:
                 self._graphs.pop(next(iter(self._graphs)))
             ent = dict(s=rgb_static.clone(), g=rgb_gripper.clone(), c=None if latent_goal is None else latent_goal.clone())
-            global _W_OVERRIDE
-            saved, _W_OVERRIDE = _W_OVERRIDE, self._weights(wdt)
-            saved_sink, _TABLES.sink = _TABLES.sink, []                          # every index table the warm-up / capture touches: pinned next to the graph
-            ent["tables"] = _TABLES.sink
-            try:                                                                 # two warm-ups: MIOpen's algorithm search, code-object loads
-                ent["graph"], ent["out"] = warm_and_capture(lambda: self._eager(ent["s"], ent["g"], ent["c"]), rgb_static.device, warmups=2)
-            finally:
-                _W_OVERRIDE = saved
-                _TABLES.sink = saved_sink
+            ent["graph"], ent["out"], ent["tables"] = self.capture(lambda: self._eager(ent["s"], ent["g"], ent["c"]), rgb_static.device, wdt)
             self._graphs[key] = ent
         self._weights(wdt)                                                       # weights whose version moved since the last call: re-cast in place
         ent["s"].copy_(rgb_static); ent["g"].copy_(rgb_gripper)

@@ -270,7 +270,9 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
     0, else the streams run on.  Environment b starts with seed ``seed + b``.
 
     ``step(perceptual_emb, latent_goal, active=None) -> (num_envs, action_dim)`` device tensor: ``perceptual_emb = {'state_images': (num_envs,
-    n_img, obs_dim)}``, ``latent_goal`` (num_envs, G) or (num_envs, 1, G), ``active`` a HOST bool mask (None = all).  An active environment whose
+    n_img, obs_dim)}`` or, with the perceptual encoders (``static_resnet`` / ``gripper_resnet``), the raw observation ``{'rgb_obs':
+    {'rgb_static': (num_envs, T, 3, H, W), 'rgb_gripper': (num_envs, T, 3, Hg, Wg)}}`` (fp32 or bf16, 2 T = the model's n_img_tokens),
+    ``latent_goal`` (num_envs, G) or (num_envs, 1, G), ``active`` a HOST bool mask (None = all).  An active environment whose
     counter is 0 replans from its own observation and goal with the next draw of its stream; every active environment emits
     ``plan[b, counter]`` and advances ``counter = (counter + 1) % multistep``; inactive ones do neither and get a zero row.  Rows of the inputs of
     environments that do not replan are not read.  ``replanned``: the environments that replanned at the last step (host list).
@@ -278,7 +280,14 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
     The m replanning environments run one chunk at the smallest bucket batch >= m (``_buckets``), padded by repeating the last one; one hipGraph
     per (sampler, bucket) holds the chain and the commit of the plans + the emission of the step's actions (csrc/env_pool.hip).  A replanning
     step is one H2D copy of the control block, one gather launch and one replay; any other step is one launch.  Neither synchronises with the
-    host.  ``warmup`` captures every bucket ahead of a control loop.  Samplers: ``_VECTOR_SAMPLERS``."""
+    host.  ``warmup`` captures every bucket ahead of a control loop.  Samplers: ``_VECTOR_SAMPLERS``.
+
+    Raw frames: only the replanning environments' frames are read and encoded.  One more launch gathers their rows of both cameras into the
+    encoders' input at the bucket batch (csrc/env_pool.hip, rounding fp32 to bf16 on the way when the encoders run under bf16 autocast, as the
+    stem would), and one more replay runs the two towers at batch mb * T with FiLM on each environment's own goal row (two graph branches, as
+    ``GraphedVisualEncoder``) straight into the chunk's observation buffer: two launches and two replays per replanning step.  The encoder
+    graphs live in the policy's own store, one per bucket; in-place weight updates are seen by the next replan; encoders in training mode or
+    MODE_HIP_GRAPH=0 run eagerly on the gathered rows."""
 
     def __init__(self, denoiser, num_envs: int, seed: int = 0, extra_args: Optional[dict] = None, **kw):
         from . import _lib as L
@@ -324,6 +333,7 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         self._templates = {}
         self._hooks = SimpleNamespace(store={}, prologue=self._gather, epilogue=self._commit)
         self._inputs = None
+        self._enc_store = {}                                                # bucket -> gathered frame buffers + that bucket's encoder graph
         self.replanned = []
 
     # ---------------------------------------------------------------------------------------------------------------- host-side bookkeeping
@@ -388,23 +398,60 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         return self._draws
 
     def _check_inputs(self, perceptual_emb: Dict, latent_goal: torch.Tensor):
-        """Shape / device contract of the inputs: host metadata only (the rows are read by the gather launch, and only those that replan)."""
+        """Shape / device contract of the inputs: host metadata only (the rows are read by the gather launches, and only those that replan).
+        Returns (state_images or None, latent_goal, (rgb_static, rgb_gripper) or None)."""
         inner = self.model.inner_model
         n = self.num_envs
+        if not isinstance(perceptual_emb, dict):
+            raise ValueError("perceptual_emb must be a dict: {'state_images': ...} or {'rgb_obs': {...}}")
+        if "state_images" in perceptual_emb and "rgb_obs" in perceptual_emb:
+            raise ValueError("give either embedded observations ('state_images') or raw camera frames ('rgb_obs'), not both")
+        frames = None
         if "state_images" not in perceptual_emb:
-            raise ValueError("VectorEnvPolicy.step takes embedded observations {'state_images': (num_envs, n_img, obs_dim)}: embed raw camera "
-                             "frames first (policy.embed(obs, latent_goal) with the policy's perceptual encoders)")
-        img = perceptual_emb["state_images"]
-        want = (n, inner.n_img_tokens, inner.obs_dim)
-        if not torch.is_tensor(img) or tuple(img.shape) != want:
-            raise ValueError(f"state_images must be {want} (one row per environment), got {tuple(getattr(img, 'shape', ()))}")
+            if "rgb_obs" not in perceptual_emb or self.encoders is None:
+                raise ValueError("VectorEnvPolicy.step takes embedded observations {'state_images': (num_envs, n_img, obs_dim)}: embed raw camera "
+                                 "frames first (policy.embed(obs, latent_goal) with the policy's perceptual encoders), or build the policy with "
+                                 "static_resnet / gripper_resnet to pass {'rgb_obs': ...}")
+            frames = self._check_frames(perceptual_emb["rgb_obs"])
+            img = None
+        else:
+            img = perceptual_emb["state_images"]
+            want = (n, inner.n_img_tokens, inner.obs_dim)
+            if not torch.is_tensor(img) or tuple(img.shape) != want:
+                raise ValueError(f"state_images must be {want} (one row per environment), got {tuple(getattr(img, 'shape', ()))}")
         gl = latent_goal
         if not torch.is_tensor(gl) or gl.shape[0] != n or gl.reshape(n, -1).shape[1] != inner.goal_dim or gl.dim() not in (2, 3):
             raise ValueError(f"latent_goal must be ({n}, {inner.goal_dim}) or ({n}, 1, {inner.goal_dim}), got {tuple(getattr(gl, 'shape', ()))}")
         dev = self._plan.device
-        if img.device != dev or gl.device != dev:
+        if (img is not None and img.device != dev) or gl.device != dev:
             raise ValueError(f"state_images and latent_goal must be on {dev}")
-        return img, gl
+        return img, gl, frames
+
+    _CAMERAS = ("rgb_static", "rgb_gripper")
+
+    def _check_frames(self, rgb):
+        """The raw observation's contract: both cameras, (num_envs, T, 3, H, W) each with one T, 2 T = n_img_tokens, fp32 or bf16, on the
+        policy's device.  An environment's frames must be one contiguous block (the environments may lie at any pitch): other layouts are
+        made so here."""
+        n, n_img = self.num_envs, self.model.inner_model.n_img_tokens
+        if not isinstance(rgb, dict) or set(rgb) != set(self._CAMERAS):
+            raise ValueError(f"rgb_obs must hold exactly the cameras {list(self._CAMERAS)}, got {sorted(rgb) if isinstance(rgb, dict) else type(rgb).__name__}")
+        out = []
+        for name in self._CAMERAS:
+            f = rgb[name]
+            if not torch.is_tensor(f) or f.dim() != 5 or f.shape[0] != n or f.shape[2] != 3 or f.numel() == 0:
+                raise ValueError(f"{name} must be ({n}, T, 3, H, W) (one row per environment), got {tuple(getattr(f, 'shape', ()))}")
+            if f.dtype not in (torch.float32, torch.bfloat16):
+                raise ValueError(f"{name} must be float32 or bfloat16, got {f.dtype}")
+            if f.device != self._plan.device:
+                raise ValueError(f"{name} must be on {self._plan.device}, got {f.device}")
+            out.append(f)
+        T = out[0].shape[1]
+        if out[1].shape[1] != T:
+            raise ValueError(f"both cameras must carry the same number of frames T, got {out[0].shape[1]} and {out[1].shape[1]}")
+        if 2 * T != n_img:
+            raise ValueError(f"2 * T frames (T = {T}) must equal the model's n_img_tokens = {n_img}")
+        return tuple(f if f[0].is_contiguous() and (n == 1 or f.stride(0) >= f[0].numel()) else f.contiguous() for f in out)
 
     # ---------------------------------------------------------------------------------------------------------------- device side
     def _stage(self, m: int, rows: np.ndarray, act: np.ndarray, out_ptr: int) -> None:
@@ -422,16 +469,68 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         self._ring_ev[i].record()
 
     def _gather(self, ent) -> None:
-        """Chunk prologue: the listed environments' observations, goals and initial noise into the entry's input buffers (one launch)."""
+        """Chunk prologue: the listed environments' observations, goals and initial noise into the entry's input buffers (one launch).  Raw
+        frames: the goals and the noise (one launch), the frames (one launch), then the encoders into the entry's observation buffer."""
         from . import _lib as L
         from .engine import _stream
-        img, gl = self._inputs
+        img, gl, frames = self._inputs
         inner = self.model.inner_model
         x = ent["bufs"][0]
-        L.check(self._lib.mode_env_gather_noise(self._ctrl.data_ptr() + 4 * (4 + self._nw), x.shape[0], self.num_envs, self._seeds.data_ptr(),
-                                                self._draws.data_ptr(), img.data_ptr(), inner.n_img_tokens * inner.obs_dim, gl.data_ptr(),
-                                                inner.goal_dim, ent["img"].data_ptr(), ent["goals"].data_ptr(), x.data_ptr(),
-                                                self.act_window_size * self.action_dim, float(self.sigma_max), _stream()), "env_gather_noise")
+        L.check(self._lib.mode_env_gather_noise(self._rows_ptr(), x.shape[0], self.num_envs, self._seeds.data_ptr(), self._draws.data_ptr(),
+                                                None if img is None else img.data_ptr(), inner.n_img_tokens * inner.obs_dim, gl.data_ptr(),
+                                                inner.goal_dim, None if img is None else ent["img"].data_ptr(), ent["goals"].data_ptr(),
+                                                x.data_ptr(), self.act_window_size * self.action_dim, float(self.sigma_max), _stream()),
+                "env_gather_noise")
+        if frames is not None:
+            self._encode(ent, frames)
+
+    def _rows_ptr(self) -> int:
+        return self._ctrl.data_ptr() + 4 * (4 + self._nw)
+
+    def _frame_dtypes(self, frames):
+        """Element type of the gathered frames: bf16 under bf16 autocast (the stem rounds an fp32 image to bf16 as it reads it, so converting in
+        the gather is exact and halves the stem's reads), else the frames' own."""
+        ac = self.encoders.autocast_dtype
+        return tuple(torch.bfloat16 if ac == torch.bfloat16 else f.dtype for f in frames)
+
+    def _gather_frames(self, mb: int, frames, bufs) -> None:
+        """frames[rows[j]] -> bufs[j] for j < mb, both cameras in one launch (csrc/env_pool.hip)."""
+        from . import _lib as L
+        from .engine import _stream
+        d = L.ModeEnvFramesDesc(rows=self._rows_ptr(), m_b=mb, num_envs=self.num_envs)
+        dt = {torch.float32: L.MODE_F32, torch.bfloat16: L.MODE_BF16}
+        for k, (f, b) in enumerate(zip(frames, bufs)):
+            d.cam[k] = L.ModeEnvFramesCam(src=f.data_ptr(), src_stride=f.stride(0) if f.shape[0] > 1 else f[0].numel(), row_elems=f[0].numel(),
+                                          dst=b.data_ptr(), src_dtype=dt[f.dtype], dst_dtype=dt[b.dtype])
+        L.check(self._lib.mode_env_gather_frames(C.byref(d), _stream()), "env_gather_frames")
+
+    def _encode(self, ent, frames) -> None:
+        """The bucket's encoders on the gathered frames, FiLM-conditioned on the gathered goals, into ``ent['img']``: a replay of the bucket's
+        encoder graph (captured on first use, and again when the frame geometry, the weights' storage or the chunk entry's buffers moved), or
+        the eager towers when the encoders are in training mode / MODE_HIP_GRAPH=0."""
+        enc = self.encoders
+        mb, n_img = ent["goals"].shape[0], self.model.inner_model.n_img_tokens
+        dts = self._frame_dtypes(frames)
+        geom = tuple((tuple(f.shape[1:]), dt) for f, dt in zip(frames, dts))
+        st = self._enc_store.get(mb)
+        if st is None or st["geom"] != geom:
+            st = self._enc_store[mb] = dict(geom=geom, graph=None,
+                                            bufs=tuple(torch.empty(mb, *f.shape[1:], dtype=dt, device=f.device) for f, dt in zip(frames, dts)))
+        self._gather_frames(mb, frames, st["bufs"])
+        goals = ent["goals"]
+        if enc.static_resnet.training or enc.gripper_resnet.training or os.environ.get("MODE_HIP_GRAPH", "1") == "0":
+            ent["img"].copy_(enc._eager(st["bufs"][0], st["bufs"][1], goals).view(mb, n_img, -1))
+            return
+        wdt = enc.autocast_dtype if enc.autocast_dtype is not None else dts[0]
+        key = (wdt, enc._param_key(), ent["img"].data_ptr(), goals.data_ptr())
+        if st["graph"] is None or st["key"] != key:
+            st["graph"] = None                                              # (the old graph's pool goes before the new capture)
+            img = ent["img"]
+            st["graph"], _, st["tables"] = enc.capture(lambda: img.copy_(enc._eager(st["bufs"][0], st["bufs"][1], goals).view(mb, n_img, -1)),
+                                                       img.device, wdt)
+            st["key"] = key
+        enc._weights(wdt)                                                   # weights whose version moved since the last replan: re-cast in place
+        st["graph"].replay()
 
     def _commit(self, ent, capturing: bool) -> None:
         """Chunk epilogue: commit + emit reading the device control block.  Outside a capture (the warm-up run) the same kernel runs with no
@@ -466,12 +565,17 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         gkey, plan = inner._chunk_plan(eng, self._solver, sig.numel() - 1)
         inner._sample_chunk(eng, gkey, plan, tpl[0], tpl[1], tpl[2], sig, float(self.model.sigma_data), hooks=self._hooks, rows=m)
 
+    @staticmethod
+    def _prepared(img, gl, frames):
+        """What the gather launches read: fp32 contiguous observation and goal rows; frames as checked."""
+        return (None if img is None else img.to(torch.float32).contiguous()), gl.to(torch.float32).contiguous(), frames
+
     @torch.no_grad()
     def warmup(self, perceptual_emb: Dict, latent_goal: torch.Tensor) -> None:
-        """Capture the chunk of every bucket now (the inputs give valid rows for the capture runs); the policy's state does not change."""
+        """Capture the chunk of every bucket now - with raw frames also every bucket's encoder graph - (the inputs give valid rows for the capture
+        runs); the policy's state does not change."""
         self.model.eval()
-        self._inputs = self._check_inputs(perceptual_emb, latent_goal)
-        self._inputs = (self._inputs[0].to(torch.float32).contiguous(), self._inputs[1].to(torch.float32).contiguous())
+        self._inputs = self._prepared(*self._check_inputs(perceptual_emb, latent_goal))
         none = np.zeros(self.num_envs, dtype=np.bool_)
         for mb in self._buckets:
             self._stage(0, np.zeros(mb, dtype=np.int32), none, self._scratch_out.data_ptr())
@@ -482,7 +586,7 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
     def step(self, perceptual_emb: Dict, latent_goal: torch.Tensor, active=None) -> torch.Tensor:
         if self.model.training or self.model.inner_model.training:       # (eval() walks every submodule: not on every step)
             self.model.eval()
-        img, gl = self._check_inputs(perceptual_emb, latent_goal)
+        inputs = self._check_inputs(perceptual_emb, latent_goal)
         act = self._active_mask(active)
         rows = np.flatnonzero(act & (self._counter == 0)).astype(np.int32)
         m = len(rows)
@@ -490,7 +594,7 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         if m:
             mb = next(b for b in self._buckets if b >= m)
             self._stage(m, np.concatenate([rows, np.full(mb - m, rows[-1], dtype=np.int32)]), act, out.data_ptr())
-            self._inputs = (img.to(torch.float32).contiguous(), gl.to(torch.float32).contiguous())
+            self._inputs = self._prepared(*inputs)
             try:
                 self._run_chunk(mb, m)
             finally:
