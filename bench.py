@@ -6,11 +6,17 @@ inputs, random-init weights (no datasets or checkpoints are reachable).
 
 A bench "step" = ONE 10-step DDIM chunk over one batch of B=128 action chunks (sample_ddim o GCDenoiser o MoDeDiT, i.e. 10
 denoiser forwards + 10 fused EDM/DDIM updates, replayed as one hipGraph).  value = n_gpus * steps * 10 / wall  [denoise-steps/s].
-Multi-GPU (inference): replicas only — each rank denoises its own B=128 batch, no data-path collective (DESIGN.md §multi-GPU);
-the data-parallel *training* step (configs[2]/[3]: fwd + bwd + gradient exchange + fused AdamW) runs in the SAME invocation on every
-rank and reports train_* / dp_mode / rccl_ranks next to the headline (also stand-alone: --mode train).
+Multi-GPU (inference): replicas only — each rank denoises its own B=128 batch, no data-path collective.
+
+A plain run measures the headline and nothing else: set-up (including the training state's device allocation, which the headline has always
+been measured on top of: main), warm-up, the timed steps, the --dump-outputs file, the JSON line.  --full adds,
+after the timed steps and in the same invocation, everything else this file measures: the dominant kernel's roofline and the sustained MFMA
+rate, the per-kernel breakdown, the rollout / B=1 / sampler / encoder legs, the data-parallel *training* step (configs[2]/[3]: fwd + bwd +
+gradient exchange + fused AdamW, on every rank: train_* / dp_mode / rccl_ranks; also stand-alone: --mode train), the agent's legs and the
+CPU baseline.  In --mode rollout it adds the agent's replanning call.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -795,8 +801,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the per-kernel breakdown and the train / rollout / B=1 legs of the default run")
+    ap.add_argument("--full", action="store_true", help="sample / rollout: after the headline, run every other measurement of this file "
+                    "(roofline, per-kernel breakdown, rollout / B=1 / sampler / encoder legs, training and agent legs, CPU baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="skip the training state's start-up allocation and, with --full, the sustained MFMA "
+                    "rate, the per-kernel breakdown and the train / rollout / B=1 / agent legs")
     ap.add_argument("--miopen-benchmark", action="store_true", help="--mode agent: torch.backends.cudnn.benchmark = True (MIOpen's exhaustive per-shape search; the "
                     "reference's trainer runs with benchmark=False, mode/training_calvin.py:96)")
     ap.add_argument("--agent-batch", type=int, default=64, help="--mode agent: samples per step (the reference's config_calvin.yaml batch_size is 64 per GPU)")
@@ -810,6 +819,7 @@ def main():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.mode not in ("sample", "rollout"):
         ap.error("--dump-outputs is implemented for --mode sample and rollout")
+    extras = args.full and not args.no_extras
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -848,7 +858,10 @@ def main():
         return agent_bench(args, world, rank, device, dist)
     M, den = build_model(device, args.dtype)
     rollout = args.mode == "rollout"
-    # the training leg's device state is allocated NOW, as a training job does at start-up (prealloc_train_state: why); MODE_BENCH_PREALLOC_TRAIN=0 = A/B
+    # the training leg's device state is allocated NOW, as a training job does at start-up (prealloc_train_state: why); MODE_BENCH_PREALLOC_TRAIN=0 = A/B.
+    # Also without --full, where no training leg follows: the headline has always been measured on top of this allocation (0.2 s), and without it
+    # the same build reads about 1 % lower (same box, runs alternated: 639.5 vs 645.0 denoise-steps/s over four pairs; a bare 14-GiB torch.empty
+    # recovers part of it, an MFMA burn of the same length none - device-memory placement, not clocks)
     train_opt = None
     if not rollout and args.dtype == "bf16" and not args.no_extras and os.environ.get("MODE_BENCH_PREALLOC_TRAIN", "1") == "1":
         train_opt = prealloc_train_state(den, device, world)
@@ -893,7 +906,7 @@ def main():
     value = denoise_steps / elapsed
     if rollout:
         agent_extra = {}
-        if rank == 0 and not args.no_extras:
+        if rank == 0 and extras:
             agent_extra = agent_replan_measure(den, device)
         if rank == 0:
             print(json.dumps({
@@ -930,13 +943,13 @@ def main():
         # the same time against the FLOPs the timed region executes (router / sigma-embedding hoisted per schedule, observation embeddings per chunk)
         res["e2e_mfma_frac_executed"] = round(flops_executed_per_chunk(B_PER_GPU) * args.steps / elapsed / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4)
         res["power"] = psamp.summary()                       # rank 0's socket over the timed region
-        if args.dtype == "bf16":
+        if args.full and args.dtype == "bf16":
             res["roofline"] = dominant_kernel_roofline(den, device)
-            if n_gpus == 1 and not args.no_extras:
+            if n_gpus == 1 and extras:
                 sp = sustained_mfma_peak(device)
                 res["roofline"]["sustained_mfma_peak"] = sp           # context for `frac`: `peak` stays the datasheet figure
                 res["roofline"]["frac_of_sustained_peak"] = round(res["roofline"]["achieved"] / sp["tflops"], 4) if sp["tflops"] else None
-            if n_gpus == 1 and not args.no_extras:
+            if n_gpus == 1 and extras:
                 res["layer_kernels"] = layer_kernel_breakdown(den, device)
                 res.update(extra_measurements(M, den, device))
     # configs[2]/[3] in the same invocation: the data-parallel training step (ALL ranks: it holds the path's one collective).  The headline above
@@ -948,7 +961,7 @@ def main():
     train_failed = False
     if rank == 0:
         print(f"[bench] headline done: {res['value']} {res['unit']} on {n_gpus} GPU(s)", file=sys.stderr, flush=True)
-    if args.dtype == "bf16" and not args.no_extras:
+    if args.dtype == "bf16" and extras:
         forced = os.environ.get("MODE_DP_ZERO1")                                # an explicit choice runs as the one and only leg (A/B runs)
         legs = [("train", forced if forced is not None else "0", None)]
         if world > 1 and forced is None and os.environ.get("MODE_BENCH_ZERO1_LEG", "1") == "1":
@@ -1015,7 +1028,7 @@ def main():
                 break
     # the path's neighbours, driver-timed in the same process (N = 1 only; after everything above, each in its own try: the headline and the
     # training leg are never at stake) - the replanning call as the agent makes it (cameras -> two FiLM-ResNet-50s -> 10-step chunk) and the agent's training step
-    if rank == 0 and n_gpus == 1 and args.dtype == "bf16" and not args.no_extras and _dry_run_layers() == 0 and not train_failed:
+    if rank == 0 and n_gpus == 1 and args.dtype == "bf16" and extras and _dry_run_layers() == 0 and not train_failed:
         try:
             res.update(agent_replan_measure(den, device))
         except Exception as e:                                                  # noqa: BLE001
@@ -1031,7 +1044,7 @@ def main():
         except Exception as e:                                                  # noqa: BLE001
             res["agent_train_error"] = repr(e)[:300]
     if rank == 0:
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if n_gpus == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline()
         print(json.dumps(res), flush=True)
     if train_failed:                                                        # the other ranks may be stuck in a collective: no final barrier

@@ -25,7 +25,7 @@ for f in sorted(glob.glob(f"{root}/pmc*/p_counter_collection.csv")):
             continue
         a = acc[(role, next(sub for sub, ro in ROLES if ro == role))][r["Counter_Name"]]
         a[0] += float(r["Counter_Value"]); a[1] += 1
-res = {"source": root, "note": "averages per launch over all sampled launches of `python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras`; "
+res = {"source": root, "note": "averages per launch over all sampled launches of `python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras`; "
                                 "one rocprofv3 --pmc pass per counter group, never combined with trace domains", "kernels": {}}
 for (role, sub), cs in sorted(acc.items(), key=lambda kv: -kv[1].get("GRBM_GUI_ACTIVE", [0, 1])[0]):
     v = {c: s / n for c, (s, n) in cs.items()}

@@ -338,7 +338,7 @@ def test_bench_train_leg_world2_dry_run_and_rccl_world1(tmp_path):
 
 
 def test_bench_main_world2_end_to_end_through_torch_distributed_run(tmp_path):
-    """The WHOLE of bench.py the way the driver launches N = 2 - ``python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2`` - on this
+    """The WHOLE of bench.py the way the driver launches N = 2 - ``python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 --full`` - on this
     one-GPU box: both ranks on cuda:0, the collective on gloo (MODE_BENCH_SHARE_GPU / MODE_BENCH_BACKEND), a 1-layer model (MODE_BENCH_DRYRUN_LAYERS:
     the gloo exchange goes through host memory).  Checks the control flow a SCALE run takes and nothing else: rendezvous, replica headline with
     MAX-over-ranks timing, all-reduce training leg first (rank count verified before timing), ZeRO-1 leg second under its own keys, ONE JSON line on
@@ -352,7 +352,7 @@ def test_bench_main_world2_end_to_end_through_torch_distributed_run(tmp_path):
                MODE_TRAIN_LEG_TIMEOUT="200", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("MODE_DP_ZERO1", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"]
+           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -375,7 +375,8 @@ def test_bench_main_world2_end_to_end_through_torch_distributed_run(tmp_path):
 
 def test_bench_dump_outputs_reproducible_across_step_counts(tmp_path):
     """``bench.py --dump-outputs DIR``: the last timed step's action chunk lands in DIR/actions.npy (float32, [B, 10, 7]); the seeded inputs make it
-    identical for any --steps / --warmup, and the JSON line reports the --steps it was given (1-layer dry-run model: plumbing, not a measurement)."""
+    identical for any --steps / --warmup, and the JSON line reports the --steps it was given and, without --full, nothing measured outside the
+    headline's timed steps (1-layer dry-run model: plumbing, not a measurement)."""
     import json
     import subprocess
     import sys
@@ -383,14 +384,15 @@ def test_bench_dump_outputs_reproducible_across_step_counts(tmp_path):
     env = dict(os.environ, MODE_BENCH_DRYRUN_LAYERS="1")
     outs = []
     for steps, warmup, d in ((2, 1, "a"), (5, 2, "b")):
-        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--no-extras",
-               "--no-cpu-baseline", "--dump-outputs", str(tmp_path / d)]
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+               "--dump-outputs", str(tmp_path / d)]
         p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, p.stderr[-3000:]
         lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
         assert len(lines) == 1, p.stdout[-2000:]
         r = json.loads(lines[0])
         assert r["steps"] == steps and r["ms_per_step"] > 0
+        assert not {"roofline", "layer_kernels", "train_ms_per_step", "agent_b1_replan_ms_graphed_encoders", "cpu_baseline"} & set(r), sorted(r)
         a = np.load(tmp_path / d / "actions.npy")
         assert a.dtype == np.float32 and a.shape == (128, 10, 7) and np.isfinite(a).all()
         outs.append(a)
