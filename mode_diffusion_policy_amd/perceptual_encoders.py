@@ -240,12 +240,6 @@ def _store_channels_last(module: nn.Module) -> None:
                 m.weight.data = m.weight.data.contiguous(memory_format=torch.channels_last)
 
 
-# {id(conv): weight already in the compute dtype}: set by GraphedVisualEncoder around its warm-up and capture, so that the per-call weight casts of
-# autocast (one launch per convolution) are not part of the replayed graph; it refreshes the copies in place when a weight's version moves.
-# Process-wide, set and restored around one call (not re-entrant: stream capture is not either).
-_W_OVERRIDE: Optional[dict] = None
-
-
 def _compute_dtype(x: torch.Tensor) -> torch.dtype:
     return torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
 
@@ -264,8 +258,9 @@ def _compute_dtype(x: torch.Tensor) -> torch.dtype:
 USE_HIP_CONV_WGRAD = __import__("os").environ.get("MODE_ENC_HIPCONV", "1") == "1"     # MODE_ENC_HIPCONV=0: A/B runs
 
 
-def _is_1x1(wshape, stride, padding, cin_mult: int = 64) -> bool:
-    return wshape[2] == 1 and wshape[3] == 1 and tuple(stride) == (1, 1) and tuple(padding) == (0, 0) and wshape[1] % cin_mult == 0 and wshape[0] % 64 == 0
+def _out_size(H: int, W_: int, kh_: int, kw_: int, stride, padding):
+    """(ho, wo) of a zero-padded, undilated convolution / pooling window."""
+    return (H + 2 * padding[0] - kh_) // stride[0] + 1, (W_ + 2 * padding[1] - kw_) // stride[1] + 1
 
 
 def _gemm_1x1_fwd(x: torch.Tensor, w_lp: torch.Tensor) -> torch.Tensor:
@@ -392,16 +387,11 @@ def _tap_table(n, H, W_, ho, wo, kh_, kw_, sh, sw, ph, pw, dev, transposed: bool
     return idx
 
 
-def _conv_taps_ok(wshape, k_per_tap: int, w_lp: Optional[torch.Tensor] = None) -> bool:
-    """Implicit-GEMM path: 64-channel K-steps inside one tap, and the weight must lie as [Cout][kh][kw][Cin] (channels_last storage)."""
-    return k_per_tap % 64 == 0 and wshape[0] % 8 == 0 and wshape[1] % 8 == 0 and (w_lp is None or w_lp.is_contiguous(memory_format=torch.channels_last))
-
-
 def _conv_fwd_taps(x: torch.Tensor, w_lp: torch.Tensor, stride, padding) -> torch.Tensor:
     """k x k convolution forward as one implicit-GEMM launch (mode_gemm with a_rows in taps, csrc/conv_gemm.hip): Y[R_out, Cout] = sum_t X[idx[t], :] W[:, t, :]^T."""
     n, cin, H, W_ = x.shape
     cout, _, kh_, kw_ = w_lp.shape
-    ho = (H + 2 * padding[0] - kh_) // stride[0] + 1; wo = (W_ + 2 * padding[1] - kw_) // stride[1] + 1
+    ho, wo = _out_size(H, W_, kh_, kw_, stride, padding)
     idx = _tap_table(n, H, W_, ho, wo, kh_, kw_, stride[0], stride[1], padding[0], padding[1], x.device)
     y = torch.empty((n, cout, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     R = n * ho * wo
@@ -425,22 +415,26 @@ def _conv_dgrad_taps(dy: torch.Tensor, w_lp: torch.Tensor, xshape, stride, paddi
     return dx
 
 
-def _conv_fwd_stats(x: torch.Tensor, w_lp: torch.Tensor, stride, padding):
-    """Training forward of a convolution that feeds a BatchNorm: y and, from the same launch's epilogue, the per-128-row-tile column sums / sums of squares of y as
-    stored (mode_conv_bn_act_fwd without epilogue terms + stat_sum / stat_sq) - the BatchNorm folds its batch statistics from them instead of re-reading y."""
+def _conv_bn_fwd(x: torch.Tensor, w_lp: torch.Tensor, stride, padding, stats: bool = False, **epilogue):
+    """Convolution + epilogue as one launch (mode_conv_bn_act_fwd, csrc/conv_gemm.hip; a 1 x 1 / stride-1 convolution reads its rows directly, any other through
+    its tap table).  ``epilogue``: the ModeConvBnDesc fields of the eval-mode BatchNorm / FiLM / residual / ReLU folded into it (conv_bn_act's inference
+    route).  ``stats``: the training route instead - y and, from the same epilogue, the per-128-row-tile column sums / sums of squares of y as stored, from
+    which the BatchNorm folds its batch statistics instead of re-reading y: returns (y, sums, sums of squares)."""
     n, cin, H, W_ = x.shape
     cout, _, kh_, kw_ = w_lp.shape
-    sh, sw = stride; ph, pw = padding
-    ho = (H + 2 * ph - kh_) // sh + 1; wo = (W_ + 2 * pw - kw_) // sw + 1
+    (sh, sw), (ph, pw) = stride, padding
+    ho, wo = _out_size(H, W_, kh_, kw_, stride, padding)
     one = kh_ == 1 and kw_ == 1 and (sh, sw) == (1, 1) and (ph, pw) == (0, 0)
     idx = None if one else _tap_table(n, H, W_, ho, wo, kh_, kw_, sh, sw, ph, pw, x.device)
     R = n * ho * wo
     y = torch.empty((n, cout, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    st = torch.empty((2, (R + 127) // 128, cout), dtype=torch.float32, device=x.device)
+    if stats:
+        st = torch.empty((2, (R + 127) // 128, cout), dtype=torch.float32, device=x.device)
+        epilogue = dict(relu=0, stat_sum=st[0].data_ptr(), stat_sq=st[1].data_ptr())
     d = L.ModeConvBnDesc(x=x.data_ptr(), ldx=cin, idx=_ptr(idx), idx_tap_stride=R, taps=kh_ * kw_, w=w_lp.data_ptr(), ldw=kh_ * kw_ * cin, y=y.data_ptr(), ldy=cout,
-                         M=R, Cin=cin, Cout=cout, relu=0, rows_per_sample=ho * wo, stat_sum=st[0].data_ptr(), stat_sq=st[1].data_ptr())
-    L.check(L.load().mode_conv_bn_act_fwd(C.byref(d), _stream()), "conv forward + BatchNorm partial statistics")
-    return y, st[0], st[1]
+                         M=R, Cin=cin, Cout=cout, rows_per_sample=ho * wo, **epilogue)
+    L.check(L.load().mode_conv_bn_act_fwd(C.byref(d), _stream()), "mode_conv_bn_act_fwd")
+    return (y, st[0], st[1]) if stats else y
 
 
 def _wgrad_taps(dy: torch.Tensor, x: torch.Tensor, wshape, stride, padding) -> torch.Tensor:
@@ -481,7 +475,7 @@ def _wgrad_taps(dy: torch.Tensor, x: torch.Tensor, wshape, stride, padding) -> t
     return dw.permute(0, 3, 1, 2)                                  # [Cout, Cin, kh, kw] view with channels_last strides
 
 
-def _aten_conv(x, w, stride, padding, why: str):
+def _aten_conv(x, w, stride, padding, why: str, bias=None, dilation=1, groups=1):
     """The ONLY way into ``F.conv2d`` (MIOpen on a ROCm device).  CPU tensors (parameter-holder use, the CPU tests' reference) and the fp32 compute dtype (the
     reference-precision / debugging mode: the library's convolutions are bf16 MFMA kernels) take it by design; the explicit A/B switches MODE_ENC_HIPCONV=0 /
     MODE_ENC_HIPSTEM=0 too.  A bf16 convolution on a ROCm device that the library's kernels do not cover (groups, dilation, a bias, channel counts that are not
@@ -490,71 +484,167 @@ def _aten_conv(x, w, stride, padding, why: str):
     if x.is_cuda and x.dtype == torch.bfloat16 and USE_HIP_CONV_WGRAD and USE_HIP_STEM and os.environ.get("MODE_ENC_ATEN_FALLBACK", "0") != "1":
         raise RuntimeError(f"perceptual_encoders: bf16 convolution outside the library's kernels ({why}; weight {tuple(w.shape)}, input {tuple(x.shape)}, "
                            f"channels_last={x.is_contiguous(memory_format=torch.channels_last)}): set MODE_ENC_ATEN_FALLBACK=1 to run it through aten / MIOpen")
-    return F.conv2d(x, w, None, stride, padding)
+    return F.conv2d(x, w, bias, stride, padding, dilation, groups)
+
+
+# Inference: convolution + eval-mode BatchNorm + FiLM + residual + ReLU as ONE launch (mode_conv_bn_act_fwd, csrc/conv_gemm.hip) - the rollout's encoders run
+# half the kernels and the convolution output never goes to memory un-normalised.  MODE_ENC_FUSE_CONV_BN=0: the two launches (A/B runs, tests).
+FUSE_CONV_BN = __import__("os").environ.get("MODE_ENC_FUSE_CONV_BN", "1") == "1"
+# training: BatchNorm partial statistics from the convolution's epilogue (ModeConvBnDesc.stat_sum / stat_sq + mode_bn_prepare_partials).  OFF by default: measured in
+# the agent's step it does not pay - 33.2-33.4 (k x k convolutions only) / 33.9-34.2 ms (all) against 33.1 without: the sums in the epilogue of a latency-bound ring
+# kernel cost what the separate, HBM-efficient statistics pass costs, and 1 x 1 convolutions would leave their tuned GEMM kernels for it.
+FUSE_CONV_STATS = __import__("os").environ.get("MODE_ENC_FUSE_CONV_STATS", "0") == "1"
+FUSE_CONV_STATS_1X1 = __import__("os").environ.get("MODE_ENC_FUSE_CONV_STATS_1X1", "0") == "1"   # ... also for 1 x 1 / stride-1 convolutions (they leave the tuned GEMM kernels for it)
+# ---- the encoders' entry on the library's kernels (round 5, csrc/conv_stem.hip, ABI 12): conv1 (3 -> 64 channels, 7 x 7 / 2: too few channels for the implicit-GEMM
+# path, MIOpen until now) gathers its im2col tile from the image as it lies (fp32 NCHW: the bf16 rounding and the layout change happen in the gather), the max-pool
+# keeps window positions for a gather-form backward.  With them no MIOpen / aten compute kernel is left in the encoders.  MODE_ENC_HIPSTEM=0: F.conv2d / F.max_pool2d.
+USE_HIP_STEM = __import__("os").environ.get("MODE_ENC_HIPSTEM", "1") == "1"
+_DT = {torch.float32: L.MODE_F32, torch.bfloat16: L.MODE_BF16}
+
+# the routes of one convolution (_route)
+_GEMM_1X1, _TAPS, _CONV_BN, _CONV_STATS, _STEM, _STEM_BN, _ATEN = "gemm_1x1", "taps", "conv_bn", "conv_stats", "stem", "stem_bn", "aten"
+
+
+def _route(conv: nn.Conv2d, x: torch.Tensor, bn: Optional[nn.BatchNorm2d] = None, residual=None, stem: bool = False):
+    """THE decision which kernels compute ``conv(x)`` - followed by ``bn`` (and ``residual``) for conv_bn_act, by ``bn`` + ReLU for the stem - from the
+    convolution, the input's dtype / layout / device, the compute dtype, grad mode and the module switches (read here, at call time).  Returns
+    ``(route, compute dtype, (ho, wo) or None, backward)``:
+
+      _GEMM_1X1   1 x 1 / stride-1 forward GEMM (mode_gemm)               _TAPS     implicit GEMM over the filter taps (mode_gemm, a_rows in taps)
+      _CONV_BN    conv + eval-BatchNorm / FiLM / residual / ReLU in ONE launch (mode_conv_bn_act_fwd; inference)
+      _CONV_STATS conv forward + the BatchNorm's partial statistics from its epilogue (training, FUSE_CONV_STATS)
+      _STEM       csrc/conv_stem.hip (``stem=True``; _STEM_BN: + eval-BatchNorm + ReLU in its epilogue)
+      _ATEN       F.conv2d (``_aten_conv``)
+      None        ``stem=True`` only: not the stem kernel's - the caller routes the channels_last input as an ordinary convolution
+
+    ``backward`` is None outside autograd, else the autograd Function's (data-gradient, weight-gradient) kernels: ``_ConvFn``'s (each _GEMM_1X1 | _TAPS |
+    _ATEN; ``route`` is then its forward kernel, _ATEN included: the Function still hands autograd the fp32 weight gradient), or the stem's (_ATEN, _STEM).
+    Moves the parameter into channels_last storage first (once; values, shape and state_dict unchanged), so no per-call weight transposes are left."""
+    w = conv.weight
+    cout, cin, kh_, kw_ = w.shape
+    cd = _compute_dtype(x)
+    grad = torch.is_grad_enabled()
+    train = grad and (w.requires_grad or x.requires_grad)
+    plain = conv.groups == 1 and conv.dilation == (1, 1) and conv.bias is None and isinstance(conv.padding, tuple)
+    stride, padding = conv.stride, conv.padding
+    if stem:
+        if not (USE_HIP_STEM and plain and x.is_cuda and x.dim() == 4 and x.dtype in _DT and cd == torch.bfloat16 and cin % 64 != 0 and cout % 16 == 0
+                and cout <= 64 and cin * kh_ * kw_ <= 256 and x.shape[1] == cin
+                and (7 * stride[0] + kh_) * (15 * stride[1] + kw_) * cin <= 8192):       # the input patch of an 8 x 16-pixel tile is staged on chip
+            return None, cd, None, None
+    if (stem or CHANNELS_LAST) and not w.is_contiguous(memory_format=torch.channels_last):
+        with torch.no_grad():
+            w.data = w.data.contiguous(memory_format=torch.channels_last)
+    if stem:
+        hw = _out_size(x.shape[2], x.shape[3], kh_, kw_, stride, padding)
+        if train:
+            return _STEM, cd, hw, (_ATEN, _STEM)
+        # the folded BatchNorm bypasses autograd and reads its statistics / affine terms as raw fp32 pointers: only when nothing of it can want a gradient (a
+        # frozen convolution in front of a trainable eval-mode BatchNorm keeps the autograd path) and every tensor is fp32 and contiguous (an encoder cast to
+        # bfloat16 would otherwise be read as garbage)
+        bn_ts = [t for t in (bn.running_mean, bn.running_var, bn.weight, bn.bias) if t is not None]
+        fold = (FUSE_CONV_BN and not bn.training and bn.running_mean is not None
+                and not (grad and any(getattr(t, "requires_grad", False) for t in (bn.weight, bn.bias) if t is not None))
+                and all(t.dtype == torch.float32 and t.is_contiguous() for t in bn_ts))
+        return (_STEM_BN if fold else _STEM), cd, hw, None
+    if not (USE_HIP_CONV_WGRAD and plain and x.is_cuda and cd == torch.bfloat16):
+        return _ATEN, cd, None, None
+    # the library's kernels read channels_last bf16 rows (x.to(cd) keeps a dense tensor's strides); the implicit GEMM steps through K in 64-channel slices of
+    # one tap and writes 8-channel vectors, and reads the weight as [Cout][kh][kw][Cin] (channels_last storage; the compute-dtype copy follows the parameter)
+    x_cl = x.is_contiguous(memory_format=torch.channels_last)
+    w_cl = w.is_contiguous(memory_format=torch.channels_last)
+    one = kh_ == 1 and kw_ == 1 and stride == (1, 1) and padding == (0, 0)
+    gemm = x_cl and one and cin % 64 == 0 and cout % 64 == 0
+    k_ok = x_cl and cin % 64 == 0 and cout % 8 == 0
+    hw = _out_size(x.shape[2], x.shape[3], kh_, kw_, stride, padding) if x_cl else None
+    bwd = None
+    if train:
+        bwd = (_GEMM_1X1 if (x_cl and one and cin % 8 == 0 and cout % 64 == 0) else _TAPS if (x_cl and cout % 64 == 0 and cin % 8 == 0 and w_cl) else _ATEN,
+               (_GEMM_1X1 if one else _TAPS) if (x_cl and cin % 8 == 0 and cout % 8 == 0) else _ATEN)
+    if bn is not None and k_ok:
+        if (FUSE_CONV_BN and not grad and not bn.training and bn.running_mean is not None and (one or w_cl)
+                and (residual is None or (residual.shape == (x.shape[0], cout) + hw and residual.is_contiguous(memory_format=torch.channels_last)))):
+            return _CONV_BN, cd, hw, None
+        if FUSE_CONV_STATS and train and bn.training and not isinstance(bn, nn.SyncBatchNorm) and w_cl and (FUSE_CONV_STATS_1X1 or not gemm):
+            return _CONV_STATS, cd, hw, bwd
+    return (_GEMM_1X1 if gemm else _TAPS if (k_ok and w_cl) else _ATEN), cd, hw, bwd
 
 
 class _ConvFn(torch.autograd.Function):
-    """y = conv2d(x, w) computed with `w_lp` (w in the compute dtype); differentiable in x and in the fp32 PARAMETER w."""
+    """y = conv2d(x, w) computed with `w_lp` (w in the compute dtype) on the kernels `_route` picked; differentiable in x and in the fp32 PARAMETER w.
+    ``plan`` = (stride, padding, forward route, (data-gradient, weight-gradient) routes); a _CONV_STATS forward also returns the partial BatchNorm statistics."""
 
     @staticmethod
-    def forward(ctx, x, w, w_lp, stride, padding, want_stats=False):
+    def forward(ctx, x, w, w_lp, plan):
+        stride, padding, fwd, _ = plan
         ctx.save_for_backward(x, w_lp)
-        ctx.conf = (tuple(stride), tuple(padding), tuple(w.shape), w.dtype)
-        if want_stats:                                            # (the caller checked the kernel's contract) y + the partial BatchNorm statistics of y
-            y, ps, pq = _conv_fwd_stats(x, w_lp, stride, padding)
+        ctx.conf = (plan, tuple(w.shape), w.dtype)
+        if fwd == _CONV_STATS:
+            y, ps, pq = _conv_bn_fwd(x, w_lp, stride, padding, stats=True)
             ctx.mark_non_differentiable(ps, pq)
             return y, ps, pq
-        if x.dtype == torch.bfloat16 and x.is_contiguous(memory_format=torch.channels_last):
-            if _is_1x1(w.shape, stride, padding):
-                return _gemm_1x1_fwd(x, w_lp)
-            if _conv_taps_ok(w.shape, w.shape[1], w_lp):
-                return _conv_fwd_taps(x, w_lp, stride, padding)
+        if fwd == _GEMM_1X1:
+            return _gemm_1x1_fwd(x, w_lp)
+        if fwd == _TAPS:
+            return _conv_fwd_taps(x, w_lp, stride, padding)
         return _aten_conv(x, w_lp, stride, padding, "training forward")
 
     @staticmethod
     def backward(ctx, dy, *_unused):
+        # (dy is bf16 like the forward's output: x and w_lp are the compute dtype)
         x, w_lp = ctx.saved_tensors
-        stride, padding, wshape, wdtype = ctx.conf
+        (stride, padding, _, (dgrad, wgrad)), wshape, wdtype = ctx.conf
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        dw = None
-        if (need_w and x.dtype == torch.bfloat16 and dy.dtype == torch.bfloat16 and wshape[0] % 8 == 0 and wshape[1] % 8 == 0
-                and x.is_contiguous(memory_format=torch.channels_last)):
+        dx = dw = None
+        if (need_w and wgrad != _ATEN) or (need_x and dgrad != _ATEN):
             dyc = dy.contiguous(memory_format=torch.channels_last)
-            if wshape[2] == 1 and wshape[3] == 1 and stride == (1, 1) and padding == (0, 0):
-                dw = _wgrad_1x1(dyc, x, wshape)
-            else:
-                dw = _wgrad_taps(dyc, x, wshape, stride, padding)
+        if need_w and wgrad != _ATEN:
+            dw = _wgrad_1x1(dyc, x, wshape) if wgrad == _GEMM_1X1 else _wgrad_taps(dyc, x, wshape, stride, padding)
             need_w = False
-        dx = None
-        if need_x and dy.dtype == torch.bfloat16 and x.is_contiguous(memory_format=torch.channels_last):
-            if _is_1x1(wshape, stride, padding, 8):
-                dx = _gemm_1x1_dgrad(dy.contiguous(memory_format=torch.channels_last), w_lp, x.shape)
-                need_x = False
-            elif _conv_taps_ok(wshape, wshape[0], w_lp):
-                dx = _conv_dgrad_taps(dy.contiguous(memory_format=torch.channels_last), w_lp, x.shape, stride, padding)
-                need_x = False
+        if need_x and dgrad != _ATEN:
+            dx = _gemm_1x1_dgrad(dyc, w_lp, x.shape) if dgrad == _GEMM_1X1 else _conv_dgrad_taps(dyc, w_lp, x.shape, stride, padding)
+            need_x = False
         if need_x or need_w:
             dxl, dwl, _ = torch.ops.aten.convolution_backward(dy, x, w_lp, None, stride, padding, (1, 1), False, (0, 0), 1, (need_x, need_w, False))
             if need_x:
                 dx = dxl
             if need_w:
                 dw = dwl.to(wdtype)
-        return dx, dw, None, None, None, None
+        return dx, dw, None, None
 
 
+# ---- the ONE store of compute-dtype convolution weights: a copy of `conv.weight` per (convolution, dtype), cached on the module (not a buffer: never in a
+# state_dict), allocated like the parameter and refreshed IN PLACE when the parameter's version counter / storage moved (`_shadow` per convolution,
+# `refresh_conv_shadows` for a whole encoder in one `_foreach_copy_`).  It is never re-allocated while the parameter's storage, shape and device stay put:
+# GraphedVisualEncoder's / VectorEnvPolicy's captured graphs hold its pointer (and keep it alive), and any of those changes alters
+# GraphedVisualEncoder._param_key, which re-captures.  An in-place refresh cannot race a reader: it is enqueued on the stream that then reads the copy - a
+# replay runs after the refresh on the same stream, and the gripper tower's side stream waits on the main stream at the fork (embed_visual_obs) and the
+# main stream on it at the join, so a refresh before the fork precedes the tower's reads and the next one follows them.  A training forward refreshes its own
+# encoder's copies on the stream that tower runs on.
 def _wver(conv: nn.Conv2d):
     """What a cached copy of `conv.weight` is valid for: torch's version counter + the module's invalidation generation (invalidate_conv_shadows)."""
     return (conv.weight._version, conv.__dict__.get("_mode_wgen", 0))
 
 
-def _shadow(conv: nn.Conv2d, dtype: torch.dtype) -> torch.Tensor:
-    """The convolution's weight in the compute dtype, cached on the module (not a buffer: never in a state_dict) and refreshed in place when the
-    parameter changes (its version counter / storage moved).  Staleness rests on torch's version counter: optimizers, `load_state_dict`, `copy_` and every
-    other in-place torch op bump it; code that writes a parameter through a raw pointer must bump it too (`torch.autograd.graph.increment_version`)."""
+def _shadow_entry(conv: nn.Conv2d, dtype: torch.dtype) -> list:
+    """[valid-for version, valid-for storage pointer, the copy] of ``conv.weight`` in ``dtype``."""
     w = conv.weight
-    ent = conv.__dict__.get("_mode_lp")
-    if ent is None or ent[2].dtype != dtype or ent[2].device != w.device or ent[2].shape != w.shape:
-        ent = conv.__dict__["_mode_lp"] = [-1, 0, torch.empty_like(w, dtype=dtype)]
+    store = conv.__dict__.get("_mode_lp")
+    if store is None:
+        store = conv.__dict__["_mode_lp"] = {}
+    ent = store.get(dtype)
+    # (the layout can only change with the storage: compared only when that moved)
+    if ent is None or ent[2].device != w.device or ent[2].shape != w.shape or (ent[1] != w.data_ptr() and ent[2].stride() != w.stride()):
+        ent = store[dtype] = [None, 0, torch.empty_like(w, dtype=dtype)]
+    return ent
+
+
+def _shadow(conv: nn.Conv2d, dtype: torch.dtype) -> torch.Tensor:
+    """The convolution's weight in the compute dtype, refreshed when the parameter changed.  Staleness rests on torch's version counter: optimizers,
+    `load_state_dict`, `copy_` and every other in-place torch op bump it; code that writes a parameter through a raw pointer must bump it too
+    (`torch.autograd.graph.increment_version`)."""
+    ent = _shadow_entry(conv, dtype)
+    w = conv.weight
     if ent[0] != _wver(conv) or ent[1] != w.data_ptr():
         with torch.no_grad():
             ent[2].copy_(w)
@@ -562,8 +652,8 @@ def _shadow(conv: nn.Conv2d, dtype: torch.dtype) -> torch.Tensor:
     return ent[2]
 
 
-def refresh_conv_shadows(module: nn.Module, dtype: torch.dtype, force: bool = False) -> None:
-    """The compute-dtype weight shadows of `module`'s convolutions in ONE multi-tensor copy (instead of one cast launch per convolution).
+def refresh_conv_shadows(module: nn.Module, dtype: torch.dtype, force: bool = False) -> List[torch.Tensor]:
+    """The compute-dtype weight copies of `module`'s convolutions in ONE multi-tensor copy (instead of one cast launch per convolution); returns them.
     ``force=False`` copies only the shadows whose parameter's version counter / storage moved.  ``force=True`` copies all of them: the encoders'
     TRAINING forward (grad mode) does that once per call, because a write through ``p.data`` (``p.data.copy_(ema)``, ``p.data.mul_()``,
     ``w.data.normal_()``) does NOT bump ``p._version`` and a version-gated cache would silently keep computing with the old weights in both the
@@ -572,23 +662,23 @@ def refresh_conv_shadows(module: nn.Module, dtype: torch.dtype, force: bool = Fa
     convs = module.__dict__.get("_mode_convs")
     if convs is None:
         convs = module.__dict__["_mode_convs"] = [m for m in module.modules() if isinstance(m, nn.Conv2d)]
-    src, dst = [], []
+    src, dst, out = [], [], []
     for c in convs:
         w = c.weight
-        ent = c.__dict__.get("_mode_lp")
-        if ent is None or ent[2].dtype != dtype or ent[2].device != w.device or ent[2].shape != w.shape:
-            ent = c.__dict__["_mode_lp"] = [-1, 0, torch.empty_like(w, dtype=dtype)]
+        ent = _shadow_entry(c, dtype)
         if force or ent[0] != _wver(c) or ent[1] != w.data_ptr():
             src.append(w.detach()); dst.append(ent[2])
             ent[0], ent[1] = _wver(c), w.data_ptr()
+        out.append(ent[2])
     if dst:
         with torch.no_grad():
             torch._foreach_copy_(dst, src)
+    return out
 
 
 def invalidate_conv_shadows(module: nn.Module) -> None:
-    """Mark every cached compute-dtype convolution weight under `module` stale (eager shadows AND the copies `GraphedVisualEncoder` replays
-    against): the next forward re-casts them in place.  Call it after writing weights in a way torch's version counter does not see -
+    """Mark every cached compute-dtype convolution weight under `module` stale (what the eager forward and the captured graphs read alike): the next
+    forward / replay re-casts them in place.  Call it after writing weights in a way torch's version counter does not see -
     ``p.data.copy_() / p.data.mul_()`` (EMA swaps), raw-pointer writes.  In-place ops on the Parameter itself, optimizers and
     ``load_state_dict`` bump the counter and need no call."""
     for m in module.modules():
@@ -596,35 +686,20 @@ def invalidate_conv_shadows(module: nn.Module) -> None:
             m.__dict__["_mode_wgen"] = m.__dict__.get("_mode_wgen", 0) + 1
 
 
-def _conv2d(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
-    """conv2d through MIOpen with the module's weight in the activations' dtype and layout.  The PARAMETER's storage is converted to channels_last
-    once (values, shape and state_dict unchanged), so no per-call weight transposes are left."""
-    w = conv.weight
-    if CHANNELS_LAST and w.dim() == 4 and not w.is_contiguous(memory_format=torch.channels_last):
-        with torch.no_grad():
-            w.data = w.data.contiguous(memory_format=torch.channels_last)
-    cd = _compute_dtype(x)
-    hip_ok = (USE_HIP_CONV_WGRAD and x.is_cuda and cd == torch.bfloat16 and conv.groups == 1 and conv.dilation == (1, 1) and conv.bias is None
-              and isinstance(conv.padding, tuple))
-    hip_1x1 = hip_ok and _is_1x1(w.shape, conv.stride, conv.padding)
-    hip_taps = hip_ok and not hip_1x1 and _conv_taps_ok(w.shape, w.shape[1])
-    if _W_OVERRIDE is not None:
-        hit = _W_OVERRIDE.get(id(conv))
-        if hit is not None and hit.dtype == cd:
-            xc = x.to(hit.dtype)
-            if hip_1x1 and xc.is_contiguous(memory_format=torch.channels_last):
-                return _gemm_1x1_fwd(xc, hit)
-            if hip_taps and xc.is_contiguous(memory_format=torch.channels_last) and hit.is_contiguous(memory_format=torch.channels_last):
-                return _conv_fwd_taps(xc, hit, conv.stride, conv.padding)
-            return _aten_conv(xc, hit, conv.stride, conv.padding, "captured weight shadow")
-    if (hip_1x1 or hip_taps) and not (torch.is_grad_enabled() and (w.requires_grad or x.requires_grad)):
+def _conv2d(conv: nn.Conv2d, x: torch.Tensor, plan=None) -> torch.Tensor:
+    """``conv(x)`` (no bias: the trunk's convolutions have none) on the route ``plan`` = `_route(conv, x)` - the library's kernels on the weight's
+    compute-dtype copy, autograd through `_ConvFn`, or aten."""
+    route, cd, _, bwd = plan if plan is not None else _route(conv, x)
+    if bwd is not None:
+        return _ConvFn.apply(x.to(cd), conv.weight, _shadow(conv, cd), (conv.stride, conv.padding, route, bwd))
+    if route == _GEMM_1X1:
         xc = x.to(cd)
-        if xc.is_contiguous(memory_format=torch.channels_last):                    # inference: the shadow also saves the per-call weight cast
-            return _gemm_1x1_fwd(xc, _shadow(conv, cd)) if hip_1x1 else _conv_fwd_taps(xc, _shadow(conv, cd), conv.stride, conv.padding)
-    if (USE_HIP_CONV_WGRAD and x.is_cuda and cd == torch.bfloat16 and torch.is_grad_enabled() and (w.requires_grad or x.requires_grad) and conv.groups == 1
-            and conv.dilation == (1, 1) and conv.bias is None and isinstance(conv.padding, tuple)):
-        return _ConvFn.apply(x.to(cd), w, _shadow(conv, cd), conv.stride, conv.padding)
-    return _aten_conv(x, w.to(x.dtype), conv.stride, conv.padding, "unsupported geometry / layout")
+        return _gemm_1x1_fwd(xc, _shadow(conv, cd))
+    if route == _TAPS:
+        xc = x.to(cd)
+        return _conv_fwd_taps(xc, _shadow(conv, cd), conv.stride, conv.padding)
+    bias = None if conv.bias is None else conv.bias.to(x.dtype)
+    return _aten_conv(x, conv.weight.to(x.dtype), conv.stride, conv.padding, "unsupported geometry / layout", bias, conv.dilation, conv.groups)
 
 
 def bn_film_act(x, bn: nn.BatchNorm2d, relu: bool = True, residual=None, pre_film=None, post_film=None, stats=None):
@@ -643,16 +718,6 @@ def bn_film_act(x, bn: nn.BatchNorm2d, relu: bool = True, residual=None, pre_fil
                              torch.is_grad_enabled(), s0, s1))
 
 
-# Inference: convolution + eval-mode BatchNorm + FiLM + residual + ReLU as ONE launch (mode_conv_bn_act_fwd, csrc/conv_gemm.hip) - the rollout's encoders run
-# half the kernels and the convolution output never goes to memory un-normalised.  MODE_ENC_FUSE_CONV_BN=0: the two launches (A/B runs, tests).
-FUSE_CONV_BN = __import__("os").environ.get("MODE_ENC_FUSE_CONV_BN", "1") == "1"
-# training: BatchNorm partial statistics from the convolution's epilogue (ModeConvBnDesc.stat_sum / stat_sq + mode_bn_prepare_partials).  OFF by default: measured in
-# the agent's step it does not pay - 33.2-33.4 (k x k convolutions only) / 33.9-34.2 ms (all) against 33.1 without: the sums in the epilogue of a latency-bound ring
-# kernel cost what the separate, HBM-efficient statistics pass costs, and 1 x 1 convolutions would leave their tuned GEMM kernels for it.
-FUSE_CONV_STATS = __import__("os").environ.get("MODE_ENC_FUSE_CONV_STATS", "0") == "1"
-FUSE_CONV_STATS_1X1 = __import__("os").environ.get("MODE_ENC_FUSE_CONV_STATS_1X1", "0") == "1"   # ... also for 1 x 1 / stride-1 convolutions (they leave the tuned GEMM kernels for it)
-
-
 def _film_arg(t, n: int, c: int):
     return None if t is None else t.reshape(n, c).to(torch.float32).contiguous()
 
@@ -660,68 +725,23 @@ def _film_arg(t, n: int, c: int):
 def conv_bn_act(conv: nn.Conv2d, bn: nn.BatchNorm2d, x, relu: bool = True, residual=None, pre_film=None, post_film=None):
     """``bn_film_act(_conv2d(conv, x), bn, ...)``; on the inference path (no grad, eval-mode BatchNorm with running statistics, bf16 compute, a channel count
     the implicit-GEMM kernel takes) as one launch."""
-    w = conv.weight
-    cd = _compute_dtype(x)
-    if (FUSE_CONV_BN and USE_HIP_CONV_WGRAD and x.is_cuda and cd == torch.bfloat16 and not torch.is_grad_enabled() and not bn.training and bn.running_mean is not None
-            and conv.groups == 1 and conv.dilation == (1, 1) and conv.bias is None and isinstance(conv.padding, tuple) and w.shape[1] % 64 == 0 and w.shape[0] % 8 == 0):
-        w_lp = None
-        if _W_OVERRIDE is not None:
-            hit = _W_OVERRIDE.get(id(conv))
-            if hit is not None and hit.dtype == cd:
-                w_lp = hit
-        if w_lp is None:
-            if CHANNELS_LAST and not w.is_contiguous(memory_format=torch.channels_last):
-                with torch.no_grad():
-                    w.data = w.data.contiguous(memory_format=torch.channels_last)
-            w_lp = _shadow(conv, cd)
-        xc = x.to(cd)
-        n, cin, H, W_ = xc.shape
-        cout, _, kh_, kw_ = w.shape
-        sh, sw = conv.stride; ph, pw = conv.padding
-        ho = (H + 2 * ph - kh_) // sh + 1; wo = (W_ + 2 * pw - kw_) // sw + 1
-        one = kh_ == 1 and kw_ == 1 and (sh, sw) == (1, 1) and (ph, pw) == (0, 0)
-        res = None if residual is None else residual.to(cd)
-        if (xc.is_contiguous(memory_format=torch.channels_last) and (one or w_lp.is_contiguous(memory_format=torch.channels_last))
-                and (res is None or (res.shape == (n, cout, ho, wo) and res.is_contiguous(memory_format=torch.channels_last)))):
-            idx = None if one else _tap_table(n, H, W_, ho, wo, kh_, kw_, sh, sw, ph, pw, xc.device)
-            pg, pb = (_film_arg(pre_film[0], n, cout), _film_arg(pre_film[1], n, cout)) if pre_film is not None else (None, None)
-            qg, qb = (_film_arg(post_film[0], n, cout), _film_arg(post_film[1], n, cout)) if post_film is not None else (None, None)
-            y = torch.empty((n, cout, ho, wo), dtype=cd, device=xc.device, memory_format=torch.channels_last)
-            R = n * ho * wo
-            d = L.ModeConvBnDesc(x=xc.data_ptr(), ldx=cin, idx=_ptr(idx), idx_tap_stride=R, taps=kh_ * kw_, w=w_lp.data_ptr(), ldw=kh_ * kw_ * cin, y=y.data_ptr(), ldy=cout,
-                                 M=R, Cin=cin, Cout=cout, bn_mean=_ptr(bn.running_mean), bn_var=_ptr(bn.running_var), bn_weight=_ptr(bn.weight), bn_bias=_ptr(bn.bias),
-                                 bn_eps=bn.eps, residual=_ptr(res), ldr=cout, relu=int(relu), pre_gamma=_ptr(pg), pre_beta=_ptr(pb), post_gamma=_ptr(qg), post_beta=_ptr(qb),
-                                 rows_per_sample=ho * wo)
-            L.check(L.load().mode_conv_bn_act_fwd(C.byref(d), _stream()), "mode_conv_bn_act_fwd")
-            return y
-    if (FUSE_CONV_STATS and USE_HIP_CONV_WGRAD and x.is_cuda and cd == torch.bfloat16 and torch.is_grad_enabled() and bn.training and not isinstance(bn, nn.SyncBatchNorm)
-            and (w.requires_grad or x.requires_grad) and conv.groups == 1 and conv.dilation == (1, 1) and conv.bias is None and isinstance(conv.padding, tuple)
-            and w.shape[1] % 64 == 0 and w.shape[0] % 8 == 0 and (FUSE_CONV_STATS_1X1 or not _is_1x1(w.shape, conv.stride, conv.padding))):
-        # training: the convolution's epilogue also writes the partial batch statistics of its output (one pass over y less per BatchNorm)
-        if CHANNELS_LAST and not w.is_contiguous(memory_format=torch.channels_last):
-            with torch.no_grad():
-                w.data = w.data.contiguous(memory_format=torch.channels_last)
-        xc = x.to(cd)
+    plan = _route(conv, x, bn, residual)
+    route, cd, hw = plan[:3]
+    if route == _CONV_BN:
         w_lp = _shadow(conv, cd)
-        if xc.is_contiguous(memory_format=torch.channels_last) and w_lp.is_contiguous(memory_format=torch.channels_last):
-            y, ps, pq = _ConvFn.apply(xc, w, w_lp, conv.stride, conv.padding, True)
-            return bn_film_act(y, bn, relu=relu, residual=residual, pre_film=pre_film, post_film=post_film, stats=(ps, pq))
-    return bn_film_act(_conv2d(conv, x), bn, relu=relu, residual=residual, pre_film=pre_film, post_film=post_film)
-
-
-# ---- the encoders' entry on the library's kernels (round 5, csrc/conv_stem.hip, ABI 12): conv1 (3 -> 64 channels, 7 x 7 / 2: too few channels for the implicit-GEMM
-# path, MIOpen until now) gathers its im2col tile from the image as it lies (fp32 NCHW: the bf16 rounding and the layout change happen in the gather), the max-pool
-# keeps window positions for a gather-form backward.  With them no MIOpen / aten compute kernel is left in the encoders.  MODE_ENC_HIPSTEM=0: F.conv2d / F.max_pool2d.
-USE_HIP_STEM = __import__("os").environ.get("MODE_ENC_HIPSTEM", "1") == "1"
-_DT = {torch.float32: L.MODE_F32, torch.bfloat16: L.MODE_BF16}
-
-
-def _stem_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
-    w = conv.weight
-    return (USE_HIP_STEM and x.is_cuda and x.dim() == 4 and x.dtype in _DT and _compute_dtype(x) == torch.bfloat16 and conv.groups == 1 and conv.dilation == (1, 1)
-            and conv.bias is None and isinstance(conv.padding, tuple) and w.shape[1] % 64 != 0 and w.shape[0] % 16 == 0 and w.shape[0] <= 64
-            and w.shape[1] * w.shape[2] * w.shape[3] <= 256 and x.shape[1] == w.shape[1]
-            and (7 * conv.stride[0] + w.shape[2]) * (15 * conv.stride[1] + w.shape[3]) * w.shape[1] <= 8192)      # the input patch of an 8 x 16-pixel tile is staged on chip
+        xc = x.to(cd)
+        n, cout = xc.shape[0], w_lp.shape[0]
+        res = None if residual is None else residual.to(cd)
+        pg, pb = (_film_arg(pre_film[0], n, cout), _film_arg(pre_film[1], n, cout)) if pre_film is not None else (None, None)
+        qg, qb = (_film_arg(post_film[0], n, cout), _film_arg(post_film[1], n, cout)) if post_film is not None else (None, None)
+        return _conv_bn_fwd(xc, w_lp, conv.stride, conv.padding, bn_mean=_ptr(bn.running_mean), bn_var=_ptr(bn.running_var), bn_weight=_ptr(bn.weight),
+                            bn_bias=_ptr(bn.bias), bn_eps=bn.eps, residual=_ptr(res), ldr=cout, relu=int(relu), pre_gamma=_ptr(pg), pre_beta=_ptr(pb),
+                            post_gamma=_ptr(qg), post_beta=_ptr(qb))
+    if route == _CONV_STATS:
+        # training: the convolution's epilogue also writes the partial batch statistics of its output (one pass over y less per BatchNorm)
+        y, ps, pq = _ConvFn.apply(x.to(cd), conv.weight, _shadow(conv, cd), (conv.stride, conv.padding, route, plan[3]))
+        return bn_film_act(y, bn, relu=relu, residual=residual, pre_film=pre_film, post_film=post_film, stats=(ps, pq))
+    return bn_film_act(_conv2d(conv, x, plan), bn, relu=relu, residual=residual, pre_film=pre_film, post_film=post_film)
 
 
 def _stem_desc(x: torch.Tensor, w_lp: torch.Tensor, stride, padding, **kw):
@@ -736,7 +756,7 @@ def _stem_fwd(x: torch.Tensor, w_lp: torch.Tensor, stride, padding, bn: Optional
     assert w_lp.dtype == torch.bfloat16 and w_lp.is_contiguous(memory_format=torch.channels_last)
     n, _, H, W_ = x.shape
     cout, _, kh_, kw_ = w_lp.shape
-    ho = (H + 2 * padding[0] - kh_) // stride[0] + 1; wo = (W_ + 2 * padding[1] - kw_) // stride[1] + 1
+    ho, wo = _out_size(H, W_, kh_, kw_, stride, padding)
     y = torch.empty((n, cout, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
     ep = {} if bn is None else dict(bn_mean=_ptr(bn.running_mean), bn_var=_ptr(bn.running_var), bn_weight=_ptr(bn.weight), bn_bias=_ptr(bn.bias), bn_eps=bn.eps)
     d = _stem_desc(x, w_lp, stride, padding, y=y.data_ptr(), relu=int(relu), **ep)
@@ -779,7 +799,7 @@ class _MaxPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, k, s, p):
         n, c, H, W_ = x.shape
-        ho = (H + 2 * p - k) // s + 1; wo = (W_ + 2 * p - k) // s + 1
+        ho, wo = _out_size(H, W_, k, k, (s, s), (p, p))
         y = torch.empty((n, c, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
         arg = torch.empty((n, ho, wo, c), dtype=torch.uint8, device=x.device) if ctx.needs_input_grad[0] else None     # window positions only when a backward will follow
         L.check(L.load().mode_maxpool_nhwc_fwd(x.data_ptr(), _DT[x.dtype], n, H, W_, c, k, s, p, y.data_ptr(), _ptr(arg), _stream()), "max-pool forward")
@@ -810,37 +830,17 @@ def max_pool(x: torch.Tensor, k: int = 3, s: int = 2, p: int = 1) -> torch.Tenso
 
 def stem_conv_bn_pool(conv: nn.Conv2d, bn: nn.BatchNorm2d, x: torch.Tensor) -> torch.Tensor:
     """``max_pool2d(relu(bn(conv(x))), 3, 2, 1)`` - the trunk's entry (timm / torchvision ResNet: conv1, bn1, act1 / relu, maxpool)."""
-    if not _stem_ok(conv, x):
+    route, _, _, bwd = _route(conv, x, bn, stem=True)
+    if route is None:
         return max_pool(bn_film_act(_conv2d(conv, _to_layout(x)), bn, relu=True))
-    w = conv.weight
-    if not w.is_contiguous(memory_format=torch.channels_last):
-        with torch.no_grad():
-            w.data = w.data.contiguous(memory_format=torch.channels_last)
-    w_lp = None
-    if _W_OVERRIDE is not None:
-        hit = _W_OVERRIDE.get(id(conv))
-        if hit is not None and hit.dtype == torch.bfloat16 and hit.is_contiguous(memory_format=torch.channels_last):
-            w_lp = hit
-    train = torch.is_grad_enabled() and (w.requires_grad or x.requires_grad)
-    if w_lp is None:
-        w_lp = _shadow(conv, torch.bfloat16)
-    if train:
-        y = bn_film_act(_StemConvFn.apply(x, w, w_lp, conv.stride, conv.padding), bn, relu=True)
-    elif FUSE_CONV_BN and not bn.training and bn.running_mean is not None and _bn_fusable(bn):
+    w_lp = _shadow(conv, torch.bfloat16)
+    if bwd is not None:
+        y = bn_film_act(_StemConvFn.apply(x, conv.weight, w_lp, conv.stride, conv.padding), bn, relu=True)
+    elif route == _STEM_BN:
         y = _stem_fwd(x, w_lp, conv.stride, conv.padding, bn=bn, relu=True)          # inference: convolution + BatchNorm + ReLU in one launch
     else:
         y = bn_film_act(_stem_fwd(x, w_lp, conv.stride, conv.padding), bn, relu=True)
     return max_pool(y)
-
-
-def _bn_fusable(bn) -> bool:
-    """The folded conv + BatchNorm inference launch bypasses autograd and reads the BatchNorm statistics / affine terms as raw fp32 pointers: only when nothing of
-    the BatchNorm can want a gradient (a frozen convolution in front of a trainable eval-mode BatchNorm must keep the autograd path) and every tensor is fp32
-    and contiguous (an encoder cast to bfloat16 would otherwise be read as garbage)."""
-    ts = [t for t in (bn.running_mean, bn.running_var, bn.weight, bn.bias) if t is not None]
-    if torch.is_grad_enabled() and any(getattr(t, "requires_grad", False) for t in (bn.weight, bn.bias) if t is not None):
-        return False
-    return all(t.dtype == torch.float32 and t.is_contiguous() for t in ts)
 
 
 # ------------------------------------------------------------------------------------------------------------------ trunk (parameter holders)
@@ -862,9 +862,6 @@ class _Block(nn.Module):
         if stride != 1 or inplanes != out:
             self.downsample = nn.Sequential(nn.Conv2d(inplanes, out, 1, stride=stride, bias=False), nn.BatchNorm2d(out))
         self.out_channels = out
-
-    def _conv(self, conv: nn.Conv2d, x):
-        return _conv2d(conv, x)
 
     def forward(self, x, pre_film=None, post_film=None):
         """``pre_film``: FiLM on the last BatchNorm's output before the skip add (resnets.py:64-71); ``post_film``: FiLM on the block output (the
@@ -1105,47 +1102,21 @@ class GraphedVisualEncoder:
         self.static_resnet, self.gripper_resnet = static_resnet, gripper_resnet
         self.autocast_dtype, self.max_graphs = autocast_dtype, max_graphs
         self._graphs = {}
-        self._fork = None
 
     def _eager(self, rgb_static, rgb_gripper, latent_goal):
-        """embed_visual_obs with the two cameras on two streams (fork / join): at rollout batch sizes every kernel is a few microseconds of a
-        dependent chain, and the two encoders do not depend on each other - captured, they become two parallel branches of the graph."""
+        """The (B, 2 T, obs_dim) tokens of :func:`embed_visual_obs` under this pair's autocast: the eager call, and what the graphs capture (the two
+        towers as two parallel branches)."""
         import contextlib
-        ac = (lambda: torch.autocast("cuda", dtype=self.autocast_dtype)) if self.autocast_dtype is not None else contextlib.nullcontext
-        B, T = rgb_static.shape[0], rgb_static.shape[1]
-        s = rgb_static.reshape(B * T, *rgb_static.shape[2:]); g = rgb_gripper.reshape(B * T, *rgb_gripper.shape[2:])
-        cur = torch.cuda.current_stream(rgb_static.device)
-        if self._fork is None or self._fork.device != rgb_static.device:
-            self._fork = torch.cuda.Stream(device=rgb_static.device)
-        self._fork.wait_stream(cur)
-        with torch.cuda.stream(self._fork), ac():
-            gt = self.gripper_resnet(g, latent_goal) if latent_goal is not None else self.gripper_resnet(g)
-        with ac():
-            st = self.static_resnet(s, latent_goal) if latent_goal is not None else self.static_resnet(s)
-        cur.wait_stream(self._fork)
-        return torch.cat([st.reshape(B, T, -1), gt.reshape(B, T, -1)], dim=1)
+        ac = torch.autocast("cuda", dtype=self.autocast_dtype) if self.autocast_dtype is not None else contextlib.nullcontext()
+        with ac:
+            return embed_visual_obs(self.static_resnet, self.gripper_resnet, rgb_static, rgb_gripper, latent_goal)["state_images"]
 
-    def _weights(self, dtype: torch.dtype) -> dict:
-        """Convolution weights of both encoders in the compute dtype, refreshed IN PLACE when a Parameter's version (or storage) changed - the graph
-        reads these copies, so an in-place weight update is seen by the next replay."""
-        cache = self.__dict__.setdefault("_wcache", {})
-        convs = self.__dict__.get("_convs")
-        if convs is None:                                                        # the module tree is fixed: walk it once
-            convs = self._convs = [m for enc in (self.static_resnet, self.gripper_resnet) for m in enc.modules() if isinstance(m, nn.Conv2d)]
-        out = {}
-        for m in convs:
-            w = m.weight
-            # one copy per (convolution, dtype, device): a graph captured for another input dtype keeps reading ITS copies - nothing a captured graph
-            # points at is ever re-allocated while the parameter itself stays where it is (a moved parameter changes _param_key -> new graphs)
-            ck = (id(m), dtype, str(w.device))
-            ent = cache.get(ck)
-            if ent is None:
-                ent = cache[ck] = [None, None, torch.empty_like(w, dtype=dtype)]
-            if ent[0] != _wver(m) or ent[1] != w.data_ptr():
-                ent[2].copy_(w)
-                ent[0], ent[1] = _wver(m), w.data_ptr()
-            out[id(m)] = ent[2]
-        return out
+    def _refresh(self, dtype: torch.dtype) -> List[torch.Tensor]:
+        """The compute-dtype convolution weights the graphs read (the shadows of both encoders, only bf16 ever is one), refreshed in place where a
+        parameter's version or storage moved; returns them."""
+        if dtype != torch.bfloat16:
+            return []
+        return refresh_conv_shadows(self.static_resnet, dtype) + refresh_conv_shadows(self.gripper_resnet, dtype)
 
     def _param_key(self):
         """Fingerprint of where EVERY tensor the captured graphs read lives (convolution / BatchNorm / FiLM parameters and the BatchNorm buffers of both
@@ -1153,20 +1124,18 @@ class GraphedVisualEncoder:
         return hash(tuple(t.data_ptr() for m in (self.static_resnet, self.gripper_resnet) for t in list(m.parameters()) + list(m.buffers())))
 
     def capture(self, fn, device, wdt: torch.dtype):
-        """(graph, fn's result, the index tables it reads) of ``fn`` - a call of the encoders - captured with the compute-dtype weight copies of
-        :meth:`_weights` and every index table the warm-up / capture touches pinned next to the graph.  Also the per-bucket encoder graphs of
-        ``rollout.VectorEnvPolicy``, which keeps them in its own store."""
+        """(graph, fn's result, what the graph reads by pointer and must keep alive) of ``fn`` - a call of the encoders - captured against the
+        freshly refreshed compute-dtype weight copies, with every index table the warm-up / capture touches pinned next to the graph.  Also the
+        per-bucket encoder graphs of ``rollout.VectorEnvPolicy``, which keeps them in its own store."""
         from .engine import warm_and_capture
-        global _W_OVERRIDE
-        saved, _W_OVERRIDE = _W_OVERRIDE, self._weights(wdt)
+        weights = self._refresh(wdt)
         saved_sink, _TABLES.sink = _TABLES.sink, []
         tables = _TABLES.sink
         try:                                                                     # two warm-ups: MIOpen's algorithm search, code-object loads
             graph, out = warm_and_capture(fn, device, warmups=2)
         finally:
-            _W_OVERRIDE = saved
             _TABLES.sink = saved_sink
-        return graph, out, tables
+        return graph, out, tables + weights
 
     @torch.no_grad()
     def __call__(self, rgb_static: torch.Tensor, rgb_gripper: torch.Tensor, latent_goal: Optional[torch.Tensor] = None):
@@ -1183,7 +1152,7 @@ class GraphedVisualEncoder:
             ent = dict(s=rgb_static.clone(), g=rgb_gripper.clone(), c=None if latent_goal is None else latent_goal.clone())
             ent["graph"], ent["out"], ent["tables"] = self.capture(lambda: self._eager(ent["s"], ent["g"], ent["c"]), rgb_static.device, wdt)
             self._graphs[key] = ent
-        self._weights(wdt)                                                       # weights whose version moved since the last call: re-cast in place
+        self._refresh(wdt)                                                       # weights whose version moved since the last call: re-cast in place
         ent["s"].copy_(rgb_static); ent["g"].copy_(rgb_gripper)
         if latent_goal is not None:
             ent["c"].copy_(latent_goal)

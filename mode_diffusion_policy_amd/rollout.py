@@ -529,7 +529,7 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
             st["graph"], _, st["tables"] = enc.capture(lambda: img.copy_(enc._eager(st["bufs"][0], st["bufs"][1], goals).view(mb, n_img, -1)),
                                                        img.device, wdt)
             st["key"] = key
-        enc._weights(wdt)                                                   # weights whose version moved since the last replan: re-cast in place
+        enc._refresh(wdt)                                                   # weights whose version moved since the last replan: re-cast in place
         st["graph"].replay()
 
     def _commit(self, ent, capturing: bool) -> None:

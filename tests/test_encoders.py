@@ -594,6 +594,22 @@ def test_weight_writes_through_dot_data_are_seen(tag):
     assert rel(y2, yr2) < 1e-2, rel(y2, yr2)
 
 
+@pytest.mark.parametrize("kw", [dict(bias=True, padding=1), dict(dilation=2, padding=2), dict(groups=4, padding=1), dict(padding="same", dilation=(2, 1)),
+                                dict(bias=True, stride=2, padding=(2, 1), dilation=(2, 1), groups=2)])
+def test_aten_route_keeps_bias_dilation_and_groups(kw):
+    """The aten route (CPU tensors here; MODE_ENC_ATEN_FALLBACK=1 on the device) is F.conv2d with the WHOLE convolution: biased, dilated and grouped
+    convolutions through `_conv2d` equal nn.Conv2d, forward and gradients."""
+    torch.manual_seed(7)
+    conv = torch.nn.Conv2d(8, 16, 3, **kw)
+    x = torch.randn(2, 8, 11, 9, requires_grad=True)
+    y = E._conv2d(conv, x)
+    dy = torch.randn_like(y)
+    gx, gw = torch.autograd.grad(y, (x, conv.weight), dy)
+    yr = conv(x)
+    gxr, gwr = torch.autograd.grad(yr, (x, conv.weight), dy)
+    assert torch.equal(y, yr) and torch.equal(gx, gxr) and torch.equal(gw, gwr)
+
+
 def test_index_table_cache_is_a_bounded_lru():
     """The implicit-GEMM convolutions' index tables (tap tables, K-group offsets) live in a byte-bounded LRU: a varying batch size must not grow
     memory without bound; a table in use elsewhere survives eviction through its other references (a captured graph pins them via `sink`)."""
