@@ -15,6 +15,7 @@
 // lane-linear images), v_mfma_f32_16x16x32_bf16 with swapped operands, output tile through LDS for 16-byte coalesced stores; the gather indices of K-step kt+2
 // are requested while K-step kt+1 is staged (one vmcnt(0) per K-step covers both, two workgroups per CU hide each other's round trips).
 #include "mode_common.h"
+#include "lds_asm.h"
 #include <type_traits>
 
 namespace mode {
@@ -36,20 +37,6 @@ struct ConvGemmParams {
 };
 
 namespace cg {
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-template <int OFF>
-__device__ __forceinline__ void lds_tr64(s16x4& dst, uint32_t addr) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-template <int OFF>
-__device__ __forceinline__ void lds_b128(bf16x8& dst, uint32_t addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-__device__ __forceinline__ bf16x8 join8(s16x4 lo, s16x4 hi) {
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
 // f(k): 32-byte column-group swizzle of a [64 k][COLS] tile (the image of gemm_bf16_tr.hip)
 template <int COLS>
 __device__ __forceinline__ int kn_swz(int row) {
@@ -218,7 +205,7 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 1) void conv_gemm_kernel(const C
     auto read_half = [&](auto KH) {
       constexpr int kh = decltype(KH)::value;
       const uint32_t ab = lds0 + a_off + so + (((fq + kh * 4) ^ sw) * 16);
-      lds_b128<0>(fa[kh][0], ab); lds_b128<2048>(fa[kh][1], ab); lds_b128<4096>(fa[kh][2], ab); lds_b128<6144>(fa[kh][3], ab);
+      lds_read128<0>(fa[kh][0], ab); lds_read128<2048>(fa[kh][1], ab); lds_read128<4096>(fa[kh][2], ab); lds_read128<6144>(fa[kh][3], ab);
       if constexpr (W_KN) {
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
@@ -227,9 +214,9 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 1) void conv_gemm_kernel(const C
         }
       } else {
         const uint32_t bb = lds0 + b_off + so + (((fq + kh * 4) ^ sw) * 16);
-        lds_b128<0>(fb[kh][0], bb);
-        if constexpr (FN > 1) lds_b128<2048>(fb[kh][1], bb);
-        if constexpr (FN > 2) { lds_b128<4096>(fb[kh][2], bb); lds_b128<6144>(fb[kh][3], bb); }
+        lds_read128<0>(fb[kh][0], bb);
+        if constexpr (FN > 1) lds_read128<2048>(fb[kh][1], bb);
+        if constexpr (FN > 2) { lds_read128<4096>(fb[kh][2], bb); lds_read128<6144>(fb[kh][3], bb); }
       }
     };
     auto mma_half = [&](auto KH) {
@@ -245,13 +232,13 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 1) void conv_gemm_kernel(const C
         }
     };
     read_half(std::integral_constant<int, 0>{});
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_sched_barrier(0);
     read_half(std::integral_constant<int, 1>{});
     __builtin_amdgcn_sched_barrier(0);
     mma_half(std::integral_constant<int, 0>{});
     __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_sched_barrier(0);
     mma_half(std::integral_constant<int, 1>{});
     __builtin_amdgcn_sched_barrier(0);
@@ -318,7 +305,7 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 1) void conv_gemm_kernel(const C
       *reinterpret_cast<uint2*>(dst) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
     }
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wait_lgkmcnt<0>();
   __builtin_amdgcn_s_barrier();
   float ssum[8], ssq[8];
 #pragma unroll

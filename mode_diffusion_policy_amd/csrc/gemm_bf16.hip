@@ -26,30 +26,11 @@
 //   * Workgroup ids are remapped per XCD and rasterised in m-tile groups so the tiles resident on one XCD share
 //     ~4 MiB of operands (one XCD L2; measured TCC hit rate 85 %).
 #include "mode_common.h"
+#include "lds_asm.h"
 
 namespace mode {
 
 constexpr int BK = 64;
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-template <int N>
-__device__ __forceinline__ void wait_lgkmcnt() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
-
-// ds_read_b128 the compiler does not track: the MFMA operands are requested with hand-counted lgkmcnt waits so the second k32 half's
-// LDS round trip stays in flight under the first half's MFMAs (hipcc's own scoreboard emitted lgkmcnt(0) before the first MFMA).
-template <int OFF>
-__device__ __forceinline__ void lds_read128(bf16x8& dst, uint32_t addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-template <int STRIDE, int CNT, int I = 0>
-__device__ __forceinline__ void lds_read_seq(bf16x8* dst, uint32_t addr) {
-  if constexpr (I < CNT) {
-    lds_read128<I * STRIDE>(dst[I], addr);
-    lds_read_seq<STRIDE, CNT, I + 1>(dst, addr);
-  }
-}
 
 // wait until at most `tiles` K-tiles (LOADS VMEM ops each) are still in flight for this wave
 template <int LOADS, int MAXT>
@@ -331,7 +312,7 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN >= 16 ? 1 : (LR ? LR : (NS ==
         }
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_s_barrier();
     constexpr int EPC = 16 / ESZ;                                  // elements per 16-byte chunk
     if constexpr (EPI == MODE_EPI_RESIDUAL_NORM && !OUT_BF16) {
@@ -390,7 +371,7 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN >= 16 ? 1 : (LR ? LR : (NS ==
       }
     }
     if (g + 1 < EPASS) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lgkmcnt<0>();
       __builtin_amdgcn_s_barrier();
     }
   }

@@ -28,6 +28,7 @@
 // Numerics: every output element is the same k-ordered fp32 MFMA accumulation chain and the same epilogue expression as gemm_bf16.hip, so
 // results are BIT-IDENTICAL to the 128x128 kernels (the batch-slice consistency tests of the sampler rely on it).
 #include "mode_common.h"
+#include "lds_asm.h"
 #include <type_traits>
 
 // (Round 5's L2 run-ahead variant of this kernel - built, bit-identical, measured, lost: profiles/r05_pp_l2touch.txt - lives in scripts/probe/gemm_bf16_pp_l2touch.hip.)
@@ -44,21 +45,6 @@ constexpr int LDS_NRM = LDS_BIAS + 8 * 1024;               // 2 x 256 floats: in
 constexpr int LDS_SS = LDS_NRM + 2 * 1024;                 // 256 rows x 64 B: per-64-column partial sums of squares of the tile's rows (DMA'd at a restart)
 constexpr int LDS_TOTAL = LDS_SS + 256 * 64;               // 154 KiB of the CU's 160
 constexpr int GM = 8;                                      // m-tiles per rasterisation band
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N>
-__device__ __forceinline__ void wait_lgkmcnt() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
-template <int OFF>
-__device__ __forceinline__ void lds_read128(bf16x8& dst, uint32_t addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-template <int BASE, int STRIDE, int CNT, int I = 0>
-__device__ __forceinline__ void lds_read_seq(bf16x8* dst, uint32_t addr) {
-  if constexpr (I < CNT) {
-    lds_read128<BASE + I * STRIDE>(dst[I], addr);
-    lds_read_seq<BASE, STRIDE, CNT, I + 1>(dst, addr);
-  }
-}
 __device__ __forceinline__ void lds_read_f4(float4& dst, uint32_t addr) {
   asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr) : "memory");
 }
@@ -196,14 +182,14 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
   auto rdA = [&](auto T_, auto H_) __attribute__((always_inline)) {
     constexpr int t = decltype(T_)::value, h = decltype(H_)::value;
     constexpr int base = (t * 2 + h) * HALF_BYTES, nf = h ? FM1 : 4;
-    lds_read_seq<base, 2048, nf>(&A_[0], a_addr[h][0]);
-    lds_read_seq<base, 2048, nf>(&A_[4], a_addr[h][1]);
+    lds_read_seq<2048, nf, base>(&A_[0], a_addr[h][0]);
+    lds_read_seq<2048, nf, base>(&A_[4], a_addr[h][1]);
   };
   auto rdB = [&](auto T_, auto H_) __attribute__((always_inline)) {
     constexpr int t = decltype(T_)::value, h = decltype(H_)::value;
     constexpr int base = (t * 2 + h) * HALF_BYTES;
-    lds_read_seq<base, 2048, 2>(&Bf[h][0], b_addr[0]);
-    lds_read_seq<base, 2048, 2>(&Bf[h][2], b_addr[1]);
+    lds_read_seq<2048, 2, base>(&Bf[h][0], b_addr[0]);
+    lds_read_seq<2048, 2, base>(&Bf[h][2], b_addr[1]);
   };
   auto mma = [&](auto AH_, auto BH_) __attribute__((always_inline)) {
     constexpr int ah = decltype(AH_)::value, bh = decltype(BH_)::value, nf = ah ? FM1 : 4;

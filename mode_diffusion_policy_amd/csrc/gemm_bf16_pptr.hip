@@ -17,6 +17,7 @@
 // Accumulators use the swapped MFMA operands of the forward kernels (D[weight column][token]): a lane owns 4 consecutive output columns of one row per
 // 16-column fragment.  No bias / activation epilogues: backward GEMMs have none.
 #include "mode_common.h"
+#include "lds_asm.h"
 #include <type_traits>
 
 namespace mode {
@@ -40,25 +41,7 @@ constexpr int LDS_A = 0;                                   // A[t][h] at (t*2+h)
 constexpr int LDS_B = 4 * HALF_BYTES;                      // W[t][h] at 64 KiB + (t*2+h) * 16 KiB
 constexpr int LDS_TOTAL = 8 * HALF_BYTES;                  // 128 KiB
 constexpr int GM = 8;
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N>
-__device__ __forceinline__ void wait_lgkmcnt() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
-template <int OFF>
-__device__ __forceinline__ void lds_read128(bf16x8& dst, uint32_t addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-template <int OFF>
-__device__ __forceinline__ void lds_tr64(s16x4& dst, uint32_t addr) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-__device__ __forceinline__ bf16x8 join8(s16x4 lo, s16x4 hi) {
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
 template <int V>
 using IC = std::integral_constant<int, V>;
 }  // namespace pptr

@@ -17,6 +17,7 @@
 // ([M, N/16], this workgroup's columns), SWIGLU scales its accumulator rows by 1/norm from any number of partials per row
 // (sum_row_partials_wave: the same function in the combine / head kernels).
 #include "mode_common.h"
+#include "lds_asm.h"
 
 namespace mode {
 
@@ -84,6 +85,96 @@ __device__ __forceinline__ void row_norm_finish(const GemmParams& p, const int (
   row_norm_reduce<RPW, NW>(p, sv, wave, lane, rsn);
 }
 
+// ---- What gemm_bf16_skinny_kernel and gemm_bf16_stream_kernel share: they differ in how A reaches the MFMAs, not in what surrounds them ----
+// Per-workgroup set-up: the expert's row segment (skinny_rows), then its bias, this lane's weight rows (value, + gate for SwiGLU) at the wave's K
+// offset kbeg and the output slab of the workgroup's K-slice (skinny_setup).  The segment bounds stay plain ints of the kernel: as members of the
+// struct they cost four VGPRs in the KST = 8 kernels.
+__device__ __forceinline__ bool skinny_rows(const GemmParams& p, int& row0, int& row_end) {   // false: the expert has no rows
+  row0 = 0; row_end = p.M;
+  if (p.offsets) { row0 = p.offsets[blockIdx.y]; row_end = p.offsets[blockIdx.y + 1]; }
+  return row_end > row0;
+}
+template <int FNW>
+struct SkinnySetup {
+  const float* bias;
+  const uint16_t* wrow[FNW];
+  char* Cout;
+};
+template <int FNW, bool OUT_BF16>
+__device__ __forceinline__ void skinny_setup(const GemmParams& p, int kbeg, int fr, int fq, SkinnySetup<FNW>& s) {
+  const int expert = blockIdx.y, n0 = blockIdx.x * 16;
+  const uint16_t* W = p.W + (long)expert * p.w_estride;
+  s.bias = p.bias ? p.bias + (long)expert * p.bias_estride : nullptr;
+  s.wrow[0] = W + (long)min(n0 + fr, p.N - 1) * p.ldw + kbeg + fq * 8;
+  if constexpr (FNW == 2) s.wrow[1] = W + ((long)min(n0 + fr, p.N - 1) + p.N) * p.ldw + kbeg + fq * 8;
+  s.Cout = reinterpret_cast<char*>(p.C) + (long)blockIdx.z * p.split_stride * (OUT_BF16 ? 2 : 4);
+}
+
+// Epilogue operands of row ml, columns n .. n+3 (wave i < MT finishes row fragment i): requested ahead of the MFMAs, not behind the reduction.
+// Unconditional loads: the caller passes clamped coordinates (a branch around them would end in an s_waitcnt vmcnt(0) on everything above), or
+// calls under its own guard.
+template <int EPI>
+__device__ __forceinline__ void skinny_epi_operands(const GemmParams& p, const float* bias, long ml, int n, float4& e0, float4& e1) {
+  if constexpr (EPI == MODE_EPI_BIAS || EPI == MODE_EPI_BIAS_GELU) e0 = *reinterpret_cast<const float4*>(bias + n);
+  if constexpr (EPI == MODE_EPI_SWIGLU) { e0 = *reinterpret_cast<const float4*>(bias + n); e1 = *reinterpret_cast<const float4*>(bias + p.N + n); }
+  if constexpr (EPI == MODE_EPI_RESIDUAL || EPI == MODE_EPI_RESIDUAL_NORM) e0 = *reinterpret_cast<const float4*>(p.resid + ml * p.ldr + n);
+  if constexpr (EPI == MODE_EPI_RESIDUAL_NORM) e1 = *reinterpret_cast<const float4*>(p.gain + n);
+}
+
+// The K-slices of the NW waves meet in LDS (red: [NW][MT][FNW][64]) and are summed in wave order (w = 1 .. NW-1 onto wave 0's value: deterministic);
+// wave i < MT then finishes row fragment i: row ml, columns n .. n+3 per lane, `ok` = the lane has an output.
+template <int MT, int EPI, bool OUT_BF16, int NW, int FNW>
+__device__ __forceinline__ void skinny_reduce_finish(const GemmParams& p, f32x4* red, const float* rsn, const f32x4 (&acc)[MT][FNW], char* Cout, int wave,
+                                                     int lane, int ml, int n, bool ok, const float4& e0, const float4& e1) {
+  const int fr = lane & 15, fq = lane >> 4;
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int j = 0; j < FNW; ++j) red[((wave * MT + i) * FNW + j) * 64 + lane] = acc[i][j];
+  __syncthreads();
+  if (wave < MT) {
+    f32x4 v[FNW];
+#pragma unroll
+    for (int j = 0; j < FNW; ++j) {
+      v[j] = red[(wave * FNW + j) * 64 + lane];
+#pragma unroll
+      for (int w = 1; w < NW; ++w) v[j] += red[((w * MT + wave) * FNW + j) * 64 + lane];
+    }
+    if constexpr (EPI == MODE_EPI_RESIDUAL_NORM) {
+      // x = acc + resid -> C (fp32); bf16(x * gain) -> C2; sum of x^2 over this workgroup's 16 columns -> ss_out[row][n0/16]: the four lanes
+      // fq = 0..3 of a row hold 4 columns each (xor-shuffles 16, 32: fixed order); every lane takes part, out-of-range ones add zeros
+      f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (ok) {
+        o[0] = v[0][0] + e0.x; o[1] = v[0][1] + e0.y; o[2] = v[0][2] + e0.z; o[3] = v[0][3] + e0.w;
+        *reinterpret_cast<float4*>(Cout + ((long)ml * p.ldc + n) * 4) = make_float4(o[0], o[1], o[2], o[3]);
+        *reinterpret_cast<uint2*>(p.C2 + (long)ml * p.ldc2 + n) = make_uint2(pack_bf16x2(o[0] * e1.x, o[1] * e1.y), pack_bf16x2(o[2] * e1.z, o[3] * e1.w));
+      }
+      float ss = o[0] * o[0] + o[1] * o[1] + o[2] * o[2] + o[3] * o[3];
+      ss += __shfl_xor(ss, 16, 64); ss += __shfl_xor(ss, 32, 64);
+      if (ok && fq == 0) p.ss_out[(long)ml * (p.N / 16) + blockIdx.x] = ss;
+    } else if (ok) {
+      f32x4 o = v[0];
+      if constexpr (EPI == MODE_EPI_BIAS || EPI == MODE_EPI_BIAS_GELU) {
+        o[0] += e0.x; o[1] += e0.y; o[2] += e0.z; o[3] += e0.w;
+        if constexpr (EPI == MODE_EPI_BIAS_GELU) { o[0] = gelu_erf_f(o[0]); o[1] = gelu_erf_f(o[1]); o[2] = gelu_erf_f(o[2]); o[3] = gelu_erf_f(o[3]); }
+      } else if constexpr (EPI == MODE_EPI_SWIGLU) {
+        if (p.ss_in) {
+          const float rs = rsn[wave * 16 + fr];
+          o[0] = swiglu_f(v[0][0], v[1][0], rs, e0.x, e1.x); o[1] = swiglu_f(v[0][1], v[1][1], rs, e0.y, e1.y);
+          o[2] = swiglu_f(v[0][2], v[1][2], rs, e0.z, e1.z); o[3] = swiglu_f(v[0][3], v[1][3], rs, e0.w, e1.w);
+        } else {
+          o[0] = (v[0][0] + e0.x) * silu_f(v[1][0] + e1.x); o[1] = (v[0][1] + e0.y) * silu_f(v[1][1] + e1.y);
+          o[2] = (v[0][2] + e0.z) * silu_f(v[1][2] + e1.z); o[3] = (v[0][3] + e0.w) * silu_f(v[1][3] + e1.w);
+        }
+      } else if constexpr (EPI == MODE_EPI_RESIDUAL) {
+        o[0] += e0.x; o[1] += e0.y; o[2] += e0.z; o[3] += e0.w;
+      }
+      if constexpr (OUT_BF16) *reinterpret_cast<uint2*>(Cout + ((long)ml * p.ldc + n) * 2) = make_uint2(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]));
+      else *reinterpret_cast<float4*>(Cout + ((long)ml * p.ldc + n) * 4) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+  }
+}
+
 template <int MT, int EPI, bool OUT_BF16, int NW, int KST>
 __global__ __launch_bounds__(NW * 64) void gemm_bf16_skinny_kernel(const GemmParams p) {
   constexpr int FNW = (EPI == MODE_EPI_SWIGLU) ? 2 : 1;            // W fragments per wave: value (+ gate)
@@ -95,23 +186,15 @@ __global__ __launch_bounds__(NW * 64) void gemm_bf16_skinny_kernel(const GemmPar
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int fr = lane & 15, fq = lane >> 4;
-  const int expert = blockIdx.y;
-  const int n0 = blockIdx.x * 16;
-  const int n = n0 + fq * 4;                                         // epilogue: a lane owns columns n .. n+3 of one row
-
-  int row0 = 0, row_end = p.M;
-  if (p.offsets) { row0 = p.offsets[expert]; row_end = p.offsets[expert + 1]; }
-  if (row_end <= row0) return;
-  const uint16_t* W = p.W + (long)expert * p.w_estride;
-  const float* bias = p.bias ? p.bias + (long)expert * p.bias_estride : nullptr;
+  const int n = blockIdx.x * 16 + fq * 4;                            // epilogue: a lane owns columns n .. n+3 of one row
 
   // this wave's K range: slice blockIdx.z of split_k, cut into NW wave slices (multiples of 32)
   const int kspl = p.K / p.split_k, kw = kspl / NW;
   const int kbeg = blockIdx.z * kspl + wave * kw;
-  const uint16_t* wrow[FNW];
-  wrow[0] = W + (long)min(n0 + fr, p.N - 1) * p.ldw + kbeg + fq * 8;
-  if constexpr (FNW == 2) wrow[1] = W + ((long)min(n0 + fr, p.N - 1) + p.N) * p.ldw + kbeg + fq * 8;
-  char* Cout = reinterpret_cast<char*>(p.C) + (long)blockIdx.z * p.split_stride * (OUT_BF16 ? 2 : 4);
+  SkinnySetup<FNW> g;
+  int row0, row_end;
+  if (!skinny_rows(p, row0, row_end)) return;
+  skinny_setup<FNW, OUT_BF16>(p, kbeg, fr, fq, g);
 
   for (int mb = row0; mb < row_end; mb += MT * 16) {
     f32x4 acc[MT][FNW];
@@ -119,7 +202,6 @@ __global__ __launch_bounds__(NW * 64) void gemm_bf16_skinny_kernel(const GemmPar
     for (int i = 0; i < MT; ++i)
 #pragma unroll
       for (int j = 0; j < FNW; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // epilogue operands of this wave's row fragment (wave i < MT finishes fragment i): requested ahead of the MFMAs, not behind the reduction
     const int ml = mb + wave * 16 + fr;
     const bool ok = wave < MT && ml < row_end && n < p.N;
     [[maybe_unused]] float4 e0 = make_float4(0.f, 0.f, 0.f, 0.f), e1 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -130,7 +212,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_bf16_skinny_kernel(const GemmPar
 #pragma unroll
       for (int u = 0; u < KST; ++u)
 #pragma unroll
-        for (int j = 0; j < FNW; ++j) wf[u][j] = load_w_nt(wrow[j] + 32 * u);
+        for (int j = 0; j < FNW; ++j) wf[u][j] = load_w_nt(g.wrow[j] + 32 * u);
       // round trip 1: gather indices of the A rows + token ids of the rows whose norms this wave computes (one uniform branch, not one per row)
       int arow_i[MT];
       [[maybe_unused]] int tok[MT * 16 / NW];
@@ -144,15 +226,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_bf16_skinny_kernel(const GemmPar
       if constexpr (EPI == MODE_EPI_SWIGLU) {
         if (p.ss_in) row_norm_tokens<MT * 16 / NW, NW>(p, mb, row_end, wave, tok);
       }
-      // epilogue operands: clamped addresses, unconditional loads (a branch around them would end in an s_waitcnt vmcnt(0) on everything above)
-      {
-        const int nc = min(n, p.N - 4);
-        const long mlc = min(ml, row_end - 1);
-        if constexpr (EPI == MODE_EPI_BIAS || EPI == MODE_EPI_BIAS_GELU) e0 = *reinterpret_cast<const float4*>(bias + nc);
-        if constexpr (EPI == MODE_EPI_SWIGLU) { e0 = *reinterpret_cast<const float4*>(bias + nc); e1 = *reinterpret_cast<const float4*>(bias + p.N + nc); }
-        if constexpr (EPI == MODE_EPI_RESIDUAL || EPI == MODE_EPI_RESIDUAL_NORM) e0 = *reinterpret_cast<const float4*>(p.resid + mlc * p.ldr + nc);
-        if constexpr (EPI == MODE_EPI_RESIDUAL_NORM) e1 = *reinterpret_cast<const float4*>(p.gain + nc);
-      }
+      skinny_epi_operands<EPI>(p, g.bias, min(ml, row_end - 1), min(n, p.N - 4), e0, e1);
       // round trip 2: the A fragments (L2) and the rows' partial sums of squares
 #pragma unroll
       for (int u = 0; u < KST; ++u)
@@ -187,7 +261,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_bf16_skinny_kernel(const GemmPar
         for (int u = 0; u < U; ++u) {
           const int ko = min(k + 32 * u, kw - 32);                   // tail steps re-read the last block and are skipped below
 #pragma unroll
-          for (int j = 0; j < FNW; ++j) wf[u][j] = *reinterpret_cast<const bf16x8*>(wrow[j] + ko);
+          for (int j = 0; j < FNW; ++j) wf[u][j] = *reinterpret_cast<const bf16x8*>(g.wrow[j] + ko);
 #pragma unroll
           for (int i = 0; i < MT; ++i) af[u][i] = *reinterpret_cast<const bf16x8*>(arow[i] + ko);
         }
@@ -201,61 +275,12 @@ __global__ __launch_bounds__(NW * 64) void gemm_bf16_skinny_kernel(const GemmPar
           }
         }
       }
-      if (ok) {
-        if constexpr (EPI == MODE_EPI_BIAS || EPI == MODE_EPI_BIAS_GELU) e0 = *reinterpret_cast<const float4*>(bias + n);
-        if constexpr (EPI == MODE_EPI_SWIGLU) { e0 = *reinterpret_cast<const float4*>(bias + n); e1 = *reinterpret_cast<const float4*>(bias + p.N + n); }
-        if constexpr (EPI == MODE_EPI_RESIDUAL || EPI == MODE_EPI_RESIDUAL_NORM) e0 = *reinterpret_cast<const float4*>(p.resid + (long)ml * p.ldr + n);
-        if constexpr (EPI == MODE_EPI_RESIDUAL_NORM) e1 = *reinterpret_cast<const float4*>(p.gain + n);
-      }
+      if (ok) skinny_epi_operands<EPI>(p, g.bias, ml, n, e0, e1);   // behind the K loop, guarded: nothing above is left to wait for
     }
 
     // ---- K-slices of the NW waves meet in LDS, summed in wave order
     if (mb != row0) __syncthreads();                                 // previous block's readers are done
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < FNW; ++j) red[((wave * MT + i) * FNW + j) * 64 + lane] = acc[i][j];
-    __syncthreads();
-    if (wave < MT) {                                                 // wave i finishes row fragment i
-      f32x4 v[FNW];
-#pragma unroll
-      for (int j = 0; j < FNW; ++j) {
-        v[j] = red[(wave * FNW + j) * 64 + lane];
-        for (int w = 1; w < NW; ++w) v[j] += red[((w * MT + wave) * FNW + j) * 64 + lane];
-      }
-      if constexpr (EPI == MODE_EPI_RESIDUAL_NORM) {
-        // x = acc + resid -> C (fp32); bf16(x * gain) -> C2; sum of x^2 over this workgroup's 16 columns -> ss_out[row][n0/16]: the four lanes
-        // fq = 0..3 of a row hold 4 columns each (xor-shuffles 16, 32: fixed order); every lane takes part, out-of-range ones add zeros
-        f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (ok) {
-          o[0] = v[0][0] + e0.x; o[1] = v[0][1] + e0.y; o[2] = v[0][2] + e0.z; o[3] = v[0][3] + e0.w;
-          *reinterpret_cast<float4*>(Cout + ((long)ml * p.ldc + n) * 4) = make_float4(o[0], o[1], o[2], o[3]);
-          *reinterpret_cast<uint2*>(p.C2 + (long)ml * p.ldc2 + n) = make_uint2(pack_bf16x2(o[0] * e1.x, o[1] * e1.y), pack_bf16x2(o[2] * e1.z, o[3] * e1.w));
-        }
-        float ss = o[0] * o[0] + o[1] * o[1] + o[2] * o[2] + o[3] * o[3];
-        ss += __shfl_xor(ss, 16, 64); ss += __shfl_xor(ss, 32, 64);
-        if (ok && fq == 0) p.ss_out[(long)ml * (p.N / 16) + blockIdx.x] = ss;
-      } else if (ok) {
-        f32x4 o = v[0];
-        if constexpr (EPI == MODE_EPI_BIAS || EPI == MODE_EPI_BIAS_GELU) {
-          o[0] += e0.x; o[1] += e0.y; o[2] += e0.z; o[3] += e0.w;
-          if constexpr (EPI == MODE_EPI_BIAS_GELU) { o[0] = gelu_erf_f(o[0]); o[1] = gelu_erf_f(o[1]); o[2] = gelu_erf_f(o[2]); o[3] = gelu_erf_f(o[3]); }
-        } else if constexpr (EPI == MODE_EPI_SWIGLU) {
-          if (p.ss_in) {
-            const float rs = rsn[wave * 16 + fr];
-            o[0] = swiglu_f(v[0][0], v[1][0], rs, e0.x, e1.x); o[1] = swiglu_f(v[0][1], v[1][1], rs, e0.y, e1.y);
-            o[2] = swiglu_f(v[0][2], v[1][2], rs, e0.z, e1.z); o[3] = swiglu_f(v[0][3], v[1][3], rs, e0.w, e1.w);
-          } else {
-            o[0] = (v[0][0] + e0.x) * silu_f(v[1][0] + e1.x); o[1] = (v[0][1] + e0.y) * silu_f(v[1][1] + e1.y);
-            o[2] = (v[0][2] + e0.z) * silu_f(v[1][2] + e1.z); o[3] = (v[0][3] + e0.w) * silu_f(v[1][3] + e1.w);
-          }
-        } else if constexpr (EPI == MODE_EPI_RESIDUAL) {
-          o[0] += e0.x; o[1] += e0.y; o[2] += e0.z; o[3] += e0.w;
-        }
-        if constexpr (OUT_BF16) *reinterpret_cast<uint2*>(Cout + ((long)ml * p.ldc + n) * 2) = make_uint2(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]));
-        else *reinterpret_cast<float4*>(Cout + ((long)ml * p.ldc + n) * 4) = make_float4(o[0], o[1], o[2], o[3]);
-      }
-    }
+    skinny_reduce_finish<MT, EPI, OUT_BF16, NW>(p, red, rsn, acc, g.Cout, wave, lane, ml, n, ok, e0, e1);
   }
 }
 
@@ -277,21 +302,12 @@ __global__ __launch_bounds__(256) void gemm_bf16_stream_kernel(const GemmParams 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15, fq = lane >> 4;
-  const int expert = blockIdx.y;
-  const int n0 = blockIdx.x * 16;
-  const int n = n0 + fq * 4;
-
-  int row0 = 0, row_end = p.M;
-  if (p.offsets) { row0 = p.offsets[expert]; row_end = p.offsets[expert + 1]; }
-  if (row_end <= row0) return;
-  const uint16_t* W = p.W + (long)expert * p.w_estride;
-  const float* bias = p.bias ? p.bias + (long)expert * p.bias_estride : nullptr;
+  const int n = blockIdx.x * 16 + fq * 4;
   const int kslice = blockIdx.z * 1024;
-  const int kbeg = kslice + wave * 256;
-  const uint16_t* wrow[FNW];
-  wrow[0] = W + (long)min(n0 + fr, p.N - 1) * p.ldw + kbeg + fq * 8;
-  if constexpr (FNW == 2) wrow[1] = W + ((long)min(n0 + fr, p.N - 1) + p.N) * p.ldw + kbeg + fq * 8;
-  char* Cout = reinterpret_cast<char*>(p.C) + (long)blockIdx.z * p.split_stride * (OUT_BF16 ? 2 : 4);
+  SkinnySetup<FNW> g;
+  int row0, row_end;
+  if (!skinny_rows(p, row0, row_end)) return;
+  skinny_setup<FNW, OUT_BF16>(p, kslice + wave * 256, fr, fq, g);
 
   for (int mb = row0; mb < row_end; mb += ROWS) {
     if (mb != row0) __syncthreads();                                 // previous block's epilogue readers are done with the shared buffer
@@ -310,17 +326,11 @@ __global__ __launch_bounds__(256) void gemm_bf16_stream_kernel(const GemmParams 
     } else if (p.a_rows) {                                           // (both batches inside one branch: one wait for all of them)
 #pragma unroll
       for (int j = 0; j < NIT; ++j) src[j] = p.a_rows[min(mb + ((j * 4 + wave) >> 1), row_end - 1)];   // rows past the segment re-read a valid row (never stored)
-      if constexpr (EPI == MODE_EPI_SWIGLU) {
-#pragma unroll
-        for (int q = 0; q < ROWS / NW; ++q) tok[q] = p.a_rows[min(mb + wave + q * NW, row_end - 1)];
-      }
+      if constexpr (EPI == MODE_EPI_SWIGLU) row_norm_tokens<ROWS / NW, NW>(p, mb, row_end, wave, tok);
     } else {
 #pragma unroll
       for (int j = 0; j < NIT; ++j) src[j] = min(mb + ((j * 4 + wave) >> 1), row_end - 1);
-      if constexpr (EPI == MODE_EPI_SWIGLU) {
-#pragma unroll
-        for (int q = 0; q < ROWS / NW; ++q) tok[q] = min(mb + wave + q * NW, row_end - 1);
-      }
+      if constexpr (EPI == MODE_EPI_SWIGLU) row_norm_tokens<ROWS / NW, NW>(p, mb, row_end, wave, tok);
     }
     // ---- round trip 2, all of it requested before anything is consumed: the A block by LDS-DMA (a wave instruction copies 1 KB of one row,
     // coalesced, straight into the padded row-major image: no registers, nothing to wait for before the weight loads go out), the epilogue
@@ -332,14 +342,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_stream_kernel(const GemmParams 
                                        (__attribute__((address_space(3))) void*)(aimg + (hr >> 1) * AROW + (hr & 1) * 1024), 16, 0, 0);
     }
     [[maybe_unused]] float4 e0 = make_float4(0.f, 0.f, 0.f, 0.f), e1 = make_float4(0.f, 0.f, 0.f, 0.f);
-    {
-      const int nc = min(n, p.N - 4);
-      const long mlc = min(ml, row_end - 1);
-      if constexpr (EPI == MODE_EPI_BIAS || EPI == MODE_EPI_BIAS_GELU) e0 = *reinterpret_cast<const float4*>(bias + nc);
-      if constexpr (EPI == MODE_EPI_SWIGLU) { e0 = *reinterpret_cast<const float4*>(bias + nc); e1 = *reinterpret_cast<const float4*>(bias + p.N + nc); }
-      if constexpr (EPI == MODE_EPI_RESIDUAL || EPI == MODE_EPI_RESIDUAL_NORM) e0 = *reinterpret_cast<const float4*>(p.resid + mlc * p.ldr + nc);
-      if constexpr (EPI == MODE_EPI_RESIDUAL_NORM) e1 = *reinterpret_cast<const float4*>(p.gain + nc);
-    }
+    skinny_epi_operands<EPI>(p, g.bias, min(ml, row_end - 1), min(n, p.N - 4), e0, e1);
     [[maybe_unused]] float sv[ROWS / NW];
     if constexpr (EPI == MODE_EPI_SWIGLU) {
       if (p.ss_in) row_norm_load<ROWS / NW>(p, tok, lane, sv);
@@ -348,11 +351,11 @@ __global__ __launch_bounds__(256) void gemm_bf16_stream_kernel(const GemmParams 
 #pragma unroll
     for (int u = 0; u < KS; ++u)
 #pragma unroll
-      for (int j = 0; j < FNW; ++j) wf[u][j] = load_w_nt(wrow[j] + 32 * u);
+      for (int j = 0; j < FNW; ++j) wf[u][j] = load_w_nt(g.wrow[j] + 32 * u);
     if constexpr (EPI == MODE_EPI_SWIGLU) {
       if (p.ss_in) row_norm_reduce<ROWS / NW, NW>(p, sv, wave, lane, rsn);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // the DMA'd A block has landed (the compiler does not track it)
+    wait_vmcnt<0>();                 // the DMA'd A block has landed (the compiler does not track it)
     __syncthreads();
     bf16x8 af[KS][MT];
 #pragma unroll
@@ -373,50 +376,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_stream_kernel(const GemmParams 
 
     // ---- K-slices of the four waves meet in LDS (over the A image: every wave has its fragments), summed in wave order
     __syncthreads();
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < FNW; ++j) red[((wave * MT + i) * FNW + j) * 64 + lane] = acc[i][j];
-    __syncthreads();
-    if (wave < MT) {                                                 // wave i finishes row fragment i
-      f32x4 v[FNW];
-#pragma unroll
-      for (int j = 0; j < FNW; ++j) {
-        v[j] = red[(wave * FNW + j) * 64 + lane];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) v[j] += red[((w * MT + wave) * FNW + j) * 64 + lane];
-      }
-      if constexpr (EPI == MODE_EPI_RESIDUAL_NORM) {
-        f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (ok) {
-          o[0] = v[0][0] + e0.x; o[1] = v[0][1] + e0.y; o[2] = v[0][2] + e0.z; o[3] = v[0][3] + e0.w;
-          *reinterpret_cast<float4*>(Cout + ((long)ml * p.ldc + n) * 4) = make_float4(o[0], o[1], o[2], o[3]);
-          *reinterpret_cast<uint2*>(p.C2 + (long)ml * p.ldc2 + n) = make_uint2(pack_bf16x2(o[0] * e1.x, o[1] * e1.y), pack_bf16x2(o[2] * e1.z, o[3] * e1.w));
-        }
-        float ss = o[0] * o[0] + o[1] * o[1] + o[2] * o[2] + o[3] * o[3];
-        ss += __shfl_xor(ss, 16, 64); ss += __shfl_xor(ss, 32, 64);
-        if (ok && fq == 0) p.ss_out[(long)ml * (p.N / 16) + blockIdx.x] = ss;
-      } else if (ok) {
-        f32x4 o = v[0];
-        if constexpr (EPI == MODE_EPI_BIAS || EPI == MODE_EPI_BIAS_GELU) {
-          o[0] += e0.x; o[1] += e0.y; o[2] += e0.z; o[3] += e0.w;
-          if constexpr (EPI == MODE_EPI_BIAS_GELU) { o[0] = gelu_erf_f(o[0]); o[1] = gelu_erf_f(o[1]); o[2] = gelu_erf_f(o[2]); o[3] = gelu_erf_f(o[3]); }
-        } else if constexpr (EPI == MODE_EPI_SWIGLU) {
-          if (p.ss_in) {
-            const float rs = rsn[wave * 16 + fr];
-            o[0] = swiglu_f(v[0][0], v[1][0], rs, e0.x, e1.x); o[1] = swiglu_f(v[0][1], v[1][1], rs, e0.y, e1.y);
-            o[2] = swiglu_f(v[0][2], v[1][2], rs, e0.z, e1.z); o[3] = swiglu_f(v[0][3], v[1][3], rs, e0.w, e1.w);
-          } else {
-            o[0] = (v[0][0] + e0.x) * silu_f(v[1][0] + e1.x); o[1] = (v[0][1] + e0.y) * silu_f(v[1][1] + e1.y);
-            o[2] = (v[0][2] + e0.z) * silu_f(v[1][2] + e1.z); o[3] = (v[0][3] + e0.w) * silu_f(v[1][3] + e1.w);
-          }
-        } else if constexpr (EPI == MODE_EPI_RESIDUAL) {
-          o[0] += e0.x; o[1] += e0.y; o[2] += e0.z; o[3] += e0.w;
-        }
-        if constexpr (OUT_BF16) *reinterpret_cast<uint2*>(Cout + ((long)ml * p.ldc + n) * 2) = make_uint2(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]));
-        else *reinterpret_cast<float4*>(Cout + ((long)ml * p.ldc + n) * 4) = make_float4(o[0], o[1], o[2], o[3]);
-      }
-    }
+    skinny_reduce_finish<MT, EPI, OUT_BF16, NW>(p, red, rsn, acc, g.Cout, wave, lane, ml, n, ok, e0, e1);
   }
 }
 
@@ -464,7 +424,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_mid_kernel(const GemmParams p) 
 #pragma unroll
     for (int i = 0; i < 2; ++i) rr[i] = *reinterpret_cast<const float4*>(p.resid + (long)min(mb + i * 16 + fr, p.M - 1) * p.ldr + min(n, p.N - 4));
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // the DMA'd A block has landed (the compiler does not track it)
+  wait_vmcnt<0>();                 // the DMA'd A block has landed (the compiler does not track it)
   __syncthreads();
   f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
   const char* a0 = aimg + fr * AROW + fq * 16;

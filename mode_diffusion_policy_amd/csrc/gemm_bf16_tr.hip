@@ -24,6 +24,7 @@
 namespace mode {
 
 __device__ __attribute__((aligned(256))) uint16_t g_zero_row[128];      // 256 B of zeros: DMA source of masked K rows
+// (one such array per translation unit - g_pptr_zero_row, g_conv_zero_row: the library is built without relocatable device code, so a __device__ variable cannot be shared)
 
 // BN = 128 | 64 output columns per workgroup (64: twice the workgroups for problems that would not fill 256 CUs); NS = LDS ring depth
 // (2: vmcnt(0) per K-step, 2 workgroups/CU hide each other's fill latency; 3: two tiles in flight under counted waits, for long-K
@@ -192,8 +193,8 @@ __global__ __launch_bounds__(256, (NS == 1 ? 3 : 2)) void gemm_tr_kernel(const T
   int slot = 0;
   for (int kt = 0; kt < nk; ++kt) {
     // tile kt landed for this wave's pieces; (NS == 3) one younger tile stays in flight across the barrier
-    if (NS >= 3 && kt + 1 < nk) tr_wait_vmcnt<LOADS>();
-    else tr_wait_vmcnt<0>();
+    if (NS >= 3 && kt + 1 < nk) wait_vmcnt<LOADS>();
+    else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     if constexpr (NS >= 2) {
       if (kt + NS - 1 < nk) {
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(256, (NS == 1 ? 3 : 2)) void gemm_tr_kernel(const T
         }
       } else {
         const uint32_t ab = lds0 + a_off + so + (((fq + kh * 4) ^ sw) * 16);
-        lds_b128<0>(fa[kh][0], ab); lds_b128<2048>(fa[kh][1], ab); lds_b128<4096>(fa[kh][2], ab); lds_b128<6144>(fa[kh][3], ab);
+        lds_read128<0>(fa[kh][0], ab); lds_read128<2048>(fa[kh][1], ab); lds_read128<4096>(fa[kh][2], ab); lds_read128<6144>(fa[kh][3], ab);
       }
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
@@ -235,13 +236,13 @@ __global__ __launch_bounds__(256, (NS == 1 ? 3 : 2)) void gemm_tr_kernel(const T
       }
     };
     read_half(std::integral_constant<int, 0>{});
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_sched_barrier(0);
     read_half(std::integral_constant<int, 1>{});                   // second half's LDS round trip runs under the first half's MFMAs
     __builtin_amdgcn_sched_barrier(0);
     mma_half(std::integral_constant<int, 0>{});
     __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_sched_barrier(0);
     mma_half(std::integral_constant<int, 1>{});
     __builtin_amdgcn_sched_barrier(0);
@@ -284,7 +285,7 @@ __global__ __launch_bounds__(256, (NS == 1 ? 3 : 2)) void gemm_tr_kernel(const T
         }
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_s_barrier();
     constexpr int EPC = 16 / ESZ;
     if constexpr (EPI == 1) {

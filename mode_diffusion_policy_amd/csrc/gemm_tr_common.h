@@ -1,7 +1,8 @@
 // Shared by the transpose-read backward GEMMs (gemm_bf16_tr.hip: ring kernels; gemm_bf16_trws.hip: the wave-specialised weight-gradient + AdamW kernel):
-// the kernel argument block, the LDS reads the compiler must not track, the column-group swizzle of a [k][n] tile.
+// the kernel argument block, the column-group swizzle of a [k][n] tile; the untracked LDS reads and waits come from lds_asm.h.
 #pragma once
 #include "mode_common.h"
+#include "lds_asm.h"
 
 namespace mode {
 
@@ -25,27 +26,6 @@ struct TrParams {
   float* ad_p; float* ad_m; float* ad_v; uint16_t* ad_lp; float* ad_ema; float* ad_gsq;
   float ad_decay, ad_b1, ad_b2, ad_eps, ad_step_size, ad_inv_bc2_sqrt, ad_gscale, ad_ema_rate;
 };
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-// LDS reads the compiler does not track (it would otherwise put `s_waitcnt vmcnt(0)` — i.e. the just-issued LDS-DMA of the NEXT tile —
-// in front of every compiler-visible LDS read): hand-counted lgkmcnt waits + sched_barriers, as in the forward kernel.
-template <int OFF>
-__device__ __forceinline__ void lds_tr64(s16x4& dst, uint32_t addr) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-template <int OFF>
-__device__ __forceinline__ void lds_b128(bf16x8& dst, uint32_t addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-__device__ __forceinline__ bf16x8 join8(s16x4 lo, s16x4 hi) {
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-template <int N>
-__device__ __forceinline__ void tr_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // f(k): 32-byte column-group swizzle of a [64 k][COLS] tile (COLS = 128: 8 groups per 256-B row; COLS = 64: 4 groups per 128-B row, odd
 // rows already sit on the other half of the banks)

@@ -16,6 +16,7 @@
 // the busiest CU of the 128 x 64 tiling it replaces (3 tiles x 384 KiB), evenly spread.
 #include "attn_core.h"
 #include "mode_common.h"
+#include "lds_asm.h"
 
 namespace mode {
 
@@ -31,21 +32,6 @@ struct QkvAttnParams {
 
 namespace qa {
 constexpr int BM = 64, BK = 64, WN = 4;
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N>
-__device__ __forceinline__ void wait_lgkmcnt() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
-template <int OFF>
-__device__ __forceinline__ void lds_read128(bf16x8& dst, uint32_t addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-template <int STRIDE, int CNT, int I = 0>
-__device__ __forceinline__ void lds_read_seq(bf16x8* dst, uint32_t addr) {
-  if constexpr (I < CNT) {
-    lds_read128<I * STRIDE>(dst[I], addr);
-    lds_read_seq<STRIDE, CNT, I + 1>(dst, addr);
-  }
-}
 
 // q | k | v tile of the epilogue in LDS: rows of 3 * HD bf16 + 16 bytes (the 16 token rows a ds_read_b128 group touches land on 16 distinct 4-bank groups)
 // The GEMM epilogue stores 8 bytes per lane, 16 lanes = 16 consecutive tile rows per LDS cycle group: with a 196-dword pitch rows r and r + 8 share their banks
@@ -214,7 +200,7 @@ __global__ __launch_bounds__(WM * 256, 1) void qkv_attn_kernel(const QkvAttnPara
       *reinterpret_cast<uint2*>(smem + trow * PITCH + ((nl * 2) ^ (trow & 8))) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
     }
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wait_lgkmcnt<0>();
   __builtin_amdgcn_s_barrier();
 
   // ---- epilogue 2: wave w = sample w of the group: qk-RMSNorm, causal softmax, PV - the stand-alone kernel's body on LDS operands

@@ -245,7 +245,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tr_adamw_ws_kernel(const TrParams
       advance();
     }
     zero_acc();
-    tr_wait_vmcnt<4 * (WS_NS - 1)>();
+    wait_vmcnt<4 * (WS_NS - 1)>();
     if (lane == 0) ws_signal(f_full);
     ws_wait_ge<false>(f_full, 4u);
     read_frags(std::integral_constant<int, 0>{}, 0u);
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tr_adamw_ws_kernel(const TrParams
       unsigned long long tq[8];
 #define WS_STAMP(k) if (dbg == 4) { tq[k] = __builtin_amdgcn_s_memtime(); }
       WS_STAMP(0)
-      tr_wait_vmcnt<4 * (WS_NS - 2)>();
+      wait_vmcnt<4 * (WS_NS - 2)>();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       WS_STAMP(1)
