@@ -860,6 +860,32 @@ typedef struct ModeEnvPoolDesc {
  * is the whole control step of the environments that do not replan. */
 int mode_env_commit_emit(const ModeEnvPoolDesc* d, void* stream);
 
+/* Temporal ensembling of overlapping plans (ACT's rule; rollout.VectorEnvPolicy(temporal_ensemble=m)).  An addition to ABI 13: a new struct
+ * and a new export, nothing existing changes.  With multistep = s < W an environment replans while rows of its older plans still predict the
+ * coming steps.  The pool keeps, per environment b, its last K = ceil(W / s) plans in a ring and its local time t[b], the number of active
+ * steps since its reset.  A plan born at local time t_p (a multiple of s) lives in slot (t_p / s) % K with birth[b][slot] = t_p; its row
+ * t - t_p predicts step t, and it is LIVE at t when 0 <= t - t_p < W.  With the live plans ordered oldest first, i = 0 .. n-1, and x_i their
+ * rows for step t, an active environment emits
+ *   out[b] = (sum_i weights[i] * x_i) / (sum_i weights[i])
+ * both sums in fp32, oldest to newest (the first term is the product weights[0] * x_0, every later one a fused multiply-add).  The caller
+ * supplies the table, for ACT weights[i] = (float)exp(-m * i): the device evaluates no transcendental, and with weights[0] = 1 a lone live
+ * plan is emitted bit for bit.  A slot whose birth is not exactly the time its position implies (t - t % s - i * s for the i-th newest) is not
+ * live, so a reset needs only birth[b][*] = -1 and t[b] = 0. */
+typedef struct ModeEnvEnsDesc {
+  ModeEnvPoolDesc pool;                  /* as for mode_env_commit_emit; pool.plan receives the newest plan as there */
+  float* ring;                           /* [num_envs, K, W, A] */
+  int32_t* birth;                        /* [num_envs, K] local time at which the slot's plan was born; negative = empty */
+  int32_t* t;                            /* [num_envs] local time */
+  const float* weights;                  /* [K] device, weights[0] > 0 */
+  int32_t K;                             /* 1..64, = ceil(W / multistep) */
+} ModeEnvEnsDesc;
+
+/* Commit + emit of a control step of the ensembled pool (one launch), both forms of mode_env_commit_emit (pool.ctrl set or NULL): for j < m the
+ * planned rows chunk[j] become slot (t / s) % K of environment rows[j]'s ring (and pool.plan[rows[j]]) with birth = t, its counter is set to 0
+ * and its draw index advances by one; then every active environment writes the weighted mean above and advances counter = (counter + 1) % s
+ * and t = t + 1; every inactive one writes a zero row and keeps both.  MODE_ERR_BAD_ARG as its sibling, and when K != ceil(W / multistep). */
+int mode_env_commit_emit_ens(const ModeEnvEnsDesc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

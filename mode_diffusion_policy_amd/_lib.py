@@ -161,6 +161,11 @@ class ModeEnvPoolDesc(C.Structure):
                 ("counter", c_vp), ("draws", c_vp), ("out", c_vp), ("active", c_u32 * (MODE_ENV_MAX // 32))]
 
 
+class ModeEnvEnsDesc(C.Structure):
+    """Commit + emit with temporal ensembling over a ring of each environment's last K plans (include/mode_hip.h, an addition to ABI 13)."""
+    _fields_ = [("pool", ModeEnvPoolDesc), ("ring", c_vp), ("birth", c_vp), ("t", c_vp), ("weights", c_vp), ("K", c_i32)]
+
+
 class ModeEnvFramesCam(C.Structure):
     """One camera of mode_env_gather_frames (include/mode_hip.h, ABI 13)."""
     _fields_ = [("src", c_vp), ("src_stride", c_i64), ("row_elems", c_i64), ("dst", c_vp), ("src_dtype", c_i32), ("dst_dtype", c_i32)]
@@ -257,6 +262,7 @@ PROTOTYPES = {
     "mode_env_gather_noise": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp]),
     "mode_env_commit_emit": (C.c_int, [P(ModeEnvPoolDesc), c_vp]),
     "mode_env_gather_frames": (C.c_int, [P(ModeEnvFramesDesc), c_vp]),
+    "mode_env_commit_emit_ens": (C.c_int, [P(ModeEnvEnsDesc), c_vp]),
 }
 
 _lib: Optional[C.CDLL] = None

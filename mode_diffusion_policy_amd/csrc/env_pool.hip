@@ -1,6 +1,7 @@
 // Per-environment replanning of a vectorised rollout (include/mode_hip.h, ABI 13; rollout.VectorEnvPolicy): the gather of the replanning
 // environments' observations with their initial noise into a chunk's input buffers, and the commit of the chunk's plans + the emission of one
-// action per active environment.  Both move a few hundred KB at most: one launch each, plain coalesced loops, no LDS.  The gather of the
+// action per active environment - the newest plan's row, or with temporal ensembling the weighted mean of the rows that the environment's last K
+// plans predict for the step (env_commit_emit_ens_kernel).  Both move a few hundred KB at most: one launch each, plain coalesced loops, no LDS.  The gather of the
 // replanning environments' camera frames into the encoders' input (mode_env_gather_frames) moves ~1.2 MB per fp32 row at 224 x 224: HBM-bound,
 // 16-byte loads and stores.
 #include "mode_common.h"
@@ -136,6 +137,91 @@ __global__ __launch_bounds__(64) void env_commit_emit_kernel(ModeEnvPoolDesc d) 
   }
 }
 
+// The ensembled pool (ModeEnvEnsDesc): the same wave per environment b, the same search for b among the chunk's rows.  A committed chunk goes to
+// ring slot (t / s) % K (and to plan[b], the newest plan); the emitted row is the weighted mean of the live plans' rows for step t, oldest first.
+// Lane i < K tests the plan i strides older than the newest, so one ballot holds the live set, bit i = age i; the rows are then loaded eight at a
+// time before the first multiply-add of the batch, so that a K-deep ring costs K / 8 load latencies and not K.  As above, the row of a plan
+// committed by this launch is read from the chunk, and birth / t / counter are written by lane 0 after every lane's reads of them.
+__global__ __launch_bounds__(64) void env_commit_emit_ens_kernel(ModeEnvEnsDesc e) {
+  const ModeEnvPoolDesc& d = e.pool;
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int NW = (d.num_envs + 31) >> 5;
+  const int32_t* ctrl = d.ctrl;
+  int m = 0;
+  uint32_t act_word;
+  float* out;
+  if (ctrl) {
+    m = min(max(ctrl[0], 0), d.num_envs);
+    out = reinterpret_cast<float*>((uint64_t)(uint32_t)ctrl[2] | ((uint64_t)(uint32_t)ctrl[3] << 32));
+    act_word = (uint32_t)ctrl[4 + (b >> 5)];
+  } else {
+    out = d.out;
+    act_word = d.active[b >> 5];
+  }
+  const bool active = (act_word >> (b & 31)) & 1u;
+  const int32_t* rows = ctrl ? ctrl + 4 + NW : nullptr;
+  int j = -1;
+  for (int i = lane; i < m; i += 64)
+    if (rows[i] == b) j = i;
+  for (int o = 32; o > 0; o >>= 1) j = max(j, __shfl_xor(j, o, 64));
+  const int s = d.multistep, K = e.K, W = d.W, A = d.A, WA = W * A;
+  const int t = max(e.t[b], 0);
+  const int q = (t / s) % K;                   // slot of the newest plan, born at tn
+  const int tn = t - t % s;
+  float* ring = e.ring + (long)b * K * WA;
+  int32_t* birth = e.birth + (long)b * K;
+  bool live = false;
+  if (lane < K) {
+    const int want = tn - lane * s;            // birth of the plan `lane` strides older than the newest
+    if (lane == 0 && j >= 0) live = true;
+    else live = want >= 0 && t - want < W && birth[(q + K - lane) % K] == want;
+  }
+  unsigned long long ages = __ballot(live);    // bit i: the plan of age i is live (wave-uniform)
+  if (j >= 0) {
+    const float* src = d.chunk + (long)j * WA;
+    float* slot = ring + (long)q * WA;
+    float* plan = d.plan + (long)b * WA;
+    for (int i = lane; i < WA; i += 64) {
+      const float v = src[i];
+      slot[i] = v; plan[i] = v;
+    }
+  }
+  float num = 0.f, den = 0.f;
+  int rank = 0;
+  const int col = lane < A ? lane : 0;
+  while (active && ages) {
+    float x[8], w[8];
+    int cnt = 0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      x[u] = 0.f; w[u] = 0.f;
+      if (ages) {
+        const int i = 63 - __clzll((long long)ages);          // the oldest plan not yet taken
+        ages &= ~(1ull << i);
+        const float* src = (i == 0 && j >= 0) ? d.chunk + (long)j * WA : ring + (long)((q + K - i) % K) * WA + (long)(t - tn + i * s) * A;
+        x[u] = src[col];
+        w[u] = e.weights[rank + u];
+        cnt = u + 1;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      if (u < cnt) {
+        if (rank + u == 0) { num = w[u] * x[u]; den = w[u]; }
+        else { num = fmaf(w[u], x[u], num); den += w[u]; }
+      }
+    }
+    rank += cnt;
+  }
+  if (lane < A) out[(long)b * A + lane] = den > 0.f ? num / den : 0.f;
+  if (lane == 0) {
+    if (j >= 0) { d.draws[b] += 1u; birth[q] = t; }
+    const int c = j >= 0 ? 0 : min(max(d.counter[b], 0), W - 1);
+    if (active) { d.counter[b] = (c + 1) % s; e.t[b] = t + 1; }
+    else if (j >= 0) d.counter[b] = 0;
+  }
+}
+
 }  // namespace mode
 
 using namespace mode;
@@ -156,6 +242,19 @@ extern "C" int mode_env_commit_emit(const ModeEnvPoolDesc* d, void* stream) {
     return MODE_ERR_BAD_ARG;
   if (d->ctrl ? !d->chunk : !d->out) return MODE_ERR_BAD_ARG;
   hipLaunchKernelGGL(env_commit_emit_kernel, dim3(d->num_envs), dim3(64), 0, (hipStream_t)stream, *d);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
+extern "C" int mode_env_commit_emit_ens(const ModeEnvEnsDesc* e, void* stream) {
+  if (!e) return MODE_ERR_BAD_ARG;
+  const ModeEnvPoolDesc* d = &e->pool;
+  if (d->num_envs <= 0 || d->num_envs > MODE_ENV_MAX || d->W <= 0 || d->A <= 0 || d->A > 64 || d->W * d->A > 4096 || d->multistep <= 0 ||
+      d->multistep > d->W || !d->plan || !d->counter || !d->draws)
+    return MODE_ERR_BAD_ARG;
+  if (d->ctrl ? !d->chunk : !d->out) return MODE_ERR_BAD_ARG;
+  if (!e->ring || !e->birth || !e->t || !e->weights || e->K < 1 || e->K > 64 || e->K != (d->W + d->multistep - 1) / d->multistep) return MODE_ERR_BAD_ARG;
+  hipLaunchKernelGGL(env_commit_emit_ens_kernel, dim3(d->num_envs), dim3(64), 0, (hipStream_t)stream, *e);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }

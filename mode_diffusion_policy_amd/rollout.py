@@ -240,6 +240,12 @@ def _buckets(num_envs: int):
     return sorted({1 << i for i in range(num_envs.bit_length()) if 1 << i <= num_envs} | {num_envs})
 
 
+def ensemble_weights(m: float, depth: int) -> np.ndarray:
+    """The weight table of temporal ensembling, ``w_i = exp(-m i)`` for the i-th oldest live plan (ACT's rule): the fp64 exponential rounded to
+    fp32, ``depth`` entries.  The kernel reads this table and evaluates no transcendental itself."""
+    return np.exp(-float(m) * np.arange(depth, dtype=np.float64)).astype(np.float32)
+
+
 @torch.no_grad()
 def env_noise(seeds, draws, act_window_size: int, action_dim: int, sigma_max: float, device="cuda") -> torch.Tensor:
     """The initial latents ``VectorEnvPolicy`` plans from: row i = draw ``draws[i]`` of the noise stream with seed ``seeds[i]`` times ``sigma_max``,
@@ -287,12 +293,32 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
     stem would), and one more replay runs the two towers at batch mb * T with FiLM on each environment's own goal row (two graph branches, as
     ``GraphedVisualEncoder``) straight into the chunk's observation buffer: two launches and two replays per replanning step.  The encoder
     graphs live in the policy's own store, one per bucket; in-place weight updates are seen by the next replan; encoders in training mode or
-    MODE_HIP_GRAPH=0 run eagerly on the gathered rows."""
+    MODE_HIP_GRAPH=0 run eagerly on the gathered rows.
 
-    def __init__(self, denoiser, num_envs: int, seed: int = 0, extra_args: Optional[dict] = None, **kw):
+    ``temporal_ensemble=m`` (a finite float >= 0; None, the default, is everything above unchanged) averages the overlapping predictions of an
+    environment's last plans instead of letting a replan overwrite them (ACT's temporal ensembling), for ``multistep = s < act_window_size = W``.
+    Let t be the environment's local time, its active steps since its last reset.  A plan born at t_p predicts step t in its row t - t_p and is
+    live while 0 <= t - t_p < W: at most K = ceil(W / s) plans (``ensemble_depth``, at most 64).  With the live plans ordered oldest first,
+    x_i their rows for step t and w_i = exp(-m i) (``ensemble_weights``: fp64 on the host, rounded to fp32), the emitted action is
+    sum_i w_i x_i / sum_i w_i, both sums in fp32 in that order; m = 0 is the mean, one live plan is emitted bit for bit (so s = W emits what a
+    policy without the option does).  Replanning, the draws, the initial latents, the buckets and the launch budget are unchanged: the commit +
+    emit launch of a step is the ensembled kernel (csrc/env_pool.hip), which also keeps the ring.  ``reset`` drops every plan of the listed
+    environments and rewinds their t to 0; inactive steps do not advance t.  ``plans`` stays the newest plan; ``plan_ring``, ``plan_births``,
+    ``local_times`` and ``ensemble_weight_table`` expose the device state."""
+
+    def __init__(self, denoiser, num_envs: int, seed: int = 0, extra_args: Optional[dict] = None, temporal_ensemble: Optional[float] = None, **kw):
         from . import _lib as L
         from .modedit import MoDeDiT
         sampler = kw.get("sampler_type", "ddim")
+        self.temporal_ensemble, self.ensemble_depth, self._ens = None, None, None   # (the base constructor calls reset)
+        if temporal_ensemble is not None:
+            m_ens = float(temporal_ensemble)
+            if not (np.isfinite(m_ens) and m_ens >= 0.0):
+                raise ValueError(f"temporal_ensemble must be None or a finite float >= 0, got {temporal_ensemble!r}")
+            W, s = int(kw.get("act_window_size", 10)), int(kw.get("multistep", 10))
+            if 1 <= s <= W and -(-W // s) > 64:
+                raise ValueError(f"temporal_ensemble keeps ceil(act_window_size / multistep) = {-(-W // s)} plans per environment; at most 64")
+            self.temporal_ensemble = m_ens
         if sampler not in _VECTOR_SAMPLERS or extra_args:
             raise ValueError(f"VectorEnvPolicy supports the deterministic fused samplers {sorted(_VECTOR_SAMPLERS)} without extra_args; got "
                              f"sampler_type={sampler!r}, extra_args={extra_args!r}")
@@ -328,6 +354,19 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         self._scratch_out = torch.zeros(n, A, dtype=torch.float32, device=dev)
         self._desc = L.ModeEnvPoolDesc(num_envs=n, W=W, A=A, multistep=self.multistep, plan=self._plan.data_ptr(),
                                        counter=self._counter_dev.data_ptr(), draws=self._draws.data_ptr())
+        self._ens = None
+        if self.temporal_ensemble is not None:
+            # the ring of each environment's last K plans with their birth times, the local times and the weight table: allocated here, once
+            K = self.ensemble_depth = -(-W // self.multistep)
+            try:
+                self._ens_ring = torch.zeros(n, K, W, A, dtype=torch.float32, device=dev)
+            except RuntimeError as e:                                        # (torch.OutOfMemoryError is one)
+                raise ValueError(f"temporal_ensemble: cannot allocate the plan ring of {n} x {K} x {W} x {A} fp32 ({4 * n * K * W * A} bytes) on {dev}: {e}") from e
+            self._ens_birth = torch.full((n, K), -1, dtype=torch.int32, device=dev)
+            self._ens_t = torch.zeros(n, dtype=torch.int32, device=dev)
+            self._ens_w = torch.from_numpy(ensemble_weights(self.temporal_ensemble, K)).to(dev)
+            self._ens = L.ModeEnvEnsDesc(ring=self._ens_ring.data_ptr(), birth=self._ens_birth.data_ptr(), t=self._ens_t.data_ptr(),
+                                         weights=self._ens_w.data_ptr(), K=K)
         self._lib = L.load()
         self._buckets = _buckets(n)
         self._templates = {}
@@ -376,14 +415,18 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         """Start a new episode in the listed environments (see the class docstring)."""
         idx = self._env_index(envs)
         self._counter[idx] = 0
-        if seeds is None:
+        if seeds is not None:
+            seeds = list(seeds)
+            if len(seeds) != len(idx):
+                raise ValueError(f"one seed per listed environment: {len(idx)} environments, {len(seeds)} seeds")
+        if not len(idx) or (seeds is None and self._ens is None):
             return
-        seeds = list(seeds)
-        if len(seeds) != len(idx):
-            raise ValueError(f"one seed per listed environment: {len(idx)} environments, {len(seeds)} seeds")
-        if len(idx):
-            dev = self._seeds.device
-            i = torch.from_numpy(idx).pin_memory().to(dev, non_blocking=True)
+        dev = self._seeds.device
+        i = torch.from_numpy(idx).pin_memory().to(dev, non_blocking=True)
+        if self._ens is not None:                                            # no plan from before the reset is live again, local time 0
+            self._ens_birth[i] = -1
+            self._ens_t[i] = 0
+        if seeds is not None:
             self._seeds[i] = _u32_as_i32(seeds).pin_memory().to(dev, non_blocking=True)
             self._draws[i] = 0
 
@@ -396,6 +439,32 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
     def draws(self) -> torch.Tensor:
         """[num_envs] int32 (uint32 bit patterns): the draw index each environment's next replan takes (device)."""
         return self._draws
+
+    def _ens_state(self, name: str) -> torch.Tensor:
+        if self._ens is None:
+            raise AttributeError("this policy was built without temporal_ensemble: it keeps one plan per environment (plans)")
+        return getattr(self, name)
+
+    @property
+    def plan_ring(self) -> torch.Tensor:
+        """[num_envs, ensemble_depth, act_window_size, action_dim] the last plans of every environment (device, ``temporal_ensemble`` only): a plan
+        born at local time t_p is in slot ``(t_p // multistep) % ensemble_depth``."""
+        return self._ens_state("_ens_ring")
+
+    @property
+    def plan_births(self) -> torch.Tensor:
+        """[num_envs, ensemble_depth] int32: the local time at which each ring slot's plan was born, -1 = empty (device)."""
+        return self._ens_state("_ens_birth")
+
+    @property
+    def local_times(self) -> torch.Tensor:
+        """[num_envs] int32: every environment's local time, its active steps since its last reset (device)."""
+        return self._ens_state("_ens_t")
+
+    @property
+    def ensemble_weight_table(self) -> torch.Tensor:
+        """[ensemble_depth] fp32: ``ensemble_weights(temporal_ensemble, ensemble_depth)`` as the kernel reads it (device)."""
+        return self._ens_state("_ens_w")
 
     def _check_inputs(self, perceptual_emb: Dict, latent_goal: torch.Tensor):
         """Shape / device contract of the inputs: host metadata only (the rows are read by the gather launches, and only those that replan).
@@ -546,7 +615,12 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
     def _launch(self, d) -> None:
         from . import _lib as L
         from .engine import _stream
-        L.check(self._lib.mode_env_commit_emit(C.byref(d), _stream()), "env_commit_emit")
+        if self._ens is None:
+            L.check(self._lib.mode_env_commit_emit(C.byref(d), _stream()), "env_commit_emit")
+            return
+        e = type(self._ens).from_buffer_copy(self._ens)                      # temporal ensembling: the same step on the ring of plans
+        e.pool = d
+        L.check(self._lib.mode_env_commit_emit_ens(C.byref(e), _stream()), "env_commit_emit_ens")
 
     def _run_chunk(self, mb: int, m: int) -> None:
         """One replanning chunk at bucket ``mb`` with ``m`` real rows (the control block is staged): gather launch + one replay."""
