@@ -425,14 +425,12 @@ int attn_long_bwd_launch(const void* qkv, const float* qg, const float* kg, cons
 
 using namespace mode;
 
-static inline uint32_t attn_thresh(float p) { return p <= 0.f ? 0u : (uint32_t)((double)p * 4294967296.0); }
-
 extern "C" int mode_attn_block_fwd(const void* qkv, const float* q_gain, const float* k_gain, void* y, int dtype, int B, int T, int H,
                                    int head_dim, float eps, uint32_t seed, float p_drop, void* stream) {
   if (!qkv || !q_gain || !k_gain || !y || B < 0 || T <= 0 || H <= 0) return MODE_ERR_BAD_ARG;
   if (B == 0) return MODE_OK;
   if (p_drop < 0.f || p_drop >= 1.f) return MODE_ERR_BAD_ARG;
-  const uint32_t th = attn_thresh(p_drop); const float ik = 1.0f / (1.0f - p_drop);
+  const uint32_t th = dropout_thresh(p_drop); const float ik = 1.0f / (1.0f - p_drop);
   hipStream_t s = (hipStream_t)stream;
   if (T > 16) return attn_long_fwd_launch(qkv, q_gain, k_gain, y, dtype, B, T, H, head_dim, eps, seed, th, ik, s);
   if (dtype == MODE_BF16) {
@@ -465,14 +463,14 @@ int attn_block_bwd_launch(const void* qkv, const float* q_gain, const float* k_g
   if (p_drop < 0.f || p_drop >= 1.f) return MODE_ERR_BAD_ARG;
   if (B == 0) return MODE_OK;
   if (T > 16)
-    return attn_long_bwd_launch(qkv, q_gain, k_gain, dy, dqkv, dgq_partial, dgk_partial, dtype, B, T, H, head_dim, eps, seed, attn_thresh(p_drop),
+    return attn_long_bwd_launch(qkv, q_gain, k_gain, dy, dqkv, dgq_partial, dgk_partial, dtype, B, T, H, head_dim, eps, seed, dropout_thresh(p_drop),
                                 1.0f / (1.0f - p_drop), dbias_partial, (hipStream_t)stream);
   const bool mf = head_dim % 16 == 0 && g_attn_bwd_mfma;
   const size_t tiles = mf ? 3 : 4;                             // 16 x 16 coefficient tiles (the MFMA form needs no transposed copy of the dropped probabilities)
   const size_t lds = dtype == MODE_BF16 ? ((size_t)4 * T * (head_dim + 1) + 4 + tiles * 256 + 2 * T + 4 + 2 * head_dim) * 4 + (size_t)2 * T * (head_dim + 8) * 2
                                         : ((size_t)6 * T * (head_dim + 1) + 4 + tiles * 256 + 2 * T + 4 + 2 * head_dim) * 4;
   if (lds > 64 * 1024 || head_dim > 128 || T > 16 || head_dim % (dtype == MODE_BF16 ? 8 : 4)) return MODE_ERR_UNSUPPORTED;
-  const uint32_t th = attn_thresh(p_drop); const float ik = 1.0f / (1.0f - p_drop);
+  const uint32_t th = dropout_thresh(p_drop); const float ik = 1.0f / (1.0f - p_drop);
   hipStream_t s = (hipStream_t)stream;
 #define MODE_ATTN_BWD(T2, MF) hipLaunchKernelGGL((attn_bwd_kernel<T2, MF>), dim3(B * H), dim3(256), lds, s, (const T2*)qkv, q_gain, k_gain, (const T2*)dy, (T2*)dqkv, \
                                                  dgq_partial, dgk_partial, B, T, H, head_dim, eps, seed, th, ik, dbias_partial)

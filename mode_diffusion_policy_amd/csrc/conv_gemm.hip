@@ -14,9 +14,7 @@
 // Kernel: the 128 x BN ring tile of the library's other GEMMs - 4 wave64 as 2 x 2, BK = 64, two-slot LDS ring filled by `global_load_lds_dwordx4` (XOR-swizzled
 // lane-linear images), v_mfma_f32_16x16x32_bf16 with swapped operands, output tile through LDS for 16-byte coalesced stores; the gather indices of K-step kt+2
 // are requested while K-step kt+1 is staged (one vmcnt(0) per K-step covers both, two workgroups per CU hide each other's round trips).
-#include "mode_common.h"
-#include "lds_asm.h"
-#include <type_traits>
+#include "gemm_tile.h"
 
 namespace mode {
 
@@ -36,22 +34,12 @@ struct ConvGemmParams {
   float* stat_sum; float* stat_sq;         // [m_tiles][N]
 };
 
-namespace cg {
-// f(k): 32-byte column-group swizzle of a [64 k][COLS] tile (the image of gemm_bf16_tr.hip)
-template <int COLS>
-__device__ __forceinline__ int kn_swz(int row) {
-  if constexpr (COLS == 128) return (row & 3) | (((row >> 3) & 1) << 2);
-  else return ((row >> 1) & 1) | (((row >> 3) & 1) << 1);
-}
-}  // namespace cg
-
 // NS = 2: one vmcnt(0) per K-step, two workgroups per CU hide each other's round trips (the training shapes: thousands of tiles).  NS = 3: two K-steps in flight
 // under a COUNTED wait - for grids that do not even fill the part once (the rollout's batch sizes), where a K-step would otherwise cost a full memory round trip
 // (stage-4 3 x 3 at B = 32: 72 K-steps x ~2 us).  Index loads are issued BEFORE the DMA of the same iteration so that the counted wait (which leaves the newest
 // K-step's DMA instructions in flight; loads retire in order) covers them.
 template <bool W_KN, int BN, bool FUSE = false, int NS = 2>
 __global__ __launch_bounds__(256, NS == 2 ? 2 : 1) void conv_gemm_kernel(const ConvGemmParams p) {
-  using namespace cg;
   constexpr int BM = 128, BKT = 64, TM = 64, TN = BN / 2, FM = 4, FN = TN / 16;
   constexpr int A_BYTES = BM * BKT * 2, W_BYTES = BN * BKT * 2, STAGE_BYTES = A_BYTES + W_BYTES;
   constexpr int W_ROW = BN * 2;                                       // W_KN image: bytes per k-row
@@ -81,8 +69,7 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 1) void conv_gemm_kernel(const C
   if constexpr (W_KN) {
 #pragma unroll
     for (int q = 0; q < NPW; ++q) {
-      const int c = pcw ^ (kn_swz<BN>((wave * NPW + q) * RPP + krw) << 1);
-      kn_col_w[q] = min(n0 + c * 8, p.N - 8);
+      kn_col_w[q] = min(n0 + kn_chunk_col<BN>((wave * NPW + q) * RPP + krw, pcw), p.N - 8);
     }
   } else {
 #pragma unroll
@@ -118,8 +105,7 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 1) void conv_gemm_kernel(const C
       const int P = wave * 4 + q;
       const uint16_t* src = p.A + (long)aidx[q] * p.lda + ck + lchunk * 8;
       src = aidx[q] < 0 ? g_conv_zero_row + (lane & 7) * 8 : src;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(base + P * 1024), 16, 0, 0);
+      dma16(src, base + P * 1024);
     }
     if constexpr (W_KN) {
 #pragma unroll
@@ -127,15 +113,13 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 1) void conv_gemm_kernel(const C
         const int P = wave * NPW + q;
         const long r = ck + P * RPP + krw;                             // weight row (output channel) of this k
         const uint16_t* src = p.W + r * p.ldw + (long)tap * p.N + kn_col_w[q];
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                         (__attribute__((address_space(3))) void*)(base + A_BYTES + P * 1024), 16, 0, 0);
+        dma16(src, base + A_BYTES + P * 1024);
       }
     } else {
 #pragma unroll
       for (int q = 0; q < PB; ++q) {
         const int P = wave * PB + q;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_src[q] + k0),
-                                         (__attribute__((address_space(3))) void*)(base + A_BYTES + P * 1024), 16, 0, 0);
+        dma16(b_src[q] + k0, base + A_BYTES + P * 1024);
       }
     }
   };
@@ -352,8 +336,6 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 1) void conv_gemm_kernel(const C
     }
   }
 }
-
-int pp_num_cus();   // gemm_bf16_pp.hip
 
 template <bool W_KN, int BN, bool FUSE, int NS>
 static int conv_launch_ns(ConvGemmParams p, hipStream_t s) {

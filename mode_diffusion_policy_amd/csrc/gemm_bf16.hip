@@ -25,8 +25,7 @@
 //   * Grouped mode: blockIdx -> (expert, row range) from the device-side expert offsets; the expert id picks the weight slab.  No host sync.
 //   * Workgroup ids are remapped per XCD and rasterised in m-tile groups so the tiles resident on one XCD share
 //     ~4 MiB of operands (one XCD L2; measured TCC hit rate 85 %).
-#include "mode_common.h"
-#include "lds_asm.h"
+#include "gemm_tile.h"
 
 namespace mode {
 
@@ -64,11 +63,8 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN >= 16 ? 1 : (LR ? LR : (NS ==
   // ---- block -> (m-tile, n-tile): XCD-contiguous chunks, GROUP_M m-tiles rasterised m-fastest
   const int nblk = p.m_tiles * p.n_tiles;
   const int sb = xcd_remap(blockIdx.x, nblk);
-  const int per_group = GROUP_M * p.n_tiles;
-  const int grp = sb / per_group, first_m = grp * GROUP_M;
-  const int gsz = min(p.m_tiles - first_m, GROUP_M);
-  const int rem = sb - grp * per_group;
-  const int mt = first_m + rem % gsz, nt = rem / gsz;
+  int mt, nt;
+  group_m_tile(sb, p.m_tiles, p.n_tiles, GROUP_M, mt, nt);
 
   int row0 = 0, row_end = 0, expert = 0;
   if (p.offsets) {
@@ -136,12 +132,10 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN >= 16 ? 1 : (LR ? LR : (NS ==
     const int koff = kt * BK;
 #pragma unroll
     for (int q = 0; q < PA; ++q)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_src[q] + koff),
-                                       (__attribute__((address_space(3))) void*)(base + (wave * PA + q) * 1024), 16, 0, 0);
+      dma16(a_src[q] + koff, base + (wave * PA + q) * 1024);
 #pragma unroll
     for (int q = 0; q < PB; ++q)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_src[q] + koff),
-                                       (__attribute__((address_space(3))) void*)(base + A_BYTES + (wave * PB + q) * 1024), 16, 0, 0);
+      dma16(b_src[q] + koff, base + A_BYTES + (wave * PB + q) * 1024);
   };
 
   f32x4 acc[FM][FN];
@@ -384,7 +378,6 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN >= 16 ? 1 : (LR ? LR : (NS ==
 enum { CFG_AUTO = 0, CFG_128x128_NS2 = 1, CFG_128x64_NS3 = 4, CFG_128x128_NS1 = 6, CFG_128x64_NS2 = 8, CFG_128x128_NS1_4WG = 13, CFG_64x64_NS3 = 14,
        CFG_PP224 = 17, CFG_PP256 = 18, CFG_128x128_NS3 = 20 };
 int gemm_bf16_pp_launch(const ModeGemmDesc* d, const GemmParams& p, int rows256, hipStream_t s);   // gemm_bf16_pp.hip: persistent ping-pong kernel, 224 / 256 x 256 tiles
-int pp_num_cus();                                                                                   // gemm_bf16_pp.hip: compute units of the current device (= its grid)
 int gemm_bf16_skinny_launch(const ModeGemmDesc* d, const GemmParams& p, hipStream_t s);   // gemm_bf16_skinny.hip: weight streamer for a handful of rows
 int gemm_bf16_mid_launch(const ModeGemmDesc* d, const GemmParams& p, hipStream_t s);      // gemm_bf16_skinny.hip: register-resident weights, no K loop (a few hundred rows)
 int g_gemm_mid_rows_rn = 512;   // "gemm_mid_rows_rn" option: the same kernel for the c_proj (+ residual + first half of ln_2) GEMM, whose [D, D] weight is small enough to be re-read by every 32-row block (rollout batches up to 36 environments)

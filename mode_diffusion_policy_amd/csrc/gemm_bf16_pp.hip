@@ -27,24 +27,18 @@
 //
 // Numerics: every output element is the same k-ordered fp32 MFMA accumulation chain and the same epilogue expression as gemm_bf16.hip, so
 // results are BIT-IDENTICAL to the 128x128 kernels (the batch-slice consistency tests of the sampler rely on it).
-#include "mode_common.h"
-#include "lds_asm.h"
-#include <type_traits>
+#include "gemm_pp_common.h"
 
 // (Round 5's L2 run-ahead variant of this kernel - built, bit-identical, measured, lost: profiles/r05_pp_l2touch.txt - lives in scripts/probe/gemm_bf16_pp_l2touch.hip.)
 
 namespace mode {
 
 namespace pp {
-constexpr int BKK = 64;
-constexpr int HALF_BYTES = 128 * BKK * 2;                  // one 128-row half-tile: 16 KiB
-constexpr int LDS_A = 0;                                   // A[t][h] at (t*2+h) * 16 KiB
-constexpr int LDS_B = 4 * HALF_BYTES;                      // W[t][h] at 64 KiB + (t*2+h) * 16 KiB
+using namespace ppc;                                       // half-tile constants, banded tile map, stage_half (gemm_pp_common.h, with PP_COMPUTE2)
 constexpr int LDS_BIAS = 8 * HALF_BYTES;                   // 8 x 1 KiB: one bias slot per wave (each wave DMAs and reads its own copy)
 constexpr int LDS_NRM = LDS_BIAS + 8 * 1024;               // 2 x 256 floats: inverse row norms of the fused ln_2 (double-buffered per restart)
 constexpr int LDS_SS = LDS_NRM + 2 * 1024;                 // 256 rows x 64 B: per-64-column partial sums of squares of the tile's rows (DMA'd at a restart)
 constexpr int LDS_TOTAL = LDS_SS + 256 * 64;               // 154 KiB of the CU's 160
-constexpr int GM = 8;                                      // m-tiles per rasterisation band
 __device__ __forceinline__ void lds_read_f4(float4& dst, uint32_t addr) {
   asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr) : "memory");
 }
@@ -58,8 +52,6 @@ __device__ __forceinline__ void lds_write_u4(uint32_t addr, u32x4 v) {
 __device__ __forceinline__ void lds_read_u4(u32x4& dst, uint32_t addr) {
   asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr) : "memory");
 }
-template <int V>
-using IC = std::integral_constant<int, V>;
 }  // namespace pp
 
 template <int EPI, bool OUT_BF16, int FM1>
@@ -76,7 +68,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
   const int wr = wave >> 2, wc = wave & 3;
 
   // ---------------------------------------------------------------------------------------------------- tile space (all scalar)
-  // grouped (MoE): rows are sorted by expert; expert e owns sorted rows [o[e], o[e+1]) and ceil(count / BM) m-tiles (device-side offsets).
+  // grouped (MoE): the expert segments of gemm_tile.h (device-side offsets).  The offset loads, the m-tile count and the tile span below are written out
+  // here (and in gemm_bf16_pptr.hip): as shared functions they changed this kernel's scalar prologue (LABNOTES.md, 2026-10-17).
   int o[9];
   int m_real;
   if (p.offsets) {
@@ -104,30 +97,11 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
 
   struct Tile { int m, n, slice, row0, row_end, expert, seg0; };
   auto map_tile = [&](int l, Tile& t) {
-    const int per_band = GM * n_tiles * S;
-    const int band = l / per_band, first_m = band * GM;
-    const int gsz = min(GM, m_real - first_m);
-    const int rem = l - band * per_band;
-    const int per_slice = gsz * n_tiles;
-    t.slice = rem / per_slice;
-    const int q = rem - t.slice * per_slice;
-    const int run = gsz * RN;
-    const int n_hi = q / run, r2 = q - n_hi * run;
-    t.m = first_m + r2 / RN;
-    t.n = n_hi * RN + r2 % RN;
+    band_tile(l, n_tiles, S, RN, m_real, t.m, t.n, t.slice);
     t.expert = 0; t.seg0 = 0;
     if (p.offsets) {
-      int tt = t.m;
-      bool found = false;
       t.row0 = 0; t.row_end = 0;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        if (!found && e < p.E) {
-          const int nt_e = (o[e + 1] - o[e] + BM - 1) / BM;
-          if (tt < nt_e) { t.row0 = o[e] + tt * BM; t.row_end = min(o[e + 1], t.row0 + BM); t.expert = e; t.seg0 = o[e]; found = true; }
-          else tt -= nt_e;
-        }
-      }
+      segment_tile9<BM>(o, p.E, t.m, t.row0, t.row_end, t.expert, t.seg0);
     } else {
       t.row0 = t.m * BM; t.row_end = min(p.M, t.row0 + BM);
     }
@@ -139,10 +113,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
   const long w_half = (long)(SWI ? p.N : 128) * p.ldw * 2;
 
   // ---------------------------------------------------------------------------------------------------- per-lane constants
-  // DMA: one global_load_lds_dwordx4 fills a 1-KiB piece = 8 rows x 128 B; lane i -> row i>>3, physical 16-B chunk i&7 which holds the
-  // LOGICAL chunk (i&7)^(i>>3) (XOR swizzle on the source address; linear destination; same XOR on the fragment reads).  A half-tile is
-  // 16 pieces: wave w fills pieces 2w and 2w+1.
-  const int r8 = lane >> 3, lchunk = (lane & 7) ^ r8;
+  // DMA: the [rows][64 k] image of gemm_tile.h (8-row 1-KiB pieces).  A half-tile is 16 pieces: wave w fills pieces 2w and 2w+1.
+  const int r8 = lane >> 3, lchunk = rk_dma_chunk(lane);
   uint32_t b_off[2];                                           // byte offsets from a W half-tile base (tile independent)
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
@@ -152,9 +124,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
     const int col = blk * 32 + ((rho >> 2) & 3) * 8 + (rho >> 4) * 4 + (rho & 3);
     b_off[q] = (uint32_t)(((long)col * p.ldw + lchunk * 8) * 2);
   }
-  // fragment reads: lane -> row (l&15) of a 16-row fragment, 16-B chunk (l>>4) [+4 for the second k32 half], chunk XOR (row & 7)
+  // fragment reads of that image: lane -> row fr of a 16-row fragment, k-chunk fq [second k32 half: + 4 chunks = byte offset ^ 64]
   const int fr = lane & 15, fq = lane >> 4;
-  const int c0 = (fq ^ (fr & 7)) * 16;
+  const int c0 = rk_frag_byte(fr, fq);
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
   uint32_t a_addr[2][2], b_addr[2];
 #pragma unroll
@@ -202,12 +174,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
           acc[ah][bh][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Bf[bh][kh * 2 + j], A_[kh * 4 + i], acc[ah][bh][i][j], 0, 0, 0);
   };
   auto stage = [&](auto OP_, auto T_, auto H_, const char* g, uint32_t o0, uint32_t o1) __attribute__((always_inline)) {
-    constexpr int op = decltype(OP_)::value, t = decltype(T_)::value, h = decltype(H_)::value;
-    constexpr int base = (op ? LDS_B : LDS_A) + (t * 2 + h) * HALF_BYTES;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + o0),
-                                     (__attribute__((address_space(3))) void*)(smem + base + (wave * 2 + 0) * 1024), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + o1),
-                                     (__attribute__((address_space(3))) void*)(smem + base + (wave * 2 + 1) * 1024), 16, 0, 0);
+    stage_half<decltype(OP_)::value, decltype(T_)::value, decltype(H_)::value>(smem, wave, g, o0, o1);
   };
   // A half 1 of the 224-row tile has 96 rows = 12 pieces: waves 6 and 7 own pieces 12-15 and stage nothing (6 % fewer DMA bytes; the loop is
   // DMA-rate bound).  Their counted waits differ (6 instead of 8 instructions per K-step): the K loop exists in two compile-time copies, one per
@@ -215,8 +182,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
   const bool stage_a1 = FM1 == 4 || wave < 6;
   constexpr IC<0> _0{};
   constexpr IC<1> _1{};
-#define PP_SB() __builtin_amdgcn_sched_barrier(0)
-#define PP_BAR() __builtin_amdgcn_s_barrier()
   bool staggered = false;                                      // true while wave row 1 runs one barrier behind wave row 0
 
   Tile cur, nxt;
@@ -293,8 +258,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
           const int chunk = (lane & 3) * 4 < p.ss_n ? (lane & 3) : 0;   // D < 1024: fewer than 16 partials per row; the reader ignores the rest
 #pragma unroll
           for (int q = 0; q < 2; ++q)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p.ss_in + (long)nrow[q] * p.ss_n + chunk * 4),
-                                             (__attribute__((address_space(3))) void*)(smem + LDS_SS + (wave * 2 + q) * 1024), 16, 0, 0);
+            dma16(p.ss_in + (long)nrow[q] * p.ss_n + chunk * 4, smem + LDS_SS + (wave * 2 + q) * 1024);
         }
       }
       // K-steps 0 and 1 complete and waited for: the state in which every output tile begins (see the epilogue)
@@ -340,17 +304,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
     // The FIRST pair of a tile is peeled (K-steps 0 and 1 were resident before it began and the previous tile's stores may still be draining -
     // vmcnt counts them - so it takes no waits, skips the A1[1] stage and requests the bias slice), and the wave role is a template argument:
     // between two barriers there is no branch.
-#define PP_COMPUTE2(AH)           \
-  PP_BAR();                       \
-  wait_lgkmcnt<0>();              \
-  PP_SB();                        \
-  __builtin_amdgcn_s_setprio(1);  \
-  mma(AH, _0);                    \
-  mma(AH, _1);                    \
-  __builtin_amdgcn_s_setprio(0);  \
-  PP_SB();                        \
-  PP_BAR();                       \
-  PP_SB();
     auto kpair = [&](auto A1_, auto FIRST_, int kt) __attribute__((always_inline)) {
       constexpr bool a1 = decltype(A1_)::value != 0, first = decltype(FIRST_)::value != 0;
       constexpr int NW = a1 ? 8 : 6;
@@ -375,8 +328,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
       if constexpr (HAS_BIAS && first) {                         // this tile's bias slice -> the wave's own LDS slot (behind the wait: not counted by it)
         const float* bsrc = p.bias + (long)cur.expert * p.bias_estride + (long)cur.n * NOUT;
         const float* bl = SWI ? (lane < 32 ? bsrc + lane * 4 : bsrc + p.N + (lane - 32) * 4) : bsrc + lane * 4;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)bl,
-                                         (__attribute__((address_space(3))) void*)(smem + LDS_BIAS + wave * 1024), 16, 0, 0);
+        dma16(bl, smem + LDS_BIAS + wave * 1024);
       }
       PP_COMPUTE2(_1)
       // P0 of K-step kt+1 [buffer 1]
@@ -404,7 +356,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
     } else {
       if (stage_a1) kloop(_1); else kloop(_0);
     }
-#undef PP_COMPUTE2
 
     // ------------------------------------------------------------------------------------------------ epilogue: registers -> global
     // bias / SwiGLU in registers (a lane owns 8 consecutive output columns of a token row), stored straight from registers, 16 bytes per lane.
@@ -528,12 +479,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
   wait_vmcnt<0>();                                             // the tail of the operand stream must land before the LDS is released
 
   if (staggered && wr == 0) PP_BAR();                                       // balance the stagger barrier of wave row 1
-#undef PP_BAR
-#undef PP_SB
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-int pp_num_cus() {   // also used by the tile heuristic (gemm_bf16.hip: pick_cfg)
+int pp_num_cus() {   // (declared in mode_common.h) also used by the tile heuristic (gemm_bf16.hip: pick_cfg)
   static std::atomic<int> ncu[kMaxDevices];                   // zero-initialised; a racing first call writes the same value twice
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return 256;
@@ -605,3 +554,6 @@ int gemm_bf16_pp_launch(const ModeGemmDesc* d, const GemmParams& p0, int rows256
 }
 
 }  // namespace mode
+#undef PP_COMPUTE2
+#undef PP_BAR
+#undef PP_SB

@@ -16,9 +16,7 @@
 //
 // Accumulators use the swapped MFMA operands of the forward kernels (D[weight column][token]): a lane owns 4 consecutive output columns of one row per
 // 16-column fragment.  No bias / activation epilogues: backward GEMMs have none.
-#include "mode_common.h"
-#include "lds_asm.h"
-#include <type_traits>
+#include "gemm_pp_common.h"
 
 namespace mode {
 
@@ -35,15 +33,9 @@ struct PpTrParams {
 };
 
 namespace pptr {
-constexpr int BKK = 64;
-constexpr int HALF_BYTES = 128 * BKK * 2;                  // one half-tile (128 rows x 64 k, or 64 k x 128 columns): 16 KiB
-constexpr int LDS_A = 0;                                   // A[t][h] at (t*2+h) * 16 KiB
-constexpr int LDS_B = 4 * HALF_BYTES;                      // W[t][h] at 64 KiB + (t*2+h) * 16 KiB
+using namespace ppc;                                       // half-tile constants, banded tile map, stage_half (gemm_pp_common.h, with PP_COMPUTE2)
 constexpr int LDS_TOTAL = 8 * HALF_BYTES;                  // 128 KiB
-constexpr int GM = 8;
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-template <int V>
-using IC = std::integral_constant<int, V>;
 }  // namespace pptr
 
 template <bool A_KM, bool OUT_BF16>
@@ -95,17 +87,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pptr_kernel(const PpTrParams p) {
       const int steps = (t.ke - t.kb + BKK - 1) / BKK;
       t.nk = max(2, (steps + 1) & ~1);                          // the loop runs K-step PAIRS; rows past the range are masked
     } else {
-      const int per_band = GM * n_tiles * S;
-      const int band = l / per_band, first_m = band * GM;
-      const int gsz = min(GM, m_real - first_m);
-      const int rem = l - band * per_band;
-      const int per_slice = gsz * n_tiles;
-      t.slice = rem / per_slice;
-      const int q = rem - t.slice * per_slice;
-      const int run = gsz * RN;
-      const int n_hi = q / run, r2 = q - n_hi * run;
-      t.m = first_m + r2 / RN;
-      t.n = n_hi * RN + r2 % RN;
+      band_tile(l, n_tiles, S, RN, m_real, t.m, t.n, t.slice);
       t.expert = 0;
       t.nk = p.K / BKK / S;
       t.kb = t.slice * t.nk * BKK; t.ke = t.kb + t.nk * BKK;
@@ -128,9 +110,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pptr_kernel(const PpTrParams p) {
   };
 
   // ---------------------------------------------------------------------------------------------------- per-lane constants
-  // [64 k][128 cols] half-tile: a 1-KiB DMA piece = 4 k-rows x 256 B; lane -> k-row (lane >> 4) of the piece, physical 16-B chunk (lane & 15) which
-  // holds the LOGICAL chunk (lane & 15) ^ (f(k) << 1), f(k) = (k & 3) | ((k >> 3) & 1) << 2.  Wave w fills pieces 2w, 2w+1: k = (2w+q)*4 + (lane >> 4),
-  // so f(k) = (lane >> 4) | (w & 1) << 2 for both pieces.
+  // [64 k][128 cols] half-tile: the [k][COLS] image of gemm_tile.h (4 k-rows per 1-KiB piece, lane -> k-row lane >> 4, physical chunk lane & 15).  Wave w
+  // fills pieces 2w, 2w+1: k = (2w+q)*4 + (lane >> 4), so kn_swz<128>(k) = (lane >> 4) | (w & 1) << 2 for both pieces - written out here and below: through
+  // kn_chunk_col / a shared address helper this kernel's compiled code changed (LABNOTES.md, 2026-10-17).
   const int kra = lane >> 4;
   const int kn_cb = ((lane & 15) ^ ((kra | ((wave & 1) << 2)) << 1)) * 16;      // byte offset of this lane's logical chunk inside a 256-B row
   const int krow0 = wave * 8 + kra;                                             // k-row of piece q = krow0 + 4 q
@@ -140,11 +122,11 @@ __global__ __launch_bounds__(512, 2) void gemm_pptr_kernel(const PpTrParams p) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) b_off[q] = (uint32_t)((long)(krow0 + 4 * q) * p.ldw * 2 + kn_cb);
   }
-  // A operand of the data gradient: [128 rows][64 k] half-tiles as in gemm_bf16_pp.hip (8-row pieces, chunk ^ (row & 7))
+  // A operand of the data gradient: [128 rows][64 k] half-tiles, the [rows][64 k] image of gemm_tile.h
   const int r8 = lane >> 3, lchunk = (lane & 7) ^ r8;
   const int fr = lane & 15, fq = lane >> 4;
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
-  // transpose-read addresses: lane (fr, fq) addresses 4 elements of k-row fq*8 + (fr >> 2), columns T*16 + (fr & 3)*4 of 16-column tile T
+  // transpose-read addresses: lane (fr, fq) addresses 4 elements of k-row fq*8 + (fr >> 2), columns T*16 + (fr & 3)*4 of 16-column tile T; fsw = kn_swz of that row
   const int fsw = (fr >> 2) | ((fq & 1) << 2);
   auto tr_addr = [&](int base, int T_) {
     return lds0 + base + (fq * 8 + (fr >> 2)) * 256 + (fr & 1) * 8 + ((((T_ ^ fsw) << 1) | ((fr >> 1) & 1)) << 4);
@@ -220,12 +202,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pptr_kernel(const PpTrParams p) {
   };
   // DMA of one half-tile: two 1-KiB pieces per wave (pieces 2w, 2w+1), uniform base + per-lane 32-bit offset
   auto stage = [&](auto OP_, auto T_, auto H_, const char* g, uint32_t o0, uint32_t o1) __attribute__((always_inline)) {
-    constexpr int op = decltype(OP_)::value, t = decltype(T_)::value, h = decltype(H_)::value;
-    constexpr int base = (op ? LDS_B : LDS_A) + (t * 2 + h) * HALF_BYTES;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + o0),
-                                     (__attribute__((address_space(3))) void*)(smem + base + (wave * 2 + 0) * 1024), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + o1),
-                                     (__attribute__((address_space(3))) void*)(smem + base + (wave * 2 + 1) * 1024), 16, 0, 0);
+    stage_half<decltype(OP_)::value, decltype(T_)::value, decltype(H_)::value>(smem, wave, g, o0, o1);
   };
   // weight gradient: half-tile of a [rows][cols] operand over the K rows [r0, r0 + 64) of the reduction range [.., ke): rows past the range read a
   // zero row (A: they must contribute exactly 0) / a clamped, finite row (W)
@@ -241,14 +218,11 @@ __global__ __launch_bounds__(512, 2) void gemm_pptr_kernel(const PpTrParams p) {
         const char* z = reinterpret_cast<const char*>(g_pptr_zero_row) + (lane & 15) * 16;
         src = r < ke ? src : z;
       }
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(smem + base + (wave * 2 + q) * 1024), 16, 0, 0);
+      dma16(src, smem + base + (wave * 2 + q) * 1024);
     }
   };
   constexpr IC<0> _0{};
   constexpr IC<1> _1{};
-#define PT_SB() __builtin_amdgcn_sched_barrier(0)
-#define PT_BAR() __builtin_amdgcn_s_barrier()
   bool staggered = false;
   bool fresh = true;
 
@@ -282,8 +256,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pptr_kernel(const PpTrParams p) {
     if (fresh) {
       // ---- (re)start the operand stream for a new m-tile / K-slice / group (see gemm_bf16_pp.hip for the barrier choreography)
       wait_vmcnt<0>();
-      if (staggered && wr == 0) PT_BAR();
-      PT_BAR();
+      if (staggered && wr == 0) PP_BAR();
+      PP_BAR();
       Wc = w_tile_base(cur);
       if constexpr (A_KM) {
         Ak = reinterpret_cast<const char*>(p.A) + (long)cur.m * BM * 2;
@@ -303,10 +277,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pptr_kernel(const PpTrParams p) {
       stA(_0, _0, 0); stA(_0, _1, 0);
       stA(_1, _0, 1); stA(_1, _1, 1);
       wait_vmcnt<0>();
-      PT_BAR();
-      if (wr == 1) PT_BAR();                                     // stagger: wave row 1 runs one barrier behind wave row 0 from here on
+      PP_BAR();
+      if (wr == 1) PP_BAR();                                     // stagger: wave row 1 runs one barrier behind wave row 0 from here on
       staggered = true;
-      PT_SB();
+      PP_SB();
       fresh = false;
     }
     const bool has_next = L + 1 < Lend;
@@ -319,17 +293,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pptr_kernel(const PpTrParams p) {
 
     // ------------------------------------------------------------------------------------------------ K loop: 4 phases = 2 K-steps (gemm_bf16_pp.hip)
     //   R(P0, t): reads W0 W1 A0 of K-step t;  stages A1[t+1]           R(P1, t): reads A1[t];  stages W0 W1 A0 of K-step t+2
-#define PT_COMPUTE2(AH)           \
-  PT_BAR();                       \
-  wait_lgkmcnt<0>();              \
-  PT_SB();                        \
-  __builtin_amdgcn_s_setprio(1);  \
-  mma(AH, _0);                    \
-  mma(AH, _1);                    \
-  __builtin_amdgcn_s_setprio(0);  \
-  PT_SB();                        \
-  PT_BAR();                       \
-  PT_SB();
     auto kpair = [&](auto FIRST_, int kt) __attribute__((always_inline)) {
       constexpr bool first = decltype(FIRST_)::value != 0;
       const bool cross = kt + 2 >= nk;
@@ -337,34 +300,33 @@ __global__ __launch_bounds__(512, 2) void gemm_pptr_kernel(const PpTrParams p) {
       const char* W2 = cross ? Wn : Wc;
       // P0 of K-step kt [buffer 0]
       rdB(_0, _0); rdB(_0, _1);
-      PT_SB();
+      PP_SB();
       rdA(_0, _0);
       if constexpr (!first) { stA(_1, _1, kt + 1); wait_vmcnt<8>(); }
-      PT_COMPUTE2(_0)
+      PP_COMPUTE2(_0)
       // P1 of K-step kt
       rdA(_0, _1);
       stW(_0, _0, W2, k2); stW(_0, _1, W2, k2);
       stA(_0, _0, k2);
       if constexpr (!first) wait_vmcnt<8>();
-      PT_COMPUTE2(_1)
+      PP_COMPUTE2(_1)
       // P0 of K-step kt+1 [buffer 1]
       rdB(_1, _0); rdB(_1, _1);
-      PT_SB();
+      PP_SB();
       rdA(_1, _0);
       stA(_0, _1, k2);
       if constexpr (!first) wait_vmcnt<8>();
-      PT_COMPUTE2(_0)
+      PP_COMPUTE2(_0)
       // P1 of K-step kt+1; K-step kt+2 [buffer 0] retired by this wait
       rdA(_1, _1);
       stW(_1, _0, W2, k2 + 1); stW(_1, _1, W2, k2 + 1);
       stA(_1, _0, k2 + 1);
       wait_vmcnt<8>();
-      PT_COMPUTE2(_1)
+      PP_COMPUTE2(_1)
     };
     kpair(_1, 0);
 #pragma unroll 1
     for (int kt = 2; kt < nk; kt += 2) kpair(_0, kt);
-#undef PT_COMPUTE2
 
     // ------------------------------------------------------------------------------------------------ epilogue: registers -> global
     // (ordering as in gemm_bf16_pp.hip: the last half-tile of the next tile's second K-step is requested, outputs are packed while every DMA still in
@@ -375,7 +337,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pptr_kernel(const PpTrParams p) {
                  ((A_KM ? (long)cur.expert * p.c_gstride : (long)cur.slice * p.split_stride) + (long)cur.row0 * p.ldc + (long)cur.n * NOUT + wc * 32) * ESZ;
       const uint32_t c_lane = (uint32_t)(fr * (int)p.ldc + fq * 4) * ESZ;
       if (cont) stA(_1, _1, 1);                                  // next tile, K-step 1, A half 1 (its slot was last read in phase 7)
-      if (wr == 0) PT_BAR();
+      if (wr == 0) PP_BAR();
       // one ROUND = one fragment row x one 128-column W half: this lane's 2 x 4 outputs of it (columns j*16 + fq*4 .. +3)
       auto round_urow = [&](int r) { const int fi = r >> 1, a = fi >> 2, i = fi & 3; return a * 128 + wr * 64 + i * 16; };
       auto round_col = [&](int r) { return (r & 1) * 128; };
@@ -393,7 +355,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pptr_kernel(const PpTrParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(pk[r][0]), "+v"(pk[r][1]));      // every output is packed before the wait below
         wait_vmcnt<0>();
-        PT_SB();
+        PP_SB();
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int urow = round_urow(r);
@@ -425,7 +387,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pptr_kernel(const PpTrParams p) {
           for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j) acc[a][b][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (wr == 1) PT_BAR();
+      if (wr == 1) PP_BAR();
     }
     if (!has_next) break;
     ++L;
@@ -434,14 +396,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pptr_kernel(const PpTrParams p) {
     Wc = Wn;
   }
   wait_vmcnt<0>();                                             // the tail of the operand stream must land before the LDS is released
-  if (staggered && wr == 0) PT_BAR();                          // balance the stagger barrier of wave row 1
-#undef PT_BAR
-#undef PT_SB
+  if (staggered && wr == 0) PP_BAR();                          // balance the stagger barrier of wave row 1
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-int pp_num_cus();   // gemm_bf16_pp.hip
-
 template <bool A_KM, bool OUT_BF16>
 static int pptr_launch(const PpTrParams& p, long t_max, hipStream_t s) {
   const int ncu = pp_num_cus();
@@ -534,3 +492,6 @@ int gather_rows_bf16(const void* in, long ld_in, const int* rows, int n, int col
 }
 
 }  // namespace mode
+#undef PP_COMPUTE2
+#undef PP_BAR
+#undef PP_SB

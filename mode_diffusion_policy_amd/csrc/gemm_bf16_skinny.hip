@@ -16,8 +16,7 @@
 // Fused ln_2 of the small-batch chain (MODE_GEMM_SMALL_ROWS): RESIDUAL_NORM publishes one sum of squares per row and 16-column group
 // ([M, N/16], this workgroup's columns), SWIGLU scales its accumulator rows by 1/norm from any number of partials per row
 // (sum_row_partials_wave: the same function in the combine / head kernels).
-#include "mode_common.h"
-#include "lds_asm.h"
+#include "gemm_tile.h"
 
 namespace mode {
 
@@ -338,8 +337,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_stream_kernel(const GemmParams 
 #pragma unroll
     for (int j = 0; j < NIT; ++j) {
       const int hr = j * 4 + wave;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p.A + (long)src[j] * p.lda + kslice + (hr & 1) * 512 + lane * 8),
-                                       (__attribute__((address_space(3))) void*)(aimg + (hr >> 1) * AROW + (hr & 1) * 1024), 16, 0, 0);
+      dma16(p.A + (long)src[j] * p.lda + kslice + (hr & 1) * 512 + lane * 8, aimg + (hr >> 1) * AROW + (hr & 1) * 1024);
     }
     [[maybe_unused]] float4 e0 = make_float4(0.f, 0.f, 0.f, 0.f), e1 = make_float4(0.f, 0.f, 0.f, 0.f);
     skinny_epi_operands<EPI>(p, g.bias, min(ml, row_end - 1), min(n, p.N - 4), e0, e1);
@@ -404,8 +402,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_mid_kernel(const GemmParams p) 
   for (int j = 0; j < 16; ++j) {
     const int hr = j * 4 + wave;                                     // half-row: row hr >> 1, 1-KiB half hr & 1
     const int srow = min(mb + (hr >> 1), p.M - 1);                  // rows past M re-read a valid row (never stored)
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p.A + (long)srow * p.lda + (hr & 1) * 512 + lane * 8),
-                                     (__attribute__((address_space(3))) void*)(aimg + (hr >> 1) * AROW + (hr & 1) * 1024), 16, 0, 0);
+    dma16(p.A + (long)srow * p.lda + (hr & 1) * 512 + lane * 8, aimg + (hr >> 1) * AROW + (hr & 1) * 1024);
   }
   // Weight fragments: loaded with four ADJACENT lanes on one row's 64 bytes of a k32 step (lane l: row l >> 2, 16-byte piece l & 3 - 16 requests
   // of 64 B per instruction instead of 64 of 16 B: the per-CU L1 request rate, one per clock, was what bounded the direct fragment loads:

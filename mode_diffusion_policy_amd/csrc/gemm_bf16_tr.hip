@@ -47,11 +47,8 @@ __global__ __launch_bounds__(256, (NS == 1 ? 3 : 2)) void gemm_tr_kernel(const T
 
   const int nblk = p.m_tiles * p.n_tiles;
   const int sb = xcd_remap(blockIdx.x, nblk);
-  const int per_group = GROUP_M * p.n_tiles;
-  const int grp = sb / per_group, first_m = grp * GROUP_M;
-  const int gsz = min(p.m_tiles - first_m, GROUP_M);
-  const int rem = sb - grp * per_group;
-  int mt = first_m + rem % gsz, nt = rem / gsz;
+  int mt, nt;
+  group_m_tile(sb, p.m_tiles, p.n_tiles, GROUP_M, mt, nt);
   if constexpr (EPI == 2) {
     // the fused optimizer epilogue is HBM-bound: workgroups that run side by side take CONSECUTIVE column tiles of one row band, so that together they
     // stream whole parameter rows (a column of tiles shares its low address bits - with m fastest, every concurrently streaming workgroup would sit on
@@ -68,15 +65,7 @@ __global__ __launch_bounds__(256, (NS == 1 ? 3 : 2)) void gemm_tr_kernel(const T
   }
   int row0 = 0, row_end = 0, expert = 0;
   if (!A_KM && p.offsets) {
-    int t = mt;
-    bool found = false;
-    for (int e = 0; e < p.E && !found; ++e) {
-      const int o0 = p.offsets[e], o1 = p.offsets[e + 1];
-      const int nt_e = (o1 - o0 + BM - 1) / BM;
-      if (t < nt_e) { row0 = o0 + t * BM; row_end = min(o1, row0 + BM); expert = e; found = true; }
-      else t -= nt_e;
-    }
-    if (!found) return;
+    if (!segment_tile_loop<BM>(p.offsets, p.E, mt, row0, row_end, expert)) return;      // expert segments (gemm_tile.h)
   } else {
     row0 = mt * BM; row_end = min(p.M, row0 + BM);
   }
@@ -142,8 +131,7 @@ __global__ __launch_bounds__(256, (NS == 1 ? 3 : 2)) void gemm_tr_kernel(const T
       } else {
         src = a_src[q] + kb + kt * BKT;
       }
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(base + P * 1024), 16, 0, 0);
+      dma16(src, base + P * 1024);
     }
 #pragma unroll
     for (int q = 0; q < NPW; ++q) {
@@ -157,8 +145,7 @@ __global__ __launch_bounds__(256, (NS == 1 ? 3 : 2)) void gemm_tr_kernel(const T
       if constexpr (A_KM && NS <= 2) {
         if (w_rows) src = r < 0 ? g_zero_row + (lane & 15) * 8 : src;       // a negative index = a zero row (out-of-image filter taps of a convolution)
       }
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(base + A_BYTES + P * 1024), 16, 0, 0);
+      dma16(src, base + A_BYTES + P * 1024);
     }
   };
 

@@ -1,8 +1,7 @@
 // Shared by the transpose-read backward GEMMs (gemm_bf16_tr.hip: ring kernels; gemm_bf16_trws.hip: the wave-specialised weight-gradient + AdamW kernel):
-// the kernel argument block, the column-group swizzle of a [k][n] tile; the untracked LDS reads and waits come from lds_asm.h.
+// the kernel argument block; the [k][n] tile image and its swizzle come from gemm_tile.h, the untracked LDS reads and waits from lds_asm.h.
 #pragma once
-#include "mode_common.h"
-#include "lds_asm.h"
+#include "gemm_tile.h"
 
 namespace mode {
 
@@ -26,13 +25,5 @@ struct TrParams {
   float* ad_p; float* ad_m; float* ad_v; uint16_t* ad_lp; float* ad_ema; float* ad_gsq;
   float ad_decay, ad_b1, ad_b2, ad_eps, ad_step_size, ad_inv_bc2_sqrt, ad_gscale, ad_ema_rate;
 };
-
-// f(k): 32-byte column-group swizzle of a [64 k][COLS] tile (COLS = 128: 8 groups per 256-B row; COLS = 64: 4 groups per 128-B row, odd
-// rows already sit on the other half of the banks)
-template <int COLS>
-__device__ __forceinline__ int kn_swz(int row) {
-  if constexpr (COLS == 128) return (row & 3) | (((row >> 3) & 1) << 2);
-  else return ((row >> 1) & 1) | (((row >> 3) & 1) << 1);
-}
 
 }  // namespace mode

@@ -148,6 +148,10 @@ __device__ __forceinline__ float sum_row_partials_wave(const float* __restrict__
   return wave_sum(s);
 }
 
+int pp_num_cus();   // gemm_bf16_pp.hip: compute units of the current device (= the persistent kernels' grid; also the ring kernels' tile heuristics)
+// dropout probability -> the 32-bit keep threshold of drop_keep (p * 2^32; 0 = keep everything)
+inline uint32_t dropout_thresh(float p) { return p <= 0.f ? 0u : (uint32_t)((double)p * 4294967296.0); }
+
 // Rows up to which the bf16 GEMM uses the weight-streaming kernel of gemm_bf16_skinny.hip ("gemm_skinny_rows" option; 0 = off)
 extern int g_gemm_skinny_rows;
 extern int g_gemm_cfg;

@@ -736,8 +736,6 @@ extern "C" int mode_colsum(const void* X, int64_t ld, int rows, int cols, int dt
   return MODE_OK;
 }
 
-static inline uint32_t drop_thresh(float p) { return p <= 0.f ? 0u : (uint32_t)((double)p * 4294967296.0); }
-
 extern "C" int mode_swiglu_fwd(const void* P, void* Hd, int64_t rows, int Hdim, int dtype, uint32_t seed, float p_drop, void* stream) {
   if (!P || !Hd || rows < 0 || Hdim <= 0 || (Hdim & 3) || p_drop < 0.f || p_drop >= 1.f) return MODE_ERR_BAD_ARG;
   const long n4 = rows * Hdim / 4;
@@ -745,11 +743,11 @@ extern "C" int mode_swiglu_fwd(const void* P, void* Hd, int64_t rows, int Hdim, 
   const float ik = 1.0f / (1.0f - p_drop);
   if (dtype == MODE_BF16)
     if (Hdim % 8 == 0 && (((uintptr_t)P | (uintptr_t)Hd) & 15) == 0)
-      hipLaunchKernelGGL(swiglu_fwd_bf16x8_kernel, dim3((unsigned)((rows * (Hdim / 8) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)P, (uint16_t*)Hd, (long)rows, Hdim, seed, drop_thresh(p_drop), ik);
+      hipLaunchKernelGGL(swiglu_fwd_bf16x8_kernel, dim3((unsigned)((rows * (Hdim / 8) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)P, (uint16_t*)Hd, (long)rows, Hdim, seed, dropout_thresh(p_drop), ik);
     else
-      hipLaunchKernelGGL(swiglu_fwd_kernel<uint16_t>, dim3((n4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)P, (uint16_t*)Hd, (long)rows, Hdim, seed, drop_thresh(p_drop), ik);
+      hipLaunchKernelGGL(swiglu_fwd_kernel<uint16_t>, dim3((n4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)P, (uint16_t*)Hd, (long)rows, Hdim, seed, dropout_thresh(p_drop), ik);
   else
-    hipLaunchKernelGGL(swiglu_fwd_kernel<float>, dim3((n4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)P, (float*)Hd, (long)rows, Hdim, seed, drop_thresh(p_drop), ik);
+    hipLaunchKernelGGL(swiglu_fwd_kernel<float>, dim3((n4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)P, (float*)Hd, (long)rows, Hdim, seed, dropout_thresh(p_drop), ik);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }
@@ -761,9 +759,9 @@ extern "C" int mode_swiglu_bwd(const void* P, const void* dHd, void* dP, int64_t
   if (n4 == 0) return MODE_OK;
   const float ik = 1.0f / (1.0f - p_drop);
   if (dtype == MODE_BF16)
-    hipLaunchKernelGGL(swiglu_bwd_kernel<uint16_t>, dim3((n4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)P, (const uint16_t*)dHd, (uint16_t*)dP, (long)rows, Hdim, seed, drop_thresh(p_drop), ik);
+    hipLaunchKernelGGL(swiglu_bwd_kernel<uint16_t>, dim3((n4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)P, (const uint16_t*)dHd, (uint16_t*)dP, (long)rows, Hdim, seed, dropout_thresh(p_drop), ik);
   else
-    hipLaunchKernelGGL(swiglu_bwd_kernel<float>, dim3((n4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)P, (const float*)dHd, (float*)dP, (long)rows, Hdim, seed, drop_thresh(p_drop), ik);
+    hipLaunchKernelGGL(swiglu_bwd_kernel<float>, dim3((n4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)P, (const float*)dHd, (float*)dP, (long)rows, Hdim, seed, dropout_thresh(p_drop), ik);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }
@@ -1080,10 +1078,10 @@ extern "C" int mode_swiglu_bwd_bias(const void* P, const void* dHd, void* dP, in
   const float ik = 1.0f / (1.0f - p_drop);
   if (E <= 4)
     hipLaunchKernelGGL(swiglu_bwd_bias_bf16x8_kernel<4>, grid, dim3(256), 0, s, (const uint16_t*)P, (const uint16_t*)dHd, (uint16_t*)dP, (long)rows, Hdim, seed,
-                       drop_thresh(p_drop), ik, expert_offsets, E, RB, partial);
+                       dropout_thresh(p_drop), ik, expert_offsets, E, RB, partial);
   else
     hipLaunchKernelGGL(swiglu_bwd_bias_bf16x8_kernel<16>, grid, dim3(256), 0, s, (const uint16_t*)P, (const uint16_t*)dHd, (uint16_t*)dP, (long)rows, Hdim, seed,
-                       drop_thresh(p_drop), ik, expert_offsets, E, RB, partial);
+                       dropout_thresh(p_drop), ik, expert_offsets, E, RB, partial);
   MODE_LAUNCH_CHECK();
   // db[e][c] = sum over row blocks of partial[rb][e][c]: rows = nrb, cols = E * 2 * Hdim
   return mode_colsum(partial, (int64_t)E * 2 * Hdim, nrb, E * 2 * Hdim, MODE_F32, nullptr, 0, 1, db, 0, (char*)workspace + (size_t)nrb * E * 2 * Hdim * 4, 0, stream);
