@@ -886,6 +886,58 @@ typedef struct ModeEnvEnsDesc {
  * and t = t + 1; every inactive one writes a zero row and keeps both.  MODE_ERR_BAD_ARG as its sibling, and when K != ceil(W / multistep). */
 int mode_env_commit_emit_ens(const ModeEnvEnsDesc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Classifier-free guidance (GCDenoiser(guidance_scale=w)).  An addition to ABI 13: new structs that wrap the old ones and new exports, nothing
+ * existing changes.  The guided denoiser is
+ *   D_w(x; sigma, obs, goal) = D_u + w * (D_c - D_u),   D_c = D(x; sigma, obs, goal),   D_u = D(x; sigma, obs, 0)
+ * and runs as ONE chain at an internal batch of 2B rows for B (latent, observation, goal) PAIRS: internal sample b is the conditional branch
+ * of pair b, internal sample b + B its unconditional branch.  Every kernel between the embedding and the head runs unchanged at batch 2B;
+ * only the two ends know about pairs.  goal_emb has no bias, so the unconditional goal embedding is exactly zero: no GEMM runs for it.
+ * ------------------------------------------------------------------------------------------------------------------ */
+
+/* mode_embed_tokens_fwd for pairs.  emb.B is the number of pairs; x / h receive 2 * emb.B * T rows.  Internal sample b + h * B (h = 0, 1) reads
+ * the sigma-token row, goal_e, img_e, actions and c_in of pair b - no input is duplicated in memory -, except that for h = 1 the goal token is
+ * 0 + pos[0].  emb.cond follows its stride: 0 = one row shared by all 2B samples, D = 2B rows, the conditional half first.
+ * MODE_ERR_UNSUPPORTED for D > 4096 (there is no fallback kernel for pairs). */
+typedef struct ModeEmbedGuidedDesc {
+  ModeEmbedDesc emb;
+} ModeEmbedGuidedDesc;
+int mode_embed_tokens_guided_fwd(const ModeEmbedGuidedDesc* d, void* stream);
+
+/* mode_head_ddim_fwd for pairs.  head.B is the number of pairs; head.u / pos / posw / u_ss are those of 2 * head.B * T token rows, head.Y the expert
+ * outputs of these rows.  One workgroup per action row of a PAIR finishes both of its hidden rows (last block's combine, final RMSNorm, output head,
+ * EDM scalings: den_c and den_u, each exactly as mode_head_ddim_fwd forms `denoised`), then
+ *   den = den_u + scale[0] * (den_c - den_u)          (fp32: one subtraction, one product, one sum, unfused)
+ * and from there on the update forms of ModeHeadDesc with den in the place of `denoised`: head.denoised receives den; the two-point multistep
+ * form (den_prev, scal[3]) and the linear form (lin, aux1, aux2) read den.  x_a / scal / denoised / x_next / den_prev / aux1 / aux2 hold one row per PAIR.
+ * scale: DEVICE fp32 scalar, read by the kernel - a new guidance scale is a 4-byte copy, a captured graph stays valid.
+ * head.F must be NULL and head.scal / scale non-NULL (MODE_ERR_BAD_ARG); shapes that only the fallback kernel of mode_head_ddim_fwd takes
+ * (D > 4096, k > 2, y_splits > 8) return MODE_ERR_UNSUPPORTED. */
+typedef struct ModeHeadGuidedDesc {
+  ModeHeadDesc head;
+  const float* scale;
+} ModeHeadGuidedDesc;
+int mode_head_ddim_guided_fwd(const ModeHeadGuidedDesc* d, void* stream);
+
+/* mode_dit_forward for pairs: mode_embed_tokens_guided_fwd, the blocks at batch 2B, mode_head_ddim_guided_fwd.  What `fwd` means here:
+ *   fwd.B                                     number of pairs
+ *   goal_e, img_e, actions, c_in, scal,
+ *   denoised, x_next, den_prev, aux1, aux2    B-row buffers (one row / scalar set per pair; the strides as in mode_dit_forward)
+ *   emb_t                                     the sigma-token rows of the pairs (stride 0: one shared row)
+ *   cond                                      stride 0: one row for all 2B samples; stride D: 2B rows, the conditional half first (goal routing:
+ *                                             emb_t + goal_e for sample b, emb_t alone for sample b + B)
+ *   meta                                      dispatch records for 2B * T tokens (meta_layer_stride as there); NULL = token routing
+ *   topk_idx_out                              int32 [L][2B * T][k]
+ *   uniform_routing                           the promise covers all 2B samples
+ *   F                                         must be NULL (MODE_ERR_BAD_ARG); scal must not be
+ * The workspace is that of batch 2B: mode_dit_workspace_bytes(dims, 2 * B, 0, dtype).  D > 4096 or k > 2: MODE_ERR_UNSUPPORTED before any launch. */
+typedef struct ModeGuidedArgs {
+  ModeForwardArgs fwd;
+  const float* scale;                                /* device fp32 scalar w, see ModeHeadGuidedDesc */
+} ModeGuidedArgs;
+int mode_dit_forward_guided(const ModeDims* dims, const ModeModelWeights* w, const ModeGuidedArgs* a,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

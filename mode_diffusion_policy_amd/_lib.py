@@ -127,6 +127,21 @@ class ModeForwardArgs(C.Structure):
                 ("F", c_vp), ("denoised", c_vp), ("x_next", c_vp), ("topk_idx_out", c_vp), ("uniform_routing", c_i32), ("den_prev", c_vp), ("lin", c_vp), ("aux1", c_vp), ("aux2", c_vp)]
 
 
+class ModeEmbedGuidedDesc(C.Structure):
+    """mode_embed_tokens_fwd for classifier-free guidance pairs (include/mode_hip.h, an addition to ABI 13): emb.B pairs, 2 * emb.B * T rows written."""
+    _fields_ = [("emb", ModeEmbedDesc)]
+
+
+class ModeHeadGuidedDesc(C.Structure):
+    """mode_head_ddim_fwd for pairs: den = den_u + scale[0] * (den_c - den_u) ahead of the solver update; ``scale`` a device fp32 scalar."""
+    _fields_ = [("head", ModeHeadDesc), ("scale", c_vp)]
+
+
+class ModeGuidedArgs(C.Structure):
+    """mode_dit_forward for pairs: fwd.B pairs at an internal batch of 2 * fwd.B (what every field means then: include/mode_hip.h)."""
+    _fields_ = [("fwd", ModeForwardArgs), ("scale", c_vp)]
+
+
 class ModeQkvAttnDesc(C.Structure):
     _fields_ = [("dtype", c_i32), ("B", c_i32), ("T", c_i32), ("H", c_i32), ("D", c_i32), ("h", c_vp), ("ldh", c_i64), ("wqkv", c_vp), ("ldw", c_i64),
                 ("bqkv", c_vp), ("q_gain", c_vp), ("k_gain", c_vp), ("eps", c_f32), ("y", c_vp), ("ldy", c_i64)]
@@ -263,6 +278,9 @@ PROTOTYPES = {
     "mode_env_commit_emit": (C.c_int, [P(ModeEnvPoolDesc), c_vp]),
     "mode_env_gather_frames": (C.c_int, [P(ModeEnvFramesDesc), c_vp]),
     "mode_env_commit_emit_ens": (C.c_int, [P(ModeEnvEnsDesc), c_vp]),
+    "mode_embed_tokens_guided_fwd": (C.c_int, [P(ModeEmbedGuidedDesc), c_vp]),
+    "mode_head_ddim_guided_fwd": (C.c_int, [P(ModeHeadGuidedDesc), c_vp]),
+    "mode_dit_forward_guided": (C.c_int, [P(ModeDims), P(ModeModelWeights), P(ModeGuidedArgs), c_vp, c_sz, c_vp]),
 }
 
 _lib: Optional[C.CDLL] = None

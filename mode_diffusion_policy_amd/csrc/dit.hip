@@ -102,7 +102,7 @@ extern "C" size_t mode_hip_sizeof(const char* n) {
   MODE_SZ(ModeModelWeights) MODE_SZ(ModeMetaLayout) MODE_SZ(ModeForwardArgs) MODE_SZ(ModeStashLayout) MODE_SZ(ModeTrainArgs) MODE_SZ(ModeLayerGrads)
   MODE_SZ(ModeModelGrads) MODE_SZ(ModeLayerWeightsT) MODE_SZ(ModeModelWeightsT) MODE_SZ(ModeBnFilmDesc) MODE_SZ(ModeQkvAttnDesc) MODE_SZ(ModeConvBnDesc)
   MODE_SZ(ModeAdamWFuse) MODE_SZ(ModeStemConvDesc) MODE_SZ(ModeEnvPoolDesc) MODE_SZ(ModeEnvFramesCam)
-  MODE_SZ(ModeEnvFramesDesc) MODE_SZ(ModeEnvEnsDesc)
+  MODE_SZ(ModeEnvFramesDesc) MODE_SZ(ModeEnvEnsDesc) MODE_SZ(ModeEmbedGuidedDesc) MODE_SZ(ModeHeadGuidedDesc) MODE_SZ(ModeGuidedArgs)
 #undef MODE_SZ
   return 0;
 }
@@ -274,16 +274,22 @@ extern "C" int mode_dit_route(const ModeDims* dims, const ModeModelWeights* w, c
   return mode_moe_route_topk_f32(logits, Ly * R, E, k, dims->router_normalize, shifted, probs, topk_idx, topk_w, stream);
 }
 
-extern "C" int mode_dit_forward(const ModeDims* dims, const ModeModelWeights* w, const ModeForwardArgs* a, void* workspace,
-                                size_t workspace_bytes, void* stream) {
+// The denoiser's launch chain.  guide_scale == NULL: mode_dit_forward.  Otherwise mode_dit_forward_guided (classifier-free guidance): a->B counts
+// PAIRS, the chain runs at the internal batch B = 2 * a->B (sample b the conditional, b + a->B the unconditional branch of pair b) and only its two
+// ends - the embedding and the head - differ; the geometry switches below see the internal batch.
+static int dit_forward_chain(const ModeDims* dims, const ModeModelWeights* w, const ModeForwardArgs* a, const float* guide_scale, void* workspace,
+                             size_t workspace_bytes, void* stream) {
   int rc = check_dims(dims);
   if (rc) return rc;
   if (!w || !w->layers || !a || !workspace) return MODE_ERR_BAD_ARG;
   if (!a->goal_e || !a->img_e || !a->actions || !a->cond) return MODE_ERR_BAD_ARG;
+  const bool guided = guide_scale != nullptr;
+  if (guided && (a->F || !a->scal)) return MODE_ERR_BAD_ARG;
+  if (guided && (dims->D > 4096 || dims->k > 2)) return MODE_ERR_UNSUPPORTED;   // the pair kernels have no fallback form: refuse before any launch
   const bool tok_route = a->meta == nullptr;                   // cond_router=False: routing on the token states, inside the chain
   if (a->B <= 0) return MODE_OK;
   const ModeDims& d = *dims;
-  const int dt = a->dtype, B = a->B, T = d.T, D = d.D, N = B * T, NK = N * d.k;
+  const int dt = a->dtype, B = guided ? 2 * a->B : a->B, T = d.T, D = d.D, N = B * T, NK = N * d.k;
   if (dt == MODE_BF16 && (D % 64 || (D / d.H) % 16 || (D / d.H) > 128)) return MODE_ERR_UNSUPPORTED;
   const WsLayout L = ws_layout(d, B, 0, dt);
   if (workspace_bytes < L.total) return MODE_ERR_WORKSPACE;
@@ -312,11 +318,12 @@ extern "C" int mode_dit_forward(const ModeDims* dims, const ModeModelWeights* w,
   // ---- sequence assembly + block 0's ln_1 + c
   ModeEmbedDesc e;
   memset(&e, 0, sizeof(e));
-  e.B = B; e.T = T; e.D = D; e.A_len = d.A_len; e.A_dim = d.A_dim; e.n_img = d.n_img; e.use_noise_token = d.use_noise_token;
+  e.B = a->B; e.T = T; e.D = D; e.A_len = d.A_len; e.A_dim = d.A_dim; e.n_img = d.n_img; e.use_noise_token = d.use_noise_token;
   e.emb_t = a->emb_t; e.emb_row_stride = a->emb_row_stride; e.goal_e = a->goal_e; e.img_e = a->img_e; e.actions = a->actions;
   e.c_in = a->c_in; e.c_in_stride = a->c_in_stride; e.w_act = w->w_act; e.pos = w->pos; e.g = w->layers[0].ln1_g;
   e.cond = a->cond; e.cond_row_stride = a->cond_row_stride; e.eps = d.eps; e.x = x; e.h = h; e.h_dtype = dt;
-  rc = mode_embed_tokens_fwd(&e, stream);
+  if (guided) { ModeEmbedGuidedDesc ge; ge.emb = e; rc = mode_embed_tokens_guided_fwd(&ge, stream); }
+  else rc = mode_embed_tokens_fwd(&e, stream);
   if (rc) return rc;
 
   for (int l = 0; l < d.L; ++l) {
@@ -397,14 +404,26 @@ extern "C" int mode_dit_forward(const ModeDims* dims, const ModeModelWeights* w,
     } else {
       ModeHeadDesc hd;
       memset(&hd, 0, sizeof(hd));
-      hd.B = B; hd.T = T; hd.D = D; hd.A_len = d.A_len; hd.A_dim = d.A_dim; hd.k = d.k;
+      hd.B = a->B; hd.T = T; hd.D = D; hd.A_len = d.A_len; hd.A_dim = d.A_dim; hd.k = d.k;
       hd.u = x; hd.Y = ybuf; hd.y_dtype = dt; hd.y_splits = ysplit; hd.y_split_stride = (long)NK * D; hd.pos = meta + ml.pos; hd.posw = reinterpret_cast<const float*>(meta + ml.posw);
       hd.g = w->ln_g; hd.eps = d.eps; hd.u_ss = fuse ? rowss : nullptr; hd.u_ss_n = ssn; hd.u_gain = lw.ln2_g; hd.w_out = w->w_out; hd.b_out = w->b_out;
       hd.x_a = a->actions; hd.scal = a->scal; hd.scal_stride = a->scal_stride;
       hd.F = a->F; hd.denoised = a->denoised; hd.x_next = a->x_next; hd.den_prev = a->den_prev; hd.lin = a->lin; hd.aux1 = a->aux1; hd.aux2 = a->aux2;
-      rc = mode_head_ddim_fwd(&hd, stream);
+      if (guided) { ModeHeadGuidedDesc gh; gh.head = hd; gh.scale = guide_scale; rc = mode_head_ddim_guided_fwd(&gh, stream); }
+      else rc = mode_head_ddim_fwd(&hd, stream);
       if (rc) return rc;
     }
   }
   return MODE_OK;
+}
+
+extern "C" int mode_dit_forward(const ModeDims* dims, const ModeModelWeights* w, const ModeForwardArgs* a, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  return dit_forward_chain(dims, w, a, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mode_dit_forward_guided(const ModeDims* dims, const ModeModelWeights* w, const ModeGuidedArgs* a, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  if (!a || !a->scale) return MODE_ERR_BAD_ARG;
+  return dit_forward_chain(dims, w, &a->fwd, a->scale, workspace, workspace_bytes, stream);
 }

@@ -343,6 +343,24 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(const ModeEmbedDesc e
                       (void*)((char*)e.h + (long)row * D * (LP_BF16 ? 2 : 4)), lane);
 }
 
+// The head kernels' solver update on one output element, given its denoised prediction `den` (guided: already combined): the `denoised` output, then
+// DDIM's / the two-point multistep / the two-stage solvers' linear update (ModeHeadDesc).
+__device__ __forceinline__ void head_update(const ModeHeadDesc& h, long oidx, float den, float xa, float sc2, float sc3) {
+  if (h.denoised) h.denoised[oidx] = den;
+  float dd = den;                                     // two-point multistep (DPM-Solver++(2M), gc_sampling.py:724-727): (1 + 1/(2r)) D - (1/(2r)) D_old
+  if (h.den_prev && sc3 != 0.0f) dd = (1.0f + sc3) * den - sc3 * h.den_prev[oidx];
+  if (h.x_next) {
+    if (h.lin) {                                        // two-stage solvers: a linear combination of this stage's input / prediction and two earlier tensors
+      float v = __builtin_fmaf(h.lin[0], xa, h.lin[1] * den);
+      if (h.aux1) v = __builtin_fmaf(h.lin[2], h.aux1[oidx], v);
+      if (h.aux2) v = __builtin_fmaf(h.lin[3], h.aux2[oidx], v);
+      h.x_next[oidx] = v;
+    } else {
+      h.x_next[oidx] = sc2 * xa + (1.0f - sc2) * dd;    // r*x + (1-r)*denoised (gc_sampling.py:948-950)
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- head
 template <int NCH, int AMAX>   // NCH > 0: D == 256*NCH, chunk loops fully unrolled (all loads of a phase in flight together); AMAX: widest action (8 or 32)
 __global__ __launch_bounds__(256) void head_ddim_kernel(const ModeHeadDesc h) {
@@ -450,19 +468,7 @@ __global__ __launch_bounds__(256) void head_ddim_kernel(const ModeHeadDesc h) {
     if (h.F) h.F[oidx] = F;
     if (scp) {
       const float den = F * sc1 + xa * sc0;               // F*c_out + x*c_skip      (score_wrappers.py:79-80)
-      if (h.denoised) h.denoised[oidx] = den;
-      float dd = den;                                     // two-point multistep (DPM-Solver++(2M), gc_sampling.py:724-727): (1 + 1/(2r)) D - (1/(2r)) D_old
-      if (h.den_prev && sc3 != 0.0f) dd = (1.0f + sc3) * den - sc3 * h.den_prev[oidx];
-      if (h.x_next) {
-        if (h.lin) {                                        // two-stage solvers: a linear combination of this stage's input / prediction and two earlier tensors
-          float v = __builtin_fmaf(h.lin[0], xa, h.lin[1] * den);
-          if (h.aux1) v = __builtin_fmaf(h.lin[2], h.aux1[oidx], v);
-          if (h.aux2) v = __builtin_fmaf(h.lin[3], h.aux2[oidx], v);
-          h.x_next[oidx] = v;
-        } else {
-          h.x_next[oidx] = sc2 * xa + (1.0f - sc2) * dd;    // r*x + (1-r)*denoised (gc_sampling.py:948-950)
-        }
-      }
+      head_update(h, oidx, den, xa, sc2, sc3);
     }
   }
 }
@@ -595,21 +601,27 @@ namespace mode {
 // One workgroup per token row (the form of the combine / head row kernels).  The token kind is uniform per workgroup: it selects a source row
 // and a positional row by POINTER (dummy = the positional table, masked by selects), so the row's loads are unconditional; only the action
 // rows' Linear(A_dim, D) sits behind a (scalar) branch.
-template <bool LP_BF16, int NC, int AMAX>   // AMAX: widest action (8 or 32; the instantiation for 8 is the original kernel)
+//
+// GUIDED (classifier-free guidance, ModeEmbedGuidedDesc): the grid has 2 * e.B * T rows; internal sample bi = b + h * e.B reads every input of PAIR b
+// (nothing is duplicated in memory), and for h = 1 the goal token's source is a select to zero - the dummy row is loaded, as for an action token.
+// Only the conditioning row and the output rows are indexed by the internal sample.
+template <bool LP_BF16, int NC, int AMAX, bool GUIDED>   // AMAX: widest action (8 or 32; the instantiation for 8 is the original kernel)
 __global__ __launch_bounds__(256) void embed_tokens_row_kernel(const ModeEmbedDesc e) {
   __shared__ float red[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int row = blockIdx.x, D = e.D, T = e.T;
-  const int b = row / T, t = row % T;
+  const int bi = row / T, t = row % T;
+  const bool unc = GUIDED && bi >= e.B;                // unconditional branch of pair bi - e.B
+  const int b = unc ? bi - e.B : bi;
   const int t0 = e.use_noise_token ? 1 : 0;            // first goal position
   const int t_img = t0 + 1, t_act = t_img + e.n_img;   // goal_seq_len == 1 on this path
   const int ai = t - t_act;
   const bool is_act = ai >= 0, is_noise = t < t0, is_goal = !is_noise && t < t_img;
   const float* src = is_noise ? e.emb_t + (long)b * e.emb_row_stride
-                   : is_goal  ? e.goal_e + (long)b * D
+                   : is_goal  ? (unc ? e.pos : e.goal_e + (long)b * D)
                    : !is_act  ? e.img_e + ((long)b * e.n_img + (t - t_img)) * D : e.pos;
   const float* pp = is_act ? e.pos + (long)(1 + ai) * D : is_goal ? e.pos : e.pos + D;   // both image tokens share pos row 1; the noise token has none
-  const bool has_src = !is_act, has_pos = !is_noise;
+  const bool has_src = !is_act && !(unc && is_goal), has_pos = !is_noise;   // (no source: the action rows' Linear, or zero when not an action row)
   const float cin = (e.c_in ? e.c_in : e.pos)[e.c_in ? (long)b * e.c_in_stride : 0];
   float a[AMAX];
   {
@@ -619,7 +631,7 @@ __global__ __launch_bounds__(256) void embed_tokens_row_kernel(const ModeEmbedDe
 #pragma unroll
     for (int j = 0; j < AMAX; ++j) a[j] = j < e.A_dim ? a[j] * (e.c_in ? cin : 1.0f) : 0.f;
   }
-  const float* cr = e.cond ? e.cond + (long)b * e.cond_row_stride : e.pos;
+  const float* cr = e.cond ? e.cond + (long)bi * e.cond_row_stride : e.pos;
   float4 v[NC], gq[NC], cq[NC];
   float ssq = 0.f;
 #pragma unroll
@@ -689,22 +701,41 @@ __global__ __launch_bounds__(256) void embed_tokens_row_kernel(const ModeEmbedDe
 }
 }  // namespace mode
 
+static bool embed_desc_complete(const ModeEmbedDesc* d) {
+  return d && d->goal_e && d->img_e && d->actions && d->w_act && d->pos && d->g && d->x && d->h && (!d->use_noise_token || d->emb_t);
+}
+static bool embed_desc_supported(const ModeEmbedDesc* d) {
+  return !(d->D & 3) && d->A_dim <= kMaxActionDim && d->T == (d->use_noise_token ? 1 : 0) + 1 + d->n_img + d->A_len;
+}
+// the one-workgroup-per-row embed kernel's instantiation ladder (G: its guided form); reads d, rows, wide, nc, st
+#define MODE_EK(G, LP, NC) do { if (wide) hipLaunchKernelGGL((embed_tokens_row_kernel<LP, NC, 32, G>), dim3(rows), dim3(256), 0, st, *d); \
+                                else hipLaunchKernelGGL((embed_tokens_row_kernel<LP, NC, 8, G>), dim3(rows), dim3(256), 0, st, *d); } while (0)
+#define MODE_EK_NC(G, LP) do { if (nc == 1) MODE_EK(G, LP, 1); else if (nc == 2) MODE_EK(G, LP, 2); else MODE_EK(G, LP, 4); } while (0)
+
+extern "C" int mode_embed_tokens_guided_fwd(const ModeEmbedGuidedDesc* gd, void* stream) {
+  const ModeEmbedDesc* d = gd ? &gd->emb : nullptr;
+  if (!embed_desc_complete(d)) return MODE_ERR_BAD_ARG;
+  if (!embed_desc_supported(d) || d->D > 4096 || d->A_dim < 1) return MODE_ERR_UNSUPPORTED;   // pairs exist in the row kernel only
+  const int rows = 2 * d->B * d->T;                                   // both branches of every pair
+  if (rows == 0) return MODE_OK;
+  const bool wide = d->A_dim > 8;
+  const hipStream_t st = (hipStream_t)stream;
+  const int nc = (d->D + 1023) / 1024;
+  if (d->h_dtype == MODE_BF16) MODE_EK_NC(true, true); else MODE_EK_NC(true, false);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
 extern "C" int mode_embed_tokens_fwd(const ModeEmbedDesc* d, void* stream) {
-  if (!d || !d->goal_e || !d->img_e || !d->actions || !d->w_act || !d->pos || !d->g || !d->x || !d->h) return MODE_ERR_BAD_ARG;
-  if (d->use_noise_token && !d->emb_t) return MODE_ERR_BAD_ARG;
-  if ((d->D & 3) || d->A_dim > kMaxActionDim || d->T != (d->use_noise_token ? 1 : 0) + 1 + d->n_img + d->A_len) return MODE_ERR_UNSUPPORTED;
+  if (!embed_desc_complete(d)) return MODE_ERR_BAD_ARG;
+  if (!embed_desc_supported(d)) return MODE_ERR_UNSUPPORTED;
   const int rows = d->B * d->T;
   if (rows == 0) return MODE_OK;
   const bool wide = d->A_dim > 8;                                     // AMAX = 32 instantiations
   if (d->D <= 4096 && d->A_dim >= 1) {                               // one workgroup per row
     const hipStream_t st = (hipStream_t)stream;
     const int nc = (d->D + 1023) / 1024;
-#define MODE_EK(LP, NC) do { if (wide) hipLaunchKernelGGL((embed_tokens_row_kernel<LP, NC, 32>), dim3(rows), dim3(256), 0, st, *d); \
-                             else hipLaunchKernelGGL((embed_tokens_row_kernel<LP, NC, 8>), dim3(rows), dim3(256), 0, st, *d); } while (0)
-#define MODE_EK_NC(LP) do { if (nc == 1) MODE_EK(LP, 1); else if (nc == 2) MODE_EK(LP, 2); else MODE_EK(LP, 4); } while (0)
-    if (d->h_dtype == MODE_BF16) MODE_EK_NC(true); else MODE_EK_NC(false);
-#undef MODE_EK_NC
-#undef MODE_EK
+    if (d->h_dtype == MODE_BF16) MODE_EK_NC(false, true); else MODE_EK_NC(false, false);
     MODE_LAUNCH_CHECK();
     return MODE_OK;
   }
@@ -722,6 +753,8 @@ extern "C" int mode_embed_tokens_fwd(const ModeEmbedDesc* d, void* stream) {
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }
+#undef MODE_EK_NC
+#undef MODE_EK
 
 namespace mode {
 // One workgroup per action row (the form of combine_norm_row_kernel): a thread owns 4 columns per 1024; every load of the row - residual, ln_2
@@ -827,48 +860,189 @@ __global__ __launch_bounds__(256) void head_ddim_row_kernel(const ModeHeadDesc h
     if (h.F) h.F[oidx] = F;
     if (has_sc) {
       const float den = F * sc1 + xa * sc0;               // F*c_out + x*c_skip      (score_wrappers.py:79-80)
-      if (h.denoised) h.denoised[oidx] = den;
-      float dd = den;                                     // two-point multistep (DPM-Solver++(2M), gc_sampling.py:724-727): (1 + 1/(2r)) D - (1/(2r)) D_old
-      if (h.den_prev && sc3 != 0.0f) dd = (1.0f + sc3) * den - sc3 * h.den_prev[oidx];
-      if (h.x_next) {
-        if (h.lin) {                                        // two-stage solvers: a linear combination of this stage's input / prediction and two earlier tensors
-          float v = __builtin_fmaf(h.lin[0], xa, h.lin[1] * den);
-          if (h.aux1) v = __builtin_fmaf(h.lin[2], h.aux1[oidx], v);
-          if (h.aux2) v = __builtin_fmaf(h.lin[3], h.aux2[oidx], v);
-          h.x_next[oidx] = v;
-        } else {
-          h.x_next[oidx] = sc2 * xa + (1.0f - sc2) * dd;    // r*x + (1-r)*denoised (gc_sampling.py:948-950)
-        }
-      }
+      head_update(h, oidx, den, xa, sc2, sc3);
     }
   }
 }
 }  // namespace mode
 
+namespace mode {
+// head_ddim_row_kernel for classifier-free guidance (ModeHeadGuidedDesc): one workgroup per action row of a PAIR finishes both of its hidden rows,
+// r = 0 the conditional branch (internal sample b), r = 1 the unconditional one (b + B).  What does not depend on the branch - final-norm gain, head
+// rows, ln_2 gain, bias, scalings, noisy action, the guidance scale - is loaded once; the two rows' residuals, partials and k x slabs expert rows
+// are requested in the same unrolled pass, so both branches' loads are in flight before the first reduction, and the reductions of the two rows share
+// their barriers.  Each branch's prediction is formed by the expressions of head_ddim_row_kernel; den = den_u + w (den_c - den_u) then enters
+// head_update in the place of `denoised`.
+template <int KK, bool FUSED, bool YBF, int YS, int NC, int AMAX>
+__global__ __launch_bounds__(256) void head_ddim_guided_row_kernel(const ModeHeadDesc h, const float* __restrict__ scale) {
+  __shared__ float red[2][4];
+  __shared__ float racc[2][4][AMAX];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ar = blockIdx.x;                                       // action-row index in [0, B*A_len), B pairs
+  const int b = ar / h.A_len, ai = ar % h.A_len, D = h.D;
+  long row[2], prow[2][KK]; float pw[2][KK], ru_nrm[2];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    row[r] = (long)(b + r * h.B) * h.T + (h.T - h.A_len) + ai;
+#pragma unroll
+    for (int j = 0; j < KK; ++j) { prow[r][j] = (long)h.pos[row[r] * KK + j] * D; pw[r][j] = h.posw[row[r] * KK + j]; }
+    float u_nrm = 1.0f;
+    if constexpr (FUSED) u_nrm = row_norm_from_partials(h.u_ss + row[r] * h.u_ss_n, h.u_ss_n, D, h.eps, lane);
+    ru_nrm[r] = __frcp_rn(u_nrm);
+  }
+  // epilogue operands (thread j < A_dim finishes output j of the pair): clamped, unconditional
+  const int jo = tid < h.A_dim ? tid : 0;
+  const long oidx = (long)ar * h.A_dim + jo;
+  const float bo = h.b_out[jo];
+  const float* scp = h.scal + (long)b * h.scal_stride;
+  const float sc0 = scp[0], sc1 = scp[1], sc2 = scp[2], sc3 = h.den_prev ? scp[3] : 0.f;
+  const float xa = h.x_a[oidx];
+  const float gw = scale[0];
+  constexpr int WQ = AMAX <= 8 ? AMAX : 1;                        // AMAX 8: the head rows are requested with the rows' loads; 32: read where used
+  float4 v[2][NC], gq[NC], wq[NC][WQ];
+  float ssq[2] = {0.f, 0.f};
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int d = tid * 4 + c * 1024;
+    const bool in = d < D;
+    const int dc = in ? d : 0;
+    gq[c] = *reinterpret_cast<const float4*>(h.g + dc);
+    if constexpr (AMAX <= 8) {
+#pragma unroll
+      for (int j = 0; j < AMAX; ++j) wq[c][j] = *reinterpret_cast<const float4*>(h.w_out + (long)(j < h.A_dim ? j : 0) * D + dc);
+    }
+    float4 gg = make_float4(1.f, 1.f, 1.f, 1.f);
+    if constexpr (FUSED) gg = *reinterpret_cast<const float4*>(h.u_gain + dc);
+    float4 uu[2], ys[2][KK][YS];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      uu[r] = *reinterpret_cast<const float4*>(h.u + row[r] * D + dc);
+#pragma unroll
+      for (int j = 0; j < KK; ++j)
+#pragma unroll
+        for (int z = 0; z < YS; ++z) {
+          const long off = (long)(z < h.y_splits ? z : 0) * h.y_split_stride + prow[r][j] + dc;
+          if constexpr (YBF) {
+            const uint2 q = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(h.Y) + off);
+            ys[r][j][z] = make_float4(bf16_bits_to_f32(q.x & 0xffff), bf16_bits_to_f32(q.x >> 16), bf16_bits_to_f32(q.y & 0xffff), bf16_bits_to_f32(q.y >> 16));
+          } else {
+            ys[r][j][z] = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(h.Y) + off);
+          }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      float4 u4 = uu[r];
+      if constexpr (FUSED) u4 = make_float4(u4.x * ru_nrm[r] * gg.x, u4.y * ru_nrm[r] * gg.y, u4.z * ru_nrm[r] * gg.z, u4.w * ru_nrm[r] * gg.w);
+      float4 nx = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int j = 0; j < KK; ++j) {
+        float4 y = ys[r][j][0];
+#pragma unroll
+        for (int z = 1; z < YS; ++z) {
+          const bool on = z < h.y_splits;
+          y.x += on ? ys[r][j][z].x : 0.f; y.y += on ? ys[r][j][z].y : 0.f; y.z += on ? ys[r][j][z].z : 0.f; y.w += on ? ys[r][j][z].w : 0.f;
+        }
+        const float w = pw[r][j];
+        nx.x = __fadd_rn(nx.x, __fmul_rn(w, y.x)); nx.y = __fadd_rn(nx.y, __fmul_rn(w, y.y));
+        nx.z = __fadd_rn(nx.z, __fmul_rn(w, y.z)); nx.w = __fadd_rn(nx.w, __fmul_rn(w, y.w));
+      }
+      v[r][c] = in ? make_float4(u4.x + nx.x, u4.y + nx.y, u4.z + nx.z, u4.w + nx.w) : make_float4(0.f, 0.f, 0.f, 0.f);
+      ssq[r] += v[r][c].x * v[r][c].x + v[r][c].y * v[r][c].y + v[r][c].z * v[r][c].z + v[r][c].w * v[r][c].w;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    ssq[r] = wave_sum(ssq[r]);
+    if (lane == 0) red[r][wave] = ssq[r];
+  }
+  __syncthreads();
+  float rnrm[2], accv[2][AMAX];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    rnrm[r] = __frcp_rn(fmaxf(sqrtf(((red[r][0] + red[r][1]) + red[r][2]) + red[r][3]) * rsqrtf((float)D), h.eps));
+#pragma unroll
+    for (int j = 0; j < AMAX; ++j) accv[r][j] = 0.f;
+  }
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    float4 n[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)                                     // v = 0 past D
+      n[r] = make_float4(v[r][c].x * rnrm[r] * gq[c].x, v[r][c].y * rnrm[r] * gq[c].y, v[r][c].z * rnrm[r] * gq[c].z, v[r][c].w * rnrm[r] * gq[c].w);
+#pragma unroll
+    for (int j = 0; j < AMAX; ++j) {
+      float4 w;
+      if constexpr (AMAX <= 8) w = wq[c][j];
+      else w = *reinterpret_cast<const float4*>(h.w_out + (long)(j < h.A_dim ? j : 0) * D + (tid * 4 + c * 1024 < D ? tid * 4 + c * 1024 : 0));
+#pragma unroll
+      for (int r = 0; r < 2; ++r) accv[r][j] += n[r].x * w.x + n[r].y * w.y + n[r].z * w.z + n[r].w * w.w;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 2; ++r)
+#pragma unroll
+    for (int j = 0; j < AMAX; ++j) accv[r][j] = wave_sum(accv[r][j]);
+  if (lane == 0) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int j = 0; j < AMAX; ++j) racc[r][wave][j] = accv[r][j];
+  }
+  __syncthreads();
+  if (tid < h.A_dim) {
+    float den[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const float F = (((racc[r][0][tid] + racc[r][1][tid]) + racc[r][2][tid]) + racc[r][3][tid]) + bo;
+      den[r] = F * sc1 + xa * sc0;                       // F*c_out + x*c_skip of the branch      (score_wrappers.py:79-80)
+    }
+    head_update(h, oidx, __fadd_rn(den[1], __fmul_rn(gw, __fsub_rn(den[0], den[1]))), xa, sc2, sc3);   // D_u + w (D_c - D_u)
+  }
+}
+}  // namespace mode
+
+static bool head_desc_complete(const ModeHeadDesc* d) {
+  return d && d->u && d->Y && d->pos && d->posw && d->g && d->w_out && d->b_out && (!d->scal || d->x_a) && (!d->u_ss || (d->u_gain && d->u_ss_n > 0));
+}
+static bool head_row_kernel_takes(const ModeHeadDesc* d) {          // shapes of the one-workgroup-per-row head kernels
+  return d->D <= 4096 && d->y_splits <= 8 && (d->k == 1 || d->k == 2) && d->A_dim >= 1;
+}
+// the head row kernels' instantiation ladder (K: head_ddim_row_kernel or its guided sibling, ...: the kernel's arguments); reads d, rows, wide, nc,
+// ys, ybf, fu, st
+#define MODE_HK(K, KK, F, YB, YS, NC, ...) do { if (wide) hipLaunchKernelGGL((K<KK, F, YB, YS, NC, 32>), dim3(rows), dim3(256), 0, st, __VA_ARGS__); \
+                                                else hipLaunchKernelGGL((K<KK, F, YB, YS, NC, 8>), dim3(rows), dim3(256), 0, st, __VA_ARGS__); } while (0)
+#define MODE_HK_NC(K, KK, F, YB, YS, ...) do { if (nc == 1) MODE_HK(K, KK, F, YB, YS, 1, __VA_ARGS__); else if (nc == 2) MODE_HK(K, KK, F, YB, YS, 2, __VA_ARGS__); else MODE_HK(K, KK, F, YB, YS, 4, __VA_ARGS__); } while (0)
+#define MODE_HK_YS(K, KK, F, YB, ...) do { if (ys == 1) MODE_HK_NC(K, KK, F, YB, 1, __VA_ARGS__); else if (ys == 2) MODE_HK_NC(K, KK, F, YB, 2, __VA_ARGS__); else if (ys == 4) MODE_HK_NC(K, KK, F, YB, 4, __VA_ARGS__); else MODE_HK_NC(K, KK, F, YB, 8, __VA_ARGS__); } while (0)
+#define MODE_HK_YB(K, KK, F, ...) do { if (ybf) MODE_HK_YS(K, KK, F, true, __VA_ARGS__); else MODE_HK_YS(K, KK, F, false, __VA_ARGS__); } while (0)
+#define MODE_HK_F(K, KK, ...) do { if (fu) MODE_HK_YB(K, KK, true, __VA_ARGS__); else MODE_HK_YB(K, KK, false, __VA_ARGS__); } while (0)
+#define MODE_HK_K(K, ...) do { \
+    const int nc = (d->D + 1023) / 1024, ys = d->y_splits <= 1 ? 1 : d->y_splits <= 2 ? 2 : d->y_splits <= 4 ? 4 : 8; \
+    const bool ybf = d->y_dtype == MODE_BF16, fu = d->u_ss != nullptr; \
+    if (d->k == 2) MODE_HK_F(K, 2, __VA_ARGS__); else MODE_HK_F(K, 1, __VA_ARGS__); } while (0)
+
+extern "C" int mode_head_ddim_guided_fwd(const ModeHeadGuidedDesc* gd, void* stream) {
+  const ModeHeadDesc* d = gd ? &gd->head : nullptr;
+  if (!head_desc_complete(d) || !gd->scale || !d->scal || d->F) return MODE_ERR_BAD_ARG;   // the raw output F has no guided form
+  if ((d->D & 3) || d->A_dim > kMaxActionDim || !head_row_kernel_takes(d)) return MODE_ERR_UNSUPPORTED;   // pairs exist in the row kernel only
+  const int rows = d->B * d->A_len;
+  const bool wide = d->A_dim > 8;
+  if (rows == 0) return MODE_OK;
+  const hipStream_t st = (hipStream_t)stream;
+  MODE_HK_K(head_ddim_guided_row_kernel, *d, gd->scale);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
 extern "C" int mode_head_ddim_fwd(const ModeHeadDesc* d, void* stream) {
-  if (!d || !d->u || !d->Y || !d->pos || !d->posw || !d->g || !d->w_out || !d->b_out) return MODE_ERR_BAD_ARG;
-  if (d->scal && !d->x_a) return MODE_ERR_BAD_ARG;
-  if (d->u_ss && (!d->u_gain || d->u_ss_n <= 0)) return MODE_ERR_BAD_ARG;
+  if (!head_desc_complete(d)) return MODE_ERR_BAD_ARG;
   if ((d->D & 3) || d->A_dim > kMaxActionDim) return MODE_ERR_UNSUPPORTED;
   const int rows = d->B * d->A_len;
   const bool wide = d->A_dim > 8;                                     // AMAX = 32 instantiations
   if (rows == 0) return MODE_OK;
-  if (d->D <= 4096 && d->y_splits <= 8 && (d->k == 1 || d->k == 2) && d->A_dim >= 1) {   // one workgroup per row
+  if (head_row_kernel_takes(d)) {                                     // one workgroup per row
     const hipStream_t st = (hipStream_t)stream;
-    const int nc = (d->D + 1023) / 1024, ys = d->y_splits <= 1 ? 1 : d->y_splits <= 2 ? 2 : d->y_splits <= 4 ? 4 : 8;
-    const bool ybf = d->y_dtype == MODE_BF16, fu = d->u_ss != nullptr;
-#define MODE_HK(KK, F, YB, YS, NC) do { if (wide) hipLaunchKernelGGL((head_ddim_row_kernel<KK, F, YB, YS, NC, 32>), dim3(rows), dim3(256), 0, st, *d); \
-                                        else hipLaunchKernelGGL((head_ddim_row_kernel<KK, F, YB, YS, NC, 8>), dim3(rows), dim3(256), 0, st, *d); } while (0)
-#define MODE_HK_NC(KK, F, YB, YS) do { if (nc == 1) MODE_HK(KK, F, YB, YS, 1); else if (nc == 2) MODE_HK(KK, F, YB, YS, 2); else MODE_HK(KK, F, YB, YS, 4); } while (0)
-#define MODE_HK_YS(KK, F, YB) do { if (ys == 1) MODE_HK_NC(KK, F, YB, 1); else if (ys == 2) MODE_HK_NC(KK, F, YB, 2); else if (ys == 4) MODE_HK_NC(KK, F, YB, 4); else MODE_HK_NC(KK, F, YB, 8); } while (0)
-#define MODE_HK_YB(KK, F) do { if (ybf) MODE_HK_YS(KK, F, true); else MODE_HK_YS(KK, F, false); } while (0)
-#define MODE_HK_F(KK) do { if (fu) MODE_HK_YB(KK, true); else MODE_HK_YB(KK, false); } while (0)
-    if (d->k == 2) MODE_HK_F(2); else MODE_HK_F(1);
-#undef MODE_HK_F
-#undef MODE_HK_YB
-#undef MODE_HK_YS
-#undef MODE_HK_NC
-#undef MODE_HK
+    MODE_HK_K(head_ddim_row_kernel, *d);
     MODE_LAUNCH_CHECK();
     return MODE_OK;
   }
@@ -880,6 +1054,12 @@ extern "C" int mode_head_ddim_fwd(const ModeHeadDesc* d, void* stream) {
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }
+#undef MODE_HK_K
+#undef MODE_HK_F
+#undef MODE_HK_YB
+#undef MODE_HK_YS
+#undef MODE_HK_NC
+#undef MODE_HK
 
 extern "C" int mode_ddim_edm_step(const float* F, const float* x_a, const float* scal, int64_t scal_stride, int B, int per_sample,
                                   float* denoised, float* x_next, void* stream) {

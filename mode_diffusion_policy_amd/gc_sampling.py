@@ -56,7 +56,7 @@ def sample_ddim(model, state, action, goal, sigmas, scaler=None, extra_args=None
     extra_args = {} if extra_args is None else extra_args
     if (isinstance(model, GCDenoiser) and isinstance(model.inner_model, MoDeDiT) and not model.inner_model.training
             and callback is None and not extra_args):
-        return model.inner_model.sample_ddim_fused(state, action, goal, sigmas, model.sigma_data)
+        return model.inner_model.sample_ddim_fused(state, action, goal, sigmas, model.sigma_data, guidance=model.guidance_scale)
     # generic path: any callable denoiser, reference step order
     s_in = action.new_ones([action.shape[0]])
     for i in range(len(sigmas) - 1):

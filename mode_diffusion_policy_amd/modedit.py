@@ -252,18 +252,22 @@ class MoDeDiT(nn.Module):
         self.probs_per_layer = [None] * self.num_layers
         return F
 
-    def _routed_forward(self, eng, B, emb_t, goal_e, img_e, x, account: bool = True, **head) -> None:
+    def _routed_forward(self, eng, B, emb_t, goal_e, img_e, x, account: bool = True, guidance=None, **head) -> None:
         """One denoiser forward with its routing.  The conditioning rows are emb_t ([1, D] for the whole batch or [B, D]), or with goal routing
         emb_t + goal_e, one row per sample (modedit.py:801-802).  Token routing: every block routes its tokens inside the chain, no dispatch
-        records; otherwise router + dispatch of the conditioning rows.  ``head``: the output head's arguments of ``DitEngine.forward``."""
+        records; otherwise router + dispatch of the conditioning rows.  ``head``: the output head's arguments of ``DitEngine.forward``.
+        ``guidance`` (the device scalar of ``_guidance``): B pairs run as 2B samples, the unconditional halves behind the conditional ones - per-sample
+        conditioning rows are [emb_t + goal_e ; emb_t] (goal routing) or emb_t twice; routing, dispatch and the usage counters cover all 2B·T tokens."""
         D, T = self.embed_dim, self.seq_len
-        N = B * T
+        N = (B if guidance is None else 2 * B) * T
         cond = (emb_t.expand(B, D) + goal_e).contiguous() if self.use_goal_in_routing else emb_t
+        if guidance is not None and (self.use_goal_in_routing or cond.shape[0] != 1):   # per-sample rows: the unconditional half has its own
+            cond = torch.cat([cond, emb_t.expand(B, D)])
         R = cond.shape[0]
         es, cs = 0 if emb_t.shape[0] == 1 else D, 0 if R == 1 else D
         if not self.cond_router:
             idx = torch.empty(self.num_layers, N, self.top_k, dtype=torch.int32, device=eng.device)
-            eng.forward(B, emb_t, es, cond, cs, None, 0, goal_e, img_e, x, topk_out=idx, **head)
+            eng.forward(B, emb_t, es, cond, cs, None, 0, goal_e, img_e, x, topk_out=idx, guidance=guidance, **head)
             self._last_topk = idx
             if account:
                 self._account_token_usage(idx, N)
@@ -271,10 +275,36 @@ class MoDeDiT(nn.Module):
         idx, w, _, _ = eng.route(cond)
         meta = eng.dispatch(idx, w, self.num_layers, R, N if R == 1 else T, N)
         ml = eng.meta_layout(N)
-        eng.forward(B, emb_t, es, cond, cs, meta.data_ptr(), ml.total_words, goal_e, img_e, x, uniform=R == 1, **head)
+        eng.forward(B, emb_t, es, cond, cs, meta.data_ptr(), ml.total_words, goal_e, img_e, x, uniform=R == 1, guidance=guidance, **head)
         self._last_topk, self._last_meta = idx, meta
         if account:
             self._account_usage(meta, ml, N)
+
+    # ------------------------------------------------------------------ classifier-free guidance
+    def _guidance(self, w):
+        """The guidance scale of a guided call as the chain reads it: ONE device fp32 scalar owned by the model, whose address every captured guided
+        graph bakes in - a new value is a 4-byte copy made here, outside any capture, never a recapture.  ``w``: None (unguided: None comes back), a
+        number, or that scalar itself (a call made from inside a chain that is being captured).  D_w = D_u + w (D_c - D_u) with D_u the prediction for
+        a zero goal: the chain then runs both branches of every sample, 2B rows (``DitEngine.forward``).  Shapes that only the fallback row kernels
+        take are refused here, before the first launch, and so is training mode (goal dropout is the training-time half of the method).
+        The scalar is per MODEL: calls are meant to follow one another on one stream.  Two denoisers with different scales that share this model
+        from different streams or threads would race on it - give each its own model then."""
+        if w is None or torch.is_tensor(w):
+            return w
+        if self.training:
+            raise ValueError("classifier-free guidance is an inference-time combine: call .eval() first (guidance_scale is set)")
+        if self.embed_dim > 4096 or self.top_k > 2:
+            raise ValueError(f"classifier-free guidance runs in the row kernels only: embed_dim <= 4096 and top_k <= 2 (got embed_dim={self.embed_dim}, "
+                             f"top_k={self.top_k})")
+        dev = self.engine.device
+        t = getattr(self, "_guid_dev", None)
+        if t is None or t.device != dev:
+            t, self._guid_val = torch.empty(1, dtype=torch.float32, device=dev), None
+            self._guid_dev = t
+        if self._guid_val != float(w):
+            t.copy_(torch.tensor([float(w)], dtype=torch.float32))
+            self._guid_val = float(w)
+        return t
 
     # ------------------------------------------------------------------ fused EDM forward / DDIM sampler
     def _prep_obs(self, eng, states, goals, uncond=False):
@@ -286,9 +316,11 @@ class MoDeDiT(nn.Module):
         return img, goals.reshape(goals.shape[0], -1)                    # (B, 1, G) after preprocess_goals: a view, still contiguous
 
     @torch.no_grad()
-    def denoise(self, states, action, goals, sigma, sigma_data: float, _account: bool = True, _obs_emb=None):
+    def denoise(self, states, action, goals, sigma, sigma_data: float, _account: bool = True, _obs_emb=None, guidance=None):
         """GCDenoiser.forward (score_wrappers.py:65-80) with c_in / c_out / c_skip fused into the HIP chain.  ``_obs_emb``: (img_e, goal_e) already
-        computed for these observations (denoise_graphed keeps them across the calls of one sampler run)."""
+        computed for these observations (denoise_graphed keeps them across the calls of one sampler run).  ``guidance``: classifier-free guidance
+        scale w (``_guidance``) - the result is D_u + w (D_c - D_u), formed in the head kernel."""
+        guidance = self._guidance(guidance)
         eng = self.engine
         dev, B = eng.device, action.shape[0]
         if B == 0:
@@ -307,25 +339,29 @@ class MoDeDiT(nn.Module):
         emb_t = eng.sigma_embed(sig)
         img_e, goal_e = _obs_emb if _obs_emb is not None else eng.embed_obs(img, goals)
         den = torch.empty_like(x)
-        self._routed_forward(eng, B, emb_t, goal_e, img_e, x, account=_account, c_in=c_in, c_in_stride=0 if R == 1 else 1,
+        self._routed_forward(eng, B, emb_t, goal_e, img_e, x, account=_account, guidance=guidance, c_in=c_in, c_in_stride=0 if R == 1 else 1,
                              scal_ptr=scal.data_ptr(), scal_stride=0 if R == 1 else 4, denoised=den)
         return den
 
     @torch.no_grad()
-    def denoise_graphed(self, states, action, goals, sigma, sigma_data: float):
+    def denoise_graphed(self, states, action, goals, sigma, sigma_data: float, guidance=None):
         """``denoise`` for a batch that shares ONE noise level (a 0-dim / 1-element sigma, device or host), replayed as a hipGraph: sigma embedding,
         fp32 router + dispatch of all layers, EDM scalings, observation embeddings and the denoiser forward are captured once per batch size with
         sigma as a DEVICE scalar, so the same graph serves every noise level of every sampler (euler, heun, dpm-solver++ ...: gc_sampling.py:165-994)
         - no per-step host work beyond three small input copies.  Goal routing: the graph also forms cond = emb + goal_emb(goal) and routes
-        and dispatches those B rows; token routing: the forward routes every token itself.  Returns None with MODE_HIP_GRAPH=0."""
+        and dispatches those B rows; token routing: the forward routes every token itself.  Returns None with MODE_HIP_GRAPH=0.
+        ``guidance``: as for ``denoise``; guided and unguided graphs are separate cache entries, the scale's value is in no key."""
         import os
+        guidance = self._guidance(guidance)
         eng = self.engine
         dev, B = eng.device, action.shape[0]
         if B == 0 or os.environ.get("MODE_HIP_GRAPH", "1") == "0":
             return None
         x = action.detach().to(device=dev, dtype=torch.float32).contiguous()
         sig = torch.as_tensor(sigma, dtype=torch.float32).detach().reshape(-1)[:1]
-        key = (B, eng.compute_dtype, eng._structs_for, str(dev), float(sigma_data), self._routing_mode())
+        guided = guidance is not None
+        Bi = 2 * B if guided else B                                      # the chain's internal batch
+        key = (B, eng.compute_dtype, eng._structs_for, str(dev), float(sigma_data), self._routing_mode(), guided)
         cache = self._route_cache.setdefault("denoise_graphs", {})
         ent = cache.get(key)
         # The observations are the same tensors for every denoiser call of a sampler run (gc_sampling.py's loops pass `state` / `goal` through
@@ -345,10 +381,10 @@ class MoDeDiT(nn.Module):
             ent = dict(img=img.clone(), goals=gl.clone(), x=x.clone(), sig=torch.empty(1, device=dev),
                        img_e=torch.empty(B * self.n_img_tokens, self.embed_dim, device=dev), goal_e=torch.empty(B, self.embed_dim, device=dev))
             ent["sig"].copy_(sig)
-            ent["ws"] = self._chunk_ws(eng, B, 1)
+            ent["ws"] = self._chunk_ws(eng, Bi, 1)
 
             def run():
-                out = self.denoise(None, ent["x"], None, ent["sig"], sigma_data, _account=False, _obs_emb=(ent["img_e"], ent["goal_e"]))
+                out = self.denoise(None, ent["x"], None, ent["sig"], sigma_data, _account=False, _obs_emb=(ent["img_e"], ent["goal_e"]), guidance=guidance)
                 return out, self._last_topk, self._last_meta if self.cond_router else None
             with eng.pinned_workspace(ent["ws"]):
                 # the warm-up and the capture route on these embeddings: routing on uninitialised memory can yield out-of-range expert ids
@@ -365,11 +401,11 @@ class MoDeDiT(nn.Module):
         ent["graph"].replay()
         if not self.cond_router:
             self._last_topk = ent["topk"]
-            self._account_token_usage(ent["topk"], B * self.seq_len)
+            self._account_token_usage(ent["topk"], Bi * self.seq_len)
         else:
             if self.use_goal_in_routing:
                 self._last_topk = ent["topk"]
-            self._account_usage(ent["meta"], eng.meta_layout(B * self.seq_len), B * self.seq_len)
+            self._account_usage(ent["meta"], eng.meta_layout(Bi * self.seq_len), Bi * self.seq_len)
         return ent["out"].clone()
 
     def _schedule_state(self, eng, sig, B, sigma_data: float, out=None, solver: str = "ddim", lin=None):
@@ -378,7 +414,7 @@ class MoDeDiT(nn.Module):
         and caches it (precompute_experts_for_inference / the cache read at modedit.py:542-546); here it is a set of device tensors the captured
         launch chain reads.  Routing decisions cached by ``precompute_experts_for_inference`` for these exact sigma values (and these weights) are
         CONSUMED here - no router launch at all; otherwise the fp32 router runs on the device.  With ``out`` the results are written in place
-        (the graph has the pointers baked in)."""
+        (the graph has the pointers baked in).  ``B`` is the chain's internal batch (twice the samples under guidance): the dispatch records are for B·T tokens."""
         T, Ly = self.seq_len, self.num_layers
         if lin is not None:
             # two-stage solvers (sample_two_stage_fused): `sig` lists the sigma of EVERY denoiser evaluation, `lin` [n, 4] the linear update of each
@@ -445,19 +481,26 @@ class MoDeDiT(nn.Module):
         inside the chain): the routing of a sampler run depends on the observations, so the captured chunk resolves it itself."""
         return self.use_goal_in_routing or not self.cond_router
 
-    def _chunk_routing(self, eng, sched, goal_e, n: int, B: int, ml, tok=None):
+    def _chunk_routing(self, eng, sched, goal_e, n: int, B: int, ml, tok=None, guided: bool = False):
         """Routing state of a captured chunk of n denoiser evaluations, issued right after the observation embeddings; returns (args of
         evaluation j -> dict, route output or None, dispatch records or None).  Goal routing: the conditioning rows of every level,
         cond[j·B + b] = emb_all[j] + goal_e[b] ([n·B, D]), one router launch over all of them and one dispatch launch; the router output
         [L, n·B, k] is, contiguously, [(L·n), B, k], so level j's records sit at meta + j·words with layer stride n·words - the layout of the
         schedule-only routing.  Token routing (``tok``: int32 [n, L, B·T, k]): every forward routes its tokens itself and writes its
-        decisions to tok[j].  The default (conditioning-row routing on sigma only) reads the schedule state's records, as before."""
+        decisions to tok[j].  The default (conditioning-row routing on sigma only) reads the schedule state's records, as before.
+        ``B`` is the chain's internal batch: with ``guided`` goal_e has B/2 rows and a level's B conditioning rows are emb_all[j] + goal_e for
+        the conditional half, emb_all[j] alone for the unconditional half."""
         D, T = self.embed_dim, self.seq_len
         emb_all = sched["emb_all"]
         cond = idx = None
         meta = sched.get("meta")
         if self.use_goal_in_routing:
-            cond = (emb_all[:, None, :] + goal_e[None, :, :]).reshape(n * B, D)
+            if guided:
+                cond = emb_all[:, None, :].repeat(1, B, 1)
+                cond[:, :B // 2] += goal_e[None, :, :]
+                cond = cond.reshape(n * B, D)
+            else:
+                cond = (emb_all[:, None, :] + goal_e[None, :, :]).reshape(n * B, D)
             if self.cond_router:
                 idx, w, _, _ = eng.route(cond)
                 meta = eng.dispatch(idx, w, self.num_layers * n, B, T, B * T)
@@ -470,25 +513,27 @@ class MoDeDiT(nn.Module):
                         uniform=cond is None, topk_out=None)
         return at, idx, meta
 
-    def _chunk_steps(self, eng, img, goals, bufs, sched, evals, tok=None):
+    def _chunk_steps(self, eng, img, goals, bufs, sched, evals, tok=None, guidance=None):
         """The observation-dependent launch chain of a fused sampler run: embeddings of the observations (+ the routing of goal-routed models)
         + one denoiser forward per entry of ``evals``; pure launches, no host sync -> capturable.  Reads the schedule state by pointer.
         An entry is (x_in, x_out, denoised, den_prev, aux1, aux2, lin): ids into the [B, A_len, A_dim] buffers ``bufs`` (None = not passed) and
         whether the head applies the schedule's linear update ``sched["lin"][j]`` (two-stage solvers, ModeHeadDesc.lin) instead of DDIM's
         (scal[2], with scal[3] weighing ``den_prev`` for two-point multistep solvers, ModeHeadDesc.den_prev).  Returns the meta layout and
-        the chunk's routing output {idx, meta} (``_chunk_routing``)."""
+        the chunk's routing output {idx, meta} (``_chunk_routing``).  ``guidance`` (device scalar): every forward is the guided one - the buffers
+        and the observation embeddings keep B rows, routing and the forwards' interior have 2B."""
         B, T = bufs[0].shape[0], self.seq_len
+        Bi = B if guidance is None else 2 * B
         img_e, goal_e = eng.embed_obs(img, goals)                        # step-invariant, hoisted (modedit.py:760,765)
-        ml = eng.meta_layout(B * T)
+        ml = eng.meta_layout(Bi * T)
         emb_all, c_in, scal = sched["emb_all"], sched["c_in"], sched["scal"]
-        at, idx, meta = self._chunk_routing(eng, sched, goal_e, len(evals), B, ml, tok)
+        at, idx, meta = self._chunk_routing(eng, sched, goal_e, len(evals), Bi, ml, tok, guided=guidance is not None)
         buf = lambda i: None if i is None else bufs[i]
         for j, (xin, xout, dout, dprev, a1, a2, lin) in enumerate(evals):
             r = at(j)
             eng.forward(B, emb_all[j], 0, r["cond"], r["cond_stride"], r["meta_ptr"], r["meta_stride"], goal_e, img_e, bufs[xin],
                         c_in=c_in.data_ptr() + 4 * j, c_in_stride=0, scal_ptr=scal.data_ptr() + 16 * j, scal_stride=0, x_next=bufs[xout],
                         uniform=r["uniform"], denoised=buf(dout), den_prev=buf(dprev), lin_ptr=sched["lin"].data_ptr() + 16 * j if lin else None,
-                        aux1=buf(a1), aux2=buf(a2), topk_out=r["topk_out"])
+                        aux1=buf(a1), aux2=buf(a2), topk_out=r["topk_out"], guidance=guidance)
         return ml, dict(idx=idx, meta=meta)
 
     @staticmethod
@@ -537,34 +582,38 @@ class MoDeDiT(nn.Module):
         return plan
 
     @torch.no_grad()
-    def sample_two_stage_fused(self, states, action, goals, sigmas, sigma_data: float, solver: str):
+    def sample_two_stage_fused(self, states, action, goals, sigmas, sigma_data: float, solver: str, guidance=None):
         """sample_heun / sample_dpm_2 / sample_dpmpp_2s (deterministic: no churn, no clipping, no callback) as ONE hipGraph replay of the fused chain:
         every stage of these solvers is linear in (stage input, its prediction, the step's state, the first stage's prediction), which the head kernel
         applies (ModeHeadDesc.lin).  The schedule-dependent part - which sigma every evaluation sees, the coefficients, embeddings, routing - is a
         plan rebuilt only when the schedule values, the weights or the batch size change.  None when the fast path does not apply."""
         import os
         assert solver in ("heun", "dpm_2", "dpmpp_2s"), solver
+        guidance = self._guidance(guidance)
         eng = self.engine
         if action.shape[0] == 0 or os.environ.get("MODE_HIP_GRAPH", "1") == "0" or sigmas.numel() < 2:
             return None
-        return self._sample_chunk(eng, *self._chunk_plan(eng, solver, sigmas.numel() - 1), states, action, goals, sigmas, sigma_data)
+        return self._sample_chunk(eng, *self._chunk_plan(eng, solver, sigmas.numel() - 1, guidance is not None), states, action, goals, sigmas, sigma_data,
+                                  guidance=guidance)
 
-    def _chunk_plan(self, eng, solver: str, n: int):
+    def _chunk_plan(self, eng, solver: str, n: int, guided: bool = False):
         """(graph key, plan) of a fused sampler over an n-step schedule for ``_sample_chunk``: "ddim" / "dpmpp_2m" (the one-evaluation-per-step
-        chain) or "heun" / "dpm_2" / "dpmpp_2s" (two-stage solvers)."""
+        chain) or "heun" / "dpm_2" / "dpmpp_2s" (two-stage solvers).  ``guided``: the classifier-free-guidance chain, kept under a key of its own, so
+        that a model used both ways keeps both graphs."""
+        cfg = ":cfg" if guided else ""
         if solver in ("ddim", "dpmpp_2m"):
             multi = solver != "ddim"
-            return ("graph:" + solver if multi else "graph"), (lambda sig: (self._ddim_evals(n, multi), sig, dict(solver=solver)))
+            return ("graph:" + solver if multi else "graph") + cfg, (lambda sig: (self._ddim_evals(n, multi), sig, dict(solver=solver)))
 
         def plan(sig):
             p = self._two_stage_plan(solver, [float(v) for v in sig.tolist()])          # (host sync: only when the schedule changed)
             evals = [(xin, xout, dout, None, a1, a2, True) for _, xin, xout, _, a1, a2, dout in p]
             ev = torch.tensor([e[0] for e in p], dtype=torch.float32, device=eng.device)
             return evals, ev, dict(lin=torch.tensor([e[3] for e in p], dtype=torch.float32))
-        return "graph:" + solver, plan
+        return "graph:" + solver + cfg, plan
 
     @torch.no_grad()
-    def sample_ddim_fused(self, states, action, goals, sigmas, sigma_data: float, solver: str = "ddim"):
+    def sample_ddim_fused(self, states, action, goals, sigmas, sigma_data: float, solver: str = "ddim", guidance=None):
         """sample_ddim (gc_sampling.py:922-951) o GCDenoiser o MoDeDiT as one hipGraph replay.  The graph holds only what depends on the
         observations (embeddings + the denoiser forwards); sigma embeddings, routing, dispatch and the EDM scalings of the schedule live in a
         schedule state that is rebuilt only when the sigma VALUES, the weights or the batch size change.
@@ -572,13 +621,15 @@ class MoDeDiT(nn.Module):
         two-point extrapolation of the denoised prediction, which the head kernel forms from the previous step's prediction (ModeHeadDesc.den_prev)."""
         assert solver in ("ddim", "dpmpp_2m"), solver
         import os
+        guidance = self._guidance(guidance)
         eng = self.engine
         dev, B = eng.device, action.shape[0]
         if B == 0:                                                       # empty batch: nothing to denoise
             return action.detach().to(device=dev, dtype=torch.float32).clone()
         n, multi = sigmas.numel() - 1, solver != "ddim"
         if os.environ.get("MODE_HIP_GRAPH", "1") != "0":               # one captured chain per solver; its buffer pattern is fixed by n
-            return self._sample_chunk(eng, *self._chunk_plan(eng, solver, n), states, action, goals, sigmas, sigma_data)
+            return self._sample_chunk(eng, *self._chunk_plan(eng, solver, n, guidance is not None), states, action, goals, sigmas, sigma_data,
+                                      guidance=guidance)
         img, goals = self._prep_obs(eng, states, goals)
         sig = sigmas.detach().to(device=dev, dtype=torch.float32).contiguous()
         x0 = action.detach().to(device=dev, dtype=torch.float32)
@@ -587,7 +638,7 @@ class MoDeDiT(nn.Module):
             x = x0.clone()
             prev = None
             for i in range(n):
-                den = self.denoise({"state_images": img}, x, goals, sig[i].reshape(1), sigma_data)
+                den = self.denoise({"state_images": img}, x, goals, sig[i].reshape(1), sigma_data, guidance=guidance)
                 r = sig[i + 1] / sig[i]
                 dd = den
                 if solver == "dpmpp_2m" and prev is not None and float(sig[i + 1]) > 0:
@@ -597,11 +648,12 @@ class MoDeDiT(nn.Module):
                 prev = den
             return x
         bufs = [x0.clone(memory_format=torch.contiguous_format)] + [torch.empty(x0.shape, dtype=torch.float32, device=dev) for _ in range(2)]
-        sched = self._schedule_state(eng, sig, B, sigma_data, solver=solver)
-        self._account_chunk(dict(sched=sched), self._chunk_steps(eng, img, goals, bufs, sched, self._ddim_evals(n, multi))[0], n, B)
+        sched = self._schedule_state(eng, sig, B if guidance is None else 2 * B, sigma_data, solver=solver)
+        self._account_chunk(dict(sched=sched), self._chunk_steps(eng, img, goals, bufs, sched, self._ddim_evals(n, multi), guidance=guidance)[0], n, B,
+                            guided=guidance is not None)
         return bufs[0]
 
-    def _sample_chunk(self, eng, gkey, plan, states, action, goals, sigmas, sigma_data: float, hooks=None, rows: Optional[int] = None):
+    def _sample_chunk(self, eng, gkey, plan, states, action, goals, sigmas, sigma_data: float, hooks=None, rows: Optional[int] = None, guidance=None):
         """The fused samplers' hipGraph path: the launch chain of ``_chunk_steps`` captured once per ``_route_cache[gkey]`` entry (one per solver)
         and replayed per call.  ``plan(sig) -> (evaluations, sigma of the schedule state, its keyword arguments)`` is asked for when the entry is
         made and when the schedule changes; a new schedule is then written into the schedule state in place (the graph has its pointers baked
@@ -611,13 +663,17 @@ class MoDeDiT(nn.Module):
         entries live in ``hooks.store[(gkey, B)]``, one per batch size; ``hooks.prologue(ent)`` writes the entry's inputs (img, goals, bufs[0])
         before every replay (and once before the capture's warm-up, which must route valid data); ``hooks.epilogue(ent, capturing)`` is
         captured at the end of the chain and reads its result, bufs[0].  The inputs then only give the shapes; returns None.  ``rows``: the
-        first ``rows`` samples are real, the rest padding - the expert-usage counters count the real ones only."""
+        first ``rows`` samples are real, the rest padding - the expert-usage counters count the real ones only.  ``guidance``: the chain is the
+        guided one (``gkey`` from ``_chunk_plan(..., guided=True)``); B stays the number of samples, the chain's interior has 2B."""
+        guidance = self._guidance(guidance)
+        guided = guidance is not None
         dev, B = eng.device, action.shape[0]
+        Bi = 2 * B if guided else B
         img, goals = self._prep_obs(eng, states, goals)
         sig = sigmas.detach().to(device=dev, dtype=torch.float32).contiguous()
         x0 = action.detach().to(device=dev, dtype=torch.float32)
         self._check_batch(B, img, goals, x0)
-        key = (B, sig.numel(), eng.compute_dtype, eng._structs_for, str(dev), float(sigma_data), self._routing_mode())   # arena pointers are static: weight updates keep graphs valid
+        key = (B, sig.numel(), eng.compute_dtype, eng._structs_for, str(dev), float(sigma_data), self._routing_mode(), guided)   # arena pointers are static: weight updates keep graphs valid
         # identity of the schedule: a host-side tag of its VALUES when the tensor came from a get_sigmas_* / get_noise_schedule generator (the
         # agent builds a fresh tensor per chunk, mode_agent.py:752) - else the caller's tensor OBJECT (kept alive below, so neither its id nor its
         # storage can be recycled while the key is live) -, the weights, and the routing cache generation.  No device read on either path.
@@ -644,7 +700,7 @@ class MoDeDiT(nn.Module):
                 else:
                     ent["sig"].copy_(sig)
                     with eng.pinned_workspace(ent["ws"]):
-                        self._schedule_state(eng, planned[1], B, sigma_data, out=ent["sched"], **planned[2])
+                        self._schedule_state(eng, planned[1], Bi, sigma_data, out=ent["sched"], **planned[2])
             ent["sched_key"] = sched_key
         if fresh:
             evals, s_sig, s_kw = planned if planned is not None else plan(sig)
@@ -654,16 +710,16 @@ class MoDeDiT(nn.Module):
                        bufs=[x0.clone(memory_format=torch.contiguous_format)] + [torch.zeros(x0.shape, dtype=torch.float32, device=dev) for _ in range(2)])
             # the graph owns its workspace: the engine's shared scratch buffer is re-allocated whenever a larger chain (a training step, a
             # bigger batch) asks for more, and a replay would then read freed memory
-            ent["ws"] = self._chunk_ws(eng, B, n)
-            ent["tok"] = self._chunk_topk_buffer(eng, n, B)
+            ent["ws"] = self._chunk_ws(eng, Bi, n)
+            ent["tok"] = self._chunk_topk_buffer(eng, n, Bi)
 
             def chain():
-                out = self._chunk_steps(eng, ent["img"], ent["goals"], ent["bufs"], ent["sched"], evals, tok=ent["tok"])
+                out = self._chunk_steps(eng, ent["img"], ent["goals"], ent["bufs"], ent["sched"], evals, tok=ent["tok"], guidance=guidance)
                 if hooks is not None:
                     hooks.epilogue(ent, torch.cuda.is_current_stream_capturing())
                 return out
             with eng.pinned_workspace(ent["ws"]):
-                ent["sched"] = self._schedule_state(eng, s_sig, B, sigma_data, **s_kw)
+                ent["sched"] = self._schedule_state(eng, s_sig, Bi, sigma_data, **s_kw)
                 if hooks is not None:
                     hooks.prologue(ent)
                 ent["graph"], (ent["ml"], ent["route"]) = warm_and_capture(chain, dev)
@@ -673,37 +729,42 @@ class MoDeDiT(nn.Module):
         else:
             hooks.prologue(ent)
         ent["graph"].replay()
-        self._account_chunk(ent, ent["ml"], len(ent["evals"]), B, rows)
+        self._account_chunk(ent, ent["ml"], len(ent["evals"]), B, rows, guided)
         return ent["bufs"][0].clone() if hooks is None else None
 
     def _chunk_ws(self, eng, B: int, n: int) -> torch.Tensor:
         """The workspace a captured chunk of n evaluations owns: the forward's, or the schedule's sigma embedding / the router's over n rows
-        (n·B conditioning rows with goal routing), whichever is larger."""
+        (n·B conditioning rows with goal routing), whichever is larger.  ``B``: the chain's internal batch."""
         rows = n * B if self.use_goal_in_routing else n
         return torch.empty(max(eng.workspace_bytes(B, 0), eng.workspace_bytes(0, rows)), dtype=torch.uint8, device=eng.device)
 
     def _chunk_topk_buffer(self, eng, n: int, B: int):
-        """Token routing: int32 [n, L, B·T, k] that the n forwards of a captured chunk write their decisions to; None otherwise."""
+        """Token routing: int32 [n, L, B·T, k] that the n forwards of a captured chunk write their decisions to (B: the chain's internal batch); None
+        otherwise."""
         if self.cond_router:
             return None
         return torch.empty(n, self.num_layers, B * self.seq_len, self.top_k, dtype=torch.int32, device=eng.device)
 
-    def _account_chunk(self, ent, ml, n: int, B: int, rows: Optional[int] = None) -> None:
+    def _account_chunk(self, ent, ml, n: int, B: int, rows: Optional[int] = None, guided: bool = False) -> None:
         """After a run of a chunk of n evaluations: ``_last_topk`` (level j of every layer at [:, j]) and the expert-usage counters, with device
         ops only - token routing: ONE histogram of the chunk's decisions; otherwise the dispatch records' per-expert counts.  ``rows`` < B: only
         the first ``rows`` samples are counted - token / goal routing: a histogram of their decisions (a goal-routed decision stands for the
-        sample's T tokens); noise-level routing sends every sample to the same experts, so the counts scale by rows / B exactly."""
+        sample's T tokens); noise-level routing sends every sample to the same experts, so the counts scale by rows / B exactly.  ``guided``: the
+        chain ran 2B samples, the unconditional halves behind the conditional ones; both halves' tokens are tokens processed and are counted (the
+        first ``rows`` samples OF EACH HALF when padded)."""
         T = self.seq_len
-        N, r = B * T, B if rows is None else rows
+        halves = 2 if guided else 1
+        N, r = halves * B * T, B if rows is None else rows
+        real = lambda t, per: t if r == B else torch.cat([t[:, :, h * B * per: (h * B + r) * per] for h in range(halves)], 2)   # the real rows of [L, n, halves·B·per, k]
         if ent.get("tok") is not None:
             self._last_topk = ent["tok"].transpose(0, 1)                 # [L, n, N, k]
-            self._account_token_usage(self._last_topk if r == B else self._last_topk[:, :, :r * T], r * T * n)
+            self._account_token_usage(real(self._last_topk, T), halves * r * T * n)
         elif self.use_goal_in_routing:
-            self._last_topk = ent["route"]["idx"].view(self.num_layers, n, B, self.top_k)
+            self._last_topk = ent["route"]["idx"].view(self.num_layers, n, halves * B, self.top_k)
             if r == B:
                 self._account_usage(ent["route"]["meta"], ml, N, n)
             else:
-                self._account_token_usage(self._last_topk[:, :, :r], r * T * n, weight=T)
+                self._account_token_usage(real(self._last_topk, 1), halves * r * T * n, weight=T)
         else:
             self._last_topk = ent["sched"]["idx"]
             self._account_usage(ent["sched"]["meta"], ml, N, n, rows=None if r == B else (r, B))

@@ -162,26 +162,28 @@ class ChunkedRolloutPolicy:
         inner = getattr(den, "inner_model", None)
         if not isinstance(inner, MoDeDiT) or inner.training or len(x) == 0 or os.environ.get("MODE_HIP_GRAPH", "1") == "0":
             return None
+        guidance = inner._guidance(getattr(den, "guidance_scale", None))   # classifier-free guidance: the device scalar every denoiser call of the chunk reads
         eng = inner.engine
         dev, B = eng.device, x.shape[0]
+        Bi = B if guidance is None else 2 * B                             # the denoiser calls' internal batch
         img, gl = inner._prep_obs(eng, perceptual_emb, latent_goal)
         inner._check_batch(B, img, gl, x)
         cache = self.__dict__.setdefault("_chunk_graphs", {})
         key = (self.sampler_type, B, eng.compute_dtype, eng._structs_for, str(dev), id(sigmas), sigmas._version, float(den.sigma_data),
-               inner._routing_mode())
+               inner._routing_mode(), guidance is not None)
         ent = cache.get(key)
         if ent is None:
             if len(cache) >= 4:
                 cache.pop(next(iter(cache)))
             ent = dict(x=x.clone(), img=img.clone(), goals=gl.clone(), sig=sigmas,
                        img_e=torch.empty(B * inner.n_img_tokens, inner.embed_dim, device=dev), goal_e=torch.empty(B, inner.embed_dim, device=dev))
-            ent["ws"] = inner._chunk_ws(eng, B, 1)
+            ent["ws"] = inner._chunk_ws(eng, Bi, 1)
             state = {"state_images": ent["img"].view(B, inner.n_img_tokens, -1)}
             goal3 = ent["goals"].view(B, 1, -1)
 
             def chunk():
                 eng.embed_obs(ent["img"], ent["goals"], out=(ent["img_e"], ent["goal_e"]))
-                cc = dict(inner=inner, sigma_data=float(den.sigma_data), obs_emb=(ent["img_e"], ent["goal_e"]), metas=[])
+                cc = dict(inner=inner, sigma_data=float(den.sigma_data), obs_emb=(ent["img_e"], ent["goal_e"]), metas=[], guidance=guidance)
                 S._set_chunk_capture(cc)
                 try:
                     out = sample_loop(den, sigmas, ent["x"], state, goal3, self.sampler_type, None)
@@ -194,7 +196,7 @@ class ChunkedRolloutPolicy:
         ent["x"].copy_(x); ent["img"].copy_(img); ent["goals"].copy_(gl)
         ent["graph"].replay()
         # expert-usage counters of every denoiser call, as the step-by-step path keeps them: [L, calls, ...]
-        N, calls, rec = B * inner.seq_len, len(ent["metas"]), torch.stack(ent["metas"], 1)
+        N, calls, rec = Bi * inner.seq_len, len(ent["metas"]), torch.stack(ent["metas"], 1)
         if not inner.cond_router:
             inner._account_token_usage(rec, N * calls)                        # token routing: one histogram of every call's decisions
         else:
@@ -636,8 +638,9 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
             dev = eng.device
             tpl = self._templates[mb] = ({"state_images": torch.zeros(mb, inner.n_img_tokens, inner.obs_dim, device=dev)},
                                          torch.zeros(mb, self.act_window_size, self.action_dim, device=dev), torch.zeros(mb, inner.goal_dim, device=dev))
-        gkey, plan = inner._chunk_plan(eng, self._solver, sig.numel() - 1)
-        inner._sample_chunk(eng, gkey, plan, tpl[0], tpl[1], tpl[2], sig, float(self.model.sigma_data), hooks=self._hooks, rows=m)
+        w = getattr(self.model, "guidance_scale", None)                  # classifier-free guidance: the bucket's mb rows run as 2·mb inside the chain
+        gkey, plan = inner._chunk_plan(eng, self._solver, sig.numel() - 1, w is not None)
+        inner._sample_chunk(eng, gkey, plan, tpl[0], tpl[1], tpl[2], sig, float(self.model.sigma_data), hooks=self._hooks, rows=m, guidance=w)
 
     @staticmethod
     def _prepared(img, gl, frames):

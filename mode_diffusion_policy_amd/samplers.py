@@ -174,7 +174,7 @@ class _Run:
         cc = _chunk_capture()
         if cc is not None and not self.kw and torch.is_tensor(sigma) and sigma.numel() == 1:
             inner = cc["inner"]
-            out = inner.denoise(None, x, None, sigma.reshape(1), cc["sigma_data"], _account=False, _obs_emb=cc["obs_emb"])
+            out = inner.denoise(None, x, None, sigma.reshape(1), cc["sigma_data"], _account=False, _obs_emb=cc["obs_emb"], guidance=cc.get("guidance"))
             cc["metas"].append(inner._last_meta if inner.cond_router else inner._last_topk)     # token routing: the call's decisions [L, N, k]
             return out
         fast = getattr(self.model, "denoise_uniform", None)              # GCDenoiser over the HIP MoDeDiT: one hipGraph replay per call

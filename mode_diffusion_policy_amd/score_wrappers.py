@@ -6,6 +6,9 @@ launches + temporaries per call).
 """
 from __future__ import annotations
 
+import math
+import numbers
+
 import torch
 from torch import nn
 
@@ -27,10 +30,31 @@ def _instantiate(cfg):
 
 
 class GCDenoiser(nn.Module):
-    def __init__(self, inner_model, sigma_data=1.0):
+    """``guidance_scale`` (settable): None = the plain denoiser, every path and result as without the argument.  A finite number w = classifier-free
+    guidance at sampling time - the model is trained with goal dropout for exactly this -:
+        D_w(x; sigma, obs, goal) = D_u + w (D_c - D_u),   D_c = D(x; sigma, obs, goal),   D_u = D(x; sigma, obs, 0)
+    (no special case for w = 0 or 1).  Guidance acts on the goal token and, with ``use_goal_in_routing``, on the router input; both branches share
+    the observation tokens, the latent, sigma and the EDM scalings.  On the HIP MoDeDiT both branches run in ONE chain at twice the batch and the
+    combine is a step of the head kernel's epilogue, ahead of any solver update: ``forward``, the graphed denoiser and every fused sampler carry
+    it, so do all samplers of ``samplers.py``.  Eval only; ``loss`` ignores it."""
+
+    def __init__(self, inner_model, sigma_data=1.0, guidance_scale=None):
         super().__init__()
         self.inner_model = _instantiate(inner_model)
         self.sigma_data = sigma_data
+        self.guidance_scale = guidance_scale
+
+    @property
+    def guidance_scale(self):
+        return self._guidance_scale
+
+    @guidance_scale.setter
+    def guidance_scale(self, w):
+        if w is not None:
+            if isinstance(w, bool) or not isinstance(w, numbers.Real) or not math.isfinite(w):
+                raise ValueError(f"guidance_scale must be None or a finite number, got {w!r}")
+            w = float(w)
+        self._guidance_scale = w
 
     def get_scalings(self, sigma):
         """c_skip, c_out, c_in   (score_wrappers.py:31-43)."""
@@ -55,11 +79,18 @@ class GCDenoiser(nn.Module):
 
     def forward(self, state, action, goal, sigma, **kwargs):
         """D(x; sigma) = F(x*c_in)*c_out + x*c_skip   (score_wrappers.py:65-80)."""
-        m = self.inner_model
-        if isinstance(m, MoDeDiT) and not m.training and not kwargs:
-            return m.denoise(state, action, goal, sigma, self.sigma_data)
+        m, w = self.inner_model, self.guidance_scale
+        if isinstance(m, MoDeDiT):
+            if w is not None and m.training:
+                raise ValueError("guidance_scale is set: classifier-free guidance is an inference-time combine, call .eval() first")
+            if not m.training and not kwargs:
+                return m.denoise(state, action, goal, sigma, self.sigma_data, guidance=w)
         c_skip, c_out, c_in = [append_dims(x, action.ndim) for x in self.get_scalings(sigma)]
-        return m(state, action * c_in, goal, sigma, **kwargs) * c_out + action * c_skip
+        den = m(state, action * c_in, goal, sigma, **kwargs) * c_out + action * c_skip
+        if w is None:
+            return den
+        den_u = m(state, action * c_in, goal, sigma, **{**kwargs, "uncond": True}) * c_out + action * c_skip   # any inner model: the reference's `uncond` flag
+        return den_u + w * (den - den_u)
 
     def denoise_uniform(self, state, action, goal, sigma):
         """D(x; sigma) for ONE noise level shared by the whole batch (what every k-diffusion style sampler asks for: ``sigma * ones``), as one
@@ -67,7 +98,7 @@ class GCDenoiser(nn.Module):
         goal routing, a foreign inner model) - the caller then takes ``forward``."""
         m = self.inner_model
         if isinstance(m, MoDeDiT) and not m.training and not torch.is_grad_enabled():
-            return m.denoise_graphed(state, action, goal, sigma, self.sigma_data)
+            return m.denoise_graphed(state, action, goal, sigma, self.sigma_data, guidance=self.guidance_scale)
         return None
 
     def first_order_ode_fused(self, state, action, goal, sigmas):
@@ -76,7 +107,7 @@ class GCDenoiser(nn.Module):
         and, multiplied out, sample_euler's without churn (gc_sampling.py:165-211: x + (x - D)/s (s' - s)).  None when the fast path does not apply."""
         m = self.inner_model
         if isinstance(m, MoDeDiT) and not m.training and not torch.is_grad_enabled() and torch.is_tensor(sigmas) and sigmas.dim() == 1:
-            return m.sample_ddim_fused(state, action, goal, sigmas, self.sigma_data)
+            return m.sample_ddim_fused(state, action, goal, sigmas, self.sigma_data, guidance=self.guidance_scale)
         return None
 
     def dpmpp_2m_fused(self, state, action, goal, sigmas):
@@ -84,7 +115,7 @@ class GCDenoiser(nn.Module):
         two-point extrapolation (1 + 1/(2r)) D - (1/(2r)) D_old of the denoised prediction.  None when the fast path does not apply."""
         m = self.inner_model
         if isinstance(m, MoDeDiT) and not m.training and not torch.is_grad_enabled() and torch.is_tensor(sigmas) and sigmas.dim() == 1:
-            return m.sample_ddim_fused(state, action, goal, sigmas, self.sigma_data, solver="dpmpp_2m")
+            return m.sample_ddim_fused(state, action, goal, sigmas, self.sigma_data, solver="dpmpp_2m", guidance=self.guidance_scale)
         return None
 
     def two_stage_fused(self, state, action, goal, sigmas, solver: str):
@@ -92,7 +123,7 @@ class GCDenoiser(nn.Module):
         every stage's update is linear and runs inside the head kernel).  None when the fast path does not apply."""
         m = self.inner_model
         if isinstance(m, MoDeDiT) and not m.training and not torch.is_grad_enabled() and torch.is_tensor(sigmas) and sigmas.dim() == 1:
-            return m.sample_two_stage_fused(state, action, goal, sigmas, self.sigma_data, solver)
+            return m.sample_two_stage_fused(state, action, goal, sigmas, self.sigma_data, solver, guidance=self.guidance_scale)
         return None
 
     def get_params(self):
