@@ -1,10 +1,16 @@
-// Row-wise fused kernels (HBM-bound): one wave64 per token row, row cached in LDS between the reduce and the normalise
-// pass, wave-shuffle reductions, float4 / 8-byte bf16 vector accesses.  D % 4 == 0.
+// Row-wise fused kernels (HBM-bound), float4 / 8-byte bf16 vector accesses, wave-shuffle reductions.  D % 4 == 0.  Two forms:
+//   - one WORKGROUP per token row (combine_norm_row_kernel, embed_tokens_row_kernel, head_ddim_row_kernel, head_ddim_guided_row_kernel): a thread
+//     owns 4 columns per 1024 and keeps them in registers, every load is unconditional and requested before the one cross-wave reduction.  This is
+//     the form every sampler call takes (D <= 4096, k <= 2, y_splits <= 8, "combine_row_max" not 0).
+//   - the fallbacks, one WAVE64 per token row, four rows per workgroup, the row cached in LDS between the reduce and the normalise pass
+//     (rmsnorm_cond_kernel, combine_norm_kernel, embed_tokens_kernel, head_ddim_kernel): any D, k <= 8, any slab count.  rmsnorm_cond has this form only.
 //   rmsnorm_cond      : ln_1(x)+c / ln_2 / final ln                        (modedit.py:72-80, 532, 539, 818)
 //   combine_norm      : MoE weighted combine + residual + next block's ln_1+c   (modedit.py:566, 595, 532)
 //   embed_tokens      : sequence assembly + first ln_1+c                    (modedit.py:760-790, 847-860)
 //   head_ddim         : last combine + final ln + Linear(D,A) + EDM/DDIM update  (modedit.py:807-808; score_wrappers.py:79-80;
 //                                                                             gc_sampling.py:948-950)
+#include <type_traits>
+
 #include "mode_common.h"
 
 namespace mode {
@@ -23,6 +29,20 @@ __device__ __forceinline__ void for_chunks(int D, int lane, F&& f) {
   }
 }
 
+template <bool LP_BF16>   // store 4 consecutive elements at element offset `off` of a bf16 (8-byte store) or fp32 tensor
+__device__ __forceinline__ void store_lp4(void* base, long off, float4 o) {
+  if constexpr (LP_BF16) {
+    uint2 pk; pk.x = pack_bf16x2(o.x, o.y); pk.y = pack_bf16x2(o.z, o.w);
+    *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(base) + off) = pk;
+  } else {
+    *reinterpret_cast<float4*>(reinterpret_cast<float*>(base) + off) = o;
+  }
+}
+
+__device__ __forceinline__ float4 scale4(float4 v, float s, float4 g) {   // v * s * g, in this order (s: the row's one reciprocal norm)
+  return make_float4(v.x * s * g.x, v.y * s * g.y, v.z * s * g.z, v.w * s * g.w);
+}
+
 // normalise the cached row: y = v / max(sqrt(ssq) * D^-1/2, eps) * g (+ cond); write fp32 and/or low-precision copies
 template <bool LP_BF16, int NCH>
 __device__ __forceinline__ void norm_store(const float* row, int D, float ssq, const float* g, const float* cond, float eps,
@@ -32,20 +52,13 @@ __device__ __forceinline__ void norm_store(const float* row, int D, float ssq, c
   for_chunks<NCH>(D, lane, [&](int d) {
     const float4 v = *reinterpret_cast<const float4*>(row + d);
     const float4 gg = *reinterpret_cast<const float4*>(g + d);
-    float4 o = make_float4(v.x * rnrm * gg.x, v.y * rnrm * gg.y, v.z * rnrm * gg.z, v.w * rnrm * gg.w);
+    float4 o = scale4(v, rnrm, gg);
     if (cond) {
       const float4 c = *reinterpret_cast<const float4*>(cond + d);
       o.x += c.x; o.y += c.y; o.z += c.z; o.w += c.w;
     }
     if (y_f32) *reinterpret_cast<float4*>(y_f32 + d) = o;
-    if (y_lp) {
-      if constexpr (LP_BF16) {
-        uint2 pk; pk.x = pack_bf16x2(o.x, o.y); pk.y = pack_bf16x2(o.z, o.w);
-        *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(y_lp) + d) = pk;
-      } else {
-        *reinterpret_cast<float4*>(reinterpret_cast<float*>(y_lp) + d) = o;
-      }
-    }
+    if (y_lp) store_lp4<LP_BF16>(y_lp, d, o);
   });
 }
 
@@ -55,13 +68,18 @@ __device__ __forceinline__ float row_norm_from_partials(const float* ss, int n, 
   return fmaxf(sqrtf(sum_row_partials_wave(ss, n, lane)) * rsqrtf((float)D), eps);   // same order as the GEMM-side consumers (gemm_bf16*.hip)
 }
 
-__device__ __forceinline__ float4 load_y4(const void* Y, bool y_bf16, long off) {
-  if (y_bf16) {
+template <bool YBF>   // one float4 of an expert output row: 4 bf16 (8 bytes) widened, or 4 fp32
+__device__ __forceinline__ float4 load_y4(const void* Y, long off) {
+  if constexpr (YBF) {
     const uint2 r = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(Y) + off);
     return make_float4(bf16_bits_to_f32(r.x & 0xffff), bf16_bits_to_f32(r.x >> 16), bf16_bits_to_f32(r.y & 0xffff),
                        bf16_bits_to_f32(r.y >> 16));
+  } else {
+    return *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(Y) + off);
   }
-  return *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(Y) + off);
+}
+__device__ __forceinline__ float4 load_y4(const void* Y, bool y_bf16, long off) {   // dtype at run time: the one-wave-per-row kernels
+  return y_bf16 ? load_y4<true>(Y, off) : load_y4<false>(Y, off);
 }
 
 // ------------------------------------------------------------------------------------------------------------ rmsnorm
@@ -168,14 +186,9 @@ __global__ __launch_bounds__(256) void combine_norm_kernel(const float* u, const
     for (int c = 0; c < NCH; ++c) {
       const int d = lane * 4 + c * 256;
       const float4 v = *reinterpret_cast<const float4*>(cache + d);
-      float4 o = make_float4(v.x * rnrm * gq[c].x, v.y * rnrm * gq[c].y, v.z * rnrm * gq[c].z, v.w * rnrm * gq[c].w);
+      float4 o = make_float4(v.x * rnrm * gq[c].x, v.y * rnrm * gq[c].y, v.z * rnrm * gq[c].z, v.w * rnrm * gq[c].w);   // (written out: scale4 re-orders this kernel's code)
       if (cr) { o.x += cq[c].x; o.y += cq[c].y; o.z += cq[c].z; o.w += cq[c].w; }
-      if constexpr (LP_BF16) {
-        uint2 pk; pk.x = pack_bf16x2(o.x, o.y); pk.y = pack_bf16x2(o.z, o.w);
-        *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(h) + (long)row * D + d) = pk;
-      } else {
-        *reinterpret_cast<float4*>(reinterpret_cast<float*>(h) + (long)row * D + d) = o;
-      }
+      store_lp4<LP_BF16>(h, (long)row * D + d, o);
     }
     return;
   }
@@ -184,6 +197,17 @@ __global__ __launch_bounds__(256) void combine_norm_kernel(const float* u, const
                            (void*)((char*)h + (long)row * D * (LP_BF16 ? 2 : 4)), lane);
 }
 
+// Numerics contract of the row-per-workgroup kernels' MoE combine, v = ln_2(u) + sum_j w_j * expert_j(row).  The block is written out in
+// combine_norm_row_kernel, head_ddim_row_kernel and head_ddim_guided_row_kernel (a shared helper changed their compiled code, LABNOTES 2026-10-18),
+// so a change to it is made in all three:
+//   - experts are added in ascending expert id, nx = nx + w * y with separately rounded __fmul_rn / __fadd_rn (never contracted into an fma);
+//   - the split-K slabs of the down-projection are added in slice order; YS is a compile-time BOUND on the slab count: slab z >= y_splits is
+//     loaded from slab 0 (clamped index) and enters the sum as a selected 0.f;
+//   - the fused ln_2 is u * (1 / max(sqrt(sum of partials) * D^-1/2, eps)) * gain: one reciprocal per row, the partials summed in the order of the
+//     GEMM-side consumers (row_norm_from_partials);
+//   - the row's norm is the cross-wave sum ((w0 + w1) + w2) + w3 of the wave sums, again with one reciprocal per row;
+//   - every load is unconditional: columns past D are clamped to column 0 and the result is masked (see below).
+//
 // Small-batch form (N <= "gemm_skinny_rows" token rows, i.e. B <= 2 environments): ONE WORKGROUP per row, a thread owns 4 columns per 1024,
 // so every load of the row (u, gains, conditioning, k x slabs expert rows) is requested at once and the kernel is two dependent round trips
 // (routing slots -> rows) plus one cross-wave reduction.  With one wave per row the 14 rows of B = 1 occupied four CUs for 12.7 us.
@@ -224,14 +248,9 @@ __global__ __launch_bounds__(256) void combine_norm_row_kernel(const float* u, c
 #pragma unroll
       for (int z = 0; z < YS; ++z) {                                 // split-K slabs of the down-projection, all requested together
         const long off = (long)(z < y_splits ? z : 0) * y_split_stride + prow[j] + dc;
-        if constexpr (YBF) {
-          const uint2 r = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(Y) + off);
-          ys[j][z] = make_float4(bf16_bits_to_f32(r.x & 0xffff), bf16_bits_to_f32(r.x >> 16), bf16_bits_to_f32(r.y & 0xffff), bf16_bits_to_f32(r.y >> 16));
-        } else {
-          ys[j][z] = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(Y) + off);
-        }
+        ys[j][z] = load_y4<YBF>(Y, off);
       }
-    if constexpr (FUSED) uu = make_float4(uu.x * ru_nrm * gg.x, uu.y * ru_nrm * gg.y, uu.z * ru_nrm * gg.z, uu.w * ru_nrm * gg.w);
+    if constexpr (FUSED) uu = scale4(uu, ru_nrm, gg);
     float4 nx = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int j = 0; j < KK; ++j) {                                   // ascending expert id: next += w * expert(x)   (modedit.py:566)
@@ -260,14 +279,9 @@ __global__ __launch_bounds__(256) void combine_norm_row_kernel(const float* u, c
   for (int c = 0; c < NC; ++c) {
     const int d = tid * 4 + c * 1024;
     if (d >= D) continue;
-    float4 o = make_float4(v[c].x * rnrm * gq[c].x, v[c].y * rnrm * gq[c].y, v[c].z * rnrm * gq[c].z, v[c].w * rnrm * gq[c].w);
+    float4 o = scale4(v[c], rnrm, gq[c]);
     if (hc) { o.x += cq[c].x; o.y += cq[c].y; o.z += cq[c].z; o.w += cq[c].w; }
-    if constexpr (LP_BF16) {
-      uint2 pk; pk.x = pack_bf16x2(o.x, o.y); pk.y = pack_bf16x2(o.z, o.w);
-      *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(h) + (long)row * D + d) = pk;
-    } else {
-      *reinterpret_cast<float4*>(reinterpret_cast<float*>(h) + (long)row * D + d) = o;
-    }
+    store_lp4<LP_BF16>(h, (long)row * D + d, o);
   }
 }
 
@@ -387,7 +401,7 @@ __global__ __launch_bounds__(256) void head_ddim_kernel(const ModeHeadDesc h) {
     float4 uu = *reinterpret_cast<const float4*>(ur + d);
     if (h.u_ss) {
       const float4 gg = *reinterpret_cast<const float4*>(h.u_gain + d);
-      uu = make_float4(uu.x * ru_nrm * gg.x, uu.y * ru_nrm * gg.y, uu.z * ru_nrm * gg.z, uu.w * ru_nrm * gg.w);
+      uu = scale4(uu, ru_nrm, gg);
     }
     float4 nx = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int j = 0; j < h.k; ++j) {
@@ -436,7 +450,7 @@ __global__ __launch_bounds__(256) void head_ddim_kernel(const ModeHeadDesc h) {
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       const float4 v = *reinterpret_cast<const float4*>(cache + lane * 4 + c * 256);
-      const float4 n = make_float4(v.x * rnrm * gq[c].x, v.y * rnrm * gq[c].y, v.z * rnrm * gq[c].z, v.w * rnrm * gq[c].w);
+      const float4 n = scale4(v, rnrm, gq[c]);
 #pragma unroll
       for (int j = 0; j < AMAX; ++j)
         if (j < h.A_dim) accv[j] += n.x * wq[c][j].x + n.y * wq[c][j].y + n.z * wq[c][j].z + n.w * wq[c][j].w;
@@ -448,7 +462,7 @@ __global__ __launch_bounds__(256) void head_ddim_kernel(const ModeHeadDesc h) {
     for (int d = lane * 4; d < D; d += 256) {
       const float4 v = *reinterpret_cast<const float4*>(cache + d);
       const float4 gg = *reinterpret_cast<const float4*>(h.g + d);
-      const float4 n = make_float4(v.x * rnrm * gg.x, v.y * rnrm * gg.y, v.z * rnrm * gg.z, v.w * rnrm * gg.w);
+      const float4 n = scale4(v, rnrm, gg);
 #pragma unroll
       for (int j = 0; j < AMAX; ++j) {
         if (j < h.A_dim) {
@@ -494,6 +508,18 @@ __global__ void sigma_embed_kernel(const float* sigma, const float* w, const flo
 }  // namespace mode
 
 using namespace mode;
+
+// Run-time values -> template parameters.  among<V0, V1, ...>(v) names a run-time value and the compile-time constants it may take (the last one
+// stands for "anything else"); dispatch(f, among..., among...) calls the generic lambda f with one std::integral_constant per value, so that
+// f's body can write kernel<A(), B(), ...>.  Every combination of the lists is instantiated, no other.
+template <auto V0, auto... Vs> struct Among { decltype(V0) v; };
+template <auto V0, auto... Vs> static Among<V0, Vs...> among(decltype(V0) v) { return {v}; }
+template <typename F> static void dispatch(F&& f) { f(); }
+template <typename F, auto V0, auto... Vs, typename... Rest>
+static void dispatch(F&& f, Among<V0, Vs...> a, Rest... rest) {
+  if (sizeof...(Vs) == 0 || a.v == V0) dispatch([&](auto... cs) { f(std::integral_constant<decltype(V0), V0>{}, cs...); }, rest...);
+  else if constexpr (sizeof...(Vs) > 0) dispatch(f, Among<Vs...>{a.v}, rest...);
+}
 
 template <bool LP>
 static void launch_rmsnorm(dim3 grid, size_t lds, hipStream_t st, const float* x, const float* g, const float* cond, int rows, int D, int rpc,
@@ -565,18 +591,11 @@ extern "C" int mode_moe_combine_norm_fused_fwd(const float* u, const float* u_ss
     const hipStream_t st = (hipStream_t)stream;
     const int nc = (D + 1023) / 1024;
     const int ysb = y_splits <= 1 ? 1 : y_splits <= 2 ? 2 : y_splits <= 4 ? 4 : 8;
-#define MODE_ROWK(LP, KK, F, NC, YB, YS) hipLaunchKernelGGL((combine_norm_row_kernel<LP, KK, F, NC, YB, YS>), dim3(N), dim3(256), 0, st, u, Y, y_splits, (long)y_split_stride, pos, posw, N, D, g, cond, rows_per_cond, eps, x_next, h, u_ss, u_ss_n, u_gain)
-#define MODE_ROWK_YS(LP, KK, F, NC, YB) do { if (ysb == 1) MODE_ROWK(LP, KK, F, NC, YB, 1); else if (ysb == 2) MODE_ROWK(LP, KK, F, NC, YB, 2); else if (ysb == 4) MODE_ROWK(LP, KK, F, NC, YB, 4); else MODE_ROWK(LP, KK, F, NC, YB, 8); } while (0)
-#define MODE_ROWK_YB(LP, KK, F, NC) do { if (ybf) MODE_ROWK_YS(LP, KK, F, NC, true); else MODE_ROWK_YS(LP, KK, F, NC, false); } while (0)
-#define MODE_ROWK_NC(LP, KK, F) do { if (nc == 1) MODE_ROWK_YB(LP, KK, F, 1); else if (nc == 2) MODE_ROWK_YB(LP, KK, F, 2); else MODE_ROWK_YB(LP, KK, F, 4); } while (0)
-#define MODE_ROWK_F(LP, KK) do { if (u_ss) MODE_ROWK_NC(LP, KK, true); else MODE_ROWK_NC(LP, KK, false); } while (0)
-    if (h_dtype == MODE_BF16) { if (k == 2) MODE_ROWK_F(true, 2); else MODE_ROWK_F(true, 1); }
-    else { if (k == 2) MODE_ROWK_F(false, 2); else MODE_ROWK_F(false, 1); }
-#undef MODE_ROWK_F
-#undef MODE_ROWK_NC
-#undef MODE_ROWK_YB
-#undef MODE_ROWK_YS
-#undef MODE_ROWK
+    dispatch([&](auto LP, auto KK, auto F, auto NC, auto YB, auto YS) {
+      hipLaunchKernelGGL((combine_norm_row_kernel<LP(), KK(), F(), NC(), YB(), YS()>), dim3(N), dim3(256), 0, st, u, Y, y_splits, (long)y_split_stride, pos,
+                         posw, N, D, g, cond, rows_per_cond, eps, x_next, h, u_ss, u_ss_n, u_gain);
+    }, among<true, false>(h_dtype == MODE_BF16), among<2, 1>(k), among<true, false>(u_ss != nullptr), among<1, 2, 4>(nc), among<true, false>(ybf != 0),
+       among<1, 2, 4, 8>(ysb));
     MODE_LAUNCH_CHECK();
     return MODE_OK;
   }
@@ -689,14 +708,9 @@ __global__ __launch_bounds__(256) void embed_tokens_row_kernel(const ModeEmbedDe
   for (int c = 0; c < NC; ++c) {
     const int d = tid * 4 + c * 1024;
     if (d >= D) continue;
-    float4 o = make_float4(v[c].x * rnrm * gq[c].x, v[c].y * rnrm * gq[c].y, v[c].z * rnrm * gq[c].z, v[c].w * rnrm * gq[c].w);
+    float4 o = scale4(v[c], rnrm, gq[c]);
     if (e.cond) { o.x += cq[c].x; o.y += cq[c].y; o.z += cq[c].z; o.w += cq[c].w; }
-    if constexpr (LP_BF16) {
-      uint2 pk; pk.x = pack_bf16x2(o.x, o.y); pk.y = pack_bf16x2(o.z, o.w);
-      *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(e.h) + (long)row * D + d) = pk;
-    } else {
-      *reinterpret_cast<float4*>(reinterpret_cast<float*>(e.h) + (long)row * D + d) = o;
-    }
+    store_lp4<LP_BF16>(e.h, (long)row * D + d, o);
   }
 }
 }  // namespace mode
@@ -707,10 +721,13 @@ static bool embed_desc_complete(const ModeEmbedDesc* d) {
 static bool embed_desc_supported(const ModeEmbedDesc* d) {
   return !(d->D & 3) && d->A_dim <= kMaxActionDim && d->T == (d->use_noise_token ? 1 : 0) + 1 + d->n_img + d->A_len;
 }
-// the one-workgroup-per-row embed kernel's instantiation ladder (G: its guided form); reads d, rows, wide, nc, st
-#define MODE_EK(G, LP, NC) do { if (wide) hipLaunchKernelGGL((embed_tokens_row_kernel<LP, NC, 32, G>), dim3(rows), dim3(256), 0, st, *d); \
-                                else hipLaunchKernelGGL((embed_tokens_row_kernel<LP, NC, 8, G>), dim3(rows), dim3(256), 0, st, *d); } while (0)
-#define MODE_EK_NC(G, LP) do { if (nc == 1) MODE_EK(G, LP, 1); else if (nc == 2) MODE_EK(G, LP, 2); else MODE_EK(G, LP, 4); } while (0)
+// launch the one-workgroup-per-row embed kernel (G: its guided form) on `rows` rows
+template <bool G>
+static void launch_embed_row(const ModeEmbedDesc* d, int rows, hipStream_t st) {
+  dispatch([&](auto LP, auto NC, auto AMAX) {
+    hipLaunchKernelGGL((embed_tokens_row_kernel<LP(), NC(), AMAX(), G>), dim3(rows), dim3(256), 0, st, *d);
+  }, among<true, false>(d->h_dtype == MODE_BF16), among<1, 2, 4>((d->D + 1023) / 1024), among<32, 8>(d->A_dim > 8 ? 32 : 8));
+}
 
 extern "C" int mode_embed_tokens_guided_fwd(const ModeEmbedGuidedDesc* gd, void* stream) {
   const ModeEmbedDesc* d = gd ? &gd->emb : nullptr;
@@ -718,10 +735,7 @@ extern "C" int mode_embed_tokens_guided_fwd(const ModeEmbedGuidedDesc* gd, void*
   if (!embed_desc_supported(d) || d->D > 4096 || d->A_dim < 1) return MODE_ERR_UNSUPPORTED;   // pairs exist in the row kernel only
   const int rows = 2 * d->B * d->T;                                   // both branches of every pair
   if (rows == 0) return MODE_OK;
-  const bool wide = d->A_dim > 8;
-  const hipStream_t st = (hipStream_t)stream;
-  const int nc = (d->D + 1023) / 1024;
-  if (d->h_dtype == MODE_BF16) MODE_EK_NC(true, true); else MODE_EK_NC(true, false);
+  launch_embed_row<true>(d, rows, (hipStream_t)stream);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }
@@ -731,30 +745,20 @@ extern "C" int mode_embed_tokens_fwd(const ModeEmbedDesc* d, void* stream) {
   if (!embed_desc_supported(d)) return MODE_ERR_UNSUPPORTED;
   const int rows = d->B * d->T;
   if (rows == 0) return MODE_OK;
-  const bool wide = d->A_dim > 8;                                     // AMAX = 32 instantiations
   if (d->D <= 4096 && d->A_dim >= 1) {                               // one workgroup per row
-    const hipStream_t st = (hipStream_t)stream;
-    const int nc = (d->D + 1023) / 1024;
-    if (d->h_dtype == MODE_BF16) MODE_EK_NC(false, true); else MODE_EK_NC(false, false);
+    launch_embed_row<false>(d, rows, (hipStream_t)stream);
     MODE_LAUNCH_CHECK();
     return MODE_OK;
   }
   const dim3 grid((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
   const size_t lds = (size_t)ROWS_PER_BLOCK * d->D * 4;
   const hipStream_t st = (hipStream_t)stream;
-#define MODE_EKF(LP, NCH) do { if (wide) hipLaunchKernelGGL((embed_tokens_kernel<LP, NCH, 32>), grid, dim3(256), lds, st, *d); \
-                               else hipLaunchKernelGGL((embed_tokens_kernel<LP, NCH, 8>), grid, dim3(256), lds, st, *d); } while (0)
-  if (d->D == 1024) {
-    if (d->h_dtype == MODE_BF16) MODE_EKF(true, 4); else MODE_EKF(false, 4);
-  } else {
-    if (d->h_dtype == MODE_BF16) MODE_EKF(true, 0); else MODE_EKF(false, 0);
-  }
-#undef MODE_EKF
+  dispatch([&](auto LP, auto NCH, auto AMAX) {                         // AMAX = 32: the instantiations for A_dim > 8
+    hipLaunchKernelGGL((embed_tokens_kernel<LP(), NCH(), AMAX()>), grid, dim3(256), lds, st, *d);
+  }, among<true, false>(d->h_dtype == MODE_BF16), among<4, 0>(d->D == 1024 ? 4 : 0), among<32, 8>(d->A_dim > 8 ? 32 : 8));
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }
-#undef MODE_EK_NC
-#undef MODE_EK
 
 namespace mode {
 // One workgroup per action row (the form of combine_norm_row_kernel): a thread owns 4 columns per 1024; every load of the row - residual, ln_2
@@ -805,14 +809,9 @@ __global__ __launch_bounds__(256) void head_ddim_row_kernel(const ModeHeadDesc h
 #pragma unroll
       for (int z = 0; z < YS; ++z) {
         const long off = (long)(z < h.y_splits ? z : 0) * h.y_split_stride + prow[j] + dc;
-        if constexpr (YBF) {
-          const uint2 r = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(h.Y) + off);
-          ys[j][z] = make_float4(bf16_bits_to_f32(r.x & 0xffff), bf16_bits_to_f32(r.x >> 16), bf16_bits_to_f32(r.y & 0xffff), bf16_bits_to_f32(r.y >> 16));
-        } else {
-          ys[j][z] = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(h.Y) + off);
-        }
+        ys[j][z] = load_y4<YBF>(h.Y, off);
       }
-    if constexpr (FUSED) uu = make_float4(uu.x * ru_nrm * gg.x, uu.y * ru_nrm * gg.y, uu.z * ru_nrm * gg.z, uu.w * ru_nrm * gg.w);
+    if constexpr (FUSED) uu = scale4(uu, ru_nrm, gg);
     float4 nx = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int j = 0; j < KK; ++j) {
@@ -839,7 +838,7 @@ __global__ __launch_bounds__(256) void head_ddim_row_kernel(const ModeHeadDesc h
   for (int j = 0; j < AMAX; ++j) accv[j] = 0.f;
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
-    const float4 n = make_float4(v[c].x * rnrm * gq[c].x, v[c].y * rnrm * gq[c].y, v[c].z * rnrm * gq[c].z, v[c].w * rnrm * gq[c].w);   // v = 0 past D
+    const float4 n = scale4(v[c], rnrm, gq[c]);   // v = 0 past D
 #pragma unroll
     for (int j = 0; j < AMAX; ++j) {
       float4 w;
@@ -922,18 +921,13 @@ __global__ __launch_bounds__(256) void head_ddim_guided_row_kernel(const ModeHea
 #pragma unroll
         for (int z = 0; z < YS; ++z) {
           const long off = (long)(z < h.y_splits ? z : 0) * h.y_split_stride + prow[r][j] + dc;
-          if constexpr (YBF) {
-            const uint2 q = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(h.Y) + off);
-            ys[r][j][z] = make_float4(bf16_bits_to_f32(q.x & 0xffff), bf16_bits_to_f32(q.x >> 16), bf16_bits_to_f32(q.y & 0xffff), bf16_bits_to_f32(q.y >> 16));
-          } else {
-            ys[r][j][z] = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(h.Y) + off);
-          }
+          ys[r][j][z] = load_y4<YBF>(h.Y, off);
         }
     }
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       float4 u4 = uu[r];
-      if constexpr (FUSED) u4 = make_float4(u4.x * ru_nrm[r] * gg.x, u4.y * ru_nrm[r] * gg.y, u4.z * ru_nrm[r] * gg.z, u4.w * ru_nrm[r] * gg.w);
+      if constexpr (FUSED) u4 = scale4(u4, ru_nrm[r], gg);
       float4 nx = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
       for (int j = 0; j < KK; ++j) {
@@ -969,7 +963,7 @@ __global__ __launch_bounds__(256) void head_ddim_guided_row_kernel(const ModeHea
     float4 n[2];
 #pragma unroll
     for (int r = 0; r < 2; ++r)                                     // v = 0 past D
-      n[r] = make_float4(v[r][c].x * rnrm[r] * gq[c].x, v[r][c].y * rnrm[r] * gq[c].y, v[r][c].z * rnrm[r] * gq[c].z, v[r][c].w * rnrm[r] * gq[c].w);
+      n[r] = scale4(v[r][c], rnrm[r], gq[c]);
 #pragma unroll
     for (int j = 0; j < AMAX; ++j) {
       float4 w;
@@ -1008,28 +1002,23 @@ static bool head_desc_complete(const ModeHeadDesc* d) {
 static bool head_row_kernel_takes(const ModeHeadDesc* d) {          // shapes of the one-workgroup-per-row head kernels
   return d->D <= 4096 && d->y_splits <= 8 && (d->k == 1 || d->k == 2) && d->A_dim >= 1;
 }
-// the head row kernels' instantiation ladder (K: head_ddim_row_kernel or its guided sibling, ...: the kernel's arguments); reads d, rows, wide, nc,
-// ys, ybf, fu, st
-#define MODE_HK(K, KK, F, YB, YS, NC, ...) do { if (wide) hipLaunchKernelGGL((K<KK, F, YB, YS, NC, 32>), dim3(rows), dim3(256), 0, st, __VA_ARGS__); \
-                                                else hipLaunchKernelGGL((K<KK, F, YB, YS, NC, 8>), dim3(rows), dim3(256), 0, st, __VA_ARGS__); } while (0)
-#define MODE_HK_NC(K, KK, F, YB, YS, ...) do { if (nc == 1) MODE_HK(K, KK, F, YB, YS, 1, __VA_ARGS__); else if (nc == 2) MODE_HK(K, KK, F, YB, YS, 2, __VA_ARGS__); else MODE_HK(K, KK, F, YB, YS, 4, __VA_ARGS__); } while (0)
-#define MODE_HK_YS(K, KK, F, YB, ...) do { if (ys == 1) MODE_HK_NC(K, KK, F, YB, 1, __VA_ARGS__); else if (ys == 2) MODE_HK_NC(K, KK, F, YB, 2, __VA_ARGS__); else if (ys == 4) MODE_HK_NC(K, KK, F, YB, 4, __VA_ARGS__); else MODE_HK_NC(K, KK, F, YB, 8, __VA_ARGS__); } while (0)
-#define MODE_HK_YB(K, KK, F, ...) do { if (ybf) MODE_HK_YS(K, KK, F, true, __VA_ARGS__); else MODE_HK_YS(K, KK, F, false, __VA_ARGS__); } while (0)
-#define MODE_HK_F(K, KK, ...) do { if (fu) MODE_HK_YB(K, KK, true, __VA_ARGS__); else MODE_HK_YB(K, KK, false, __VA_ARGS__); } while (0)
-#define MODE_HK_K(K, ...) do { \
-    const int nc = (d->D + 1023) / 1024, ys = d->y_splits <= 1 ? 1 : d->y_splits <= 2 ? 2 : d->y_splits <= 4 ? 4 : 8; \
-    const bool ybf = d->y_dtype == MODE_BF16, fu = d->u_ss != nullptr; \
-    if (d->k == 2) MODE_HK_F(K, 2, __VA_ARGS__); else MODE_HK_F(K, 1, __VA_ARGS__); } while (0)
+// call f with the head row kernels' template parameters <KK, FUSED, YBF, YS, NC, AMAX> for the shapes of d, as compile-time constants
+template <typename F>
+static void dispatch_head_row(const ModeHeadDesc* d, F&& f) {
+  dispatch(f, among<2, 1>(d->k), among<true, false>(d->u_ss != nullptr), among<true, false>(d->y_dtype == MODE_BF16),
+           among<1, 2, 4, 8>(d->y_splits <= 1 ? 1 : d->y_splits <= 2 ? 2 : d->y_splits <= 4 ? 4 : 8), among<1, 2, 4>((d->D + 1023) / 1024),
+           among<32, 8>(d->A_dim > 8 ? 32 : 8));
+}
 
 extern "C" int mode_head_ddim_guided_fwd(const ModeHeadGuidedDesc* gd, void* stream) {
   const ModeHeadDesc* d = gd ? &gd->head : nullptr;
   if (!head_desc_complete(d) || !gd->scale || !d->scal || d->F) return MODE_ERR_BAD_ARG;   // the raw output F has no guided form
   if ((d->D & 3) || d->A_dim > kMaxActionDim || !head_row_kernel_takes(d)) return MODE_ERR_UNSUPPORTED;   // pairs exist in the row kernel only
   const int rows = d->B * d->A_len;
-  const bool wide = d->A_dim > 8;
   if (rows == 0) return MODE_OK;
-  const hipStream_t st = (hipStream_t)stream;
-  MODE_HK_K(head_ddim_guided_row_kernel, *d, gd->scale);
+  dispatch_head_row(d, [&](auto KK, auto F, auto YB, auto YS, auto NC, auto AMAX) {
+    hipLaunchKernelGGL((head_ddim_guided_row_kernel<KK(), F(), YB(), YS(), NC(), AMAX()>), dim3(rows), dim3(256), 0, (hipStream_t)stream, *d, gd->scale);
+  });
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }
@@ -1038,28 +1027,23 @@ extern "C" int mode_head_ddim_fwd(const ModeHeadDesc* d, void* stream) {
   if (!head_desc_complete(d)) return MODE_ERR_BAD_ARG;
   if ((d->D & 3) || d->A_dim > kMaxActionDim) return MODE_ERR_UNSUPPORTED;
   const int rows = d->B * d->A_len;
-  const bool wide = d->A_dim > 8;                                     // AMAX = 32 instantiations
   if (rows == 0) return MODE_OK;
   if (head_row_kernel_takes(d)) {                                     // one workgroup per row
-    const hipStream_t st = (hipStream_t)stream;
-    MODE_HK_K(head_ddim_row_kernel, *d);
+    dispatch_head_row(d, [&](auto KK, auto F, auto YB, auto YS, auto NC, auto AMAX) {
+      hipLaunchKernelGGL((head_ddim_row_kernel<KK(), F(), YB(), YS(), NC(), AMAX()>), dim3(rows), dim3(256), 0, (hipStream_t)stream, *d);
+    });
     MODE_LAUNCH_CHECK();
     return MODE_OK;
   }
   const dim3 grid((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
   const size_t lds = (size_t)ROWS_PER_BLOCK * d->D * 4;
   const hipStream_t st = (hipStream_t)stream;
-  if (d->D == 1024) { if (wide) hipLaunchKernelGGL((head_ddim_kernel<4, 32>), grid, dim3(256), lds, st, *d); else hipLaunchKernelGGL((head_ddim_kernel<4, 8>), grid, dim3(256), lds, st, *d); }
-  else { if (wide) hipLaunchKernelGGL((head_ddim_kernel<0, 32>), grid, dim3(256), lds, st, *d); else hipLaunchKernelGGL((head_ddim_kernel<0, 8>), grid, dim3(256), lds, st, *d); }
+  dispatch([&](auto NCH, auto AMAX) {                                  // AMAX = 32: the instantiations for A_dim > 8
+    hipLaunchKernelGGL((head_ddim_kernel<NCH(), AMAX()>), grid, dim3(256), lds, st, *d);
+  }, among<4, 0>(d->D == 1024 ? 4 : 0), among<32, 8>(d->A_dim > 8 ? 32 : 8));
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }
-#undef MODE_HK_K
-#undef MODE_HK_F
-#undef MODE_HK_YB
-#undef MODE_HK_YS
-#undef MODE_HK_NC
-#undef MODE_HK
 
 extern "C" int mode_ddim_edm_step(const float* F, const float* x_a, const float* scal, int64_t scal_stride, int B, int per_sample,
                                   float* denoised, float* x_next, void* stream) {

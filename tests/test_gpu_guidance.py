@@ -141,7 +141,8 @@ def test_guided_embed_kernel(D, A_dim, lp, cond_stride):
 def test_guided_head_kernel(D, A_dim, ybf):
     """3 pairs, A_len = 3; k in {1, 2}, y_splits in {1, 4}, with / without fused-ln_2 partials, the den_prev and the lin update forms, per-pair and shared
     scalings.  Restatement in fp64; bound: fp32 rounding of D-term reductions (<= 1e-5 relative per branch) through the combine.  Also against the
-    combine of two unguided head launches (the twin on all 2B rows)."""
+    combine of two unguided head launches (the twin on all 2B rows), and each branch of the twin directly against its restatement at that
+    per-branch bound: the unguided head row kernel's own check."""
     lib, p, st = L.load(), H.p, H.stream()
     B, A_len, n_img, eps = 3, 3, 2, 1e-6
     T = 1 + 1 + n_img + A_len
@@ -195,6 +196,8 @@ def test_guided_head_kernel(D, A_dim, ybf):
                         tol = 1e-5 * (2.5 * nrm(dh[0]) + 1.5 * nrm(dh[1]))
                         assert nrm(f(den) - want) <= tol, (what, nrm(f(den) - want), tol)
                         assert nrm(f(den) - f(twin)) <= tol, what
+                        for hf, br in enumerate((both[:B], both[B:])):                    # the unguided head row kernel itself, per branch
+                            assert nrm(f(br) - dh[hf]) <= 1e-5 * nrm(dh[hf]), (what, hf, nrm(f(br) - dh[hf]), 1e-5 * nrm(dh[hf]))
                         if form == "den_prev":
                             dd = torch.where(s[..., 3] != 0, (1 + s[..., 3]) * want - s[..., 3] * f(den_prev), want)
                             xw = s[..., 2] * f(x_a) + (1 - s[..., 2]) * dd
