@@ -11,6 +11,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import gc
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -33,6 +34,12 @@ def _stream() -> int:
     if _raw_stream is not None:
         return _raw_stream(torch.cuda.current_device())
     return torch.cuda.current_stream().cuda_stream
+
+
+def graphs_enabled() -> bool:
+    """The hipGraph switch: MODE_HIP_GRAPH=0 sends every graphed path (denoiser, samplers, rollout chunks, perceptual encoders) down its step-by-step
+    launch chain.  Read at every call, so it can be flipped mid-process."""
+    return os.environ.get("MODE_HIP_GRAPH", "1") != "0"
 
 
 @contextlib.contextmanager
@@ -187,20 +194,16 @@ class DitEngine:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws.data_ptr(), self._ws.numel()
 
+    @contextlib.contextmanager
     def pinned_workspace(self, ws: torch.Tensor):
         """Context manager: every launch chain issued inside uses ``ws`` (a tensor the caller keeps alive next to its hipGraph) instead of
-        the engine's growable scratch buffer — a replay must not read a pointer that a later, larger request freed."""
-        eng = self
-
-        class _Pin:
-            def __enter__(self_inner):
-                self_inner.prev = eng._ws_pin
-                eng._ws_pin = ws
-
-            def __exit__(self_inner, *exc):
-                eng._ws_pin = self_inner.prev
-                return False
-        return _Pin()
+        the engine's growable scratch buffer — a replay must not read a pointer that a later, larger request freed.  Nests: leaving it, by an
+        exception too, restores the pin that was in force on entry."""
+        prev, self._ws_pin = self._ws_pin, ws
+        try:
+            yield
+        finally:
+            self._ws_pin = prev
 
     def meta_layout(self, N: int) -> L.ModeMetaLayout:
         ml = L.ModeMetaLayout()

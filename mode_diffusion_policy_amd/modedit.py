@@ -9,15 +9,42 @@ There is no CPU / eager fallback: calling ``forward`` without the library or off
 from __future__ import annotations
 
 import logging
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .engine import DitEngine, warm_and_capture
+from .engine import DitEngine, graphs_enabled, warm_and_capture
 
 logger = logging.getLogger(__name__)
+
+
+def _f32(t, dev):
+    """A call's tensor as the launch chain reads it: fp32, contiguous, on the engine's device (the tensor itself when it already is all that)."""
+    return t.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+
+def _edm_rows(s, sigma_data: float, next=None, ms=None):
+    """The rows the chain reads per noise level ``s`` [n] (score_wrappers.py:31-43): c_in [n] and scal [n, 4] = [c_skip, c_out, s'/s, ms] - ``next``: the
+    level each step goes to (DDIM's update, 0 without), ``ms``: the two-point multistep weight (``_dpmpp_2m_weights``, 0 without)."""
+    s2 = s * s + sigma_data ** 2
+    c_in = (1.0 / s2.sqrt()).contiguous()
+    return c_in, torch.stack([sigma_data ** 2 / s2, s * sigma_data / s2.sqrt(), torch.zeros_like(s) if next is None else next / s,
+                              torch.zeros_like(s) if ms is None else ms], 1).contiguous()
+
+
+class _Eval(NamedTuple):
+    """One denoiser evaluation of a captured chunk (``_chunk_steps``): ids into the chunk's [B, A_len, A_dim] buffers (None = not passed) and whether
+    the head applies the schedule's linear update ``sched["lin"][j]`` (two-stage solvers, ModeHeadDesc.lin) instead of DDIM's (scal[2], with scal[3]
+    weighing ``den_prev`` for two-point multistep solvers, ModeHeadDesc.den_prev).  No sigma, no coefficient: a list of these is a buffer PATTERN."""
+    x_in: int
+    x_out: int
+    den_out: Optional[int] = None
+    den_prev: Optional[int] = None
+    aux1: Optional[int] = None
+    aux2: Optional[int] = None
+    lin: bool = False
 
 
 class _Holder(nn.Module):
@@ -233,18 +260,11 @@ class MoDeDiT(nn.Module):
             from .training import dit_forward_train        # HIP forward with activation stash + HIP backward behind autograd
             return dit_forward_train(self, states, actions, goals, sigma, uncond)
         eng = self.engine
-        dev = eng.device
-        B = actions.shape[0]
+        dev, B = eng.device, actions.shape[0]
         if B == 0:                                                       # empty batch: empty prediction, no launches
             return torch.empty(0, self.action_seq_len, self.action_dim, dtype=torch.float32, device=dev)
-        f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        img, goals = self._prep_obs(eng, states, goals, uncond)
-        acts = f(actions)
-        self._check_batch(B, img, goals, acts)
-        sig = f(sigma).reshape(-1)
-        if sig.numel() not in (1, B):
-            raise ValueError("sigma must be a scalar or have one entry per sample")
-        emb_t = eng.sigma_embed(sig)
+        img, goals, acts = self._inputs(eng, states, actions, goals, uncond)
+        emb_t = eng.sigma_embed(self._sigma_rows(eng, sigma, B))
         img_e, goal_e = eng.embed_obs(img, goals)
         F = torch.empty(B, self.action_seq_len, self.action_dim, dtype=torch.float32, device=dev)
         self._routed_forward(eng, B, emb_t, goal_e, img_e, acts, F=F)
@@ -259,26 +279,24 @@ class MoDeDiT(nn.Module):
         ``guidance`` (the device scalar of ``_guidance``): B pairs run as 2B samples, the unconditional halves behind the conditional ones - per-sample
         conditioning rows are [emb_t + goal_e ; emb_t] (goal routing) or emb_t twice; routing, dispatch and the usage counters cover all 2B·T tokens."""
         D, T = self.embed_dim, self.seq_len
-        N = (B if guidance is None else 2 * B) * T
+        Bi = self._internal_batch(B, guidance is not None)
         cond = (emb_t.expand(B, D) + goal_e).contiguous() if self.use_goal_in_routing else emb_t
         if guidance is not None and (self.use_goal_in_routing or cond.shape[0] != 1):   # per-sample rows: the unconditional half has its own
             cond = torch.cat([cond, emb_t.expand(B, D)])
-        R = cond.shape[0]
+        R, N = cond.shape[0], Bi * T
         es, cs = 0 if emb_t.shape[0] == 1 else D, 0 if R == 1 else D
-        if not self.cond_router:
-            idx = torch.empty(self.num_layers, N, self.top_k, dtype=torch.int32, device=eng.device)
+        if self.cond_router:
+            idx, w, _, _ = eng.route(cond)
+            rec = self._last_meta = eng.dispatch(idx, w, self.num_layers, R, N if R == 1 else T, N)
+            ml = eng.meta_layout(N)
+            eng.forward(B, emb_t, es, cond, cs, rec.data_ptr(), ml.total_words, goal_e, img_e, x, uniform=R == 1, guidance=guidance, **head)
+        else:
+            ml, rec = None, torch.empty(self.num_layers, N, self.top_k, dtype=torch.int32, device=eng.device)
+            idx = rec                                                    # token routing: the call's record IS its decisions
             eng.forward(B, emb_t, es, cond, cs, None, 0, goal_e, img_e, x, topk_out=idx, guidance=guidance, **head)
-            self._last_topk = idx
-            if account:
-                self._account_token_usage(idx, N)
-            return
-        idx, w, _, _ = eng.route(cond)
-        meta = eng.dispatch(idx, w, self.num_layers, R, N if R == 1 else T, N)
-        ml = eng.meta_layout(N)
-        eng.forward(B, emb_t, es, cond, cs, meta.data_ptr(), ml.total_words, goal_e, img_e, x, uniform=R == 1, guidance=guidance, **head)
-        self._last_topk, self._last_meta = idx, meta
+        self._last_topk = idx
         if account:
-            self._account_usage(meta, ml, N)
+            self._account_calls(eng, [rec], Bi, ml)
 
     # ------------------------------------------------------------------ classifier-free guidance
     def _guidance(self, w):
@@ -307,13 +325,53 @@ class MoDeDiT(nn.Module):
         return t
 
     # ------------------------------------------------------------------ fused EDM forward / DDIM sampler
-    def _prep_obs(self, eng, states, goals, uncond=False):
-        f = lambda t: t.detach().to(device=eng.device, dtype=torch.float32).contiguous()
-        img = f(states["state_images"])
+    def _inputs(self, eng, states, action, goals, uncond=False):
+        """The input contract of every path: (state_images [B, n_img, obs_dim], goals [B, G], x [B, A_len, A_dim]) as ``_f32`` tensors, any other shape
+        refused (``_check_batch``).  ``states=None``: the caller holds these observations' embeddings already - only x is converted."""
+        x = _f32(action, eng.device)
+        if states is None:
+            return None, None, x
+        img = _f32(states["state_images"], eng.device)
         if img.dim() != 3 or img.shape[1] != self.n_img_tokens or img.shape[2] != self.obs_dim:
             raise ValueError(f"state_images must be (B, {self.n_img_tokens}, {self.obs_dim}), got {tuple(img.shape)}")
-        goals = f(self.preprocess_goals(goals, 1, uncond=bool(uncond)))
-        return img, goals.reshape(goals.shape[0], -1)                    # (B, 1, G) after preprocess_goals: a view, still contiguous
+        goals = _f32(self.preprocess_goals(goals, 1, uncond=bool(uncond)), eng.device)
+        goals = goals.reshape(goals.shape[0], -1)                        # (B, 1, G) after preprocess_goals: a view, still contiguous
+        self._check_batch(x.shape[0], img, goals, x)
+        return img, goals, x
+
+    @staticmethod
+    def _sigma_rows(eng, sigma, B: int):
+        """The noise levels of one call as a flat fp32 device vector: one for the whole batch, or one per sample."""
+        sig = _f32(sigma, eng.device).reshape(-1)
+        if sig.numel() not in (1, B):
+            raise ValueError("sigma must be a scalar or have one entry per sample")
+        return sig
+
+    @staticmethod
+    def _internal_batch(B: int, guided: bool) -> int:
+        """Rows the chain runs for B samples: under classifier-free guidance every sample is a (conditional, unconditional) pair."""
+        return 2 * B if guided else B
+
+    def _graph_key(self, eng, B: int, sigma_data: float, guided: bool):
+        """What every captured chain depends on besides its own schedule / sampler (arena pointers are static: weight updates keep graphs valid)."""
+        return (B, eng.compute_dtype, eng._structs_for, str(eng.device), float(sigma_data), self._routing_mode(), guided)
+
+    def _capture_entry(self, eng, cache: dict, key, capacity: int, img, goals, x, guided: bool, body, before=None, **extra) -> tuple:
+        """A new entry of a store of captured denoiser chains (``denoise_graphed``'s, ``ChunkedRolloutPolicy``'s): its own copies of the inputs, the
+        observation-embedding buffers, the workspace the graph owns and ``extra``; ``body(ent)`` is warmed up and captured into ``ent["graph"]`` on that
+        workspace, after ``before(ent)``.  Returns (entry, what the CAPTURED call of ``body`` returned: the tensors a replay writes).  A store at
+        ``capacity`` drops its oldest entry first (no hoarding)."""
+        if len(cache) >= capacity:
+            cache.pop(next(iter(cache)))
+        B, dev = x.shape[0], eng.device
+        ent = dict(img=img.clone(), goals=goals.clone(), x=x.clone(), img_e=torch.empty(B * self.n_img_tokens, self.embed_dim, device=dev),
+                   goal_e=torch.empty(B, self.embed_dim, device=dev), ws=self._chunk_ws(eng, self._internal_batch(B, guided), 1), **extra)
+        with eng.pinned_workspace(ent["ws"]):
+            if before is not None:
+                before(ent)
+            ent["graph"], out = warm_and_capture(lambda: body(ent), dev)
+        cache[key] = ent
+        return ent, out
 
     @torch.no_grad()
     def denoise(self, states, action, goals, sigma, sigma_data: float, _account: bool = True, _obs_emb=None, guidance=None):
@@ -324,19 +382,11 @@ class MoDeDiT(nn.Module):
         eng = self.engine
         dev, B = eng.device, action.shape[0]
         if B == 0:
-            return action.detach().to(device=dev, dtype=torch.float32).clone()
-        x = action.detach().to(device=dev, dtype=torch.float32).contiguous()
-        if _obs_emb is None:
-            img, goals = self._prep_obs(eng, states, goals)
-            self._check_batch(B, img, goals, x)
-        sig = sigma.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        if sig.numel() not in (1, B):
-            raise ValueError("sigma must be a scalar or have one entry per sample")
-        R = sig.numel()
-        s2 = sig * sig + sigma_data ** 2
-        c_in = (1.0 / s2.sqrt()).contiguous()
-        scal = torch.stack([sigma_data ** 2 / s2, sig * sigma_data / s2.sqrt(), torch.zeros_like(sig), torch.zeros_like(sig)], 1).contiguous()
-        emb_t = eng.sigma_embed(sig)
+            return _f32(action, dev).clone()
+        img, goals, x = self._inputs(eng, states if _obs_emb is None else None, action, goals)
+        sig = self._sigma_rows(eng, sigma, B)
+        c_in, scal = _edm_rows(sig, sigma_data)
+        R, emb_t = sig.numel(), eng.sigma_embed(sig)
         img_e, goal_e = _obs_emb if _obs_emb is not None else eng.embed_obs(img, goals)
         den = torch.empty_like(x)
         self._routed_forward(eng, B, emb_t, goal_e, img_e, x, account=_account, guidance=guidance, c_in=c_in, c_in_stride=0 if R == 1 else 1,
@@ -351,17 +401,14 @@ class MoDeDiT(nn.Module):
         - no per-step host work beyond three small input copies.  Goal routing: the graph also forms cond = emb + goal_emb(goal) and routes
         and dispatches those B rows; token routing: the forward routes every token itself.  Returns None with MODE_HIP_GRAPH=0.
         ``guidance``: as for ``denoise``; guided and unguided graphs are separate cache entries, the scale's value is in no key."""
-        import os
         guidance = self._guidance(guidance)
         eng = self.engine
         dev, B = eng.device, action.shape[0]
-        if B == 0 or os.environ.get("MODE_HIP_GRAPH", "1") == "0":
+        if B == 0 or not graphs_enabled():
             return None
-        x = action.detach().to(device=dev, dtype=torch.float32).contiguous()
         sig = torch.as_tensor(sigma, dtype=torch.float32).detach().reshape(-1)[:1]
         guided = guidance is not None
-        Bi = 2 * B if guided else B                                      # the chain's internal batch
-        key = (B, eng.compute_dtype, eng._structs_for, str(dev), float(sigma_data), self._routing_mode(), guided)
+        key = self._graph_key(eng, B, sigma_data, guided)
         cache = self._route_cache.setdefault("denoise_graphs", {})
         ent = cache.get(key)
         # The observations are the same tensors for every denoiser call of a sampler run (gc_sampling.py's loops pass `state` / `goal` through
@@ -370,42 +417,28 @@ class MoDeDiT(nn.Module):
         src = (states["state_images"], goals)
         okey = (src[0]._version, src[1]._version, eng._wkey)
         fresh = ent is None or ent.get("obs_ref") is None or ent["obs_ref"][0] is not src[0] or ent["obs_ref"][1] is not src[1] or ent["obs_key"] != okey
-        if fresh:
-            img, gl = self._prep_obs(eng, states, goals)
-            self._check_batch(B, img, gl, x)
-        elif x.shape != ent["x"].shape:
+        img, gl, x = self._inputs(eng, states if fresh else None, action, goals)
+        if not fresh and x.shape != ent["x"].shape:
             raise ValueError(f"action must be {tuple(ent['x'].shape)}, got {tuple(x.shape)}")
+        # embedded OUTSIDE the graph, and ahead of its warm-up: routing on uninitialised memory can yield out-of-range expert ids
+        embed = lambda e: eng.embed_obs(e["img"], e["goals"], out=(e["img_e"], e["goal_e"]))
         if ent is None:
-            if len(cache) >= 8:                                          # a handful of batch sizes is the use case; do not hoard graphs
-                cache.pop(next(iter(cache)))
-            ent = dict(img=img.clone(), goals=gl.clone(), x=x.clone(), sig=torch.empty(1, device=dev),
-                       img_e=torch.empty(B * self.n_img_tokens, self.embed_dim, device=dev), goal_e=torch.empty(B, self.embed_dim, device=dev))
-            ent["sig"].copy_(sig)
-            ent["ws"] = self._chunk_ws(eng, Bi, 1)
-
-            def run():
-                out = self.denoise(None, ent["x"], None, ent["sig"], sigma_data, _account=False, _obs_emb=(ent["img_e"], ent["goal_e"]), guidance=guidance)
+            def run(e):
+                out = self.denoise(None, e["x"], None, e["sig"], sigma_data, _account=False, _obs_emb=(e["img_e"], e["goal_e"]), guidance=guidance)
                 return out, self._last_topk, self._last_meta if self.cond_router else None
-            with eng.pinned_workspace(ent["ws"]):
-                # the warm-up and the capture route on these embeddings: routing on uninitialised memory can yield out-of-range expert ids
-                eng.embed_obs(ent["img"], ent["goals"], out=(ent["img_e"], ent["goal_e"]))
-                ent["graph"], (ent["out"], ent["topk"], ent["meta"]) = warm_and_capture(run, dev)
-            cache[key] = ent
+            ent, res = self._capture_entry(eng, cache, key, 8, img, gl, x, guided, run, before=embed, sig=sig.to(dev, copy=True))
+            ent["out"], ent["topk"], ent["meta"] = res
         if fresh:
             ent["img"].copy_(img); ent["goals"].copy_(gl)
-            eng.embed_obs(ent["img"], ent["goals"], out=(ent["img_e"], ent["goal_e"]))
+            embed(ent)
             # (a Bernoulli goal mask - training mode with goal_drop > 0 - must be redrawn per call: no reuse then)
             keep = not (self.training and getattr(self, "goal_drop", 0.0) > 0)
             ent["obs_ref"], ent["obs_key"] = (src if keep else None), okey
         ent["x"].copy_(x); ent["sig"].copy_(sig, non_blocking=True)
         ent["graph"].replay()
-        if not self.cond_router:
+        if self._routes_per_chunk():
             self._last_topk = ent["topk"]
-            self._account_token_usage(ent["topk"], Bi * self.seq_len)
-        else:
-            if self.use_goal_in_routing:
-                self._last_topk = ent["topk"]
-            self._account_usage(ent["meta"], eng.meta_layout(Bi * self.seq_len), Bi * self.seq_len)
+        self._account_calls(eng, [ent["meta"] if self.cond_router else ent["topk"]], self._internal_batch(B, guided))
         return ent["out"].clone()
 
     def _schedule_state(self, eng, sig, B, sigma_data: float, out=None, solver: str = "ddim", lin=None):
@@ -416,47 +449,36 @@ class MoDeDiT(nn.Module):
         CONSUMED here - no router launch at all; otherwise the fp32 router runs on the device.  With ``out`` the results are written in place
         (the graph has the pointers baked in).  ``B`` is the chain's internal batch (twice the samples under guidance): the dispatch records are for B·T tokens."""
         T, Ly = self.seq_len, self.num_layers
-        if lin is not None:
-            # two-stage solvers (sample_two_stage_fused): `sig` lists the sigma of EVERY denoiser evaluation, `lin` [n, 4] the linear update of each
-            n = sig.numel()
-            s, nxt = sig.contiguous(), torch.zeros_like(sig)
-        else:
-            n = sig.numel() - 1
-            s, nxt = sig[:-1].contiguous(), sig[1:]
-        s2 = s * s + sigma_data ** 2
-        ms = self._dpmpp_2m_weights(sig) if (solver == "dpmpp_2m" and lin is None) else torch.zeros_like(s)
-        st = dict(c_in=(1.0 / s2.sqrt()).contiguous(),
-                  scal=torch.stack([sigma_data ** 2 / s2, s * sigma_data / s2.sqrt(), nxt / s, ms], 1).contiguous(),
-                  emb_all=eng.sigma_embed(s))                            # [n, D]: one conditioning row per step
-        if self._routes_per_chunk():
-            # goal / token routing depends on the observations: it is resolved inside the captured chunk (_chunk_routing), not here - and a
-            # routing cache filled by precompute_experts_for_inference for ONE goal never stands in for the others
-            if lin is not None:
-                st["lin"] = lin.to(device=eng.device, dtype=torch.float32).contiguous()
-            if out is None:
-                return st
-            for k_ in st:
-                out[k_].copy_(st[k_])
-            return out
-        cached = None
-        if all(blk.fused_experts for blk in self.blocks) and getattr(self, "_fused_for", None) == eng._wkey:
-            keys = [float(v) for v in s.tolist()]                        # (host sync: only when the schedule state is (re)built)
-            if all(k_ in blk.fused_experts for blk in self.blocks for k_ in keys):
-                cached = keys
-        if cached is not None:
-            idx = torch.tensor([[blk.fused_experts[k_][0] for k_ in cached] for blk in self.blocks], dtype=torch.int32, device=eng.device)
-            w = torch.tensor([[blk.fused_experts[k_][1] for k_ in cached] for blk in self.blocks], dtype=torch.float32, device=eng.device)
-        else:
-            idx, w, _, _ = eng.route(st["emb_all"])                      # [L, n, k]: routing for ALL steps up front
-        N = B * T
-        st.update(idx=idx.contiguous(), w=w.contiguous(), meta=eng.dispatch(idx.contiguous(), w.contiguous(), Ly * n, 1, N, N), from_cache=cached is not None)
+        # two-stage solvers (sample_two_stage_fused): `sig` lists the sigma of EVERY denoiser evaluation, `lin` [n, 4] the linear update of each
+        s, nxt = (sig.contiguous(), torch.zeros_like(sig)) if lin is not None else (sig[:-1].contiguous(), sig[1:])
+        n = s.numel()
+        ms = self._dpmpp_2m_weights(sig) if (solver == "dpmpp_2m" and lin is None) else None
+        c_in, scal = _edm_rows(s, sigma_data, nxt, ms)
+        st = dict(c_in=c_in, scal=scal, emb_all=eng.sigma_embed(s))      # emb_all [n, D]: one conditioning row per step
         if lin is not None:
             st["lin"] = lin.to(device=eng.device, dtype=torch.float32).contiguous()
+        # goal / token routing depends on the observations: it is resolved inside the captured chunk (_chunk_routing), not here - and a
+        # routing cache filled by precompute_experts_for_inference for ONE goal never stands in for the others
+        if not self._routes_per_chunk():
+            cached = None
+            if all(blk.fused_experts for blk in self.blocks) and getattr(self, "_fused_for", None) == eng._wkey:
+                keys = [float(v) for v in s.tolist()]                    # (host sync: only when the schedule state is (re)built)
+                if all(k_ in blk.fused_experts for blk in self.blocks for k_ in keys):
+                    cached = keys
+            if cached is not None:
+                idx = torch.tensor([[blk.fused_experts[k_][0] for k_ in cached] for blk in self.blocks], dtype=torch.int32, device=eng.device)
+                w = torch.tensor([[blk.fused_experts[k_][1] for k_ in cached] for blk in self.blocks], dtype=torch.float32, device=eng.device)
+            else:
+                idx, w, _, _ = eng.route(st["emb_all"])                  # [L, n, k]: routing for ALL steps up front
+            N = B * T
+            st.update(idx=idx.contiguous(), w=w.contiguous(), meta=eng.dispatch(idx.contiguous(), w.contiguous(), Ly * n, 1, N, N), from_cache=cached is not None)
         if out is None:
             return st
-        for k_ in ("c_in", "scal", "emb_all", "idx", "w", "meta") + (("lin",) if lin is not None else ()):
-            out[k_].copy_(st[k_])
-        out["from_cache"] = st["from_cache"]
+        for k_, v in st.items():                                         # device tensors in place (the graph reads them); from_cache is a host value
+            if k_ == "from_cache":
+                out[k_] = v
+            else:
+                out[k_].copy_(v)
         return out
 
     @staticmethod
@@ -515,25 +537,23 @@ class MoDeDiT(nn.Module):
 
     def _chunk_steps(self, eng, img, goals, bufs, sched, evals, tok=None, guidance=None):
         """The observation-dependent launch chain of a fused sampler run: embeddings of the observations (+ the routing of goal-routed models)
-        + one denoiser forward per entry of ``evals``; pure launches, no host sync -> capturable.  Reads the schedule state by pointer.
-        An entry is (x_in, x_out, denoised, den_prev, aux1, aux2, lin): ids into the [B, A_len, A_dim] buffers ``bufs`` (None = not passed) and
-        whether the head applies the schedule's linear update ``sched["lin"][j]`` (two-stage solvers, ModeHeadDesc.lin) instead of DDIM's
-        (scal[2], with scal[3] weighing ``den_prev`` for two-point multistep solvers, ModeHeadDesc.den_prev).  Returns the meta layout and
-        the chunk's routing output {idx, meta} (``_chunk_routing``).  ``guidance`` (device scalar): every forward is the guided one - the buffers
-        and the observation embeddings keep B rows, routing and the forwards' interior have 2B."""
+        + one denoiser forward per entry of ``evals`` (``_Eval`` records over the buffers ``bufs``); pure launches, no host sync -> capturable.
+        Reads the schedule state by pointer.  Returns the meta layout and the chunk's routing output {idx, meta} (``_chunk_routing``).  ``guidance``
+        (device scalar): every forward is the guided one - the buffers and the observation embeddings keep B rows, routing and the forwards' interior have 2B."""
         B, T = bufs[0].shape[0], self.seq_len
-        Bi = B if guidance is None else 2 * B
+        Bi = self._internal_batch(B, guidance is not None)
         img_e, goal_e = eng.embed_obs(img, goals)                        # step-invariant, hoisted (modedit.py:760,765)
         ml = eng.meta_layout(Bi * T)
         emb_all, c_in, scal = sched["emb_all"], sched["c_in"], sched["scal"]
         at, idx, meta = self._chunk_routing(eng, sched, goal_e, len(evals), Bi, ml, tok, guided=guidance is not None)
         buf = lambda i: None if i is None else bufs[i]
-        for j, (xin, xout, dout, dprev, a1, a2, lin) in enumerate(evals):
+        for j, ev in enumerate(evals):
             r = at(j)
-            eng.forward(B, emb_all[j], 0, r["cond"], r["cond_stride"], r["meta_ptr"], r["meta_stride"], goal_e, img_e, bufs[xin],
-                        c_in=c_in.data_ptr() + 4 * j, c_in_stride=0, scal_ptr=scal.data_ptr() + 16 * j, scal_stride=0, x_next=bufs[xout],
-                        uniform=r["uniform"], denoised=buf(dout), den_prev=buf(dprev), lin_ptr=sched["lin"].data_ptr() + 16 * j if lin else None,
-                        aux1=buf(a1), aux2=buf(a2), topk_out=r["topk_out"], guidance=guidance)
+            eng.forward(B, emb_all[j], 0, r["cond"], r["cond_stride"], r["meta_ptr"], r["meta_stride"], goal_e, img_e, bufs[ev.x_in],
+                        c_in=c_in.data_ptr() + 4 * j, c_in_stride=0, scal_ptr=scal.data_ptr() + 16 * j, scal_stride=0, x_next=bufs[ev.x_out],
+                        uniform=r["uniform"], denoised=buf(ev.den_out), den_prev=buf(ev.den_prev),
+                        lin_ptr=sched["lin"].data_ptr() + 16 * j if ev.lin else None, aux1=buf(ev.aux1), aux2=buf(ev.aux2), topk_out=r["topk_out"],
+                        guidance=guidance)
         return ml, dict(idx=idx, meta=meta)
 
     @staticmethod
@@ -541,7 +561,7 @@ class MoDeDiT(nn.Module):
         """``_chunk_steps`` entries of an n-step DDIM run: the state (buffer 0) is updated in place.  ``multistep`` (DPM-Solver++(2M)): the head
         also writes each step's denoised prediction to buffer 1 / 2 alternately and reads the previous step's from the other one."""
         den = lambda s: 1 + (s & 1) if multistep and s >= 0 else None
-        return [(0, 0, den(s), den(s - 1), None, None, False) for s in range(n)]
+        return [_Eval(x_in=0, x_out=0, den_out=den(s), den_prev=den(s - 1)) for s in range(n)]
 
     # ---- two-stage solvers on the fused chain (Heun, DPM-Solver-2, DPM-Solver++(2S)) -------------------------------------------------------
     @staticmethod
@@ -587,11 +607,10 @@ class MoDeDiT(nn.Module):
         every stage of these solvers is linear in (stage input, its prediction, the step's state, the first stage's prediction), which the head kernel
         applies (ModeHeadDesc.lin).  The schedule-dependent part - which sigma every evaluation sees, the coefficients, embeddings, routing - is a
         plan rebuilt only when the schedule values, the weights or the batch size change.  None when the fast path does not apply."""
-        import os
         assert solver in ("heun", "dpm_2", "dpmpp_2s"), solver
         guidance = self._guidance(guidance)
         eng = self.engine
-        if action.shape[0] == 0 or os.environ.get("MODE_HIP_GRAPH", "1") == "0" or sigmas.numel() < 2:
+        if action.shape[0] == 0 or not graphs_enabled() or sigmas.numel() < 2:
             return None
         return self._sample_chunk(eng, *self._chunk_plan(eng, solver, sigmas.numel() - 1, guidance is not None), states, action, goals, sigmas, sigma_data,
                                   guidance=guidance)
@@ -607,7 +626,7 @@ class MoDeDiT(nn.Module):
 
         def plan(sig):
             p = self._two_stage_plan(solver, [float(v) for v in sig.tolist()])          # (host sync: only when the schedule changed)
-            evals = [(xin, xout, dout, None, a1, a2, True) for _, xin, xout, _, a1, a2, dout in p]
+            evals = [_Eval(x_in=xin, x_out=xout, den_out=dout, aux1=a1, aux2=a2, lin=True) for _, xin, xout, _, a1, a2, dout in p]
             ev = torch.tensor([e[0] for e in p], dtype=torch.float32, device=eng.device)
             return evals, ev, dict(lin=torch.tensor([e[3] for e in p], dtype=torch.float32))
         return "graph:" + solver + cfg, plan
@@ -620,20 +639,17 @@ class MoDeDiT(nn.Module):
         ``solver="dpmpp_2m"``: sample_dpmpp_2m (gc_sampling.py:700-734) on the same chain - its step is DDIM's exponential-integrator step applied to a
         two-point extrapolation of the denoised prediction, which the head kernel forms from the previous step's prediction (ModeHeadDesc.den_prev)."""
         assert solver in ("ddim", "dpmpp_2m"), solver
-        import os
         guidance = self._guidance(guidance)
         eng = self.engine
         dev, B = eng.device, action.shape[0]
         if B == 0:                                                       # empty batch: nothing to denoise
-            return action.detach().to(device=dev, dtype=torch.float32).clone()
+            return _f32(action, dev).clone()
         n, multi = sigmas.numel() - 1, solver != "ddim"
-        if os.environ.get("MODE_HIP_GRAPH", "1") != "0":               # one captured chain per solver; its buffer pattern is fixed by n
+        if graphs_enabled():                                             # one captured chain per solver; its buffer pattern is fixed by n
             return self._sample_chunk(eng, *self._chunk_plan(eng, solver, n, guidance is not None), states, action, goals, sigmas, sigma_data,
                                       guidance=guidance)
-        img, goals = self._prep_obs(eng, states, goals)
-        sig = sigmas.detach().to(device=dev, dtype=torch.float32).contiguous()
-        x0 = action.detach().to(device=dev, dtype=torch.float32)
-        self._check_batch(B, img, goals, x0)
+        img, goals, x0 = self._inputs(eng, states, action, goals)
+        sig = _f32(sigmas, dev)
         if self._routes_per_chunk():                                    # goal / token routing without graphs: the per-step generic path
             x = x0.clone()
             prev = None
@@ -648,7 +664,7 @@ class MoDeDiT(nn.Module):
                 prev = den
             return x
         bufs = [x0.clone(memory_format=torch.contiguous_format)] + [torch.empty(x0.shape, dtype=torch.float32, device=dev) for _ in range(2)]
-        sched = self._schedule_state(eng, sig, B if guidance is None else 2 * B, sigma_data, solver=solver)
+        sched = self._schedule_state(eng, sig, self._internal_batch(B, guidance is not None), sigma_data, solver=solver)
         self._account_chunk(dict(sched=sched), self._chunk_steps(eng, img, goals, bufs, sched, self._ddim_evals(n, multi), guidance=guidance)[0], n, B,
                             guided=guidance is not None)
         return bufs[0]
@@ -668,12 +684,10 @@ class MoDeDiT(nn.Module):
         guidance = self._guidance(guidance)
         guided = guidance is not None
         dev, B = eng.device, action.shape[0]
-        Bi = 2 * B if guided else B
-        img, goals = self._prep_obs(eng, states, goals)
-        sig = sigmas.detach().to(device=dev, dtype=torch.float32).contiguous()
-        x0 = action.detach().to(device=dev, dtype=torch.float32)
-        self._check_batch(B, img, goals, x0)
-        key = (B, sig.numel(), eng.compute_dtype, eng._structs_for, str(dev), float(sigma_data), self._routing_mode(), guided)   # arena pointers are static: weight updates keep graphs valid
+        Bi = self._internal_batch(B, guided)
+        img, goals, x0 = self._inputs(eng, states, action, goals)
+        sig = _f32(sigmas, dev)
+        key = (sig.numel(),) + self._graph_key(eng, B, sigma_data, guided)
         # identity of the schedule: a host-side tag of its VALUES when the tensor came from a get_sigmas_* / get_noise_schedule generator (the
         # agent builds a fresh tensor per chunk, mode_agent.py:752) - else the caller's tensor OBJECT (kept alive below, so neither its id nor its
         # storage can be recycled while the key is live) -, the weights, and the routing cache generation.  No device read on either path.
@@ -752,9 +766,8 @@ class MoDeDiT(nn.Module):
         sample's T tokens); noise-level routing sends every sample to the same experts, so the counts scale by rows / B exactly.  ``guided``: the
         chain ran 2B samples, the unconditional halves behind the conditional ones; both halves' tokens are tokens processed and are counted (the
         first ``rows`` samples OF EACH HALF when padded)."""
-        T = self.seq_len
-        halves = 2 if guided else 1
-        N, r = halves * B * T, B if rows is None else rows
+        T, halves = self.seq_len, 2 if guided else 1
+        N, r = self._internal_batch(B, guided) * T, B if rows is None else rows
         real = lambda t, per: t if r == B else torch.cat([t[:, :, h * B * per: (h * B + r) * per] for h in range(halves)], 2)   # the real rows of [L, n, halves·B·per, k]
         if ent.get("tok") is not None:
             self._last_topk = ent["tok"].transpose(0, 1)                 # [L, n, N, k]
@@ -769,6 +782,16 @@ class MoDeDiT(nn.Module):
             self._last_topk = ent["sched"]["idx"]
             self._account_usage(ent["sched"]["meta"], ml, N, n, rows=None if r == B else (r, B))
 
+    def _account_calls(self, eng, recs, Bi: int, ml=None) -> None:
+        """The expert-usage counters after ``len(recs)`` denoiser calls at internal batch ``Bi``.  ``recs``: per call its dispatch records [L, words], or
+        under token routing its decisions [L, Bi·T, k] - ONE histogram of them all.  ``ml``: the records' layout, when the caller has it at hand."""
+        N, calls = Bi * self.seq_len, len(recs)
+        rec = recs[0] if calls == 1 else torch.stack(recs, 1)            # [L, calls, ...]
+        if not self.cond_router:
+            self._account_token_usage(rec, N * calls)
+        else:
+            self._account_usage(rec, eng.meta_layout(N) if ml is None else ml, N, calls)
+
     def _add_usage(self, counts, n_tokens: int) -> None:
         """Expert-usage counters (modedit.py:568-572, 594): ``counts`` [L, E] added on the device - no host sync on the hot path - and
         ``n_tokens`` to every block's token count."""
@@ -779,9 +802,9 @@ class MoDeDiT(nn.Module):
             blk.total_tokens_processed += n_tokens
 
     def _account_usage(self, meta, ml, n_tokens: int, n: int = 1, rows=None) -> None:
-        """Usage counters from dispatch records: ``meta`` [L·n, words], n forwards of n_tokens tokens each per layer (layer-major).  ``rows`` =
-        (r, B): count r of the records' B samples (records of one routing row for the whole batch: every count is a multiple of B)."""
-        counts = meta[:, ml.counts: ml.counts + self.num_experts]
+        """Usage counters from dispatch records: ``meta`` [L·n, words] or [L, n, words], n forwards of n_tokens tokens each per layer (layer-major).
+        ``rows`` = (r, B): count r of the records' B samples (records of one routing row for the whole batch: every count is a multiple of B)."""
+        counts = meta[..., ml.counts: ml.counts + self.num_experts]
         counts = counts if n == 1 else counts.reshape(self.num_layers, n, -1).sum(1)
         if rows is not None:
             counts, n_tokens = counts.long() * rows[0] // rows[1], n_tokens * rows[0] // rows[1]
@@ -792,6 +815,7 @@ class MoDeDiT(nn.Module):
         Ly, E = self.num_layers, self.num_experts
         self._add_usage(torch.zeros(Ly, E, dtype=torch.int64, device=idx.device).scatter_add_(
             1, idx.reshape(Ly, -1).long(), torch.full((Ly, idx[0].numel()), weight, dtype=torch.int64, device=idx.device)), n_tokens)
+
     def sync_expert_usage(self):
         """Fold the device-side counters into the per-block host tensors the agent's heat-map reads (mode_agent.py:466-511)."""
         if getattr(self, "_usage_dev", None) is not None:

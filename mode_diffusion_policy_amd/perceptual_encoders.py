@@ -34,7 +34,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib as L
-from .engine import _ptr, _stream
+from .engine import _ptr, _stream, graphs_enabled
 
 
 # ------------------------------------------------------------------------------------------------------------------ fused op
@@ -1139,8 +1139,7 @@ class GraphedVisualEncoder:
 
     @torch.no_grad()
     def __call__(self, rgb_static: torch.Tensor, rgb_gripper: torch.Tensor, latent_goal: Optional[torch.Tensor] = None):
-        import os
-        if self.static_resnet.training or self.gripper_resnet.training or rgb_static.device.type != "cuda" or os.environ.get("MODE_HIP_GRAPH", "1") == "0":
+        if self.static_resnet.training or self.gripper_resnet.training or rgb_static.device.type != "cuda" or not graphs_enabled():
             return {"state_images": self._eager(rgb_static, rgb_gripper, latent_goal)}       # batch statistics / no device: nothing to replay
         wdt = self.autocast_dtype if self.autocast_dtype is not None else rgb_static.dtype
         key = (tuple(rgb_static.shape), rgb_static.dtype, tuple(rgb_gripper.shape), rgb_gripper.dtype,

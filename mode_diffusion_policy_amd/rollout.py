@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import gc_sampling as gs
+from .engine import graphs_enabled
 
 
 def get_noise_schedule(n_sampling_steps: int, noise_schedule_type: str, sigma_min: float, sigma_max: float, device="cpu") -> torch.Tensor:
@@ -156,51 +157,35 @@ class ChunkedRolloutPolicy:
         of the chunk routes its own samples / tokens inside the graph.  None = not applicable (training mode, MODE_HIP_GRAPH=0): the caller takes the
         step-by-step path."""
         from . import samplers as S
-        from .engine import warm_and_capture
         from .modedit import MoDeDiT
         den = self.model
         inner = getattr(den, "inner_model", None)
-        if not isinstance(inner, MoDeDiT) or inner.training or len(x) == 0 or os.environ.get("MODE_HIP_GRAPH", "1") == "0":
+        if not isinstance(inner, MoDeDiT) or inner.training or len(x) == 0 or not graphs_enabled():
             return None
         guidance = inner._guidance(getattr(den, "guidance_scale", None))   # classifier-free guidance: the device scalar every denoiser call of the chunk reads
         eng = inner.engine
-        dev, B = eng.device, x.shape[0]
-        Bi = B if guidance is None else 2 * B                             # the denoiser calls' internal batch
-        img, gl = inner._prep_obs(eng, perceptual_emb, latent_goal)
-        inner._check_batch(B, img, gl, x)
+        img, gl, x = inner._inputs(eng, perceptual_emb, x, latent_goal)
+        B, guided = x.shape[0], guidance is not None
         cache = self.__dict__.setdefault("_chunk_graphs", {})
-        key = (self.sampler_type, B, eng.compute_dtype, eng._structs_for, str(dev), id(sigmas), sigmas._version, float(den.sigma_data),
-               inner._routing_mode(), guidance is not None)
+        key = (self.sampler_type, id(sigmas), sigmas._version) + inner._graph_key(eng, B, den.sigma_data, guided)
         ent = cache.get(key)
         if ent is None:
-            if len(cache) >= 4:
-                cache.pop(next(iter(cache)))
-            ent = dict(x=x.clone(), img=img.clone(), goals=gl.clone(), sig=sigmas,
-                       img_e=torch.empty(B * inner.n_img_tokens, inner.embed_dim, device=dev), goal_e=torch.empty(B, inner.embed_dim, device=dev))
-            ent["ws"] = inner._chunk_ws(eng, Bi, 1)
-            state = {"state_images": ent["img"].view(B, inner.n_img_tokens, -1)}
-            goal3 = ent["goals"].view(B, 1, -1)
-
-            def chunk():
+            def chunk(ent):                                                  # the observations are embedded INSIDE the graph, once per replay
+                state, goal3 = {"state_images": ent["img"].view(B, inner.n_img_tokens, -1)}, ent["goals"].view(B, 1, -1)
                 eng.embed_obs(ent["img"], ent["goals"], out=(ent["img_e"], ent["goal_e"]))
                 cc = dict(inner=inner, sigma_data=float(den.sigma_data), obs_emb=(ent["img_e"], ent["goal_e"]), metas=[], guidance=guidance)
                 S._set_chunk_capture(cc)
                 try:
-                    out = sample_loop(den, sigmas, ent["x"], state, goal3, self.sampler_type, None)
-                    return out, cc["metas"]
+                    return sample_loop(den, sigmas, ent["x"], state, goal3, self.sampler_type, None), cc["metas"]
                 finally:
                     S._set_chunk_capture(None)
-            with eng.pinned_workspace(ent["ws"]):                            # (the warm-up also does the schedule's host-side reads)
-                ent["graph"], (ent["out"], ent["metas"]) = warm_and_capture(chunk, dev)
-            cache[key] = ent
+            # (the warm-up also does the schedule's host-side reads)
+            ent, res = inner._capture_entry(eng, cache, key, 4, img, gl, x, guided, chunk, sig=sigmas)
+            ent["out"], ent["metas"] = res
         ent["x"].copy_(x); ent["img"].copy_(img); ent["goals"].copy_(gl)
         ent["graph"].replay()
-        # expert-usage counters of every denoiser call, as the step-by-step path keeps them: [L, calls, ...]
-        N, calls, rec = Bi * inner.seq_len, len(ent["metas"]), torch.stack(ent["metas"], 1)
-        if not inner.cond_router:
-            inner._account_token_usage(rec, N * calls)                        # token routing: one histogram of every call's decisions
-        else:
-            inner._account_usage(rec.flatten(0, 1), eng.meta_layout(N), N, calls)
+        # expert-usage counters of every denoiser call, as the step-by-step path keeps them
+        inner._account_calls(eng, ent["metas"], inner._internal_batch(B, guided))
         return ent["out"].clone()
 
     @torch.no_grad()
@@ -589,7 +574,7 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
                                             bufs=tuple(torch.empty(mb, *f.shape[1:], dtype=dt, device=f.device) for f, dt in zip(frames, dts)))
         self._gather_frames(mb, frames, st["bufs"])
         goals = ent["goals"]
-        if enc.static_resnet.training or enc.gripper_resnet.training or os.environ.get("MODE_HIP_GRAPH", "1") == "0":
+        if enc.static_resnet.training or enc.gripper_resnet.training or not graphs_enabled():
             ent["img"].copy_(enc._eager(st["bufs"][0], st["bufs"][1], goals).view(mb, n_img, -1))
             return
         wdt = enc.autocast_dtype if enc.autocast_dtype is not None else dts[0]

@@ -192,6 +192,20 @@ class _Run:
         return x if self.scaler is None else self.scaler.clip_output(x)
 
 
+def _fused_route(model, method: str, state, action, goal, sigmas, *extra, draws: bool):
+    """The fused route of a deterministic sampler: ``GCDenoiser.<method>(state, action, goal, sigmas, *extra)`` - the whole call as one hipGraph replay -, or None when the model
+    has none, it does not apply, or this call is itself being captured into a chunk (``_chunk_capture``).  ``draws``: the reference draws
+    ``eps = randn_like(action)`` on EVERY step of this sampler, churn or not (gc_sampling.py:196), and so does its step loop here: the fused route
+    makes the same draws and discards them, so the generator leaves the call in the state the reference leaves it in (the next chunk's initial
+    latent for a given seed is the reference's).  n tiny launches, ~3 us of host each."""
+    fused = getattr(model, method, None) if _chunk_capture() is None else None
+    out = fused(state, action, goal, sigmas, *extra) if fused is not None else None
+    if out is not None and draws:
+        for _ in range(len(sigmas) - 1):
+            torch.randn_like(action)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------------ samplers
 @torch.no_grad()
 def sample_euler(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None, s_churn=0.0, s_tmin=0.0,
@@ -199,15 +213,9 @@ def sample_euler(model, state, action, goal, sigmas, scaler=None, extra_args=Non
     """Euler steps of Karras et al. (2022) Algorithm 2 (gc_sampling.py:165-211); an ODE solver for s_churn = 0.  Without churn, clipping, callback
     and extra arguments the step  x + (x - D)/s (s' - s)  is  (s'/s) x + (1 - s'/s) D  - the fused DDIM update -, so a GCDenoiser over the HIP
     MoDeDiT takes the whole call as one hipGraph replay (same result to fp32 rounding of the rearranged update)."""
-    if s_churn <= 0 and scaler is None and callback is None and not extra_args and _chunk_capture() is None:
-        fused = getattr(model, "first_order_ode_fused", None)
-        out = fused(state, action, goal, sigmas) if fused is not None else None
+    if s_churn <= 0 and scaler is None and callback is None and not extra_args:
+        out = _fused_route(model, "first_order_ode_fused", state, action, goal, sigmas, draws=True)
         if out is not None:
-            # The reference draws `eps = randn_like(action)` on EVERY step, churn or not (gc_sampling.py:196), and so does the step loop below: the
-            # fused route makes the same draws and discards them, so the generator leaves this call in the state the reference leaves it in (the
-            # next chunk's initial latent for a given seed is the reference's).  n tiny launches, ~3 us of host each.
-            for _ in range(len(sigmas) - 1):
-                torch.randn_like(action)
             return out
     run = _Run(model, state, goal, action, extra_args, callback, scaler, "x")
     for i in range(len(sigmas) - 1):
@@ -235,25 +243,14 @@ def sample_euler_ancestral(model, state, action, goal, sigmas, scaler=None, extr
     return action
 
 
-def _two_stage_fused(model, state, action, goal, sigmas, solver, draws: bool):
-    """The fused route of the deterministic two-stage solvers (GCDenoiser.two_stage_fused); ``draws``: the reference draws ``eps = randn_like(action)``
-    on every step of this sampler, churn or not - made and discarded here too, so the generator leaves the call as the reference leaves it."""
-    fused = getattr(model, "two_stage_fused", None)
-    out = fused(state, action, goal, sigmas, solver) if fused is not None else None
-    if out is not None and draws:
-        for _ in range(len(sigmas) - 1):
-            torch.randn_like(action)
-    return out
-
-
 @torch.no_grad()
 def sample_heun(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None, s_churn=0.0, s_tmin=0.0,
                 s_tmax=float("inf"), s_noise=1.0):
     """Heun (2nd-order) steps of Algorithm 2: Euler predictor, trapezoidal corrector, plain Euler into sigma = 0 (gc_sampling.py:257-312).  Without
     churn, clipping, callback and extra arguments a GCDenoiser over the HIP MoDeDiT takes the whole call as one hipGraph replay (both stages' updates
     inside the head kernel; same result to fp32 rounding of the multiplied-out recurrence)."""
-    if s_churn <= 0 and scaler is None and callback is None and not extra_args and _chunk_capture() is None:
-        out = _two_stage_fused(model, state, action, goal, sigmas, "heun", draws=True)
+    if s_churn <= 0 and scaler is None and callback is None and not extra_args:
+        out = _fused_route(model, "two_stage_fused", state, action, goal, sigmas, "heun", draws=True)
         if out is not None:
             return out
     run = _Run(model, state, goal, action, extra_args, callback, scaler, "x")
@@ -278,8 +275,8 @@ def sample_heun(model, state, action, goal, sigmas, scaler=None, extra_args=None
 def sample_dpm_2(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None, s_churn=0.0, s_tmin=0.0,
                  s_tmax=float("inf"), s_noise=1.0):
     """Midpoint method in log-sigma (DPM-Solver-2 flavoured), Euler into sigma = 0 (gc_sampling.py:315-373).  Fused route as in sample_heun."""
-    if s_churn <= 0 and scaler is None and callback is None and not extra_args and _chunk_capture() is None:
-        out = _two_stage_fused(model, state, action, goal, sigmas, "dpm_2", draws=True)
+    if s_churn <= 0 and scaler is None and callback is None and not extra_args:
+        out = _fused_route(model, "two_stage_fused", state, action, goal, sigmas, "dpm_2", draws=True)
         if out is not None:
             return out
     run = _Run(model, state, goal, action, extra_args, callback, scaler, "action")
@@ -358,9 +355,8 @@ def sample_lms(model, state, action, goal, sigmas, scaler=None, extra_args=None,
 def sample_dpmpp_2m(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None):
     """DPM-Solver++(2M): exponential-integrator steps with a two-point extrapolation of the denoised prediction (gc_sampling.py:700-734).  Without
     callback and extra arguments a GCDenoiser over the HIP MoDeDiT takes the whole call as one hipGraph replay (the extrapolation inside the head kernel)."""
-    if callback is None and not extra_args and _chunk_capture() is None:
-        fused = getattr(model, "dpmpp_2m_fused", None)
-        out = fused(state, action, goal, sigmas) if fused is not None else None
+    if callback is None and not extra_args:
+        out = _fused_route(model, "dpmpp_2m_fused", state, action, goal, sigmas, draws=False)
         if out is not None:
             return out
     run = _Run(model, state, goal, action, extra_args, callback, None, "action")
@@ -410,8 +406,8 @@ def sample_dpmpp_2s_ancestral(model, state, action, goal, sigmas, scaler=None, e
 @torch.no_grad()
 def sample_dpmpp_2s(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None, eta=1.0):
     """Deterministic DPM-Solver++(2S) (gc_sampling.py:956-994).  Fused route as in sample_heun (this sampler draws no noise)."""
-    if scaler is None and callback is None and not extra_args and _chunk_capture() is None:
-        out = _two_stage_fused(model, state, action, goal, sigmas, "dpmpp_2s", draws=False)
+    if scaler is None and callback is None and not extra_args:
+        out = _fused_route(model, "two_stage_fused", state, action, goal, sigmas, "dpmpp_2s", draws=False)
         if out is not None:
             return out
     run = _Run(model, state, goal, action, extra_args, callback, scaler, "action")

@@ -92,39 +92,37 @@ class GCDenoiser(nn.Module):
         den_u = m(state, action * c_in, goal, sigma, **{**kwargs, "uncond": True}) * c_out + action * c_skip   # any inner model: the reference's `uncond` flag
         return den_u + w * (den - den_u)
 
+    def _fused_model(self, *schedules):
+        """The HIP MoDeDiT when its fused routes apply - eval mode, no autograd, every schedule given a 1-d tensor -, else None."""
+        m = self.inner_model
+        ok = isinstance(m, MoDeDiT) and not m.training and not torch.is_grad_enabled() and all(torch.is_tensor(s) and s.dim() == 1 for s in schedules)
+        return m if ok else None
+
     def denoise_uniform(self, state, action, goal, sigma):
         """D(x; sigma) for ONE noise level shared by the whole batch (what every k-diffusion style sampler asks for: ``sigma * ones``), as one
         hipGraph replay of the HIP chain (``MoDeDiT.denoise_graphed``).  Returns None when the fast path does not apply (training mode, token /
         goal routing, a foreign inner model) - the caller then takes ``forward``."""
-        m = self.inner_model
-        if isinstance(m, MoDeDiT) and not m.training and not torch.is_grad_enabled():
-            return m.denoise_graphed(state, action, goal, sigma, self.sigma_data, guidance=self.guidance_scale)
-        return None
+        m = self._fused_model()
+        return None if m is None else m.denoise_graphed(state, action, goal, sigma, self.sigma_data, guidance=self.guidance_scale)
 
     def first_order_ode_fused(self, state, action, goal, sigmas):
         """The whole deterministic first-order solve  x <- (s'/s) x + (1 - s'/s) D(x; s)  over ``sigmas`` as one hipGraph replay
         (``MoDeDiT.sample_ddim_fused``).  That update is both sample_ddim's (gc_sampling.py:922-951: exp(-t')/exp(-t) = s'/s, -expm1(-h) = 1 - s'/s)
         and, multiplied out, sample_euler's without churn (gc_sampling.py:165-211: x + (x - D)/s (s' - s)).  None when the fast path does not apply."""
-        m = self.inner_model
-        if isinstance(m, MoDeDiT) and not m.training and not torch.is_grad_enabled() and torch.is_tensor(sigmas) and sigmas.dim() == 1:
-            return m.sample_ddim_fused(state, action, goal, sigmas, self.sigma_data, guidance=self.guidance_scale)
-        return None
+        m = self._fused_model(sigmas)
+        return None if m is None else m.sample_ddim_fused(state, action, goal, sigmas, self.sigma_data, guidance=self.guidance_scale)
 
     def dpmpp_2m_fused(self, state, action, goal, sigmas):
         """sample_dpmpp_2m (gc_sampling.py:700-734) as one hipGraph replay: the same chain as the first-order solve, the head kernel applying the step to the
         two-point extrapolation (1 + 1/(2r)) D - (1/(2r)) D_old of the denoised prediction.  None when the fast path does not apply."""
-        m = self.inner_model
-        if isinstance(m, MoDeDiT) and not m.training and not torch.is_grad_enabled() and torch.is_tensor(sigmas) and sigmas.dim() == 1:
-            return m.sample_ddim_fused(state, action, goal, sigmas, self.sigma_data, solver="dpmpp_2m", guidance=self.guidance_scale)
-        return None
+        m = self._fused_model(sigmas)
+        return None if m is None else m.sample_ddim_fused(state, action, goal, sigmas, self.sigma_data, solver="dpmpp_2m", guidance=self.guidance_scale)
 
     def two_stage_fused(self, state, action, goal, sigmas, solver: str):
         """sample_heun / sample_dpm_2 / sample_dpmpp_2s without churn, clipping or callback as one hipGraph replay (``MoDeDiT.sample_two_stage_fused``:
         every stage's update is linear and runs inside the head kernel).  None when the fast path does not apply."""
-        m = self.inner_model
-        if isinstance(m, MoDeDiT) and not m.training and not torch.is_grad_enabled() and torch.is_tensor(sigmas) and sigmas.dim() == 1:
-            return m.sample_two_stage_fused(state, action, goal, sigmas, self.sigma_data, solver, guidance=self.guidance_scale)
-        return None
+        m = self._fused_model(sigmas)
+        return None if m is None else m.sample_two_stage_fused(state, action, goal, sigmas, self.sigma_data, solver, guidance=self.guidance_scale)
 
     def get_params(self):
         return self.inner_model.parameters()
