@@ -241,6 +241,8 @@ int mode_conv_bn_act_fwd(const ModeConvBnDesc* desc, void* stream);
  * mode_rmsnorm_cond_fwd — y = x / max(||x||_2 * D^-1/2, eps) * g  (+ cond[row / rows_per_cond])
  * Replaces RMSNorm (modedit.py:72-80) and the additive conditioning `ln_1(x) + c` (modedit.py:532); with cond == NULL
  * it is the plain ln_2 / final ln (modedit.py:539, 818).  x fp32 [rows, D]; writes any of y_f32 / y_lp (may be NULL).
+ * D <= 4096: the kernel caches 4 rows in 64 KiB of LDS; wider rows return MODE_ERR_UNSUPPORTED, and so do the one-wave-per-row forms of
+ * mode_moe_combine_norm*_fwd, mode_embed_tokens_fwd and mode_head_ddim_fwd (k > 2, more than 8 slabs, D > 4096), which cache rows the same way.
  * ------------------------------------------------------------------------------------------------------------------ */
 int mode_rmsnorm_cond_fwd(const float* x, const float* g, const float* cond, int rows, int D, int rows_per_cond,
                           float eps, float* y_f32, void* y_lp, int lp_dtype, void* stream);

@@ -16,6 +16,9 @@
 namespace mode {
 
 constexpr int ROWS_PER_BLOCK = 4;   // 4 waves
+// The one-wave-per-row kernels cache ROWS_PER_BLOCK rows in dynamic LDS and are launched without the large-LDS attribute: their launchers refuse
+// what does not fit in 64 KiB (D > 4096) with MODE_ERR_UNSUPPORTED, as rmsnorm_bwd_launch does, instead of returning the launch's hipError_t.
+constexpr size_t kWaveRowLdsMax = 64 * 1024;
 
 // Visit the float4 chunks of one row owned by this lane: d = lane*4 + c*256.  NCH > 0 (D == 256*NCH) fully unrolls, so every
 // global load of the row is in flight before the first use; NCH == 0 is the generic (any D % 4 == 0) loop.
@@ -539,6 +542,7 @@ extern "C" int mode_rmsnorm_cond_fwd(const float* x, const float* g, const float
   if (rows_per_cond <= 0) rows_per_cond = 1;
   const dim3 grid((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
   const size_t lds = (size_t)ROWS_PER_BLOCK * D * 4;
+  if (lds > kWaveRowLdsMax) return MODE_ERR_UNSUPPORTED;
   if (lp_dtype == MODE_BF16) launch_rmsnorm<true>(grid, lds, (hipStream_t)stream, x, g, cond, rows, D, rows_per_cond, eps, y_f32, y_lp);
   else launch_rmsnorm<false>(grid, lds, (hipStream_t)stream, x, g, cond, rows, D, rows_per_cond, eps, y_f32, y_lp);
   MODE_LAUNCH_CHECK();
@@ -599,6 +603,7 @@ extern "C" int mode_moe_combine_norm_fused_fwd(const float* u, const float* u_ss
     MODE_LAUNCH_CHECK();
     return MODE_OK;
   }
+  if (lds > kWaveRowLdsMax) return MODE_ERR_UNSUPPORTED;
   if (h_dtype == MODE_BF16)
     launch_combine<true>(grid, lds, (hipStream_t)stream, u, Y, ybf, y_splits, (long)y_split_stride, pos, posw, N, D, k, g, cond, rows_per_cond, eps, x_next, h,
                          u_ss, u_ss_n, u_gain);
@@ -752,6 +757,7 @@ extern "C" int mode_embed_tokens_fwd(const ModeEmbedDesc* d, void* stream) {
   }
   const dim3 grid((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
   const size_t lds = (size_t)ROWS_PER_BLOCK * d->D * 4;
+  if (lds > kWaveRowLdsMax) return MODE_ERR_UNSUPPORTED;
   const hipStream_t st = (hipStream_t)stream;
   dispatch([&](auto LP, auto NCH, auto AMAX) {                         // AMAX = 32: the instantiations for A_dim > 8
     hipLaunchKernelGGL((embed_tokens_kernel<LP(), NCH(), AMAX()>), grid, dim3(256), lds, st, *d);
@@ -1037,6 +1043,7 @@ extern "C" int mode_head_ddim_fwd(const ModeHeadDesc* d, void* stream) {
   }
   const dim3 grid((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
   const size_t lds = (size_t)ROWS_PER_BLOCK * d->D * 4;
+  if (lds > kWaveRowLdsMax) return MODE_ERR_UNSUPPORTED;
   const hipStream_t st = (hipStream_t)stream;
   dispatch([&](auto NCH, auto AMAX) {                                  // AMAX = 32: the instantiations for A_dim > 8
     hipLaunchKernelGGL((head_ddim_kernel<NCH(), AMAX()>), grid, dim3(256), lds, st, *d);

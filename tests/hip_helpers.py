@@ -87,6 +87,54 @@ def qkv_attn(h, wqkv, bqkv, qg, kg, B, T, H, eps=1e-6):
     return lib.mode_qkv_attn_fwd(C.byref(d), stream()), y
 
 
+CANARY = -1536.0          # exact in bf16 and fp32
+
+
+class Guarded:
+    """A NaN-prefilled [rows, cols] output `t` with at least 2 canary rows before and after it (the pad is a multiple of 8 elements, so that `t` keeps the
+    allocation's 16-byte alignment); `intact()` after the launch: nothing was written outside `t`."""
+
+    def __init__(self, rows, cols, dtype=torch.float32, fill=float("nan")):
+        self.pad = -(-2 * cols // 8) * 8
+        self.buf = torch.full((2 * self.pad + rows * cols,), CANARY, dtype=dtype, device="cuda")
+        self.t = self.buf[self.pad: self.pad + rows * cols].view(rows, cols)
+        self.t.fill_(fill)
+        assert self.t.data_ptr() % 16 == 0
+
+    def intact(self):
+        return bool((self.buf[: self.pad] == CANARY).all()) and bool((self.buf[self.pad + self.t.numel():] == CANARY).all())
+
+
+def launch_guard(D, *tensors, pos=None, n_sorted=None):
+    """Host-side contract of the row kernels, asserted before every launch: D % 4 == 0, 16-byte aligned base pointers, pos inside [0, n_sorted)."""
+    assert D % 4 == 0, D
+    for t in tensors:
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.data_ptr() % 16 == 0), "unaligned or non-contiguous operand"
+    if pos is not None:
+        assert pos.dtype == torch.int32 and int(pos.min()) >= 0 and int(pos.max()) < n_sorted, "pos outside the sorted rows"
+
+
+def combine_fused(u, Y, pos, posw, g, cond, rpc, x_next, h, u_ss=None, u_gain=None, eps=1e-6):
+    """mode_moe_combine_norm_fused_fwd on Y [S, N*k, D]; x_next / h are Guarded outputs or None.  Returns the status."""
+    lib = L.load()
+    (N, D), (S, NK, _), k = u.shape, Y.shape, pos.shape[1]
+    assert NK == N * k and posw.shape == pos.shape and (u_ss is None or D % u_ss.shape[1] == 0)
+    launch_guard(D, u, Y, pos, posw, g, cond, u_ss, u_gain, x_next and x_next.t, h and h.t, pos=pos, n_sorted=NK)
+    return lib.mode_moe_combine_norm_fused_fwd(p(u), p(u_ss), 0 if u_ss is None else u_ss.shape[1], p(u_gain), p(Y), dt_of(Y), S, NK * D, p(pos), p(posw),
+                                               N, D, k, p(g), p(cond), rpc, eps, p(x_next and x_next.t), p(h and h.t),
+                                               dt_of(h.t) if h else L.MODE_F32, stream())
+
+
+def head_desc(u, Y, pos, posw, g, w_out, b_out, B, T, A_len, eps=1e-6, u_ss=None, u_gain=None, x_a=None, scal=None, scal_stride=0, **out):
+    """ModeHeadDesc on Y [S, N*k, D]; out: F / denoised / x_next / den_prev / lin / aux1 / aux2 as tensors."""
+    (N, D), (S, NK, _), k, A_dim = u.shape, Y.shape, pos.shape[1], w_out.shape[0]
+    assert N == B * T and NK == N * k and (u_ss is None or D % u_ss.shape[1] == 0) and (scal is None or scal.shape[0] >= (B if scal_stride else 1))
+    launch_guard(D, u, Y, pos, posw, g, w_out, b_out, u_ss, u_gain, x_a, scal, *out.values(), pos=pos, n_sorted=NK)
+    return L.ModeHeadDesc(B=B, T=T, D=D, A_len=A_len, A_dim=A_dim, k=k, u=p(u), Y=p(Y), y_dtype=dt_of(Y), y_splits=S, y_split_stride=NK * D, pos=p(pos),
+                          posw=p(posw), g=p(g), eps=eps, w_out=p(w_out), b_out=p(b_out), x_a=p(x_a), scal=p(scal), scal_stride=scal_stride,
+                          u_ss=p(u_ss), u_ss_n=0 if u_ss is None else u_ss.shape[1], u_gain=p(u_gain), **{k_: p(v) for k_, v in out.items()})
+
+
 def combine_norm(u, Y, pos, posw, k, g, cond, rows_per_cond, eps=1e-6, h_dtype=torch.bfloat16):
     lib = L.load()
     N, D = u.shape

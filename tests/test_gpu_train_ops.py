@@ -477,3 +477,262 @@ def test_moe_aux_stats_vs_torch_expressions(Ly, R, T, E, k, tok):
     L.check(lib.mode_moe_aux_stats(idx.data_ptr(), w.data_ptr(), Ly, R, T, E, k, shifted.data_ptr(), Rs, frac.data_ptr(), lb.data_ptr(), zl.data_ptr(),
                                    st[Ly * E + 2 * Ly:].data_ptr(), st[Ly * E + 2 * Ly + 1:].data_ptr(), None, None, None), "aux")
     assert rel(lb, lbref) < 1e-5
+
+
+# ================================================================================================================== small fp32 kernels, one by one
+# References: tests/row_refs.py (fp64; every backward is torch autograd of the forward expression), validated on the CPU by
+# tests/test_row_kernel_references.py.  Outputs are NaN-prefilled between canary rows (hip_helpers.Guarded).  Bounds: fp32 kernels rel-L2 < 1e-5 (the
+# header's number); sums over samples, per element, n_terms * 2^-24 * sum|term| + 1e-5 |ref| with the terms taken from the reference; copies exact.
+import math  # noqa: E402
+
+import row_refs as R  # noqa: E402
+
+FP32 = 1e-5
+U24 = 2.0 ** -24
+
+
+def log_uniform(n, lo, hi, seed):
+    """n values over [lo, hi], log-uniform, the two ends included (the first is lo; the last hi when n > 1)."""
+    s = torch.exp(math.log(lo) + torch.rand(n, generator=torch.Generator().manual_seed(seed)) * (math.log(hi) - math.log(lo)))
+    s[0] = lo
+    if n > 1:
+        s[-1] = hi
+    return s
+
+
+def sum_check(got, ref, mag, n_terms, what):
+    """|got - ref| <= n_terms * 2^-24 * sum|term| + 1e-5 |ref| per element (never a relative error of the sum: cancellation makes that meaningless)."""
+    err, bound = (got.double().cpu() - ref).abs(), n_terms * U24 * mag + FP32 * ref.abs()
+    worst = float((err / bound.clamp_min(1e-300)).max())
+    print(f"{what}: max |err| {float(err.max()):.2e}, worst err / bound {worst:.3f}")
+    assert bool((err <= bound).all()), (what, worst)
+
+
+@pytest.mark.parametrize("n", [1, 255, 1027])
+def test_gelu_fwd_bwd(n):
+    """Router GELU (erf form) and its backward against F.gelu and its autograd in fp64: n values over [-6, 6] with 0, +-1e-4 and +-10 among them (n = 1:
+    -1e-4 alone).  rel-L2 of the whole vector: at x = -10 the exact result, -7.6e-23, is below what fp32's 1 + erf resolves."""
+    lib = L.load()
+    x = torch.rand(n, generator=torch.Generator().manual_seed(n)) * 12 - 6
+    special = torch.tensor([0.0, 1e-4, -1e-4, 10.0, -10.0])
+    x[: min(n, 5)] = special[:n] if n >= 5 else special[2: 2 + n]
+    dout = rnd(n, seed=n + 1)
+    xd, dd = x.to(dev()), dout.to(dev())
+    out, dpre = H.Guarded(1, n), H.Guarded(1, n)
+    L.check(lib.mode_gelu_fwd(xd.data_ptr(), out.t.data_ptr(), n, H.stream()))
+    L.check(lib.mode_gelu_bwd(xd.data_ptr(), dd.data_ptr(), dpre.t.data_ptr(), n, H.stream()))
+    torch.cuda.synchronize()
+    assert out.intact() and dpre.intact()
+    y, dx = R.gelu(x, dout)
+    ey, ed = rel(out.t[0], y), rel(dpre.t[0], dx)
+    print(f"gelu n={n}: fwd {ey:.2e} bwd {ed:.2e} (< {FP32:.0e})")
+    assert ey < FP32 and ed < FP32, (n, ey, ed)
+    if n >= 5:
+        assert float(out.t[0, 0]) == 0.0 and abs(float(dpre.t[0, 0]) - 0.5 * float(dout[0])) <= 1e-6 * abs(float(dout[0]))      # gelu(0) = 0, gelu'(0) = 1/2
+
+
+@pytest.mark.parametrize("n", [7, 70, 448])
+@pytest.mark.parametrize("B", [1, 3, 37])
+def test_edm_noise_scale_and_loss(B, n):
+    """mode_edm_noise_scale / mode_edm_loss against GCDenoiser.loss's expressions in fp64 (dF by autograd), per-sample sigma over [2e-3, 80]; 37 x 70 and
+    37 x 448 take more than one pass of the loss kernel's 1024-thread loop.  The loss is deterministic: two launches, the same bits.
+
+    x_scaled holds the 1e-5 of fp32 kernels.  dF and the loss cannot, through the conditioning of the expression itself: the target divides
+    action - c_skip * noised, which cancels to ~sigma, by c_out ~ sigma - at sigma = 2e-3 one fp32 rounding of `noised` is 3e-5 of the target.  The same
+    expressions in fp32 torch on the CPU are 1.6e-5 .. 1.9e-5 (B = 1) / 0.7e-5 .. 1.0e-5 (B = 3) / 3.5e-6 .. 4.6e-6 (B = 37) from fp64 in dF and up to
+    1.2e-5 in the loss; the bound is 4x that gap (factor 4), measured per case here, where it exceeds the project number (dF: 1e-5; loss:
+    B n 2^-24 sum|term| + 1e-5 |ref|).  The kernel measures 1.2e-5 .. 1.4e-5 / 6.3e-6 .. 6.7e-6 / 2.7e-6 .. 4.1e-6 in dF: inside the CPU's own gap."""
+    lib, sd = L.load(), 0.5
+    sigma = log_uniform(B, 2e-3, 80.0, seed=B + n)
+    Fh, act, noise = rnd(B, n, seed=1), rnd(B, n, seed=2), rnd(B, n, seed=3)
+    Fd, ad, nd, sg = Fh.to(dev()), act.to(dev()), noise.to(dev()), sigma.to(dev())
+    xs, dF, loss, loss2, dF2 = H.Guarded(B, n), H.Guarded(B, n), H.Guarded(1, 4), H.Guarded(1, 4), H.Guarded(B, n)
+    L.check(lib.mode_edm_noise_scale(ad.data_ptr(), nd.data_ptr(), sg.data_ptr(), sd, B, n, xs.t.data_ptr(), H.stream()))
+    L.check(lib.mode_edm_loss(Fd.data_ptr(), ad.data_ptr(), nd.data_ptr(), sg.data_ptr(), sd, B, n, loss.t.data_ptr(), dF.t.data_ptr(), H.stream()))
+    L.check(lib.mode_edm_loss(Fd.data_ptr(), ad.data_ptr(), nd.data_ptr(), sg.data_ptr(), sd, B, n, loss2.t.data_ptr(), dF2.t.data_ptr(), H.stream()))
+    torch.cuda.synchronize()
+    assert all(o.intact() for o in (xs, dF, loss, loss2, dF2))
+    assert torch.equal(loss.t[0, :1], loss2.t[0, :1]) and torch.equal(dF.t, dF2.t) and bool(torch.isnan(loss.t[0, 1:]).all())
+    l64, d64, terms = R.edm_loss(Fh, act, noise, sigma, sd)
+    l32, d32, _ = R.edm_loss(Fh, act, noise, sigma, sd, dtype=torch.float32)
+    gap_d, gap_l = rel(d32, d64), abs(float(l32) - float(l64))
+    e_x, e_d, e_l = rel(xs.t, R.edm_noise_scale(act, noise, sigma, sd)), rel(dF.t, d64), abs(float(loss.t[0, 0]) - float(l64))
+    b_d, b_l = max(FP32, 4 * gap_d), max(B * n * U24 * float(terms.abs().sum()) + FP32 * float(l64), 4 * gap_l)
+    print(f"edm B={B} n={n}: x_scaled {e_x:.2e} (< {FP32:.0e}); dF {e_d:.2e} (fp32-CPU gap {gap_d:.2e}, bound {b_d:.2e}); "
+          f"loss |err| {e_l:.2e} (fp32-CPU gap {gap_l:.2e}, bound {b_l:.2e}, loss {float(l64):.3e})")
+    assert e_x < FP32 and e_d < b_d and e_l <= b_l, (B, n, e_x, e_d, b_d, e_l, b_l)
+
+
+@pytest.mark.parametrize("D", [4, 260])
+@pytest.mark.parametrize("B", [1, 15, 16, 17, 33])
+def test_pos_emb_bwd(B, D):
+    """dpos against autograd of the sequence assembly in fp64, over t0 in {0, 1}, n_img in {1, 2, 3} (3: the scalar tail loop) and A_len in {1, 10}; the
+    batch sizes sit on both sides of the kernel's 16-sample load blocks.  A reference whose action rows are off by one must be missed."""
+    lib = L.load()
+    for t0 in (0, 1):
+        for n_img in (1, 2, 3):
+            for A_len in (1, 10):
+                T = t0 + 1 + n_img + A_len
+                dx0 = rnd(B, T, D, seed=B + D + T)
+                dxd, dpos = dx0.to(dev()), H.Guarded(1 + A_len, D)
+                assert dxd.data_ptr() % 16 == 0
+                L.check(lib.mode_pos_emb_bwd(dxd.data_ptr(), B, T, D, t0, n_img, A_len, dpos.t.data_ptr(), H.stream()))
+                torch.cuda.synchronize()
+                assert dpos.intact()
+                ref, mag = R.pos_emb_bwd(dx0, t0, n_img, A_len)
+                n_terms = torch.full((1 + A_len, 1), float(B), dtype=torch.float64); n_terms[1] = B * (1 + n_img)
+                sum_check(dpos.t, ref, mag, n_terms, f"pos_emb_bwd B={B} D={D} t0={t0} n_img={n_img} A_len={A_len}")
+                if A_len > 1:
+                    bad, _ = R.pos_emb_bwd(dx0, t0, n_img, A_len, shift=1)
+                    assert bool(((dpos.t.double().cpu() - bad).abs() > n_terms * U24 * mag + FP32 * bad.abs())[1:].any()), "an off-by-one row map would pass"
+
+
+@pytest.mark.parametrize("D", [4, 260])
+@pytest.mark.parametrize("B", [1, 16, 17, 40])
+def test_sigma_embed_bwd(B, D):
+    lib = L.load()
+    de1, sigma = rnd(B, D, seed=B + D), log_uniform(B, 1e-3, 80.0, seed=B)
+    dd, sg, dw, db = de1.to(dev()), sigma.to(dev()), H.Guarded(1, D), H.Guarded(1, D)
+    L.check(lib.mode_sigma_embed_bwd(dd.data_ptr(), sg.data_ptr(), B, D, dw.t.data_ptr(), db.t.data_ptr(), H.stream()))
+    torch.cuda.synchronize()
+    assert dw.intact() and db.intact()
+    rw, rb, mw, mb = R.sigma_embed_bwd(de1, sigma)
+    sum_check(dw.t[0], rw, mw, B, f"sigma_embed_bwd dw B={B} D={D}")
+    sum_check(db.t[0], rb, mb, B, f"sigma_embed_bwd db B={B} D={D}")
+
+
+@pytest.mark.parametrize("D", [3, 260])
+@pytest.mark.parametrize("n", [1, 9])
+def test_rowcopy_f32(n, D):
+    """Strided / indexed fp32 row moves: strided source and destination with ld > D, an indexed source, an indexed destination (a permutation: no two
+    rows collide), each with and without `add`.  Exact without `add`; rows and columns of dst that are not addressed keep their prefill."""
+    lib = L.load()
+    g = torch.Generator().manual_seed(n + D)
+    rows_s, rows_d, ld_s, ld_d, ld_a, fill = 2 * n + 3, 2 * n + 4, D + 2, D + 5, D + 1, 7.5
+    src, add = rnd(rows_s, ld_s, seed=1), rnd(n, ld_a, seed=2)
+    sidx = torch.randint(0, rows_s, (n,), generator=g).int()
+    didx = torch.randperm(rows_d, generator=g)[:n].int()
+    sd_, ad_, si, di = src.to(dev()), add.to(dev()), sidx.to(dev()), didx.to(dev())
+    for use_sidx, use_didx in ((False, False), (True, False), (False, True), (True, True)):
+        for with_add in (False, True):
+            dst = H.Guarded(rows_d, ld_d, fill=fill)
+            s0, ss, d0, ds = 1, 2, 2, 2
+            sr = sidx.long() if use_sidx else s0 + ss * torch.arange(n)
+            dr = didx.long() if use_didx else d0 + ds * torch.arange(n)
+            assert int(sr.max()) < rows_s and int(dr.max()) < rows_d and dr.unique().numel() == n
+            L.check(lib.mode_rowcopy_f32(sd_.data_ptr(), ld_s, s0, ss, si.data_ptr() if use_sidx else None, dst.t.data_ptr(), ld_d, d0, ds,
+                                         di.data_ptr() if use_didx else None, ad_.data_ptr() if with_add else None, ld_a, n, D, H.stream()))
+            torch.cuda.synchronize()
+            assert dst.intact()
+            ref = torch.full((rows_d, ld_d), fill, dtype=torch.float64)
+            ref[dr, :D] = src[sr, :D].double() + (add[:, :D].double() if with_add else 0.0)
+            got = dst.t.cpu()
+            touched = torch.zeros(rows_d, ld_d, dtype=torch.bool); touched[dr, :D] = True
+            assert bool((got[~touched] == fill).all()), "rows / columns that are not addressed changed"
+            if with_add:
+                assert rel(got, ref) < FP32
+            else:
+                assert torch.equal(got.double(), ref), (n, D, use_sidx, use_didx)
+
+
+@pytest.mark.parametrize("rate", [0.0, 0.999, 1.0])
+@pytest.mark.parametrize("n", [4, 1028, 4100])
+def test_ema_update(n, rate):
+    """ema -= rate * (ema - p): `rate` is the weight of the NEW value (1 - decay), 0 leaves ema as it is, bit for bit, 1 replaces it by p up to one
+    rounding of ema - p.  n % 4 != 0 is refused (MODE_ERR_BAD_ARG: the kernel moves float4s) before any launch."""
+    lib = L.load()
+    e0, w = rnd(n + 3, seed=n), rnd(n + 3, seed=n + 1)
+    ema, wd = H.Guarded(1, n), w[:n].to(dev())
+    ema.t[0].copy_(e0[:n])
+    L.check(lib.mode_ema_update(ema.t.data_ptr(), wd.data_ptr(), n, rate, H.stream()))
+    torch.cuda.synchronize()
+    assert ema.intact()
+    r32 = float(torch.tensor(rate, dtype=torch.float32))
+    ref = e0[:n].double() - r32 * (e0[:n].double() - w[:n].double())
+    print(f"ema n={n} rate={rate}: {rel(ema.t[0], ref):.2e} (< {FP32:.0e})")
+    assert rel(ema.t[0], ref) < FP32
+    if rate == 0.0:
+        assert torch.equal(ema.t[0].cpu(), e0[:n])
+    odd, wo = H.Guarded(1, n + 4), w.to(dev())
+    odd.t[0, : n + 3].copy_(e0)
+    assert lib.mode_ema_update(odd.t.data_ptr(), wo.data_ptr(), n + 3, rate, H.stream()) == -1           # n % 4 == 3
+    torch.cuda.synchronize()
+    assert odd.intact() and torch.equal(odd.t[0, : n + 3].cpu(), e0)
+
+
+def router_case(B, T, E, k, seed):
+    """Max-shifted fp32 logits (row 0: a logit gap of 40, its top probability is clamped at 1 - 1e-9; row 1: an exact tie at the maximum), the fp32 probs
+    the router forward hands to the backward, unsorted distinct expert ids per token and an upstream gradient in ascending-expert slot order."""
+    g = torch.Generator().manual_seed(seed)
+    logits = rnd(B, E, seed=seed, scale=1.5)
+    logits[0, E // 2] += 40.0
+    if B > 1:
+        logits[1, E - 1] = logits[1].max()
+        logits[1, 0] = logits[1, E - 1]
+    shifted = (logits - logits.max(-1, keepdim=True).values).contiguous()
+    probs = torch.softmax(shifted, -1).clamp(1e-9, 1 - 1e-9).contiguous()
+    assert float(probs[0].max()) == 1.0 and (B == 1 or int((shifted[1] == 0).sum()) >= 2)
+    idx = torch.rand(B, T, E, generator=g).argsort(-1)[..., :k].int().contiguous()
+    return shifted, probs, idx, rnd(B * T, k, seed=seed + 1)
+
+
+@pytest.mark.parametrize("E,k", [(4, 2), (3, 3), (8, 3), (16, 8), (40, 5)])
+@pytest.mark.parametrize("T", [1, 14])
+@pytest.mark.parametrize("B", [1, 63, 65])
+def test_moe_router_bwd(B, T, E, k):
+    """dlogits against autograd in fp64 of softmax -> clamp -> gather -> optional renormalisation with dw as the upstream gradient: the four EMAX
+    instantiations (E <= 4, 8, 16, 64), unsorted ids (the kernel's compare-exchange sort), ids per row and per token, B on both sides of the 64-thread
+    block.  The clamped row gets exactly zero.  A reference with two slots' gradients swapped must be missed."""
+    lib = L.load()
+    shifted, probs, idx, dw = router_case(B, T, E, k, seed=B + T + E)
+    pd, dwd = probs.to(dev()), dw.to(dev())
+    for normalize in (0, 1):
+        for per_token in (0, 1):
+            ids = idx if per_token else idx[:, :1].expand(B, T, k).contiguous()
+            idd = (ids if per_token else idx[:, 0]).contiguous().to(dev())
+            dl = H.Guarded(B, E)
+            L.check(lib.mode_moe_router_bwd(dwd.data_ptr(), idd.data_ptr(), pd.data_ptr(), B, T, E, k, normalize, per_token, dl.t.data_ptr(), H.stream()))
+            torch.cuda.synchronize()
+            assert dl.intact()
+            ref = R.router_bwd(shifted, dw, ids, normalize, T)
+            assert bool((dl.t[0] == 0).all()) and bool((ref[0] == 0).all()), "the clamp passes no gradient"
+            if B > 1:
+                e = rel(dl.t, ref)
+                print(f"router_bwd B={B} T={T} E={E} k={k} normalize={normalize} per_token={per_token}: {e:.2e} (< {FP32:.0e})")
+                assert e < FP32, (B, T, E, k, normalize, per_token, e)
+                if k > 1:
+                    assert rel(dl.t, R.router_bwd(shifted, dw.flip(1), ids, normalize, T)) > 100 * FP32, "swapped slot gradients would pass"
+
+
+@pytest.mark.parametrize("E,k", [(4, 2), (3, 3), (8, 3), (16, 8), (40, 5)])
+def test_moe_router_bwd_aux(E, k):
+    """The auxiliary router losses on 2 layers of 33 rows (T = 14, ids per token): lb_coef alone, z_coef + shifted alone, both; and the documented
+    refusals.  Reference: autograd in fp64 of the combine-weight term plus sum(w * lb_coef[layer]) plus z_coef / 2 * log(sum exp(l) + 1e-6)^2 through
+    l = logits - logits.max(), row 1 holding an exact tie at the maximum (torch.max: the first tied column carries the shift's gradient).
+
+    The z-loss gradient uses the device's fast exp / log and still holds the 1e-5 of fp32 kernels (measured 1.4e-7; the same expression in fp32 torch
+    on the CPU is 0.7e-7 .. 1.5e-7 from fp64), so no bound is derived for it."""
+    lib = L.load()
+    rpl, T = 33, 14
+    B = 2 * rpl
+    shifted, probs, idx, dw = router_case(B, T, E, k, seed=E + k)
+    lb, zc = rnd(2, E, seed=3, scale=0.1).contiguous(), torch.tensor([0.37])
+    sh, pd, dwd, idd, lbd, zcd = (t.to(dev()) for t in (shifted, probs, dw, idx, lb, zc))
+    for normalize in (0, 1):
+        for use_lb, use_z in ((True, False), (False, True), (True, True)):
+            dl = H.Guarded(B, E)
+            L.check(lib.mode_moe_router_bwd_aux(dwd.data_ptr(), idd.data_ptr(), pd.data_ptr(), sh.data_ptr() if use_z else None, lbd.data_ptr() if use_lb else None,
+                                                zcd.data_ptr() if use_z else None, B, rpl, T, E, k, normalize, 1, dl.t.data_ptr(), H.stream()))
+            torch.cuda.synchronize()
+            assert dl.intact()
+            aux = dict(rows_per_layer=rpl, **(dict(lb_coef=lb) if use_lb else {}), **(dict(z_coef=float(zc)) if use_z else {}))
+            ref = R.router_bwd(shifted, dw, idx, normalize, T, **aux)
+            e = rel(dl.t, ref)
+            print(f"router_bwd_aux E={E} k={k} normalize={normalize} lb={use_lb} z={use_z}: {e:.2e} (< {FP32:.0e})")
+            assert e < FP32, (E, k, normalize, use_lb, use_z, e)
+    dl = H.Guarded(B, E)
+    args = (dwd.data_ptr(), idd.data_ptr(), pd.data_ptr())
+    assert lib.mode_moe_router_bwd_aux(*args, None, lbd.data_ptr(), None, B, rpl + 1, T, E, k, 1, 1, dl.t.data_ptr(), H.stream()) == -1   # B % rows_per_layer
+    assert lib.mode_moe_router_bwd_aux(*args, None, None, zcd.data_ptr(), B, rpl, T, E, k, 1, 1, dl.t.data_ptr(), H.stream()) == -1      # z_coef without shifted
+    torch.cuda.synchronize()
+    assert dl.intact() and bool(torch.isnan(dl.t).all())
