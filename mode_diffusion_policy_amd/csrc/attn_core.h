@@ -161,8 +161,8 @@ __device__ __forceinline__ void attn_wave_bf16(const Src& src, const float* __re
   for (int r = 0; r < 4; ++r) {
     const int d0 = (fq * 4 + r) * 8;
     if (tv && d0 < HD)
-      *reinterpret_cast<uint4*>(yrow + d0) = make_uint4(pack_bf16x2(ov[r][0], ov[r][1]), pack_bf16x2(ov[r][2], ov[r][3]),
-                                                        pack_bf16x2(ov[r][4], ov[r][5]), pack_bf16x2(ov[r][6], ov[r][7]));
+      store_out16<StorePolicy::attn>(yrow + d0, out_u4{pack_bf16x2(ov[r][0], ov[r][1]), pack_bf16x2(ov[r][2], ov[r][3]),
+                                                        pack_bf16x2(ov[r][4], ov[r][5]), pack_bf16x2(ov[r][6], ov[r][7])});
   }
 }
 

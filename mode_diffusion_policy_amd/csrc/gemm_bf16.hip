@@ -334,9 +334,9 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN >= 16 ? 1 : (LR ? LR : (NS ==
           if (ok) {
             f = *reinterpret_cast<const float4*>(smem + rl * CROW + ((ch ^ (rl & CSWZ)) << 4));
             f.x += rr[u].x; f.y += rr[u].y; f.z += rr[u].z; f.w += rr[u].w;
-            *reinterpret_cast<float4*>(Cout + (m * p.ldc + n) * 4) = f;
-            *reinterpret_cast<uint2*>(p.C2 + m * p.ldc2 + n) =
-                make_uint2(pack_bf16x2(f.x * gq[u].x, f.y * gq[u].y), pack_bf16x2(f.z * gq[u].z, f.w * gq[u].w));
+            store_out16<StorePolicy::ring>(Cout + (m * p.ldc + n) * 4, as_out_u4(f));
+            store_out8<StorePolicy::ring>(p.C2 + m * p.ldc2 + n,
+                                          out_u2{pack_bf16x2(f.x * gq[u].x, f.y * gq[u].y), pack_bf16x2(f.z * gq[u].z, f.w * gq[u].w)});
           }
           float ss = ss4_f(f.x, f.y, f.z, f.w);                      // (shared with gemm_bf16_mid_kernel: mode_common.h)
           ss += __shfl_xor(ss, 8, 64); ss += __shfl_xor(ss, 4, 64); ss += __shfl_xor(ss, 2, 64); ss += __shfl_xor(ss, 1, 64);
@@ -358,10 +358,10 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN >= 16 ? 1 : (LR ? LR : (NS ==
         v = *reinterpret_cast<uint4*>(&f);
       }
       if constexpr (OUT_BF16) {
-        if (n + 8 <= p.N) *reinterpret_cast<uint4*>(Cout + (m * p.ldc + n) * 2) = v;
-        else *reinterpret_cast<uint2*>(Cout + (m * p.ldc + n) * 2) = make_uint2(v.x, v.y);   // N % 8 == 4 tail
+        if (n + 8 <= p.N) store_out16<StorePolicy::ring>(Cout + (m * p.ldc + n) * 2, out_u4{v.x, v.y, v.z, v.w});
+        else store_out8<StorePolicy::ring>(Cout + (m * p.ldc + n) * 2, out_u2{v.x, v.y});   // N % 8 == 4 tail
       } else {
-        *reinterpret_cast<uint4*>(Cout + (m * p.ldc + n) * 4) = v;
+        store_out16<StorePolicy::ring>(Cout + (m * p.ldc + n) * 4, out_u4{v.x, v.y, v.z, v.w});
       }
     }
     if (g + 1 < EPASS) {

@@ -359,7 +359,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
 
     // ------------------------------------------------------------------------------------------------ epilogue: registers -> global
     // bias / SwiGLU in registers (a lane owns 8 consecutive output columns of a token row), stored straight from registers, 16 bytes per lane.
-    // What makes an epilogue expensive here is not its VALU work but its STORES: CDNA4's vmcnt counts stores, the L2 is write-through, and a
+    // What makes an epilogue expensive here is not its VALU work but its STORES: CDNA4's vmcnt counts stores (the XCD's L2 is write-BACK for plain stores: a line
+    // stays dirty there until it is evicted or the kernel boundary writes it back; the cache policy of these stores is StorePolicy's, mode_common.h), and a
     // counted wait of the next tile's K loop that is reached before the stores have drained stalls on them (measured: 8.9 us of a 58 us launch;
     // staging through LDS for whole-row stores cost more in barriers than it saved).  So the order is: (1) the LAST half-tile of the next output
     // tile's second K-step is requested, (2) all outputs are computed and packed while every DMA still in flight lands, (3) `vmcnt(0)` - by now
@@ -367,6 +368,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
     // run without any vmcnt wait; the first counted wait (phase 8) comes ~4.5k cycles after the stores were issued.
     {
       const int rows_valid = cur.row_end - cur.row0;
+      constexpr int POL = SWI ? StorePolicy::pp_h : HAS_BIAS ? StorePolicy::pp_b : StorePolicy::pp_y;   // cache policy of the output stores (mode_common.h), per epilogue
       // store addressing = UNIFORM tile base (scalar registers) + one 32-bit per-lane offset shared by all rounds: the row / column a round adds is
       // wave-uniform, so a lane's 14 stores need ONE address VGPR (64-bit per-round addresses had pushed the kernel into spills whose reloads -
       // vmcnt counts stores too - serialised the stores)
@@ -444,7 +446,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           const int urow = round_urow(r);
-          if (fr < rows_valid - urow) *reinterpret_cast<u32x4*>(Ct + ((long)urow * p.ldc + round_col(r)) * 2 + c_lane) = pk[r];
+          if (fr < rows_valid - urow) store_out16<POL>(Ct + ((long)urow * p.ldc + round_col(r)) * 2, c_lane, pk[r]);
         }
       } else {
         wait_vmcnt<0>();
@@ -454,9 +456,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
           outputs(r, ov);
           const int urow = round_urow(r);
           if (fr < rows_valid - urow) {
-            float* c = reinterpret_cast<float*>(Ct + ((long)urow * p.ldc + round_col(r)) * 4 + c_lane);
-            *reinterpret_cast<float4*>(c) = make_float4(ov[0], ov[1], ov[2], ov[3]);
-            *reinterpret_cast<float4*>(c + 4) = make_float4(ov[4], ov[5], ov[6], ov[7]);
+            char* c = Ct + ((long)urow * p.ldc + round_col(r)) * 4;
+            store_out16<POL>(c, c_lane, as_out_u4(make_float4(ov[0], ov[1], ov[2], ov[3])));
+            store_out16<POL>(c + 16, c_lane, as_out_u4(make_float4(ov[4], ov[5], ov[6], ov[7])));
           }
         }
       }

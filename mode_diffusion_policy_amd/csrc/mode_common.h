@@ -30,6 +30,71 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, v);
 }
 
+// ---- cache policy of the forward chain's OUTPUT stores ---------------------------------------------------------------
+// Every output of a layer kernel is read by the NEXT kernel, mostly from other XCDs, so what a kernel leaves dirty in its XCD's L2 is written
+// back at the kernel boundary.  The policy of each output's stores is a compile-time constant of this one table (values never change with it):
+//   ST_PLAIN     write-back: the line stays (dirty) in the writer's L2
+//   ST_NT        `nt`: streaming hint, the line still stays in the writer's L2
+//   ST_SC1       write-through at device scope: the line leaves the writer's L2 as the store retires
+//   ST_SC0_SC1   the same at system scope
+// An output keeps ST_PLAIN unless another policy won the A/B on the benchmark's headline (LABNOTES.md, profiles/store_policy.txt); an arm is a
+// library of its own (scripts/build_store_variant.sh <tag> -DMODE_ST_PP_Y=0 ...) selected with MODE_HIP_LIB.  Stores of 4 bytes (row sums, the
+// head's action rows) have no form here: a 4-byte write-through store costs ~6x a 16-byte one per byte.
+enum { ST_PLAIN = 0, ST_NT = 1, ST_SC1 = 2, ST_SC0_SC1 = 3 };
+#ifndef MODE_ST_PP_H
+#define MODE_ST_PP_H 2      // ping-pong GEMM, SwiGLU epilogue: the expert up-projection's H               (sc1: with PP_Y, -2.4 % per chunk)
+#endif
+#ifndef MODE_ST_PP_Y
+#define MODE_ST_PP_Y 2      // ping-pong GEMM, NONE epilogue: the expert down-projection's K-slice slabs of Y
+#endif
+#ifndef MODE_ST_PP_B
+#define MODE_ST_PP_B 0      // ping-pong GEMM, BIAS epilogue: not an output of the benchmark's chain - never measured, stays plain
+#endif
+#ifndef MODE_ST_RING
+#define MODE_ST_RING 0      // ring GEMM epilogues: c_proj's x (fp32) and h (bf16)
+#endif
+#ifndef MODE_ST_ATTN
+#define MODE_ST_ATTN 0      // attention output y (attn_core.h: the attention kernel and the fused QKV+attention kernel)
+#endif
+#ifndef MODE_ST_ROW
+#define MODE_ST_ROW 0       // row kernels: x / h of combine+ln_1 and of the token embedding, x_next of the head
+#endif
+struct StorePolicy {
+  static constexpr int pp_h = MODE_ST_PP_H, pp_y = MODE_ST_PP_Y, pp_b = MODE_ST_PP_B, ring = MODE_ST_RING, attn = MODE_ST_ATTN, row = MODE_ST_ROW;
+};
+
+typedef unsigned out_u4 __attribute__((ext_vector_type(4)));
+typedef unsigned out_u2 __attribute__((ext_vector_type(2)));
+// 16-byte / 8-byte output store through a per-lane pointer.  The asm forms end in the wait states a store of more than 8 bytes needs before its
+// data registers may be overwritten (the compiler pads only its own stores).
+template <int POL>
+__device__ __forceinline__ void store_out16(void* p, out_u4 v) {
+  static_assert(POL >= ST_PLAIN && POL <= ST_SC0_SC1, "unknown store policy");
+  if constexpr (POL == ST_PLAIN) *reinterpret_cast<out_u4*>(p) = v;
+  else if constexpr (POL == ST_NT) __builtin_nontemporal_store(v, reinterpret_cast<out_u4*>(p));
+  else if constexpr (POL == ST_SC1) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+  else asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+}
+template <int POL>
+__device__ __forceinline__ void store_out8(void* p, out_u2 v) {
+  static_assert(POL >= ST_PLAIN && POL <= ST_SC0_SC1, "unknown store policy");
+  if constexpr (POL == ST_PLAIN) *reinterpret_cast<out_u2*>(p) = v;
+  else if constexpr (POL == ST_NT) __builtin_nontemporal_store(v, reinterpret_cast<out_u2*>(p));
+  else if constexpr (POL == ST_SC1) asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
+  else asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
+}
+// 16-byte store to a wave-UNIFORM base (scalar registers) + one 32-bit per-lane byte offset: the ping-pong epilogue's addressing, which keeps a
+// lane's stores on ONE address VGPR.  The leading wait states cover a base that a VALU instruction has just written.
+template <int POL>
+__device__ __forceinline__ void store_out16(char* ubase, uint32_t lane_off, out_u4 v) {
+  static_assert(POL >= ST_PLAIN && POL <= ST_SC0_SC1, "unknown store policy");
+  if constexpr (POL == ST_PLAIN) *reinterpret_cast<out_u4*>(ubase + lane_off) = v;
+  else if constexpr (POL == ST_NT) __builtin_nontemporal_store(v, reinterpret_cast<out_u4*>(ubase + lane_off));
+  else if constexpr (POL == ST_SC1) asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" ::"v"(lane_off), "v"(v), "s"(ubase) : "memory");
+  else asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc0 sc1\n\ts_nop 1" ::"v"(lane_off), "v"(v), "s"(ubase) : "memory");
+}
+__device__ __forceinline__ out_u4 as_out_u4(float4 f) { return __builtin_bit_cast(out_u4, f); }
+
 // Independent 32-bit dropout stream per (step seed, stream id).  The keep-masks hash (element index XOR stream seed); with consecutive integers
 // as per-layer seeds the mask of layer l+1 would be the mask of layer l with its element indices XORed by a small constant (a permutation of
 // the same stream).  Stream id = 2*layer (attention dropout) / 2*layer + 1 (expert dropout).  oracle/mode_oracle.py restates this bit for bit.

@@ -32,14 +32,11 @@ __device__ __forceinline__ void for_chunks(int D, int lane, F&& f) {
   }
 }
 
-template <bool LP_BF16>   // store 4 consecutive elements at element offset `off` of a bf16 (8-byte store) or fp32 tensor
+// store 4 consecutive elements at element offset `off` of a bf16 (8-byte store) or fp32 tensor; POL: the store's cache policy (mode_common.h)
+template <bool LP_BF16, int POL = ST_PLAIN>
 __device__ __forceinline__ void store_lp4(void* base, long off, float4 o) {
-  if constexpr (LP_BF16) {
-    uint2 pk; pk.x = pack_bf16x2(o.x, o.y); pk.y = pack_bf16x2(o.z, o.w);
-    *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(base) + off) = pk;
-  } else {
-    *reinterpret_cast<float4*>(reinterpret_cast<float*>(base) + off) = o;
-  }
+  if constexpr (LP_BF16) store_out8<POL>(reinterpret_cast<uint16_t*>(base) + off, out_u2{pack_bf16x2(o.x, o.y), pack_bf16x2(o.z, o.w)});
+  else store_out16<POL>(reinterpret_cast<float*>(base) + off, as_out_u4(o));
 }
 
 __device__ __forceinline__ float4 scale4(float4 v, float s, float4 g) {   // v * s * g, in this order (s: the row's one reciprocal norm)
@@ -269,7 +266,7 @@ __global__ __launch_bounds__(256) void combine_norm_row_kernel(const float* u, c
     }
     v[c] = make_float4(uu.x + nx.x, uu.y + nx.y, uu.z + nx.z, uu.w + nx.w);   // x + next_states (:595)
     if (!in) v[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (x_next && in) *reinterpret_cast<float4*>(x_next + (long)row * D + d) = v[c];
+    if (x_next && in) store_out16<StorePolicy::row>(x_next + (long)row * D + d, as_out_u4(v[c]));
     ssq += v[c].x * v[c].x + v[c].y * v[c].y + v[c].z * v[c].z + v[c].w * v[c].w;
   }
   if (!hh) return;
@@ -284,7 +281,7 @@ __global__ __launch_bounds__(256) void combine_norm_row_kernel(const float* u, c
     if (d >= D) continue;
     float4 o = scale4(v[c], rnrm, gq[c]);
     if (hc) { o.x += cq[c].x; o.y += cq[c].y; o.z += cq[c].z; o.w += cq[c].w; }
-    store_lp4<LP_BF16>(h, (long)row * D + d, o);
+    store_lp4<LP_BF16, StorePolicy::row>(h, (long)row * D + d, o);
   }
 }
 
@@ -701,7 +698,7 @@ __global__ __launch_bounds__(256) void embed_tokens_row_kernel(const ModeEmbedDe
     const float4 s4 = has_src ? sv : make_float4(o[0], o[1], o[2], o[3]);
     const float4 p4 = has_pos ? pv : make_float4(0.f, 0.f, 0.f, 0.f);
     v[c] = in ? make_float4(s4.x + p4.x, s4.y + p4.y, s4.z + p4.z, s4.w + p4.w) : make_float4(0.f, 0.f, 0.f, 0.f);
-    if (in) *reinterpret_cast<float4*>(e.x + (long)row * D + d) = v[c];
+    if (in) store_out16<StorePolicy::row>(e.x + (long)row * D + d, as_out_u4(v[c]));
     ssq += v[c].x * v[c].x + v[c].y * v[c].y + v[c].z * v[c].z + v[c].w * v[c].w;
   }
   ssq = wave_sum(ssq);
@@ -715,7 +712,7 @@ __global__ __launch_bounds__(256) void embed_tokens_row_kernel(const ModeEmbedDe
     if (d >= D) continue;
     float4 o = scale4(v[c], rnrm, gq[c]);
     if (e.cond) { o.x += cq[c].x; o.y += cq[c].y; o.z += cq[c].z; o.w += cq[c].w; }
-    store_lp4<LP_BF16>(e.h, (long)row * D + d, o);
+    store_lp4<LP_BF16, StorePolicy::row>(e.h, (long)row * D + d, o);
   }
 }
 }  // namespace mode
