@@ -70,20 +70,33 @@ def rmsnorm(x, g, cond=None, rows_per_cond=1, eps=1e-6, lp_dtype=torch.bfloat16,
     return y32, ylp
 
 
-def attn(qkv, qg, kg, B, T, H, hd, eps=1e-6, seed=0, p_drop=0.0):
+def attn(qkv, qg, kg, B, T, H, hd, eps=1e-6, seed=0, p_drop=0.0, out=None):
+    """mode_attn_block_fwd.  out: a Guarded [B*T, H*hd] to write into; then the status is returned (the caller decides what it means), else y."""
     lib = L.load()
-    y = torch.full((B * T, H * hd), float("nan"), dtype=qkv.dtype, device=qkv.device)
-    L.check(lib.mode_attn_block_fwd(p(qkv), p(qg), p(kg), p(y), dt_of(qkv), B, T, H, hd, eps, seed, p_drop, stream()), "attn")
+    y = out.t if out is not None else torch.full((B * T, H * hd), float("nan"), dtype=qkv.dtype, device=qkv.device)
+    rc = lib.mode_attn_block_fwd(p(qkv), p(qg), p(kg), p(y), dt_of(qkv), B, T, H, hd, eps, seed, p_drop, stream())
+    if out is not None:
+        return rc
+    L.check(rc, "attn")
     return y
 
 
-def qkv_attn(h, wqkv, bqkv, qg, kg, B, T, H, eps=1e-6):
-    """mode_qkv_attn_fwd: returns (status, y) - the caller decides what an UNSUPPORTED (-2) shape means."""
+def attn_bwd(qkv, qg, kg, dy, B, T, H, hd, eps=1e-6, seed=0, p_drop=0.0):
+    """mode_attn_block_bwd into Guarded outputs: returns (status, dqkv [B*T, 3D], dgq_partial [B*H, hd], dgk_partial [B*H, hd])."""
     lib = L.load()
-    D = h.shape[1]
-    y = torch.full((B * T, D), float("nan"), dtype=h.dtype, device=h.device)
+    dqkv, pq, pk = Guarded(B * T, 3 * H * hd, qkv.dtype), Guarded(B * H, hd), Guarded(B * H, hd)
+    rc = lib.mode_attn_block_bwd(p(qkv), p(qg), p(kg), p(dy), p(dqkv.t), p(pq.t), p(pk.t), dt_of(qkv), B, T, H, hd, eps, seed, p_drop, stream())
+    return rc, dqkv, pq, pk
+
+
+def qkv_attn(h, wqkv, bqkv, qg, kg, B, T, H, eps=1e-6, D=None, out=None, ldy=None):
+    """mode_qkv_attn_fwd: returns (status, y) - the caller decides what an UNSUPPORTED (-2) shape means.  h / wqkv may be column slices of wider
+    buffers (D = the logical width); out: a Guarded [B*T, ldy] whose first D columns are y."""
+    lib = L.load()
+    D = D or h.shape[1]
+    y = out.t if out is not None else torch.full((B * T, D), float("nan"), dtype=h.dtype, device=h.device)
     d = L.ModeQkvAttnDesc(dtype=dt_of(h), B=B, T=T, H=H, D=D, h=p(h), ldh=h.stride(0), wqkv=p(wqkv), ldw=wqkv.stride(0), bqkv=p(bqkv), q_gain=p(qg),
-                          k_gain=p(kg), eps=eps, y=p(y), ldy=y.stride(0))
+                          k_gain=p(kg), eps=eps, y=p(y), ldy=ldy or y.stride(0))
     return lib.mode_qkv_attn_fwd(C.byref(d), stream()), y
 
 
