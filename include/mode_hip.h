@@ -940,6 +940,53 @@ typedef struct ModeGuidedArgs {
 int mode_dit_forward_guided(const ModeDims* dims, const ModeModelWeights* w, const ModeGuidedArgs* a,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Camera frames as the camera delivers them -> the perceptual encoders' input (camera.CameraTransform, the policies' camera_transforms=).
+ * An addition to ABI 13: two new structs and a new export, nothing existing changes.  One launch for up to two cameras; per camera
+ *   source       uint8, n rows (environments / samples) of T frames; a frame is a contiguous H x W x 3 block (HWC), a row's frames are
+ *                contiguous, rows are src_stride BYTES apart (src_stride >= T * H * W * 3)
+ *   destination  [m_b * T, 3, OH, OW] contiguous NCHW, MODE_F32 or MODE_BF16: the tensor the stem reads
+ * Output row j (j < m_b) reads source row rows[j]; an entry outside [0, num_envs) leaves output row j untouched; rows == NULL means j -> j and
+ * needs m_b <= num_envs.  Nothing is read from rows that are not listed.
+ *
+ * For one frame and channel c, with u[y][x] the uint8 source:
+ *  1. resize   R[oy][ox] = sum_j sum_i wy[oy][j] * wx[ox][i] * u[ymin(oy) + j][xmin(ox) + i]
+ *     with, per axis, torch's antialiased bilinear (triangle) filter, align_corners = False: scale = in / out, support = max(scale, 1),
+ *     center = scale * (o + 0.5), xmin = max(0, int(center - support + 0.5)), xmax = min(in, int(center + support + 0.5)),
+ *     w_i = max(0, 1 - |(i + xmin - center + 0.5) / support|) for xmin + i < xmax, divided by their sum.  (= F.interpolate(mode="bilinear",
+ *     align_corners=False, antialias=True); for an upscale the same as antialias=False.)  The taps and the weights' numerators are formed in
+ *     exact integer arithmetic, so in == out gives weights of exactly 1 and the source levels come out exact.
+ *  2. quantise L = clamp(rint(R), 0, 255), round to nearest even: what a uint8-in / uint8-out resize yields
+ *  3. shift and normalise, (sx, sy) = shifts[frame] (frame = j * T + t, the OUTPUT frame), each component clamped into [0, 2 pad] on the device
+ *     before use (a shift never indexes memory):
+ *       out[c][y][x] = (L[c][clamp(y + sy - pad, 0, OH - 1)][clamp(x + sx - pad, 0, OW - 1)] * (1/255) - mean[c]) * inv_std[c]
+ *     i.e. DrQ-v2's RandomShiftsAug: the integer crop at (sx, sy) of the image edge-replicated by pad.  shifts == NULL: no shift, whatever pad.
+ * Arithmetic in fp32 (both filter passes are fused-multiply-add chains in tap order, the horizontal one first; the normalisation is one
+ * product, one difference, one product, unfused); a bf16 store rounds to nearest even.
+ *
+ * Before any launch, with dst untouched: MODE_ERR_BAD_ARG for null or inconsistent pointers (src without dst, no camera at all, rows == NULL with
+ * m_b > num_envs, a misaligned dst / shifts), non-positive sizes, src_stride too small, pad < 0, NaN mean / inv_std, m_b outside 1..65535;
+ * MODE_ERR_UNSUPPORTED for in / out > 8 on an axis, a dst_dtype other than the two, m_b * T > 65535, a side above 16384, or a geometry of which
+ * not even one output row's working set (its source rows as bytes and as an fp32 [3][OW] image each, and the filter tables) fits 64 KiB of LDS.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct ModeFramePrepCam {
+  const void* src;                       /* uint8 [n, T, H, W, 3], rows src_stride bytes apart; NULL (with dst) = camera skipped */
+  int64_t src_stride;
+  void* dst;                             /* [m_b * T, 3, OH, OW] */
+  const int32_t* shifts;                 /* NULL or [m_b * T, 2] device: (sx, sy) per output frame */
+  int32_t T, H, W, OH, OW;
+  int32_t dst_dtype;                     /* MODE_F32 | MODE_BF16 */
+  int32_t pad;                           /* >= 0 */
+  float mean[3], inv_std[3];
+} ModeFramePrepCam;
+typedef struct ModeFramePrepDesc {
+  const int32_t* rows;                   /* NULL or [m_b] device */
+  int32_t m_b;                           /* 1..65535 */
+  int32_t num_envs;                      /* source rows */
+  ModeFramePrepCam cam[2];               /* static, gripper */
+} ModeFramePrepDesc;
+int mode_frames_preprocess(const ModeFramePrepDesc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

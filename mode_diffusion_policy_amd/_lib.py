@@ -191,6 +191,17 @@ class ModeEnvFramesDesc(C.Structure):
     _fields_ = [("rows", c_vp), ("m_b", c_i32), ("num_envs", c_i32), ("cam", ModeEnvFramesCam * 2)]
 
 
+class ModeFramePrepCam(C.Structure):
+    """One camera of mode_frames_preprocess (include/mode_hip.h, an addition to ABI 13)."""
+    _fields_ = [("src", c_vp), ("src_stride", c_i64), ("dst", c_vp), ("shifts", c_vp), ("T", c_i32), ("H", c_i32), ("W", c_i32), ("OH", c_i32),
+                ("OW", c_i32), ("dst_dtype", c_i32), ("pad", c_i32), ("mean", c_f32 * 3), ("inv_std", c_f32 * 3)]
+
+
+class ModeFramePrepDesc(C.Structure):
+    """uint8 HWC camera frames -> resized, shifted, normalised NCHW encoder input, both cameras in one launch (include/mode_hip.h)."""
+    _fields_ = [("rows", c_vp), ("m_b", c_i32), ("num_envs", c_i32), ("cam", ModeFramePrepCam * 2)]
+
+
 P = C.POINTER
 # name -> (restype, argtypes): every symbol include/mode_hip.h declares
 PROTOTYPES = {
@@ -281,6 +292,7 @@ PROTOTYPES = {
     "mode_embed_tokens_guided_fwd": (C.c_int, [P(ModeEmbedGuidedDesc), c_vp]),
     "mode_head_ddim_guided_fwd": (C.c_int, [P(ModeHeadGuidedDesc), c_vp]),
     "mode_dit_forward_guided": (C.c_int, [P(ModeDims), P(ModeModelWeights), P(ModeGuidedArgs), c_vp, c_sz, c_vp]),
+    "mode_frames_preprocess": (C.c_int, [P(ModeFramePrepDesc), c_vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1096,7 +1096,11 @@ class GraphedVisualEncoder:
     (scripts/encoder_eval_latency.py).  The graph reads parameters and BatchNorm buffers where they live: in-place updates (``load_state_dict``,
     an EMA swap) are seen by the next replay; re-allocated parameters (``.to()``, ``.half()``) or a switch to training mode re-capture.
 
-    ``autocast_dtype``: run under ``torch.autocast`` like the reference's trainer / evaluation precision (None = the tensors' own dtype)."""
+    ``autocast_dtype``: run under ``torch.autocast`` like the reference's trainer / evaluation precision (None = the tensors' own dtype).
+
+    ``camera_transforms=(static, gripper)`` (two ``camera.CameraTransform``) in a call: the frames are the cameras' uint8 ``(B, T, H, W, 3)``, and one
+    launch resizes and normalises both cameras straight into the graph entry's input buffers - bf16 under bf16 autocast (the rounding the stem
+    applies to an fp32 image), fp32 otherwise.  The graph key is that of the transformed frames."""
 
     def __init__(self, static_resnet: nn.Module, gripper_resnet: nn.Module, autocast_dtype: Optional[torch.dtype] = torch.bfloat16, max_graphs: int = 4):
         self.static_resnet, self.gripper_resnet = static_resnet, gripper_resnet
@@ -1138,21 +1142,36 @@ class GraphedVisualEncoder:
         return graph, out, tables + weights
 
     @torch.no_grad()
-    def __call__(self, rgb_static: torch.Tensor, rgb_gripper: torch.Tensor, latent_goal: Optional[torch.Tensor] = None):
-        if self.static_resnet.training or self.gripper_resnet.training or rgb_static.device.type != "cuda" or not graphs_enabled():
-            return {"state_images": self._eager(rgb_static, rgb_gripper, latent_goal)}       # batch statistics / no device: nothing to replay
-        wdt = self.autocast_dtype if self.autocast_dtype is not None else rgb_static.dtype
-        key = (tuple(rgb_static.shape), rgb_static.dtype, tuple(rgb_gripper.shape), rgb_gripper.dtype,
-               None if latent_goal is None else (tuple(latent_goal.shape), latent_goal.dtype), str(rgb_static.device), self._param_key())
+    def __call__(self, rgb_static: torch.Tensor, rgb_gripper: torch.Tensor, latent_goal: Optional[torch.Tensor] = None, camera_transforms=None):
+        dev = rgb_static.device
+        eager = self.static_resnet.training or self.gripper_resnet.training or dev.type != "cuda" or not graphs_enabled()
+        fill = None
+        if camera_transforms is not None:                                        # uint8 camera frames: what the towers read is the transforms' output
+            from .camera import preprocess_cameras
+            (ts, tg), raw = camera_transforms, (rgb_static, rgb_gripper)
+            dt = torch.bfloat16 if self.autocast_dtype == torch.bfloat16 else torch.float32
+            fill = lambda out=(None, None): preprocess_cameras(raw[0], raw[1], ts, tg, out=out, dtype=dt)
+            sig = (ts.out_shape(raw[0].shape), dt, tg.out_shape(raw[1].shape), dt)
+        else:
+            sig = (tuple(rgb_static.shape), rgb_static.dtype, tuple(rgb_gripper.shape), rgb_gripper.dtype)
+        if eager:                                                                # batch statistics / no device: nothing to replay
+            s, g = fill() if fill is not None else (rgb_static, rgb_gripper)
+            return {"state_images": self._eager(s, g, latent_goal)}
+        wdt = self.autocast_dtype if self.autocast_dtype is not None else sig[1]
+        key = sig + (None if latent_goal is None else (tuple(latent_goal.shape), latent_goal.dtype), str(dev), self._param_key())
         ent = self._graphs.get(key)
         if ent is None:
             if len(self._graphs) >= self.max_graphs:
                 self._graphs.pop(next(iter(self._graphs)))
-            ent = dict(s=rgb_static.clone(), g=rgb_gripper.clone(), c=None if latent_goal is None else latent_goal.clone())
-            ent["graph"], ent["out"], ent["tables"] = self.capture(lambda: self._eager(ent["s"], ent["g"], ent["c"]), rgb_static.device, wdt)
+            s, g = fill() if fill is not None else (rgb_static.clone(), rgb_gripper.clone())   # (valid frames for the warm-up and capture runs)
+            ent = dict(s=s, g=g, c=None if latent_goal is None else latent_goal.clone())
+            ent["graph"], ent["out"], ent["tables"] = self.capture(lambda: self._eager(ent["s"], ent["g"], ent["c"]), dev, wdt)
             self._graphs[key] = ent
         self._refresh(wdt)                                                       # weights whose version moved since the last call: re-cast in place
-        ent["s"].copy_(rgb_static); ent["g"].copy_(rgb_gripper)
+        if fill is not None:
+            fill((ent["s"], ent["g"]))                                           # one launch, both cameras, straight into the graph's inputs
+        else:
+            ent["s"].copy_(rgb_static); ent["g"].copy_(rgb_gripper)
         if latent_goal is not None:
             ent["c"].copy_(latent_goal)
         ent["graph"].replay()

@@ -91,12 +91,17 @@ class ChunkedRolloutPolicy:
 
     With ``static_resnet`` / ``gripper_resnet`` (the agent's perceptual encoders, mode_agent.py:132-160) ``step`` also takes the environment's
     observation as the agent does - ``{'rgb_obs': {'rgb_static': (B, T, 3, H, W), 'rgb_gripper': ...}}`` - and embeds it on replanning steps
-    (``MoDEAgent.forward``, mode_agent.py:598-603) through ``GraphedVisualEncoder``: one more hipGraph replay instead of ~640 eager launches."""
+    (``MoDEAgent.forward``, mode_agent.py:598-603) through ``GraphedVisualEncoder``: one more hipGraph replay instead of ~640 eager launches.
+
+    ``camera_transforms={'rgb_static': CameraTransform, 'rgb_gripper': CameraTransform}`` (needs the encoders; None, the default, changes nothing):
+    ``rgb_obs`` then holds the cameras' own frames, uint8 ``(B, T, H, W, 3)`` at the cameras' resolution on the policy's device, and one launch
+    (camera.py, csrc/frame_prep.hip) resizes, normalises and writes them straight into the encoder graph's input buffers."""
 
     def __init__(self, denoiser, num_sampling_steps: int = 10, sigma_min: float = 0.001, sigma_max: float = 80.0,
                  noise_scheduler: str = "exponential", sampler_type: str = "ddim", act_window_size: int = 10, multistep: int = 10,
                  action_dim: int = 7, generator: Optional[torch.Generator] = None, static_resnet=None, gripper_resnet=None,
-                 encoder_autocast: Optional[torch.dtype] = torch.bfloat16):
+                 encoder_autocast: Optional[torch.dtype] = torch.bfloat16, camera_transforms: Optional[dict] = None):
+        self.camera_transforms = self._checked_transforms(camera_transforms, static_resnet is not None and gripper_resnet is not None)
         if multistep > act_window_size:
             raise ValueError("multistep cannot exceed the planned window")
         if (static_resnet is None) != (gripper_resnet is None):
@@ -112,6 +117,55 @@ class ChunkedRolloutPolicy:
         self.generator = generator
         self.need_precompute_experts_for_inference = True
         self.reset()
+
+    _CAMERAS = ("rgb_static", "rgb_gripper")
+
+    @classmethod
+    def _checked_transforms(cls, camera_transforms, have_encoders: bool):
+        """``camera_transforms=`` of the constructor: None, or a dict of one CameraTransform per camera of a policy that owns the encoders."""
+        if camera_transforms is None:
+            return None
+        from .camera import CameraTransform
+        if not isinstance(camera_transforms, dict) or set(camera_transforms) != set(cls._CAMERAS):
+            raise ValueError(f"camera_transforms must be a dict with exactly the keys {list(cls._CAMERAS)}, got "
+                             f"{sorted(camera_transforms) if isinstance(camera_transforms, dict) else type(camera_transforms).__name__}")
+        for name in cls._CAMERAS:
+            if not isinstance(camera_transforms[name], CameraTransform):
+                raise ValueError(f"camera_transforms[{name!r}] must be a CameraTransform, got {type(camera_transforms[name]).__name__}")
+        if not have_encoders:
+            raise ValueError("camera_transforms feed the policy's perceptual encoders: pass static_resnet / gripper_resnet as well")
+        return dict(camera_transforms)
+
+    def _frames_device(self) -> torch.device:
+        return next(self.model.inner_model.parameters()).device
+
+    def _check_u8_frames(self, rgb, n: Optional[int] = None):
+        """The raw observation's contract of a policy built with ``camera_transforms``: both cameras, uint8 (n, T, H, W, 3) each with one T,
+        2 T = n_img_tokens, on the policy's device, at most 8 source pixels per output pixel; a row's frames one contiguous block (made so here)."""
+        from .camera import check_frames_u8
+        n_img = self.model.inner_model.n_img_tokens
+        if not isinstance(rgb, dict) or set(rgb) != set(self._CAMERAS):
+            raise ValueError(f"rgb_obs must hold exactly the cameras {list(self._CAMERAS)}, got {sorted(rgb) if isinstance(rgb, dict) else type(rgb).__name__}")
+        out = []
+        for name in self._CAMERAS:
+            f = rgb[name]
+            if torch.is_tensor(f) and f.dtype != torch.uint8:
+                raise ValueError(f"{name}: a policy built with camera_transforms takes the camera's uint8 (n, T, H, W, 3) frames, got {f.dtype} "
+                                 f"{tuple(f.shape)}; float frames go to a policy without camera_transforms")
+            if not torch.is_tensor(f) or f.dim() != 5 or (n is not None and f.shape[0] != n):
+                raise ValueError(f"{name} must be uint8 ({'n' if n is None else n}, T, H, W, 3) (one row per environment), got {tuple(getattr(f, 'shape', ()))}")
+            f = check_frames_u8(f, name, self._frames_device())
+            self.camera_transforms[name].check_source(f.shape[2], f.shape[3], name)
+            out.append(f)
+        if out[1].shape[:2] != out[0].shape[:2]:
+            raise ValueError(f"both cameras must carry the same rows and number of frames T, got {tuple(out[0].shape[:2])} and {tuple(out[1].shape[:2])}")
+        T = out[0].shape[1]
+        if 2 * T != n_img:
+            raise ValueError(f"2 * T frames (T = {T}) must equal the model's n_img_tokens = {n_img}")
+        return tuple(out)
+
+    def _transform_pair(self):
+        return tuple(self.camera_transforms[name] for name in self._CAMERAS)
 
     def reset(self) -> None:
         """Start of an episode (the reference agent's ``reset``): replan at the next ``step``."""
@@ -197,7 +251,11 @@ class ChunkedRolloutPolicy:
             raise ValueError("raw observations ('rgb_obs') need the policy's perceptual encoders: pass static_resnet / gripper_resnet")
         rgb = obs["rgb_obs"]
         goal = latent_goal.reshape(latent_goal.shape[0], -1)
-        emb = self.encoders(rgb["rgb_static"], rgb["rgb_gripper"], goal)
+        if self.camera_transforms is not None:
+            s, g = self._check_u8_frames(rgb)
+            emb = self.encoders(s, g, goal, camera_transforms=self._transform_pair())
+        else:
+            emb = self.encoders(rgb["rgb_static"], rgb["rgb_gripper"], goal)
         return {"state_images": emb["state_images"].to(torch.float32)}
 
     @torch.no_grad()
@@ -280,7 +338,9 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
     stem would), and one more replay runs the two towers at batch mb * T with FiLM on each environment's own goal row (two graph branches, as
     ``GraphedVisualEncoder``) straight into the chunk's observation buffer: two launches and two replays per replanning step.  The encoder
     graphs live in the policy's own store, one per bucket; in-place weight updates are seen by the next replan; encoders in training mode or
-    MODE_HIP_GRAPH=0 run eagerly on the gathered rows.
+    MODE_HIP_GRAPH=0 run eagerly on the gathered rows.  With ``camera_transforms`` (see ``ChunkedRolloutPolicy``) the frames are the cameras'
+    uint8 ``(num_envs, T, H, W, 3)`` and that gather launch is the fused resize + normalise of the replanning rows (csrc/frame_prep.hip, the same
+    rows of the control block), writing bf16 under bf16 autocast and fp32 otherwise: the launch budget is unchanged.
 
     ``temporal_ensemble=m`` (a finite float >= 0; None, the default, is everything above unchanged) averages the overlapping predictions of an
     environment's last plans instead of letting a replan overwrite them (ACT's temporal ensembling), for ``multistep = s < act_window_size = W``.
@@ -297,6 +357,7 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         from . import _lib as L
         from .modedit import MoDeDiT
         sampler = kw.get("sampler_type", "ddim")
+        self._checked_transforms(kw.get("camera_transforms"), kw.get("static_resnet") is not None and kw.get("gripper_resnet") is not None)
         self.temporal_ensemble, self.ensemble_depth, self._ens = None, None, None   # (the base constructor calls reset)
         if temporal_ensemble is not None:
             m_ens = float(temporal_ensemble)
@@ -483,12 +544,15 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
             raise ValueError(f"state_images and latent_goal must be on {dev}")
         return img, gl, frames
 
-    _CAMERAS = ("rgb_static", "rgb_gripper")
+    def _frames_device(self) -> torch.device:
+        return self._plan.device
 
     def _check_frames(self, rgb):
         """The raw observation's contract: both cameras, (num_envs, T, 3, H, W) each with one T, 2 T = n_img_tokens, fp32 or bf16, on the
         policy's device.  An environment's frames must be one contiguous block (the environments may lie at any pitch): other layouts are
         made so here."""
+        if getattr(self, "camera_transforms", None) is not None:
+            return self._check_u8_frames(rgb, self.num_envs)
         n, n_img = self.num_envs, self.model.inner_model.n_img_tokens
         if not isinstance(rgb, dict) or set(rgb) != set(self._CAMERAS):
             raise ValueError(f"rgb_obs must hold exactly the cameras {list(self._CAMERAS)}, got {sorted(rgb) if isinstance(rgb, dict) else type(rgb).__name__}")
@@ -547,12 +611,18 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         """Element type of the gathered frames: bf16 under bf16 autocast (the stem rounds an fp32 image to bf16 as it reads it, so converting in
         the gather is exact and halves the stem's reads), else the frames' own."""
         ac = self.encoders.autocast_dtype
-        return tuple(torch.bfloat16 if ac == torch.bfloat16 else f.dtype for f in frames)
+        if ac == torch.bfloat16:
+            return (torch.bfloat16,) * len(frames)
+        return tuple(torch.float32 if self.camera_transforms is not None else f.dtype for f in frames)   # (uint8 camera frames: fp32 out)
 
     def _gather_frames(self, mb: int, frames, bufs) -> None:
         """frames[rows[j]] -> bufs[j] for j < mb, both cameras in one launch (csrc/env_pool.hip)."""
         from . import _lib as L
         from .engine import _stream
+        if self.camera_transforms is not None:                              # the cameras' uint8 frames: resized and normalised on the way
+            from .camera import launch
+            launch([(t, f, b, None) for t, f, b in zip(self._transform_pair(), frames, bufs)], self._rows_ptr(), mb, self.num_envs)
+            return
         d = L.ModeEnvFramesDesc(rows=self._rows_ptr(), m_b=mb, num_envs=self.num_envs)
         dt = {torch.float32: L.MODE_F32, torch.bfloat16: L.MODE_BF16}
         for k, (f, b) in enumerate(zip(frames, bufs)):
@@ -567,11 +637,14 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         enc = self.encoders
         mb, n_img = ent["goals"].shape[0], self.model.inner_model.n_img_tokens
         dts = self._frame_dtypes(frames)
-        geom = tuple((tuple(f.shape[1:]), dt) for f, dt in zip(frames, dts))
+        shapes = [tuple(f.shape[1:]) for f in frames]                      # of one environment's gathered frames
+        if self.camera_transforms is not None:
+            shapes = [t.out_shape(f.shape)[1:] for t, f in zip(self._transform_pair(), frames)]
+        geom = tuple((tuple(f.shape[1:]), shp, dt) for f, shp, dt in zip(frames, shapes, dts))   # (source H, W included: the kernel's tables)
         st = self._enc_store.get(mb)
         if st is None or st["geom"] != geom:
             st = self._enc_store[mb] = dict(geom=geom, graph=None,
-                                            bufs=tuple(torch.empty(mb, *f.shape[1:], dtype=dt, device=f.device) for f, dt in zip(frames, dts)))
+                                            bufs=tuple(torch.empty(mb, *shp, dtype=dt, device=f.device) for f, shp, dt in zip(frames, shapes, dts)))
         self._gather_frames(mb, frames, st["bufs"])
         goals = ent["goals"]
         if enc.static_resnet.training or enc.gripper_resnet.training or not graphs_enabled():
