@@ -803,6 +803,12 @@ int mode_maxpool_nhwc_bwd(const void* dy, const uint8_t* argmax, int dtype, int 
  *   x0[e] = sigma_max * z
  * A function of (s, d, e) only: an environment's noise does not depend on which others replan with it or on the bucket size.
  *
+ * Warm start (mode_env_gather_warm, an addition to ABI 13).  A replan that resumes from the environment's previous plan starts, with the same z
+ * of the same (s, d, e) and e = w * A + a, from that plan advanced by `shift` rows - its last row held beyond the end - at noise level
+ * sigma_start:
+ *   x0[w][a] = fma(sigma_start, z, plan[min(w + shift, W - 1)][a])    (fp32, one rounding)
+ * so sigma_start = 0 is the shifted plan itself.
+ *
  * Control block (int32 words, device), written once per replanning step and read by both entry points:
  *   [0] m       real rows: the first m entries of `rows` are distinct environments
  *   [1]         reserved (0)
@@ -820,6 +826,15 @@ int mode_maxpool_nhwc_bwd(const void* dy, const uint8_t* argmax, int dtype, int 
 int mode_env_gather_noise(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
                           const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
                           float* img_out, float* goal_out, float* x0, int noise_floats, float sigma_max, void* stream);
+
+/* The same gather with warm-started latents (one launch; the formula above): rows, seeds, draws, the optional image and goal gathers and the
+ * treatment of entries outside [0, num_envs) as for mode_env_gather_noise, and
+ *   x0[j][w][a] = plan[r][min(w + shift, W - 1)][a] + sigma_start * z(seeds[r], draws[r], w * A + a)
+ * plan [num_envs, W, A] fp32 is only read.  MODE_ERR_BAD_ARG, before any launch: rows, seeds, draws, x0 or plan NULL, m_b <= 0, num_envs <= 0,
+ * W <= 0, A <= 0, W * A > 4096, shift outside [1, W - 1], sigma_start negative or not finite. */
+int mode_env_gather_warm(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
+                         const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
+                         float* img_out, float* goal_out, float* x0, const float* plan, int W, int A, int shift, float sigma_start, void* stream);
 
 /* Gather of the replanning environments' camera frames into the perceptual encoders' input (one launch, both cameras; rollout.VectorEnvPolicy
  * with raw observations).  For j < m_b, r = rows[j] (the control block's rows; entries outside [0, num_envs) leave row j untouched) and each

@@ -286,6 +286,7 @@ PROTOTYPES = {
     "mode_maxpool_nhwc_fwd": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mode_maxpool_nhwc_bwd": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mode_env_gather_noise": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp]),
+    "mode_env_gather_warm": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp]),
     "mode_env_commit_emit": (C.c_int, [P(ModeEnvPoolDesc), c_vp]),
     "mode_env_gather_frames": (C.c_int, [P(ModeEnvFramesDesc), c_vp]),
     "mode_env_commit_emit_ens": (C.c_int, [P(ModeEnvEnsDesc), c_vp]),

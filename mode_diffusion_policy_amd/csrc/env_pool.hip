@@ -1,10 +1,12 @@
 // Per-environment replanning of a vectorised rollout (include/mode_hip.h, ABI 13; rollout.VectorEnvPolicy): the gather of the replanning
-// environments' observations with their initial noise into a chunk's input buffers, and the commit of the chunk's plans + the emission of one
-// action per active environment - the newest plan's row, or with temporal ensembling the weighted mean of the rows that the environment's last K
+// environments' observations with their initial noise - or, warm-started, their previous plan's tail noised to an intermediate level - into a
+// chunk's input buffers, and the commit of the chunk's plans + the emission of one action per active environment - the newest plan's row, or with temporal ensembling the weighted mean of the rows that the environment's last K
 // plans predict for the step (env_commit_emit_ens_kernel).  Both move a few hundred KB at most: one launch each, plain coalesced loops, no LDS.  The gather of the
 // replanning environments' camera frames into the encoders' input (mode_env_gather_frames) moves ~1.2 MB per fp32 row at 224 x 224: HBM-bound,
 // 16-byte loads and stores.
 #include "mode_common.h"
+
+#include <cfloat>
 
 namespace mode {
 
@@ -15,13 +17,10 @@ __device__ __forceinline__ float env_normal(uint32_t k, uint32_t e) {
   return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);                            // cospi: no rounding of 2 pi u2 before the cosine
 }
 
-__global__ __launch_bounds__(256) void env_gather_noise_kernel(const int32_t* __restrict__ rows, int num_envs, const uint32_t* __restrict__ seeds,
-                                                               const uint32_t* __restrict__ draws, const float* __restrict__ img, long img_floats,
-                                                               const float* __restrict__ goals, long goal_floats, float* __restrict__ img_out,
-                                                               float* __restrict__ goal_out, float* __restrict__ x0, int noise_floats, float sigma_max) {
-  const int j = blockIdx.x;
-  const int r = rows[j];
-  if (r < 0 || r >= num_envs) return;
+// Observation and goal rows of environment r -> row j of a chunk's inputs (256 threads; either pair may be absent)
+__device__ __forceinline__ void env_gather_obs(const int r, const int j, const float* __restrict__ img, const long img_floats,
+                                               const float* __restrict__ goals, const long goal_floats, float* __restrict__ img_out,
+                                               float* __restrict__ goal_out) {
   if (img && img_out) {
     const float* src = img + (long)r * img_floats;
     float* dst = img_out + (long)j * img_floats;
@@ -32,9 +31,41 @@ __global__ __launch_bounds__(256) void env_gather_noise_kernel(const int32_t* __
     float* dst = goal_out + (long)j * goal_floats;
     for (long i = threadIdx.x; i < goal_floats; i += 256) dst[i] = src[i];
   }
+}
+
+__global__ __launch_bounds__(256) void env_gather_noise_kernel(const int32_t* __restrict__ rows, int num_envs, const uint32_t* __restrict__ seeds,
+                                                               const uint32_t* __restrict__ draws, const float* __restrict__ img, long img_floats,
+                                                               const float* __restrict__ goals, long goal_floats, float* __restrict__ img_out,
+                                                               float* __restrict__ goal_out, float* __restrict__ x0, int noise_floats, float sigma_max) {
+  const int j = blockIdx.x;
+  const int r = rows[j];
+  if (r < 0 || r >= num_envs) return;
+  env_gather_obs(r, j, img, img_floats, goals, goal_floats, img_out, goal_out);
   const uint32_t k = mode_stream_seed(seeds[r], draws[r]);
   float* dst = x0 + (long)j * noise_floats;
   for (int e = threadIdx.x; e < noise_floats; e += 256) dst[e] = sigma_max * env_normal(k, (uint32_t)e);
+}
+
+// The warm-started form of the gather above (rollout.VectorEnvPolicy(warm_start=k)): the same rows, the same stream element z, but the latent is
+// the environment's previous plan advanced by `shift` rows - its last row held beyond the end - noised to sigma_start, one fused multiply-add per
+// element.  plan is only read: the commit launch that wrote it is earlier in the stream.
+__global__ __launch_bounds__(256) void env_gather_warm_kernel(const int32_t* __restrict__ rows, int num_envs, const uint32_t* __restrict__ seeds,
+                                                              const uint32_t* __restrict__ draws, const float* __restrict__ img, long img_floats,
+                                                              const float* __restrict__ goals, long goal_floats, float* __restrict__ img_out,
+                                                              float* __restrict__ goal_out, float* __restrict__ x0, const float* __restrict__ plan, int W,
+                                                              int A, int shift, float sigma_start) {
+  const int j = blockIdx.x;
+  const int r = rows[j];
+  if (r < 0 || r >= num_envs) return;
+  env_gather_obs(r, j, img, img_floats, goals, goal_floats, img_out, goal_out);
+  const uint32_t k = mode_stream_seed(seeds[r], draws[r]);
+  const int WA = W * A;
+  const float* old = plan + (long)r * WA;
+  float* dst = x0 + (long)j * WA;
+  for (int e = threadIdx.x; e < WA; e += 256) {
+    const int w = e / A, a = e - w * A;
+    dst[e] = fmaf(sigma_start, env_normal(k, (uint32_t)e), old[min(w + shift, W - 1) * A + a]);
+  }
 }
 
 // Frames of the replanning environments -> the encoders' input [m_b * T, C, H, W].  grid (x blocks per row, m_b, 2 cameras), 256 threads; each
@@ -232,6 +263,18 @@ extern "C" int mode_env_gather_noise(const int32_t* rows, int m_b, int num_envs,
   if (!rows || !seeds || !draws || !x0 || m_b <= 0 || num_envs <= 0 || noise_floats <= 0 || img_floats < 0 || goal_floats < 0) return MODE_ERR_BAD_ARG;
   hipLaunchKernelGGL(env_gather_noise_kernel, dim3(m_b), dim3(256), 0, (hipStream_t)stream, rows, num_envs, seeds, draws, state_images, (long)img_floats,
                      goals, (long)goal_floats, img_out, goal_out, x0, noise_floats, sigma_max);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
+extern "C" int mode_env_gather_warm(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
+                                    const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
+                                    float* img_out, float* goal_out, float* x0, const float* plan, int W, int A, int shift, float sigma_start,
+                                    void* stream) {
+  if (!rows || !seeds || !draws || !x0 || !plan || m_b <= 0 || num_envs <= 0 || img_floats < 0 || goal_floats < 0) return MODE_ERR_BAD_ARG;
+  if (W <= 0 || A <= 0 || (long)W * A > 4096 || shift < 1 || shift >= W || !(sigma_start >= 0.f) || !(sigma_start <= FLT_MAX)) return MODE_ERR_BAD_ARG;
+  hipLaunchKernelGGL(env_gather_warm_kernel, dim3(m_b), dim3(256), 0, (hipStream_t)stream, rows, num_envs, seeds, draws, state_images, (long)img_floats,
+                     goals, (long)goal_floats, img_out, goal_out, x0, plan, W, A, shift, sigma_start);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }

@@ -311,6 +311,33 @@ def env_noise(seeds, draws, act_window_size: int, action_dim: int, sigma_max: fl
     return x
 
 
+@torch.no_grad()
+def env_warm_latents(plans: torch.Tensor, seeds, draws, shift: int, sigma_start: float) -> torch.Tensor:
+    """The initial latents of a warm-started replan (``VectorEnvPolicy(warm_start=k)``): row i is ``plans[i]`` advanced by ``shift`` rows, its last
+    row held beyond the end, plus ``sigma_start`` times draw ``draws[i]`` of the noise stream with seed ``seeds[i]`` - the stream element
+    ``env_noise`` scales by ``sigma_max``:  ``x0[i, w, a] = plans[i, min(w + shift, W - 1), a] + sigma_start * z_i[w, a]`` (fp32; formula:
+    include/mode_hip.h).  ``plans`` (n, W, A) on a ROCm device, 1 <= shift < W, sigma_start finite and >= 0; returns (n, W, A) fp32 there."""
+    from . import _lib as L
+    from .engine import _stream
+    seeds, draws = list(seeds), list(draws)
+    if not torch.is_tensor(plans) or plans.dim() != 3 or plans.shape[0] == 0:
+        raise ValueError(f"env_warm_latents: plans must be a (n, W, A) tensor, got {tuple(getattr(plans, 'shape', ()))}")
+    n, W, A = plans.shape
+    if len(seeds) != n or len(draws) != n:
+        raise ValueError("env_warm_latents: one seed and one draw index per plan")
+    if plans.device.type != "cuda":
+        raise ValueError("env_warm_latents: plans must be on a ROCm device")
+    dev = plans.device
+    old = plans.to(torch.float32).contiguous()
+    s, d = _u32_as_i32(seeds).to(dev), _u32_as_i32(draws).to(dev)
+    rows = torch.arange(n, dtype=torch.int32, device=dev)
+    x = torch.empty(n, W, A, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().mode_env_gather_warm(rows.data_ptr(), n, n, s.data_ptr(), d.data_ptr(), None, 0, None, 0, None, None, x.data_ptr(),
+                                              old.data_ptr(), W, A, int(shift), float(sigma_start), _stream()), "env_gather_warm")
+    return x
+
+
 class VectorEnvPolicy(ChunkedRolloutPolicy):
     """``MoDEAgent.reset`` / ``step`` (mode_agent.py:584-637) for each of ``num_envs`` environments of a batch on its own: every environment keeps
     its own plan, its own position in it and its own noise stream, so a batch behaves like ``num_envs`` independent agents whose episodes start,
@@ -351,12 +378,40 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
     policy without the option does).  Replanning, the draws, the initial latents, the buckets and the launch budget are unchanged: the commit +
     emit launch of a step is the ensembled kernel (csrc/env_pool.hip), which also keeps the ring.  ``reset`` drops every plan of the listed
     environments and rewinds their t to 0; inactive steps do not advance t.  ``plans`` stays the newest plan; ``plan_ring``, ``plan_births``,
-    ``local_times`` and ``ensemble_weight_table`` expose the device state."""
+    ``local_times`` and ``ensemble_weight_table`` expose the device state.
 
-    def __init__(self, denoiser, num_envs: int, seed: int = 0, extra_args: Optional[dict] = None, temporal_ensemble: Optional[float] = None, **kw):
+    ``warm_start=k`` (an int, 1 <= k <= num_sampling_steps - 1, with ``multistep = s < act_window_size = W``; None, the default, is everything above
+    unchanged: the same code paths, launches and results) resumes a replan from the environment's previous plan instead of from noise (SDEdit-style
+    warm starting).  An environment is WARM once a plan has been committed for it since its last ``reset`` (a host mirror beside the counters;
+    pausing changes nothing), so the first replan of an episode is always cold: today's replan, ``sigma_max * z`` through the full schedule.  A
+    warm replan starts from ``env_warm_latents(plans[b], seed, draw, shift=s, sigma_start=sigmas[k])`` - the unexecuted tail of the old plan, its
+    last row held, noised to level k with the same stream element z a cold replan would scale by sigma_max - and runs the policy's solver on
+    ``sigmas[k:]``: num_sampling_steps - k denoiser steps instead of num_sampling_steps (``dpmpp_2m`` starts its history afresh at step k).  Both
+    kinds consume one draw.  The sub-schedule is one tensor per device whose values are bit-equal to the full schedule's, so the routing
+    pre-cache serves it; warm chunks keep chunk and encoder graphs of their own per bucket (captured by ``warmup`` too), so alternating kinds
+    never recapture.  A step whose replanners are all of one kind costs what it did: one gather launch and one replay.  A step with both runs
+    two chunks, each at its own bucket: the cold one is staged first with an empty active mask into a scratch output - it commits its plans
+    (counter 0, draw + 1, with ensembling the ring slot and its birth) and emits nothing - then the warm one with the step's mask and output,
+    whose commit + emit launch emits the just-committed cold environments from ``plans`` (or the ring) like any environment that did not replan.
+    This holds for the ensembled kernel as well, so ``temporal_ensemble`` combines with it; the warm start then reads ``plans``, the newest
+    plan, not the ensembled trajectory.  ``guidance_scale`` needs nothing extra.  ``replanned_warm``: the warm ones among ``replanned``.  What
+    warm-started plans do to task success is NOT measured in this repository (no trained checkpoint, no simulator): only the mechanics - exact
+    latents, schedule and bookkeeping - and the cost (profiles/vector_env_warm_start.txt) are pinned."""
+
+    def __init__(self, denoiser, num_envs: int, seed: int = 0, extra_args: Optional[dict] = None, temporal_ensemble: Optional[float] = None,
+                 warm_start: Optional[int] = None, **kw):
         from . import _lib as L
         from .modedit import MoDeDiT
         sampler = kw.get("sampler_type", "ddim")
+        self.warm_start = None
+        if warm_start is not None:
+            n_steps, W, s = int(kw.get("num_sampling_steps", 10)), int(kw.get("act_window_size", 10)), int(kw.get("multistep", 10))
+            if isinstance(warm_start, bool) or not isinstance(warm_start, (int, np.integer)) or not 1 <= int(warm_start) <= n_steps - 1:
+                raise ValueError(f"warm_start must be None or an int in [1, num_sampling_steps - 1] = [1, {n_steps - 1}], got {warm_start!r}")
+            if not s < W:
+                raise ValueError(f"warm_start resumes from the unexecuted tail of the previous plan: it needs multistep < act_window_size, got "
+                                 f"multistep={s}, act_window_size={W}")
+            self.warm_start = int(warm_start)
         self._checked_transforms(kw.get("camera_transforms"), kw.get("static_resnet") is not None and kw.get("gripper_resnet") is not None)
         self.temporal_ensemble, self.ensemble_depth, self._ens = None, None, None   # (the base constructor calls reset)
         if temporal_ensemble is not None:
@@ -378,6 +433,7 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
             raise ValueError(f"num_envs must be in [1, {L.MODE_ENV_MAX}], got {num_envs}")
         self.num_envs = int(num_envs)
         self._counter = np.zeros(self.num_envs, dtype=np.int64)              # host mirror of the device counters: decides who replans
+        self._warm = np.zeros(self.num_envs, dtype=np.bool_)                 # a plan was committed since the last reset: decides who replans warm
         super().__init__(denoiser, **kw)
         inner = denoiser.inner_model
         W, A = self.act_window_size, self.action_dim
@@ -418,10 +474,13 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         self._lib = L.load()
         self._buckets = _buckets(n)
         self._templates = {}
-        self._hooks = SimpleNamespace(store={}, prologue=self._gather, epilogue=self._commit)
         self._inputs = None
         self._enc_store = {}                                                # bucket -> gathered frame buffers + that bucket's encoder graph
-        self.replanned = []
+        self._hooks = SimpleNamespace(store={}, prologue=self._gather, epilogue=self._commit, enc=self._enc_store)
+        # warm chunks: a store of their own for the chunk graphs (an entry's key holds the schedule's length) and for the encoder graphs (an
+        # entry's key holds the chunk entry's buffers), so that cold and warm chunks alternating at one bucket never recapture
+        self._hooks_warm = SimpleNamespace(store={}, prologue=lambda ent: self._gather(ent, True), epilogue=self._commit, enc={})
+        self.replanned, self.replanned_warm = [], []
 
     # ---------------------------------------------------------------------------------------------------------------- host-side bookkeeping
     def _env_index(self, envs) -> np.ndarray:
@@ -463,6 +522,7 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         """Start a new episode in the listed environments (see the class docstring)."""
         idx = self._env_index(envs)
         self._counter[idx] = 0
+        self._warm[idx] = False
         if seeds is not None:
             seeds = list(seeds)
             if len(seeds) != len(idx):
@@ -588,21 +648,36 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         self._ctrl.copy_(self._ring[i], non_blocking=True)
         self._ring_ev[i].record()
 
-    def _gather(self, ent) -> None:
-        """Chunk prologue: the listed environments' observations, goals and initial noise into the entry's input buffers (one launch).  Raw
-        frames: the goals and the noise (one launch), the frames (one launch), then the encoders into the entry's observation buffer."""
+    def _gather(self, ent, warm: bool = False) -> None:
+        """Chunk prologue: the listed environments' observations, goals and initial latents into the entry's input buffers (one launch) - the
+        noise of a cold replan, or (``warm``) the latents of ``env_warm_latents``: their plans advanced by ``multistep`` rows and noised to
+        ``sigmas[warm_start]``.  Raw frames: the goals and the latents (one launch), the frames (one launch), then the encoders of the chunk's
+        kind into the entry's observation buffer."""
         from . import _lib as L
         from .engine import _stream
         img, gl, frames = self._inputs
         inner = self.model.inner_model
         x = ent["bufs"][0]
-        L.check(self._lib.mode_env_gather_noise(self._rows_ptr(), x.shape[0], self.num_envs, self._seeds.data_ptr(), self._draws.data_ptr(),
-                                                None if img is None else img.data_ptr(), inner.n_img_tokens * inner.obs_dim, gl.data_ptr(),
-                                                inner.goal_dim, None if img is None else ent["img"].data_ptr(), ent["goals"].data_ptr(),
-                                                x.data_ptr(), self.act_window_size * self.action_dim, float(self.sigma_max), _stream()),
-                "env_gather_noise")
+        rows = (self._rows_ptr(), x.shape[0], self.num_envs, self._seeds.data_ptr(), self._draws.data_ptr(),
+                None if img is None else img.data_ptr(), inner.n_img_tokens * inner.obs_dim, gl.data_ptr(), inner.goal_dim,
+                None if img is None else ent["img"].data_ptr(), ent["goals"].data_ptr(), x.data_ptr())
+        if warm:
+            L.check(self._lib.mode_env_gather_warm(*rows, self._plan.data_ptr(), self.act_window_size, self.action_dim, self.multistep,
+                                                   self._warm_schedule(x.device)[1], _stream()), "env_gather_warm")
+        else:
+            L.check(self._lib.mode_env_gather_noise(*rows, self.act_window_size * self.action_dim, float(self.sigma_max), _stream()),
+                    "env_gather_noise")
         if frames is not None:
-            self._encode(ent, frames)
+            self._encode(ent, frames, (self._hooks_warm if warm else self._hooks).enc)
+
+    def _warm_schedule(self, dev):
+        """(``sigmas[warm_start:]``, ``float(sigmas[warm_start])``) of a warm replan, built once per device (one host read): the schedule is a
+        contiguous clone handed to the sampler as the SAME object every call, like ``_schedule``'s, so that it is recognised without a compare."""
+        cached = getattr(self, "_sigmas_warm", None)
+        if cached is None or cached[0].device != torch.device(dev):
+            sub = self._schedule(dev)[self.warm_start:].contiguous().clone()
+            cached = self._sigmas_warm = (sub, float(sub[0]))
+        return cached
 
     def _rows_ptr(self) -> int:
         return self._ctrl.data_ptr() + 4 * (4 + self._nw)
@@ -630,10 +705,10 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
                                           dst=b.data_ptr(), src_dtype=dt[f.dtype], dst_dtype=dt[b.dtype])
         L.check(self._lib.mode_env_gather_frames(C.byref(d), _stream()), "env_gather_frames")
 
-    def _encode(self, ent, frames) -> None:
+    def _encode(self, ent, frames, store) -> None:
         """The bucket's encoders on the gathered frames, FiLM-conditioned on the gathered goals, into ``ent['img']``: a replay of the bucket's
         encoder graph (captured on first use, and again when the frame geometry, the weights' storage or the chunk entry's buffers moved), or
-        the eager towers when the encoders are in training mode / MODE_HIP_GRAPH=0."""
+        the eager towers when the encoders are in training mode / MODE_HIP_GRAPH=0.  ``store``: the encoder store of the chunk's kind."""
         enc = self.encoders
         mb, n_img = ent["goals"].shape[0], self.model.inner_model.n_img_tokens
         dts = self._frame_dtypes(frames)
@@ -641,9 +716,9 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         if self.camera_transforms is not None:
             shapes = [t.out_shape(f.shape)[1:] for t, f in zip(self._transform_pair(), frames)]
         geom = tuple((tuple(f.shape[1:]), shp, dt) for f, shp, dt in zip(frames, shapes, dts))   # (source H, W included: the kernel's tables)
-        st = self._enc_store.get(mb)
+        st = store.get(mb)
         if st is None or st["geom"] != geom:
-            st = self._enc_store[mb] = dict(geom=geom, graph=None,
+            st = store[mb] = dict(geom=geom, graph=None,
                                             bufs=tuple(torch.empty(mb, *shp, dtype=dt, device=f.device) for f, shp, dt in zip(frames, shapes, dts)))
         self._gather_frames(mb, frames, st["bufs"])
         goals = ent["goals"]
@@ -682,15 +757,16 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         e.pool = d
         L.check(self._lib.mode_env_commit_emit_ens(C.byref(e), _stream()), "env_commit_emit_ens")
 
-    def _run_chunk(self, mb: int, m: int) -> None:
-        """One replanning chunk at bucket ``mb`` with ``m`` real rows (the control block is staged): gather launch + one replay."""
+    def _run_chunk(self, mb: int, m: int, warm: bool = False) -> None:
+        """One replanning chunk at bucket ``mb`` with ``m`` real rows (the control block is staged): gather launch + one replay.  ``warm``: the
+        warm-started chunk - the warm gather, the schedule from ``warm_start`` on, the warm chunks' stores."""
         inner = self.model.inner_model
         eng = inner.engine
         if self.need_precompute_experts_for_inference:
             if not inner._routes_per_chunk():                               # goal / token routing resolve their routing inside the chunk
                 self.precompute_expert_for_inference()
             self.need_precompute_experts_for_inference = False
-        sig = self._schedule(eng.device)
+        sig = self._warm_schedule(eng.device)[0] if warm else self._schedule(eng.device)
         tpl = self._templates.get(mb)
         if tpl is None:
             dev = eng.device
@@ -698,7 +774,8 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
                                          torch.zeros(mb, self.act_window_size, self.action_dim, device=dev), torch.zeros(mb, inner.goal_dim, device=dev))
         w = getattr(self.model, "guidance_scale", None)                  # classifier-free guidance: the bucket's mb rows run as 2·mb inside the chain
         gkey, plan = inner._chunk_plan(eng, self._solver, sig.numel() - 1, w is not None)
-        inner._sample_chunk(eng, gkey, plan, tpl[0], tpl[1], tpl[2], sig, float(self.model.sigma_data), hooks=self._hooks, rows=m, guidance=w)
+        inner._sample_chunk(eng, gkey, plan, tpl[0], tpl[1], tpl[2], sig, float(self.model.sigma_data),
+                            hooks=self._hooks_warm if warm else self._hooks, rows=m, guidance=w)
 
     @staticmethod
     def _prepared(img, gl, frames):
@@ -713,8 +790,9 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         self._inputs = self._prepared(*self._check_inputs(perceptual_emb, latent_goal))
         none = np.zeros(self.num_envs, dtype=np.bool_)
         for mb in self._buckets:
-            self._stage(0, np.zeros(mb, dtype=np.int32), none, self._scratch_out.data_ptr())
-            self._run_chunk(mb, 0)
+            for warm in (False, True) if self.warm_start is not None else (False,):
+                self._stage(0, np.zeros(mb, dtype=np.int32), none, self._scratch_out.data_ptr())
+                self._run_chunk(mb, 0, warm)
         self._inputs = None
 
     @torch.no_grad()
@@ -726,12 +804,21 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         rows = np.flatnonzero(act & (self._counter == 0)).astype(np.int32)
         m = len(rows)
         out = torch.empty(self.num_envs, self.action_dim, dtype=torch.float32, device=self._plan.device)
+        warm = rows[self._warm[rows]] if self.warm_start is not None else rows[:0]
         if m:
-            mb = next(b for b in self._buckets if b >= m)
-            self._stage(m, np.concatenate([rows, np.full(mb - m, rows[-1], dtype=np.int32)]), act, out.data_ptr())
+            # one chunk per kind of replanner.  With both kinds the cold chunk goes first, staged with no active environment and the scratch
+            # output: its launch commits its plans and emits nothing; the warm chunk's launch then emits the whole step, the cold ones from plans
+            cold = rows[~self._warm[rows]] if len(warm) else rows
+            chunks = [(r, w) for r, w in ((cold, False), (warm, True)) if len(r)]
+            none = np.zeros(self.num_envs, dtype=np.bool_)
             self._inputs = self._prepared(*inputs)
             try:
-                self._run_chunk(mb, m)
+                for i, (r, w) in enumerate(chunks):
+                    last = i == len(chunks) - 1
+                    mb = next(b for b in self._buckets if b >= len(r))
+                    self._stage(len(r), np.concatenate([r, np.full(mb - len(r), r[-1], dtype=np.int32)]), act if last else none,
+                                out.data_ptr() if last else self._scratch_out.data_ptr())
+                    self._run_chunk(mb, len(r), w)
             finally:
                 self._inputs = None
         else:
@@ -741,7 +828,8 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
             C.memmove(d.active, words.ctypes.data, 4 * self._nw)
             self._launch(d)
         self._counter[act] = (self._counter[act] + 1) % self.multistep
-        self.replanned = rows.tolist()
+        self._warm[rows] = True
+        self.replanned, self.replanned_warm = rows.tolist(), warm.tolist()
         return out
 
 
