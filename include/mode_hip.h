@@ -815,6 +815,20 @@ int mode_maxpool_nhwc_bwd(const void* dy, const uint8_t* argmax, int dtype, int 
  *   [2], [3]    device address of this step's [num_envs, A] fp32 action output, low word first
  *   [4, 4 + NW)                 active bitmask, NW = ceil(num_envs / 32): bit b % 32 of word b / 32 = environment b is active
  *   [4 + NW, 4 + NW + num_envs) rows
+ *   [4 + NW + num_envs, 4 + 2 NW + num_envs)  candidate selection only (below): has-previous-plan bitmask, laid out like the active bitmask.  The
+ *                               caller allocates the longer block; no other entry point reads past `rows`.
+ *
+ * Candidate selection (mode_env_gather_*_cand, mode_env_select; rollout.VectorEnvPolicy(candidates=N); an addition to ABI 13).  A replan draws N
+ * candidate plans and keeps the one closest to what the environment's previous plan P predicted for the coming steps (the backward-coherence
+ * criterion of Bidirectional Decoding).  The chunk runs at batch m_b * N, environment-major: chunk row j * N + c is candidate c of rows[j], and
+ * its latent is the stream element z(seeds[r], draws[r] * N + c, e), the index in uint32 arithmetic modulo 2^32; a replan still advances draws[r]
+ * by one, so candidates of different replans never share a draw.  With shift = multistep, L = W - shift and a caller-supplied table weights[L]
+ * (rollout.coherence_weights: (float)(rho ^ w), the device evaluates no transcendental), candidate c scores, in fp32,
+ *   score_c = sum_{w < L} weights[w] * sum_a (X_c[w][a] - P[w + shift][a])^2
+ * each term accumulated as fma(weights[w], d * d, acc) by the lane that owns element w * A + a (elements 64 apart), the 64 partial sums then
+ * added pairwise by wave shuffles.  The selected candidate has the smallest score; the lowest index wins ties; a NaN score never beats a
+ * non-NaN one; if every score is NaN candidate 0 is selected.  An environment whose has-previous-plan bit is clear scores exactly 0 for every
+ * candidate and so selects candidate 0.
  * ------------------------------------------------------------------------------------------------------------------ */
 #define MODE_ENV_MAX 1024
 
@@ -835,6 +849,18 @@ int mode_env_gather_noise(const int32_t* rows, int m_b, int num_envs, const uint
 int mode_env_gather_warm(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
                          const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
                          float* img_out, float* goal_out, float* x0, const float* plan, int W, int A, int shift, float sigma_start, void* stream);
+
+/* The two gathers with a candidate axis (one launch each, grid (m_b, N)): for j < m_b, c < N, r = rows[j] (out-of-range entries leave the N rows
+ * of j untouched), img_out[j * N + c] = state_images[r], goal_out[j * N + c] = goals[r], and x0[j * N + c] is the latent of the form above with
+ * draw index draws[r] * N + c (uint32, modulo 2^32).  N = 1 is mode_env_gather_noise / mode_env_gather_warm.  MODE_ERR_BAD_ARG as their
+ * siblings, and for N outside [1, 64]. */
+int mode_env_gather_noise_cand(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
+                               const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
+                               float* img_out, float* goal_out, float* x0, int noise_floats, float sigma_max, int N, void* stream);
+int mode_env_gather_warm_cand(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
+                              const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
+                              float* img_out, float* goal_out, float* x0, const float* plan, int W, int A, int shift, float sigma_start, int N,
+                              void* stream);
 
 /* Gather of the replanning environments' camera frames into the perceptual encoders' input (one launch, both cameras; rollout.VectorEnvPolicy
  * with raw observations).  For j < m_b, r = rows[j] (the control block's rows; entries outside [0, num_envs) leave row j untouched) and each
@@ -902,6 +928,27 @@ typedef struct ModeEnvEnsDesc {
  * and its draw index advances by one; then every active environment writes the weighted mean above and advances counter = (counter + 1) % s
  * and t = t + 1; every inactive one writes a zero row and keeps both.  MODE_ERR_BAD_ARG as its sibling, and when K != ceil(W / multistep). */
 int mode_env_commit_emit_ens(const ModeEnvEnsDesc* d, void* stream);
+
+/* Selection among the N candidates of every replanning row (one launch, one workgroup per row j < m_b; the formula and the rule above).  For
+ * r = rows[j] in [0, num_envs) - other entries leave everything of row j untouched, and with `count` set so do the rows j >= *count -:
+ *   scores[r][c] = score_c of chunk[j * N + c] against plan[r] (0 when bit r of has_prev is clear), selected[r] = the selected candidate,
+ *   chosen[j]    = chunk[j * N + selected[r]], W * A floats, bit for bit
+ * so that mode_env_commit_emit(_ens) with pool.chunk = chosen commits the selected plans.  Padding rows that repeat a real row write the same
+ * values again.  plan is only read.  MODE_ERR_BAD_ARG, before any launch: a NULL desc or pointer (count may be NULL), N outside [1, 64], W <= 0,
+ * A <= 0, W * A > 4096, shift outside [1, W - 1], m_b <= 0, num_envs <= 0. */
+typedef struct ModeEnvSelectDesc {
+  const int32_t* rows;                   /* [m_b] device (the control block's rows) */
+  const uint32_t* has_prev;              /* [ceil(num_envs / 32)] device bitmask: environment b has a previous plan (the control block's extension) */
+  const int32_t* count;                  /* device, or NULL: the first *count rows are real, the others are skipped (the control block's [0]) */
+  const float* chunk;                    /* [m_b * N, W, A] the chain's result */
+  const float* plan;                     /* [num_envs, W, A] the previous plans */
+  const float* weights;                  /* [W - shift] device */
+  float* chosen;                         /* [m_b, W, A] */
+  int32_t* selected;                     /* [num_envs] */
+  float* scores;                         /* [num_envs, N] */
+  int32_t m_b, num_envs, W, A, shift, N;
+} ModeEnvSelectDesc;
+int mode_env_select(const ModeEnvSelectDesc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Classifier-free guidance (GCDenoiser(guidance_scale=w)).  An addition to ABI 13: new structs that wrap the old ones and new exports, nothing

@@ -1,7 +1,9 @@
 // Per-environment replanning of a vectorised rollout (include/mode_hip.h, ABI 13; rollout.VectorEnvPolicy): the gather of the replanning
 // environments' observations with their initial noise - or, warm-started, their previous plan's tail noised to an intermediate level - into a
 // chunk's input buffers, and the commit of the chunk's plans + the emission of one action per active environment - the newest plan's row, or with temporal ensembling the weighted mean of the rows that the environment's last K
-// plans predict for the step (env_commit_emit_ens_kernel).  Both move a few hundred KB at most: one launch each, plain coalesced loops, no LDS.  The gather of the
+// plans predict for the step (env_commit_emit_ens_kernel).  With candidate selection (rollout.VectorEnvPolicy(candidates=N)) the gathers fill N
+// rows per environment and env_select_kernel picks, between the chain and the commit, the candidate closest to the previous plan's tail (staged in LDS).
+// All move a few hundred KB at most: one launch each, plain coalesced loops, no LDS beside that tail.  The gather of the
 // replanning environments' camera frames into the encoders' input (mode_env_gather_frames) moves ~1.2 MB per fp32 row at 224 x 224: HBM-bound,
 // 16-byte loads and stores.
 #include "mode_common.h"
@@ -33,15 +35,17 @@ __device__ __forceinline__ void env_gather_obs(const int r, const int j, const f
   }
 }
 
+// Both gathers run on grid (m_b, N): block (j, c) fills chunk row j * N + c, candidate c of environment rows[j], from draw draws[r] * N + c of
+// its stream (uint32 arithmetic).  N = 1 - a replan without candidate selection - is row j from draw draws[r].
 __global__ __launch_bounds__(256) void env_gather_noise_kernel(const int32_t* __restrict__ rows, int num_envs, const uint32_t* __restrict__ seeds,
                                                                const uint32_t* __restrict__ draws, const float* __restrict__ img, long img_floats,
                                                                const float* __restrict__ goals, long goal_floats, float* __restrict__ img_out,
                                                                float* __restrict__ goal_out, float* __restrict__ x0, int noise_floats, float sigma_max) {
-  const int j = blockIdx.x;
-  const int r = rows[j];
+  const int r = rows[blockIdx.x];
   if (r < 0 || r >= num_envs) return;
+  const int j = blockIdx.x * gridDim.y + blockIdx.y;
   env_gather_obs(r, j, img, img_floats, goals, goal_floats, img_out, goal_out);
-  const uint32_t k = mode_stream_seed(seeds[r], draws[r]);
+  const uint32_t k = mode_stream_seed(seeds[r], draws[r] * gridDim.y + blockIdx.y);
   float* dst = x0 + (long)j * noise_floats;
   for (int e = threadIdx.x; e < noise_floats; e += 256) dst[e] = sigma_max * env_normal(k, (uint32_t)e);
 }
@@ -54,11 +58,11 @@ __global__ __launch_bounds__(256) void env_gather_warm_kernel(const int32_t* __r
                                                               const float* __restrict__ goals, long goal_floats, float* __restrict__ img_out,
                                                               float* __restrict__ goal_out, float* __restrict__ x0, const float* __restrict__ plan, int W,
                                                               int A, int shift, float sigma_start) {
-  const int j = blockIdx.x;
-  const int r = rows[j];
+  const int r = rows[blockIdx.x];
   if (r < 0 || r >= num_envs) return;
+  const int j = blockIdx.x * gridDim.y + blockIdx.y;
   env_gather_obs(r, j, img, img_floats, goals, goal_floats, img_out, goal_out);
-  const uint32_t k = mode_stream_seed(seeds[r], draws[r]);
+  const uint32_t k = mode_stream_seed(seeds[r], draws[r] * gridDim.y + blockIdx.y);
   const int WA = W * A;
   const float* old = plan + (long)r * WA;
   float* dst = x0 + (long)j * WA;
@@ -253,16 +257,84 @@ __global__ __launch_bounds__(64) void env_commit_emit_ens_kernel(ModeEnvEnsDesc 
   }
 }
 
+// Candidate selection (ModeEnvSelectDesc; the formula and the rule: include/mode_hip.h).  One workgroup of four waves per replanning row j.  The
+// previous plan's tail - the L * A floats from row `shift` on, at most 16 KB - is staged in LDS once; the waves take the N candidates round-robin,
+// a wave's lanes run the L * A elements coalesced and add their partial sums by shuffles; thread 0 takes the argmin of the <= 64 scores; then
+// every thread copies the winner's W * A floats.  At most N * 16 KB read per row: latency-bound, plain loops.
+__global__ __launch_bounds__(256) void env_select_kernel(ModeEnvSelectDesc d) {
+  __shared__ float tail[4096];
+  __shared__ float score[64];
+  __shared__ int winner;
+  const int j = blockIdx.x, tid = threadIdx.x;
+  const int r = d.rows[j];
+  if (r < 0 || r >= d.num_envs || (d.count && j >= d.count[0])) return;          // (uniform over the workgroup)
+  const int N = d.N, WA = d.W * d.A, LA = (d.W - d.shift) * d.A;
+  const bool has_prev = (d.has_prev[r >> 5] >> (r & 31)) & 1u;
+  const float* prev = d.plan + (long)r * WA + d.shift * d.A;
+  for (int e = tid; e < LA; e += 256) tail[e] = prev[e];
+  __syncthreads();
+  const int wave = tid >> 6, lane = tid & 63;
+  for (int c = wave; c < N; c += 4) {
+    float acc = 0.f;
+    if (has_prev) {
+      const float* x = d.chunk + ((long)j * N + c) * WA;
+      for (int e = lane; e < LA; e += 64) {
+        const float df = x[e] - tail[e];
+        acc = fmaf(d.weights[e / d.A], df * df, acc);
+      }
+      for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    }
+    if (lane == 0) score[c] = acc;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int best = 0;
+    float bs = score[0];
+    for (int c = 1; c < N; ++c) {
+      const float v = score[c];
+      if (v < bs || (bs != bs && v == v)) { best = c; bs = v; }                 // strict: the lowest index wins ties; a NaN only loses
+    }
+    winner = best;
+    d.selected[r] = best;
+  }
+  if (tid < N) d.scores[(long)r * N + tid] = score[tid];
+  __syncthreads();
+  const float* src = d.chunk + ((long)j * N + winner) * WA;
+  float* dst = d.chosen + (long)j * WA;
+  for (int e = tid; e < WA; e += 256) dst[e] = src[e];
+}
+
 }  // namespace mode
 
 using namespace mode;
 
+extern "C" int mode_env_gather_noise_cand(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
+                                          const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
+                                          float* img_out, float* goal_out, float* x0, int noise_floats, float sigma_max, int N, void* stream) {
+  if (!rows || !seeds || !draws || !x0 || m_b <= 0 || num_envs <= 0 || noise_floats <= 0 || img_floats < 0 || goal_floats < 0) return MODE_ERR_BAD_ARG;
+  if (N < 1 || N > 64) return MODE_ERR_BAD_ARG;
+  hipLaunchKernelGGL(env_gather_noise_kernel, dim3(m_b, N), dim3(256), 0, (hipStream_t)stream, rows, num_envs, seeds, draws, state_images, (long)img_floats,
+                     goals, (long)goal_floats, img_out, goal_out, x0, noise_floats, sigma_max);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
 extern "C" int mode_env_gather_noise(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
                                      const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
                                      float* img_out, float* goal_out, float* x0, int noise_floats, float sigma_max, void* stream) {
-  if (!rows || !seeds || !draws || !x0 || m_b <= 0 || num_envs <= 0 || noise_floats <= 0 || img_floats < 0 || goal_floats < 0) return MODE_ERR_BAD_ARG;
-  hipLaunchKernelGGL(env_gather_noise_kernel, dim3(m_b), dim3(256), 0, (hipStream_t)stream, rows, num_envs, seeds, draws, state_images, (long)img_floats,
-                     goals, (long)goal_floats, img_out, goal_out, x0, noise_floats, sigma_max);
+  return mode_env_gather_noise_cand(rows, m_b, num_envs, seeds, draws, state_images, img_floats, goals, goal_floats, img_out, goal_out, x0, noise_floats,
+                                    sigma_max, 1, stream);
+}
+
+extern "C" int mode_env_gather_warm_cand(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
+                                         const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
+                                         float* img_out, float* goal_out, float* x0, const float* plan, int W, int A, int shift, float sigma_start,
+                                         int N, void* stream) {
+  if (!rows || !seeds || !draws || !x0 || !plan || m_b <= 0 || num_envs <= 0 || img_floats < 0 || goal_floats < 0) return MODE_ERR_BAD_ARG;
+  if (W <= 0 || A <= 0 || (long)W * A > 4096 || shift < 1 || shift >= W || !(sigma_start >= 0.f) || !(sigma_start <= FLT_MAX)) return MODE_ERR_BAD_ARG;
+  if (N < 1 || N > 64) return MODE_ERR_BAD_ARG;
+  hipLaunchKernelGGL(env_gather_warm_kernel, dim3(m_b, N), dim3(256), 0, (hipStream_t)stream, rows, num_envs, seeds, draws, state_images, (long)img_floats,
+                     goals, (long)goal_floats, img_out, goal_out, x0, plan, W, A, shift, sigma_start);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }
@@ -271,10 +343,15 @@ extern "C" int mode_env_gather_warm(const int32_t* rows, int m_b, int num_envs, 
                                     const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
                                     float* img_out, float* goal_out, float* x0, const float* plan, int W, int A, int shift, float sigma_start,
                                     void* stream) {
-  if (!rows || !seeds || !draws || !x0 || !plan || m_b <= 0 || num_envs <= 0 || img_floats < 0 || goal_floats < 0) return MODE_ERR_BAD_ARG;
-  if (W <= 0 || A <= 0 || (long)W * A > 4096 || shift < 1 || shift >= W || !(sigma_start >= 0.f) || !(sigma_start <= FLT_MAX)) return MODE_ERR_BAD_ARG;
-  hipLaunchKernelGGL(env_gather_warm_kernel, dim3(m_b), dim3(256), 0, (hipStream_t)stream, rows, num_envs, seeds, draws, state_images, (long)img_floats,
-                     goals, (long)goal_floats, img_out, goal_out, x0, plan, W, A, shift, sigma_start);
+  return mode_env_gather_warm_cand(rows, m_b, num_envs, seeds, draws, state_images, img_floats, goals, goal_floats, img_out, goal_out, x0, plan, W, A,
+                                   shift, sigma_start, 1, stream);
+}
+
+extern "C" int mode_env_select(const ModeEnvSelectDesc* d, void* stream) {
+  if (!d || !d->rows || !d->has_prev || !d->chunk || !d->plan || !d->weights || !d->chosen || !d->selected || !d->scores) return MODE_ERR_BAD_ARG;
+  if (d->N < 1 || d->N > 64 || d->W <= 0 || d->A <= 0 || (long)d->W * d->A > 4096 || d->shift < 1 || d->shift >= d->W || d->m_b <= 0 || d->num_envs <= 0)
+    return MODE_ERR_BAD_ARG;
+  hipLaunchKernelGGL(env_select_kernel, dim3(d->m_b), dim3(256), 0, (hipStream_t)stream, *d);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }

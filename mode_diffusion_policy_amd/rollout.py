@@ -291,6 +291,12 @@ def ensemble_weights(m: float, depth: int) -> np.ndarray:
     return np.exp(-float(m) * np.arange(depth, dtype=np.float64)).astype(np.float32)
 
 
+def coherence_weights(rho: float, length: int) -> np.ndarray:
+    """The weight table of candidate selection (``VectorEnvPolicy(candidates=N, coherence_decay=rho)``), ``w_i = rho ** i`` for the i-th coming
+    step: the fp64 power rounded to fp32, ``length`` entries.  The kernel reads this table and evaluates no transcendental itself."""
+    return (float(rho) ** np.arange(length, dtype=np.float64)).astype(np.float32)
+
+
 @torch.no_grad()
 def env_noise(seeds, draws, act_window_size: int, action_dim: int, sigma_max: float, device="cuda") -> torch.Tensor:
     """The initial latents ``VectorEnvPolicy`` plans from: row i = draw ``draws[i]`` of the noise stream with seed ``seeds[i]`` times ``sigma_max``,
@@ -336,6 +342,58 @@ def env_warm_latents(plans: torch.Tensor, seeds, draws, shift: int, sigma_start:
         L.check(L.load().mode_env_gather_warm(rows.data_ptr(), n, n, s.data_ptr(), d.data_ptr(), None, 0, None, 0, None, None, x.data_ptr(),
                                               old.data_ptr(), W, A, int(shift), float(sigma_start), _stream()), "env_gather_warm")
     return x
+
+
+def _mask_words(mask: np.ndarray, nw: int) -> np.ndarray:
+    """A host bool vector as ``nw`` little-endian uint32 words, bit b % 32 of word b // 32 = entry b (the control block's bitmasks)."""
+    bits = np.packbits(mask, bitorder="little")
+    return np.pad(bits, (0, 4 * nw - bits.size)).view("<u4")
+
+
+@torch.no_grad()
+def select_coherent(chunk: torch.Tensor, prev: torch.Tensor, has_prev, shift: int, weights):
+    """The candidate selection of ``VectorEnvPolicy(candidates=N)`` on explicit rows (csrc/env_pool.hip; formula: include/mode_hip.h): ``chunk``
+    (n, N, W, A) holds N candidate plans per row, ``prev`` (n, W, A) the rows' previous plans, ``has_prev`` n host bools, 1 <= shift < W,
+    ``weights`` the W - shift weights of the coming steps (``coherence_weights``).  Candidate c of row i scores
+    ``sum_w weights[w] * sum_a (chunk[i, c, w, a] - prev[i, w + shift, a]) ** 2`` in fp32 (0 where ``has_prev[i]`` is false); the smallest score
+    is selected, the lowest index on ties, a NaN score only when every score is NaN (then candidate 0).  Returns ``(chosen (n, W, A) fp32,
+    selected (n,) int32, scores (n, N) fp32)`` on the inputs' device."""
+    from . import _lib as L
+    from .engine import _stream
+    if not torch.is_tensor(chunk) or chunk.dim() != 4 or chunk.numel() == 0:
+        raise ValueError(f"select_coherent: chunk must be a non-empty (n, N, W, A) tensor, got {tuple(getattr(chunk, 'shape', ()))}")
+    n, N, W, A = chunk.shape
+    if not 1 <= N <= 64:
+        raise ValueError(f"select_coherent: the number of candidates N must be in [1, 64], got {N}")
+    if W * A > 4096:
+        raise ValueError(f"select_coherent: W * A must be at most 4096, got {W} * {A}")
+    if not torch.is_tensor(prev) or tuple(prev.shape) != (n, W, A):
+        raise ValueError(f"select_coherent: prev must be ({n}, {W}, {A}), one previous plan per row, got {tuple(getattr(prev, 'shape', ()))}")
+    has = np.asarray(has_prev.cpu() if torch.is_tensor(has_prev) else has_prev)
+    if has.dtype != np.bool_ or has.shape != (n,):
+        raise ValueError(f"select_coherent: has_prev must be {n} host bools, got {has.dtype} {has.shape}")
+    if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not 1 <= int(shift) <= W - 1:
+        raise ValueError(f"select_coherent: shift must be an int in [1, W - 1] = [1, {W - 1}], got {shift!r}")
+    wt = np.asarray(weights.cpu() if torch.is_tensor(weights) else weights, dtype=np.float32).reshape(-1)
+    if wt.size != W - int(shift):
+        raise ValueError(f"select_coherent: weights must have W - shift = {W - int(shift)} entries, got {wt.size}")
+    if chunk.device.type != "cuda" or prev.device != chunk.device:
+        raise ValueError("select_coherent: chunk and prev must be on one ROCm device")
+    dev = chunk.device
+    x, old = chunk.to(torch.float32).contiguous(), prev.to(torch.float32).contiguous()
+    nw = (n + 31) // 32
+    rows = torch.arange(n, dtype=torch.int32, device=dev)
+    mask = torch.from_numpy(_mask_words(has, nw).view("<i4").copy()).to(dev)
+    wdev = torch.from_numpy(wt.copy()).to(dev)
+    chosen = torch.empty(n, W, A, dtype=torch.float32, device=dev)
+    selected = torch.empty(n, dtype=torch.int32, device=dev)
+    scores = torch.empty(n, N, dtype=torch.float32, device=dev)
+    d = L.ModeEnvSelectDesc(rows=rows.data_ptr(), has_prev=mask.data_ptr(), count=None, chunk=x.data_ptr(), plan=old.data_ptr(),
+                            weights=wdev.data_ptr(), chosen=chosen.data_ptr(), selected=selected.data_ptr(), scores=scores.data_ptr(), m_b=n,
+                            num_envs=n, W=W, A=A, shift=int(shift), N=N)
+    with torch.cuda.device(dev):
+        L.check(L.load().mode_env_select(C.byref(d), _stream()), "env_select")
+    return chosen, selected, scores
 
 
 class VectorEnvPolicy(ChunkedRolloutPolicy):
@@ -396,13 +454,59 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
     This holds for the ensembled kernel as well, so ``temporal_ensemble`` combines with it; the warm start then reads ``plans``, the newest
     plan, not the ensembled trajectory.  ``guidance_scale`` needs nothing extra.  ``replanned_warm``: the warm ones among ``replanned``.  What
     warm-started plans do to task success is NOT measured in this repository (no trained checkpoint, no simulator): only the mechanics - exact
-    latents, schedule and bookkeeping - and the cost (profiles/vector_env_warm_start.txt) are pinned."""
+    latents, schedule and bookkeeping - and the cost (profiles/vector_env_warm_start.txt) are pinned.
+
+    ``candidates=N`` (an int, 2 <= N <= 64, with ``multistep = s < act_window_size = W`` and ``num_envs * N <= MODE_ENV_MAX``; None, the default,
+    and 1 are everything above unchanged: the same code paths, launches, draws and results) draws N candidate plans per replan and keeps the one
+    closest to what the environment's previous plan predicted for the coming steps (the backward-coherence criterion of Bidirectional Decoding,
+    Liu et al.).  A replan at bucket mb runs its chunk at batch mb * N, environment-major: chunk row j * N + c is candidate c of the j-th
+    replanner, its observation and goal rows written N times, its latent the stream element ``z(seed, draws[b] * N + c)`` (uint32 arithmetic)
+    - a replan still advances ``draws[b]`` by one, so ``env_noise`` / ``env_warm_latents`` reproduce any candidate from (seed, draw, c).  With
+    P = ``plans[b]`` (the newest plan, also under ensembling), L = W - s and ``wt = coherence_weights(coherence_decay, L)`` (``coherence_decay`` a
+    finite float in (0, 1], default 0.5, only legal with ``candidates``), candidate c scores ``sum_{w<L} wt[w] * sum_a (X_c[w, a] - P[w + s, a])**2``
+    in fp32; the smallest score is selected, the lowest index on ties, a NaN score never before a non-NaN one (all NaN: candidate 0).  An
+    environment with no plan committed since its last ``reset`` scores 0 for every candidate and takes candidate 0.  The selection is one more
+    kernel inside the chunk's graph, between the chain and the commit (csrc/env_pool.hip; ``select_coherent`` runs it on explicit rows); which
+    replanners have a previous plan travels in the control block, so a replanning step is still one H2D copy, one gather launch and one replay
+    per chunk kind, with no host sync.  The selected plan is what is committed and emitted; everything downstream - counter, ring slot and birth
+    under ``temporal_ensemble``, ``plans`` - is unchanged.  ``selected`` (num_envs,) int32, -1 before any replan, and ``candidate_scores``
+    (num_envs, N) expose the last replan's choice.  With ``warm_start=k`` a warm replan's candidates are ``env_warm_latents(plans[b], seed,
+    draws[b] * N + c, s, sigmas[k])`` through the sub-schedule; with raw frames the encoders still run once per environment at batch mb * T and
+    their rows are broadcast to the N candidate rows inside the encoder graph.  Known cost: a cold replan (an episode's first) also runs N
+    candidates and keeps the first - running cold chunks at N = 1 would need a second family of graphs.  What candidate selection does to task
+    success is NOT measured in this repository: only the mechanics and the cost (profiles/vector_env_candidates.txt) are pinned."""
 
     def __init__(self, denoiser, num_envs: int, seed: int = 0, extra_args: Optional[dict] = None, temporal_ensemble: Optional[float] = None,
-                 warm_start: Optional[int] = None, **kw):
+                 warm_start: Optional[int] = None, candidates: Optional[int] = None, coherence_decay: Optional[float] = None, **kw):
         from . import _lib as L
         from .modedit import MoDeDiT
         sampler = kw.get("sampler_type", "ddim")
+        self.candidates, self.coherence_decay, self._ncand = None, None, 1
+        if candidates is not None:
+            W, s = int(kw.get("act_window_size", 10)), int(kw.get("multistep", 10))
+            if isinstance(candidates, bool) or not isinstance(candidates, (int, np.integer)) or not 1 <= int(candidates) <= 64:
+                raise ValueError(f"candidates must be None or an int in [1, 64], got {candidates!r}")
+            self.candidates = int(candidates)
+            if self.candidates > 1:
+                if not s < W:
+                    raise ValueError(f"candidates scores each candidate against the unexecuted tail of the previous plan: it needs multistep < "
+                                     f"act_window_size, got multistep={s}, act_window_size={W}")
+                if isinstance(num_envs, (int, np.integer)) and int(num_envs) * self.candidates > L.MODE_ENV_MAX:
+                    raise ValueError(f"num_envs * candidates must be at most {L.MODE_ENV_MAX} (the largest batch a chunk runs at), got "
+                                     f"{int(num_envs)} * {self.candidates}")
+                self._ncand = self.candidates
+        if coherence_decay is not None:
+            if candidates is None:
+                raise ValueError("coherence_decay weighs the candidates' scores: it is only legal with candidates=N")
+            try:
+                rho = float(coherence_decay)
+            except (TypeError, ValueError):
+                rho = float("nan")
+            if isinstance(coherence_decay, bool) or not (np.isfinite(rho) and 0.0 < rho <= 1.0):
+                raise ValueError(f"coherence_decay must be a finite float in (0, 1], got {coherence_decay!r}")
+            self.coherence_decay = rho
+        elif candidates is not None:
+            self.coherence_decay = 0.5
         self.warm_start = None
         if warm_start is not None:
             n_steps, W, s = int(kw.get("num_sampling_steps", 10)), int(kw.get("act_window_size", 10)), int(kw.get("multistep", 10))
@@ -450,6 +554,13 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         self._draws = torch.zeros(n, dtype=torch.int32, device=dev)          # uint32 bit patterns
         self._seeds = _u32_as_i32(range(seed, seed + n)).to(dev)
         nctrl = 4 + self._nw + n                                             # control block: include/mode_hip.h (ABI 13)
+        self._sel = None
+        if self._ncand > 1:
+            # candidate selection: the control block grows by the has-previous-plan bitmask behind the rows; the last selection per environment
+            nctrl += self._nw
+            self._selected = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            self._cand_scores = torch.zeros(n, self._ncand, dtype=torch.float32, device=dev)
+            self._coh_w = torch.from_numpy(coherence_weights(self.coherence_decay, W - self.multistep)).to(dev)
         self._ctrl = torch.zeros(nctrl, dtype=torch.int32, device=dev)
         # pinned staging of the control block, a ring: a slot is rewritten only after the copy that read it has run (its event)
         self._ring = [torch.zeros(nctrl, dtype=torch.int32, pin_memory=True) for _ in range(4)]
@@ -458,6 +569,10 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         self._scratch_out = torch.zeros(n, A, dtype=torch.float32, device=dev)
         self._desc = L.ModeEnvPoolDesc(num_envs=n, W=W, A=A, multistep=self.multistep, plan=self._plan.data_ptr(),
                                        counter=self._counter_dev.data_ptr(), draws=self._draws.data_ptr())
+        if self._ncand > 1:
+            self._sel = L.ModeEnvSelectDesc(rows=self._rows_ptr(), has_prev=self._rows_ptr() + 4 * n, count=self._ctrl.data_ptr(),
+                                            plan=self._plan.data_ptr(), weights=self._coh_w.data_ptr(), selected=self._selected.data_ptr(),
+                                            scores=self._cand_scores.data_ptr(), num_envs=n, W=W, A=A, shift=self.multistep, N=self._ncand)
         self._ens = None
         if self.temporal_ensemble is not None:
             # the ring of each environment's last K plans with their birth times, the local times and the weight table: allocated here, once
@@ -515,8 +630,7 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         return a
 
     def _active_words(self, act: np.ndarray) -> np.ndarray:
-        bits = np.packbits(act, bitorder="little")
-        return np.pad(bits, (0, 4 * self._nw - bits.size)).view("<u4")
+        return _mask_words(act, self._nw)
 
     def reset(self, envs=None, seeds=None) -> None:
         """Start a new episode in the listed environments (see the class docstring)."""
@@ -547,6 +661,21 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
     def draws(self) -> torch.Tensor:
         """[num_envs] int32 (uint32 bit patterns): the draw index each environment's next replan takes (device)."""
         return self._draws
+
+    def _cand_state(self, name: str) -> torch.Tensor:
+        if self._sel is None:
+            raise AttributeError("this policy was built without candidates (or with candidates=1): every replan draws one plan")
+        return getattr(self, name)
+
+    @property
+    def selected(self) -> torch.Tensor:
+        """[num_envs] int32: the candidate chosen at every environment's last replan, -1 before any (device, ``candidates`` only)."""
+        return self._cand_state("_selected")
+
+    @property
+    def candidate_scores(self) -> torch.Tensor:
+        """[num_envs, candidates] fp32: the scores of every environment's last replan (device, ``candidates`` only)."""
+        return self._cand_state("_cand_scores")
 
     def _ens_state(self, name: str) -> torch.Tensor:
         if self._ens is None:
@@ -645,6 +774,8 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         buf[2:4] = np.array([out_ptr], dtype="<u8").view("<i4")
         buf[4:4 + nw] = self._active_words(act).view("<i4")
         buf[4 + nw:4 + nw + len(rows)] = rows
+        if self._sel is not None:                 # who has a plan to be coherent with: committed since its last reset, as of before this step
+            buf[4 + nw + self.num_envs:] = _mask_words(self._warm, nw).view("<i4")
         self._ctrl.copy_(self._ring[i], non_blocking=True)
         self._ring_ev[i].record()
 
@@ -658,10 +789,20 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         img, gl, frames = self._inputs
         inner = self.model.inner_model
         x = ent["bufs"][0]
-        rows = (self._rows_ptr(), x.shape[0], self.num_envs, self._seeds.data_ptr(), self._draws.data_ptr(),
+        N = self._ncand
+        rows = (self._rows_ptr(), x.shape[0] // N, self.num_envs, self._seeds.data_ptr(), self._draws.data_ptr(),
                 None if img is None else img.data_ptr(), inner.n_img_tokens * inner.obs_dim, gl.data_ptr(), inner.goal_dim,
                 None if img is None else ent["img"].data_ptr(), ent["goals"].data_ptr(), x.data_ptr())
-        if warm:
+        if N > 1:                                                            # candidates: N rows per environment, draw index draws * N + c
+            if "chosen" not in ent:                                          # (a new entry: this call is ahead of its capture)
+                ent["chosen"] = torch.zeros(x.shape[0] // N, *x.shape[1:], dtype=torch.float32, device=x.device)
+            if warm:
+                L.check(self._lib.mode_env_gather_warm_cand(*rows, self._plan.data_ptr(), self.act_window_size, self.action_dim, self.multistep,
+                                                            self._warm_schedule(x.device)[1], N, _stream()), "env_gather_warm_cand")
+            else:
+                L.check(self._lib.mode_env_gather_noise_cand(*rows, self.act_window_size * self.action_dim, float(self.sigma_max), N, _stream()),
+                        "env_gather_noise_cand")
+        elif warm:
             L.check(self._lib.mode_env_gather_warm(*rows, self._plan.data_ptr(), self.act_window_size, self.action_dim, self.multistep,
                                                    self._warm_schedule(x.device)[1], _stream()), "env_gather_warm")
         else:
@@ -710,7 +851,8 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         encoder graph (captured on first use, and again when the frame geometry, the weights' storage or the chunk entry's buffers moved), or
         the eager towers when the encoders are in training mode / MODE_HIP_GRAPH=0.  ``store``: the encoder store of the chunk's kind."""
         enc = self.encoders
-        mb, n_img = ent["goals"].shape[0], self.model.inner_model.n_img_tokens
+        N = self._ncand
+        mb, n_img = ent["goals"].shape[0] // N, self.model.inner_model.n_img_tokens
         dts = self._frame_dtypes(frames)
         shapes = [tuple(f.shape[1:]) for f in frames]                      # of one environment's gathered frames
         if self.camera_transforms is not None:
@@ -721,17 +863,23 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
             st = store[mb] = dict(geom=geom, graph=None,
                                             bufs=tuple(torch.empty(mb, *shp, dtype=dt, device=f.device) for f, shp, dt in zip(frames, shapes, dts)))
         self._gather_frames(mb, frames, st["bufs"])
-        goals = ent["goals"]
+        goals, img = ent["goals"], ent["img"]
+        if N == 1:
+            towers = lambda: img.copy_(enc._eager(st["bufs"][0], st["bufs"][1], goals).view(mb, n_img, -1))
+        else:
+            # candidates: the towers run once per environment at batch mb * T, FiLM on a contiguous copy of the mb goal rows (the first of each
+            # environment's N); the mb embedding rows are then broadcast to the environment's N candidate rows
+            def towers():
+                emb = enc._eager(st["bufs"][0], st["bufs"][1], goals.view(mb, N, -1)[:, 0].contiguous())
+                img.view(mb, N, n_img, -1).copy_(emb.view(mb, 1, n_img, -1).expand(mb, N, n_img, -1))
         if enc.static_resnet.training or enc.gripper_resnet.training or not graphs_enabled():
-            ent["img"].copy_(enc._eager(st["bufs"][0], st["bufs"][1], goals).view(mb, n_img, -1))
+            towers()
             return
         wdt = enc.autocast_dtype if enc.autocast_dtype is not None else dts[0]
         key = (wdt, enc._param_key(), ent["img"].data_ptr(), goals.data_ptr())
         if st["graph"] is None or st["key"] != key:
             st["graph"] = None                                              # (the old graph's pool goes before the new capture)
-            img = ent["img"]
-            st["graph"], _, st["tables"] = enc.capture(lambda: img.copy_(enc._eager(st["bufs"][0], st["bufs"][1], goals).view(mb, n_img, -1)),
-                                                       img.device, wdt)
+            st["graph"], _, st["tables"] = enc.capture(towers, img.device, wdt)
             st["key"] = key
         enc._refresh(wdt)                                                   # weights whose version moved since the last replan: re-cast in place
         st["graph"].replay()
@@ -741,6 +889,16 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         replan and no active environment into a scratch row block: it loads the code object and changes nothing."""
         d = type(self._desc).from_buffer_copy(self._desc)
         d.chunk = ent["bufs"][0].data_ptr()
+        if self._sel is not None:
+            # candidates: between the chain and the commit, the selection of each real row's most coherent candidate into the entry's
+            # ``chosen`` rows, which the commit then takes for the chunk.  It reads the control block in the warm-up run too: there it writes,
+            # for the rows staged, what the replay writes again (no row when ``warmup`` staged none).
+            from . import _lib as L
+            from .engine import _stream
+            sel = type(self._sel).from_buffer_copy(self._sel)
+            sel.chunk, sel.chosen, sel.m_b = d.chunk, ent["chosen"].data_ptr(), ent["chosen"].shape[0]
+            L.check(self._lib.mode_env_select(C.byref(sel), _stream()), "env_select")
+            d.chunk = sel.chosen
         if capturing:
             d.ctrl = self._ctrl.data_ptr()
         else:
@@ -769,13 +927,13 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         sig = self._warm_schedule(eng.device)[0] if warm else self._schedule(eng.device)
         tpl = self._templates.get(mb)
         if tpl is None:
-            dev = eng.device
-            tpl = self._templates[mb] = ({"state_images": torch.zeros(mb, inner.n_img_tokens, inner.obs_dim, device=dev)},
-                                         torch.zeros(mb, self.act_window_size, self.action_dim, device=dev), torch.zeros(mb, inner.goal_dim, device=dev))
+            dev, B = eng.device, mb * self._ncand                           # (candidates: N chunk rows per environment)
+            tpl = self._templates[mb] = ({"state_images": torch.zeros(B, inner.n_img_tokens, inner.obs_dim, device=dev)},
+                                         torch.zeros(B, self.act_window_size, self.action_dim, device=dev), torch.zeros(B, inner.goal_dim, device=dev))
         w = getattr(self.model, "guidance_scale", None)                  # classifier-free guidance: the bucket's mb rows run as 2·mb inside the chain
         gkey, plan = inner._chunk_plan(eng, self._solver, sig.numel() - 1, w is not None)
         inner._sample_chunk(eng, gkey, plan, tpl[0], tpl[1], tpl[2], sig, float(self.model.sigma_data),
-                            hooks=self._hooks_warm if warm else self._hooks, rows=m, guidance=w)
+                            hooks=self._hooks_warm if warm else self._hooks, rows=m * self._ncand, guidance=w)
 
     @staticmethod
     def _prepared(img, gl, frames):
