@@ -118,6 +118,37 @@ class Guarded:
         return bool((self.buf[: self.pad] == CANARY).all()) and bool((self.buf[self.pad + self.t.numel():] == CANARY).all())
 
 
+class GuardedCols(Guarded):
+    """A Guarded [rows, ld] buffer whose logical output `out` is the columns [col0, col0 + cols) of every row: NaN-prefilled, every other column of
+    those rows holding the canary value like the rows around them.  `intact()`: neither the canary rows nor the pad columns were written."""
+
+    def __init__(self, rows, cols, ld, dtype=torch.float32, col0=0):
+        assert col0 + cols <= ld
+        super().__init__(rows, ld, dtype, fill=CANARY)
+        self.out = self.t[:, col0: col0 + cols]
+        self.out.fill_(float("nan"))
+        self.ld, self.cols, self.col0 = ld, cols, col0
+        assert self.out.data_ptr() % 16 == 0
+
+    def intact(self):
+        return super().intact() and bool((self.t[:, : self.col0] == CANARY).all()) and bool((self.t[:, self.col0 + self.cols:] == CANARY).all())
+
+
+def gemm_into(A, W, out, M, N, K, epilogue=L.EPI_NONE, bias=None, resid=None, a_rows=None, offsets=None, num_experts=0, w_estride=0, b_estride=0,
+              split_k=0, split_stride=0, flags=0, C2=None, gain=None, row_ss_out=None, row_ss=None, row_eps=0.0, lda=None, ldw=None):
+    """mode_gemm through a full descriptor into GuardedCols outputs; returns the status (the caller decides what it means).  A / W / resid may be column
+    slices of wider buffers (their row strides are the leading dimensions; W is the first expert's [Nw, K] view); out / C2: GuardedCols (ldc / ldc2 are their
+    widths); row_ss_out: a Guarded [M, N / group]; row_ss: [tokens, row_ss_n]."""
+    lib = L.load()
+    d = L.ModeGemmDesc(dtype=dt_of(A), epilogue=epilogue, out_dtype=dt_of(out.out), M=M, N=N, K=K, A=p(A), lda=lda if lda is not None else A.stride(0),
+                       W=p(W), ldw=ldw if ldw is not None else W.stride(0), w_expert_stride=w_estride, bias=p(bias), bias_expert_stride=b_estride,
+                       resid=p(resid), ldr=0 if resid is None else resid.stride(0), C=p(out.out), ldc=out.ld, a_rows=p(a_rows), expert_offsets=p(offsets),
+                       num_experts=num_experts, split_k=split_k, split_stride=split_stride, flags=flags, C2=p(C2 and C2.out), ldc2=C2.ld if C2 else 0,
+                       gain=p(gain), row_ss_out=p(row_ss_out and row_ss_out.t), row_ss=p(row_ss), row_ss_n=0 if row_ss is None else row_ss.shape[1],
+                       row_eps=row_eps)
+    return lib.mode_gemm(C.byref(d), stream())
+
+
 def launch_guard(D, *tensors, pos=None, n_sorted=None):
     """Host-side contract of the row kernels, asserted before every launch: D % 4 == 0, 16-byte aligned base pointers, pos inside [0, n_sorted)."""
     assert D % 4 == 0, D
