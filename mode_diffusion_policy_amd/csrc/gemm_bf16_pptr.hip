@@ -205,8 +205,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pptr_kernel(const PpTrParams p) {
     stage_half<decltype(OP_)::value, decltype(T_)::value, decltype(H_)::value>(smem, wave, g, o0, o1);
   };
   // weight gradient: half-tile of a [rows][cols] operand over the K rows [r0, r0 + 64) of the reduction range [.., ke): rows past the range read a
-  // zero row (A: they must contribute exactly 0) / a clamped, finite row (W)
-  auto stage_kn = [&](auto OP_, auto T_, auto H_, const char* colbase, long ld2, int r0, int ke) __attribute__((always_inline)) {
+  // zero row (A: they must contribute exactly 0) / a clamped, finite row (W).  An EMPTY range has no row of its own to clamp to (ke - 1 lies in the
+  // group before it, or - for a first group that starts above row 0 - outside every group, where the caller owes no finite value: 0 * NaN would make
+  // the all-zero C_z a NaN tile): its W operand comes from the zero row as well (`empty` is wave-uniform)
+  auto stage_kn = [&](auto OP_, auto T_, auto H_, const char* colbase, long ld2, int r0, int ke, bool empty) __attribute__((always_inline)) {
     constexpr int op = decltype(OP_)::value, t = decltype(T_)::value, h = decltype(H_)::value;
     constexpr int base = (op ? LDS_B : LDS_A) + (t * 2 + h) * HALF_BYTES;
 #pragma unroll
@@ -214,10 +216,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pptr_kernel(const PpTrParams p) {
       const int r = r0 + krow0 + 4 * q;
       const int rc = max(min(r, ke - 1), 0);
       const char* src = colbase + ((long)rc * ld2 + kn_cb);
-      if constexpr (op == 0) {
-        const char* z = reinterpret_cast<const char*>(g_pptr_zero_row) + (lane & 15) * 16;
-        src = r < ke ? src : z;
-      }
+      const char* z = reinterpret_cast<const char*>(g_pptr_zero_row) + (lane & 15) * 16;
+      if constexpr (op == 0) src = r < ke ? src : z;
+      else src = empty ? z : src;
       dma16(src, smem + base + (wave * 2 + q) * 1024);
     }
   };
@@ -242,12 +243,12 @@ __global__ __launch_bounds__(512, 2) void gemm_pptr_kernel(const PpTrParams p) {
   // stage half h of operand op for K-step k (counted from the tile's K origin) into buffer t
   auto stA = [&](auto T_, auto H_, int k) __attribute__((always_inline)) {
     constexpr int h = decltype(H_)::value;
-    if constexpr (A_KM) stage_kn(_0, T_, H_, Ak + h * 256, lda2, cur.kb + k * BKK, cur.ke);
+    if constexpr (A_KM) stage_kn(_0, T_, H_, Ak + h * 256, lda2, cur.kb + k * BKK, cur.ke, false);
     else stage(_0, T_, H_, Ak + (long)k * 128, a_off[h][0], a_off[h][1]);
   };
   auto stW = [&](auto T_, auto H_, const char* wbase, int k) __attribute__((always_inline)) {
     constexpr int h = decltype(H_)::value;
-    if constexpr (A_KM) stage_kn(_1, T_, H_, wbase + h * 256, ldw2, cur.kb + k * BKK, cur.ke);
+    if constexpr (A_KM) stage_kn(_1, T_, H_, wbase + h * 256, ldw2, cur.kb + k * BKK, cur.ke, cur.kb >= cur.ke);
     else stage(_1, T_, H_, wbase + (long)k * w_kstep + h * 256, b_off[0], b_off[1]);
   };
 
