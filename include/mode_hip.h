@@ -514,6 +514,48 @@ int mode_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, flo
 int mode_ema_update(float* ema, const float* p, int64_t n, float rate, void* stream);      /* stand-alone EMA pass (foreign optimizers) */
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Device-side gradient norms (an addition to ABI 13): per-tensor squared norms for logging (MoDEAgent.on_before_zero_grad,
+ * mode/models/mode_agent.py:304-363), global-norm clipping with torch.nn.utils.clip_grad_norm_'s definitions, and a step that
+ * leaves every buffer untouched when the gradient is not finite.  Nothing is read back: the AdamW launches read the state on the device.
+ *
+ * The flat gradient buffer is cut into CHUNKS of at most MODE_GRAD_CHUNK elements, none of which spans two tensors (the table is built
+ * on the host once; alignment padding, frozen tensors and the arena's dead region simply have no chunk).  Two stages:
+ *
+ * stage 1 (one workgroup of 256 threads per chunk, grid stride over chunks [first, first + count)):
+ *   partial[c] = sum of g[lo + i]^2, i < n, in a FIXED order: thread t owns the 16-byte groups t, t + 256, ... of the chunk and keeps one
+ *   fp32 accumulator per group lane (<= 16 additions each, squares rounded to fp32 first), adds them as (a0 + a1) + (a2 + a3), the 64
+ *   lanes of a wave combine in a 6-level butterfly, and thread 0 adds the 4 wave sums in ascending order through LDS.  No atomics: the
+ *   bits of partial[c] depend on the chunk's data alone - not on the grid, not on the launch the chunk was part of, not on the run.
+ *   A tail that is no multiple of 4 is read element by element; nothing at or beyond lo + n is touched.
+ * stage 2 (one workgroup): tensor_sq[t] = the partials [tensor_chunk_begin[t], tensor_chunk_begin[t + 1]) summed in ascending order in
+ *   fp64, stored as fp32; total = the tensors' fp64 sums in ascending tensor order; then
+ *     total_norm = |grad_scale| * sqrt(total)                       (the norm of the SCALED gradient, e.g. of the data-parallel average)
+ *     coef       = min(1, max_norm / (total_norm + 1e-6))           (max_norm <= 0: measure only, coef = 1)
+ *     scale      = grad_scale * coef                                (one fp32 multiply; what the AdamW launches multiply g by)
+ *     nonfinite  = !isfinite(total_norm);  skip = nonfinite && skip_nonfinite;  skipped += skip
+ *   Squares are formed in fp32 as torch does, so |g| above ~1.8e19 counts as non-finite. */
+#define MODE_GRAD_CHUNK 16384
+typedef struct ModeGradChunk {
+  int64_t lo;                            /* first element (offset into g), a multiple of 4: 16-byte aligned */
+  int32_t n;                             /* 0..MODE_GRAD_CHUNK elements of ONE tensor */
+  int32_t tensor;                        /* index of that tensor (informational: stage 2 goes by tensor_chunk_begin) */
+} ModeGradChunk;
+typedef struct ModeGradClipState {
+  float total_norm, coef, scale;
+  int32_t nonfinite, skip, skipped;      /* skipped: running count of skipped steps (never reset by the library) */
+  int32_t pad[2];
+} ModeGradClipState;
+/* chunks, partial, tensor_chunk_begin, tensor_sq and st are device pointers; g is 16-byte aligned; partial is indexed like chunks. */
+int mode_grad_sumsq(const float* g, const ModeGradChunk* chunks, int first, int count, float* partial, void* stream);
+int mode_grad_clip_finish(const float* partial, const int32_t* tensor_chunk_begin, int n_tensors, float max_norm, float grad_scale,
+                          int skip_nonfinite, float* tensor_sq, ModeGradClipState* st, void* stream);
+/* mode_adamw_step with the gradient scale read from st->scale on the device (same multiply, same bits as passing that value);
+ * st->skip != 0: the launch returns before its first store - p, m, v, ema and lp_bf16 keep their bits. */
+int mode_adamw_step_clipped(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                            float weight_decay, int step, void* lp_bf16, float* ema, float ema_rate, const ModeGradClipState* st,
+                            void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Whole-denoiser forward: the launch chain of one MoDeDiT.forward (modedit.py:741-821) [+ GCDenoiser.forward scalings
  * + one sample_ddim update], issued from C++ so a 10-step sampler is ~100 back-to-back launches per step with no host
  * logic in between (and can be captured into a hipGraph by the caller).

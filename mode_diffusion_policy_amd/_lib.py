@@ -208,6 +208,19 @@ class ModeFramePrepDesc(C.Structure):
     _fields_ = [("rows", c_vp), ("m_b", c_i32), ("num_envs", c_i32), ("cam", ModeFramePrepCam * 2)]
 
 
+MODE_GRAD_CHUNK = 16384
+
+
+class ModeGradChunk(C.Structure):
+    """One chunk of mode_grad_sumsq (include/mode_hip.h, an addition to ABI 13): at most MODE_GRAD_CHUNK elements of ONE tensor, lo 16-byte aligned."""
+    _fields_ = [("lo", c_i64), ("n", c_i32), ("tensor", c_i32)]
+
+
+class ModeGradClipState(C.Structure):
+    """Device-side result of mode_grad_clip_finish, read by mode_adamw_step_clipped (include/mode_hip.h)."""
+    _fields_ = [("total_norm", c_f32), ("coef", c_f32), ("scale", c_f32), ("nonfinite", c_i32), ("skip", c_i32), ("skipped", c_i32), ("pad", c_i32 * 2)]
+
+
 P = C.POINTER
 # name -> (restype, argtypes): every symbol include/mode_hip.h declares
 PROTOTYPES = {
@@ -275,6 +288,10 @@ PROTOTYPES = {
     "mode_adamw_step": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, c_i32, C.c_float, c_vp, c_vp,
                                   C.c_float, c_vp]),
     "mode_ema_update": (C.c_int, [c_vp, c_vp, c_i64, C.c_float, c_vp]),
+    "mode_grad_sumsq": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "mode_grad_clip_finish": (C.c_int, [c_vp, c_vp, c_i32, C.c_float, C.c_float, c_i32, c_vp, c_vp, c_vp]),
+    "mode_adamw_step_clipped": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, c_i32, c_vp, c_vp,
+                                          C.c_float, c_vp, c_vp]),
     "mode_adamw_fuse_gsq_floats": (c_i64, [P(ModeDims)]),
     "mode_dit_backward": (C.c_int, [P(ModeDims), P(ModeModelWeights), P(ModeModelWeightsT), P(ModeTrainArgs), c_vp, c_vp, P(ModeModelGrads),
                                     c_vp, c_sz, c_vp]),

@@ -954,7 +954,12 @@ extern "C" int mode_sigma_embed_bwd(const float* de1, const float* sigma, int B,
 // low-precision weights the next forward reads never need a separate cast pass.  Arithmetic follows torch's single-tensor AdamW order.
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                     long n4, float decay, float b1, float b2, float eps, float step_size, float inv_bc2_sqrt,
-                                                    float gscale, uint16_t* __restrict__ lp, float* __restrict__ ema, float ema_rate) {
+                                                    float gscale, uint16_t* __restrict__ lp, float* __restrict__ ema, float ema_rate,
+                                                    const ModeGradClipState* __restrict__ clip) {
+  if (clip) {                                          // device-side clipping (grad_norm.hip): the scale comes from the measured state; a skipped step returns before any store
+    if (clip->skip) return;
+    gscale = clip->scale;
+  }
   // pure stream: every byte is touched once per step -> non-temporal accesses, two float4 groups in flight per thread and stream
   typedef float f4 __attribute__((ext_vector_type(4)));
   typedef unsigned u2 __attribute__((ext_vector_type(2)));
@@ -1010,7 +1015,24 @@ extern "C" int mode_adamw_step(float* p, const float* g, float* m, float* v, int
   const long n4 = n / 4;
   const int blocks = (int)std::min<long>((n4 + 511) / 512, g_adamw_blocks > 0 ? g_adamw_blocks : 256);
   hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, 1.f - lr * weight_decay, beta1, beta2, eps,
-                     (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), grad_scale, (uint16_t*)lp_bf16, ema, ema_rate);
+                     (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), grad_scale, (uint16_t*)lp_bf16, ema, ema_rate, (const ModeGradClipState*)nullptr);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
+// mode_adamw_step with the gradient scale (and the skip flag) read from the device-side clip state: same launch geometry, same kernel, same multiply
+extern "C" int mode_adamw_step_clipped(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                                       float weight_decay, int step, void* lp_bf16, float* ema, float ema_rate, const ModeGradClipState* st,
+                                       void* stream) {
+  if (!st || ((uintptr_t)st & 3)) return MODE_ERR_BAD_ARG;
+  if (n == 0) return MODE_OK;
+  if (!p || !g || !m || !v || n < 0 || n % 4 || step < 1 || (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) || ((uintptr_t)lp_bf16 & 7))
+    return MODE_ERR_BAD_ARG;
+  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+  const long n4 = n / 4;
+  const int blocks = (int)std::min<long>((n4 + 511) / 512, g_adamw_blocks > 0 ? g_adamw_blocks : 256);
+  hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, 1.f - lr * weight_decay, beta1, beta2, eps,
+                     (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), 1.f, (uint16_t*)lp_bf16, ema, ema_rate, st);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }

@@ -17,6 +17,202 @@ import torch
 from . import _lib as L
 from .engine import _stream
 
+GRAD_CHUNK = L.MODE_GRAD_CHUNK
+
+
+def build_chunk_table(spans, chunk: int = GRAD_CHUNK) -> Dict:
+    """Chunk table of ``mode_grad_sumsq`` (include/mode_hip.h) - a pure function of ``(spans, chunk)``, no device involved.
+
+    ``spans``: ``[(lo, numel, included)]`` in ascending ``lo`` - element offset and TRUE element count of each tensor inside one flat gradient
+    buffer.  Every included tensor is cut into chunks of at most ``chunk`` elements: no chunk spans two tensors, every ``lo`` is a multiple of 4
+    elements (16 bytes), alignment padding between tensors and every excluded span are simply not covered.  Returns ``lo`` / ``n`` / ``tensor``
+    (one entry per chunk; ``tensor`` counts the INCLUDED tensors), ``begin`` (``[n_tensors + 1]``: tensor t owns the chunks
+    ``[begin[t], begin[t + 1])`` - none for an empty tensor) and ``index`` (position in ``spans`` of every included tensor)."""
+    if chunk <= 0 or chunk % 4:
+        raise ValueError("chunk must be a positive multiple of 4 elements")
+    lo_, n_, t_, begin, index = [], [], [], [0], []
+    end = 0
+    for i, (lo, numel, included) in enumerate(spans):
+        if not included:
+            continue
+        lo, numel = int(lo), int(numel)
+        if numel < 0 or lo < end:
+            raise ValueError("spans must be ascending and must not overlap")
+        if lo % 4:
+            raise NotImplementedError("every tensor must start on a 16-byte boundary of its flat gradient buffer")
+        t = len(index)
+        for o in range(0, numel, chunk):
+            lo_.append(lo + o); n_.append(min(chunk, numel - o)); t_.append(t)
+        end = lo + numel
+        index.append(i)
+        begin.append(len(lo_))
+    return dict(lo=lo_, n=n_, tensor=t_, begin=begin, index=index)
+
+
+def chunk_slices(table: Dict, slices):
+    """Chunk-index ranges of arena slices: ``([(first, count)] - one per ``(lo, hi)`` of ``slices`` -, [(first, count)] of every chunk outside them)``.
+    The ranges partition the table; a chunk that straddles a slice boundary is refused (the per-block gradient events cover whole tensors)."""
+    import bisect
+    los, ns = table["lo"], table["n"]
+    per, taken = [], []
+    for lo, hi in slices:
+        a, b = bisect.bisect_left(los, lo), bisect.bisect_left(los, hi)
+        if (a > 0 and los[a - 1] + ns[a - 1] > lo) or (b > a and los[b - 1] + ns[b - 1] > hi):
+            raise ValueError(f"a gradient chunk straddles the boundary of slice [{lo}, {hi})")
+        per.append((a, b - a)); taken.append((a, b))
+    rest, prev = [], 0
+    for a, b in sorted(taken):
+        if a < prev:
+            raise ValueError("slices overlap")
+        if prev < a:
+            rest.append((prev, a - prev))
+        prev = max(prev, b)
+    if prev < len(los):
+        rest.append((prev, len(los) - prev))
+    return per, rest
+
+
+class GradClip:
+    """Gradient norms on the device: per-tensor squared norms (the reference's ``on_before_zero_grad`` log, mode_agent.py:304-363), global-norm
+    clipping as ``torch.nn.utils.clip_grad_norm_`` defines it, and a step that changes NOTHING when the gradient is not finite.
+
+    ``GradClip(max_norm=1.0, skip_nonfinite=True)``; ``max_norm=None`` measures only (both attributes are read at each measurement and may be
+    changed between steps).  Hand it to the optimizers - ``FusedAdamW(model, clip=clip)``,
+    ``FlatAdamW(params, clip=clip)`` - which become its MEMBERS: the norm is taken over all of them together (the reference clips the agent's one
+    parameter list: denoiser + both encoders).  One member: ``opt.step()`` measures by itself.  Several: call ``clip.measure()`` once every member's
+    gradients are complete, then each member's ``step()`` - a step without a fresh measurement raises, each measurement is consumed once per member.
+
+    ``mode_grad_sumsq`` leaves one fp32 partial per chunk of <= 16384 elements (fixed summation order, no atomics: same bits for any grid, any split
+    into launches, any run); ``mode_grad_clip_finish`` sums them per tensor and in total in fp64 and writes ``ModeGradClipState``; every AdamW launch
+    (``mode_adamw_step_clipped``) reads ``scale = grad_scale * coef`` there.  No ``.item()``, no synchronize, no host read: ``total_norm``, ``coef``,
+    ``scale``, ``nonfinite``, ``skipped`` are device scalars and ``tensor_sq`` an fp32 device vector, one entry per ``names`` - every tensor that has a
+    gradient (frozen tensors, ``gripper_embed.weight`` and ``FlatAdamW`` parameters whose ``.grad`` is None are absent; un-routed experts are exact
+    zeros).  ``total_norm`` is the norm of the SCALED gradient (``grad_scale`` carries the data-parallel 1/world), squares are formed in fp32 as
+    torch forms them, so ``|g|`` above ~1.8e19 counts as non-finite.
+
+    A skipped step (``nonfinite`` with ``skip_nonfinite``) leaves weights, both moments, the EMA and the bf16 shadow bit-unchanged, but nothing on the
+    host knows: ``step_count`` - hence the bias correction and any LR scheduler - advances, i.e. it counts ATTEMPTED steps; ``skipped`` counts the
+    skips.  ``skip_nonfinite=False`` follows the formula like torch: the weights are poisoned, ``nonfinite`` is still set.
+
+    The chunk table is built on the host and uploaded when the set of tensors with a gradient changes (new arena, ``freeze_router()``, another set
+    of ``.grad is None``), never per step.  Not supported: ``fuse_expert_step`` (those gradients are never stored) and ZeRO-1 (a rank holds only its
+    shard of the reduced gradient)."""
+
+    def __init__(self, max_norm=None, skip_nonfinite: bool = True):
+        if max_norm is not None and not float(max_norm) > 0.0:
+            raise ValueError("max_norm must be positive (None: measure only)")
+        self.max_norm = None if max_norm is None else float(max_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.names = []
+        self.tensor_sq = None
+        self._members, self._key, self._segs = [], None, {}
+        self._state = self._state_f = self._chunks = self._begin = self._partial = None
+        self._fresh, self._measured_scale, self._uploaded = set(), None, None
+        self.lib = L.load()
+
+    def _attach(self, opt) -> None:
+        if all(m is not opt for m in self._members):
+            self._members.append(opt)
+            self._key = None
+
+    @property
+    def joint(self) -> bool:
+        return len(self._members) > 1
+
+    def _scalar(self, i, as_float=True):
+        if self._state is None:
+            raise RuntimeError("GradClip: nothing measured yet")
+        return (self._state_f if as_float else self._state)[i]
+
+    total_norm = property(lambda self: self._scalar(0))
+    coef = property(lambda self: self._scalar(1))
+    scale = property(lambda self: self._scalar(2))
+    nonfinite = property(lambda self: self._scalar(3, False))
+    skip = property(lambda self: self._scalar(4, False))
+    skipped = property(lambda self: self._scalar(5, False))
+
+    def _ensure(self) -> None:
+        """(Re)build and upload the chunk table when a member's set of gradient tensors changed; a no-op otherwise."""
+        key = tuple(m._clip_key() for m in self._members)
+        if key == self._key:
+            return
+        import numpy as np
+        lo, n, tn, begin, names, segs, dev = [], [], [], [0], [], {}, None
+        for m in self._members:
+            segs[id(m)] = []
+            for grad, spans in m._clip_segments():
+                dev = grad.device if dev is None else dev
+                if grad.device != dev:
+                    raise ValueError("GradClip: every member's gradients must live on one device")
+                tab = build_chunk_table([(o, k, True) for _, o, k in spans])
+                segs[id(m)].append(dict(grad=grad, first=len(lo), count=len(tab["lo"]), table=tab, slices={}))
+                tn += [t + len(names) for t in tab["tensor"]]
+                begin += [b + len(lo) for b in tab["begin"][1:]]
+                lo += tab["lo"]; n += tab["n"]
+                names += [nm for nm, _, _ in spans]
+        if dev is None:
+            raise RuntimeError("GradClip: no member has a gradient buffer yet (run a backward first)")
+        arr = np.zeros(max(1, len(lo)), dtype=np.dtype([("lo", "<i8"), ("n", "<i4"), ("tensor", "<i4")]))
+        arr["lo"][:len(lo)], arr["n"][:len(lo)], arr["tensor"][:len(lo)] = lo, n, tn
+        assert arr.itemsize == C.sizeof(L.ModeGradChunk)
+        # pinned staging + asynchronous copies: even a rebuild does not stall the host on the device
+        self._chunks = torch.from_numpy(arr.view(np.uint8)).pin_memory().to(dev, non_blocking=True)
+        self._begin = torch.tensor(begin, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        self._partial = torch.zeros(max(1, len(lo)), dtype=torch.float32, device=dev)
+        self.tensor_sq = torch.zeros(len(names), dtype=torch.float32, device=dev)
+        if self._state is None or self._state.device != dev:
+            self._state = torch.zeros(C.sizeof(L.ModeGradClipState) // 4, dtype=torch.int32, device=dev)     # `skipped` survives a rebuild of the table
+            self._state_f = self._state.view(torch.float32)
+        self._uploaded = torch.cuda.Event()                     # a side stream that measures (FusedAdamW.step(overlap=True)) waits for the tables once
+        self._uploaded.record()
+        self.names, self._segs, self._key = names, segs, key
+
+    def _stage1(self, seg, first: int = 0, count=None) -> None:
+        """mode_grad_sumsq over the chunks [first, first + count) of one member's segment, on the current stream."""
+        count = seg["count"] - first if count is None else count
+        if count > 0:
+            base = seg["first"]
+            L.check(self.lib.mode_grad_sumsq(seg["grad"].data_ptr(), self._chunks.data_ptr() + 16 * base, int(first), int(count),
+                                             self._partial.data_ptr() + 4 * base, _stream()), "grad_sumsq")
+
+    def _finish(self, grad_scale: float) -> None:
+        L.check(self.lib.mode_grad_clip_finish(self._partial.data_ptr(), self._begin.data_ptr(), len(self.names), float(self.max_norm or 0.0), float(grad_scale),
+                                               int(self.skip_nonfinite), self.tensor_sq.data_ptr(), self._state.data_ptr(), _stream()), "grad_clip_finish")
+
+    def _block_ranges(self, seg, slices):
+        key = tuple(slices)
+        if key not in seg["slices"]:
+            seg["slices"] = {key: chunk_slices(seg["table"], slices)}
+        return seg["slices"][key]
+
+    @torch.no_grad()
+    def measure(self, grad_scale: float = 1.0) -> None:
+        """Joint measurement over ALL members on the current stream (call when every member's gradients are complete; ``grad_scale`` is the scale
+        their steps apply, e.g. 1/world): stage 1 over every member's gradients, then the finish.  Each member's next ``step()`` consumes it."""
+        if not self._members:
+            raise RuntimeError("GradClip.measure(): no optimizer was constructed with this clip")
+        for m in self._members:
+            m._clip_prepare()
+        self._ensure()
+        for m in self._members:
+            for seg in self._segs[id(m)]:
+                self._stage1(seg)
+        self._finish(grad_scale)
+        self._fresh, self._measured_scale = {id(m) for m in self._members}, float(grad_scale)
+
+    def _consume_check(self, opt, grad_scale) -> float:
+        """A member of a JOINT clip is about to step: refuses (before the member changed anything) without a fresh measurement or with another scale."""
+        if id(opt) not in self._fresh:
+            raise RuntimeError("GradClip: step() of a member of a joint clip without a fresh clip.measure() (call it once all members' gradients are "
+                               "complete; every measurement is consumed once per member)")
+        if grad_scale is not None and float(grad_scale) != self._measured_scale:
+            raise ValueError(f"step(grad_scale={grad_scale}) differs from the scale given to clip.measure() ({self._measured_scale}): the members' shared "
+                             "scale was fixed there")
+        return self._measured_scale
+
+    def _consumed(self, opt) -> None:
+        self._fresh.discard(id(opt))
+
 
 class FusedAdamW:
     """``fuse_expert_step=True`` (opt-in; single process, no gradient accumulation - what the reference's training loop is,
@@ -39,7 +235,11 @@ class FusedAdamW:
     step before continuing."""
 
     def __init__(self, model, lr: float = 1e-4, betas: Tuple[float, float] = (0.9, 0.95), eps: float = 1e-8, weight_decay: float = 0.05,
-                 fuse_expert_step: bool = False, fused_side_stream: bool = True):
+                 fuse_expert_step: bool = False, fused_side_stream: bool = True, clip=None):
+        if clip is not None and fuse_expert_step:
+            raise NotImplementedError("fuse_expert_step with a GradClip: the expert gradients are never stored and their update happens inside the "
+                                      "backward, before a norm could exist")
+        self.clip = clip                                     # a GradClip: device-side gradient norms / global-norm clipping / non-finite-safe steps (its docstring)
         self.model = model
         eng = model.engine                                   # adopts the parameters into the arena
         self.eng, self.arena = eng, eng.arena
@@ -71,6 +271,8 @@ class FusedAdamW:
             if prev._fused_pending:
                 raise RuntimeError("another FusedAdamW of this model has a fused backward pending: call its step() / finish_fused_step() first")
             model._fused_optimizer = None
+        if clip is not None:
+            clip._attach(self)
         if self.fuse_expert_step:
             self.fuse_expert_step = False
             self.set_fuse_expert_step(True)                      # model._fused_optimizer = self: training.py's backward asks this object for the ModeAdamWFuse of the step
@@ -82,6 +284,9 @@ class FusedAdamW:
             raise RuntimeError("set_fuse_expert_step(): a fused backward is pending - call step() / finish_fused_step() first")
         on = bool(on)
         if on:
+            if self.clip is not None:
+                raise NotImplementedError("fuse_expert_step with a GradClip: the expert gradients are never stored and their update happens inside "
+                                          "the backward, before a norm could exist")
             if self.eng.compute_dtype != "bf16":
                 raise ValueError("fuse_expert_step needs the bf16 compute mode (the fused epilogue lives in the bf16 weight-gradient GEMM)")
             if self.model.embed_dim % 128:
@@ -122,6 +327,8 @@ class FusedAdamW:
         this backward must write gradients as usual.  Raises where a fused update would be silently wrong."""
         if not self.fuse_expert_step:
             return None
+        if self.clip is not None:
+            raise NotImplementedError("fuse_expert_step with a GradClip: the expert update inside the backward cannot wait for a gradient norm")
         eng, ar = self.eng, self.arena
         if eng.arena is not ar:
             raise RuntimeError("the parameter arena was rebuilt (model.to()/half()?): create a new FusedAdamW")
@@ -196,6 +403,25 @@ class FusedAdamW:
                 raise NotImplementedError("frozen parameter ranges must start and end on 16-byte boundaries of the arena")
         return merged
 
+    # ---- GradClip membership ---------------------------------------------------------------------------------------------------
+    def _clip_key(self):
+        ar = self.arena
+        return (id(ar), None if ar.grad is None else ar.grad.data_ptr(), tuple(p.requires_grad for _, p in self.eng.named_params()))
+
+    def _clip_segments(self):
+        """[(flat gradient buffer, [(name, element offset, numel)] ascending)]: every tensor the optimizer updates - frozen tensors and the arena's
+        dead region (``gripper_embed.weight``) have no gradient and are left out, as is the alignment padding between tensors."""
+        ar = self.arena
+        if ar.grad is None:
+            raise RuntimeError("no gradients: run a training forward + backward first")
+        base, n_red = ar.flat.data_ptr(), ar.bounds["no_decay"]
+        spans = sorted(((p.data_ptr() - base) // 4, nm, p.numel()) for nm, p in self.eng.named_params() if p.requires_grad)
+        return [(ar.grad, [(nm, lo, n) for lo, nm, n in spans if lo < n_red])]
+
+    def _clip_prepare(self) -> None:
+        if self.eng.arena is not self.arena or self.arena.grad is None:
+            raise RuntimeError("GradClip.measure(): the FusedAdamW member has no gradients (or its arena was rebuilt)")
+
     def _launch(self, lo: int, hi: int, gp, lp, grad_scale: float) -> None:
         for flo, fhi in self._frozen:                          # carve frozen slices (and, after a fused backward, the expert matrices) out of [lo, hi)
             if flo < hi and fhi > lo:
@@ -210,6 +436,13 @@ class FusedAdamW:
     def _launch_raw(self, lo: int, hi: int, gp, lp, grad_scale: float) -> None:
         ar = self.arena
         ema, rate = self._ema_now
+        if self.clip is not None:                              # the scale (and the skip flag) come from the device-side state of the measurement
+            L.check(self.eng.lib.mode_adamw_step_clipped(ar.flat[lo:hi].data_ptr(), ar.grad[lo:hi].data_ptr(), self.exp_avg[lo:hi].data_ptr(),
+                                                         self.exp_avg_sq[lo:hi].data_ptr(), hi - lo, float(gp["lr"]), float(gp["betas"][0]),
+                                                         float(gp["betas"][1]), float(gp["eps"]), float(gp["weight_decay"]), self.step_count,
+                                                         None if lp is None else lp[lo:hi].data_ptr(), None if ema is None else ema.flat[lo:hi].data_ptr(),
+                                                         float(rate), self.clip._state.data_ptr(), _stream()), "adamw_step_clipped")
+            return
         L.check(self.eng.lib.mode_adamw_step(ar.flat[lo:hi].data_ptr(), ar.grad[lo:hi].data_ptr(), self.exp_avg[lo:hi].data_ptr(),
                                              self.exp_avg_sq[lo:hi].data_ptr(), hi - lo, float(gp["lr"]), float(gp["betas"][0]),
                                              float(gp["betas"][1]), float(gp["eps"]), float(gp["weight_decay"]), self.step_count,
@@ -283,6 +516,9 @@ class FusedAdamW:
         the ranks with different step counts / partially updated slices)."""
         if zero1 not in ("fp32", "bf16"):
             raise ValueError("zero1 must be None, 'fp32' or 'bf16'")
+        if self.clip is not None:
+            raise NotImplementedError("ZeRO-1 with a GradClip: each rank holds only its shard of the reduced gradient (the global norm would need a "
+                                      "scalar all-reduce)")
         # (an `ema=` is sharded like the moments: each rank averages its own shard - where it holds exact fp32 masters in both gather modes - and
         #  gather_state() completes it; mode/callbacks/ema.py:101-126 runs the callback on every rank after every optimizer step)
         ar = self.arena
@@ -349,7 +585,13 @@ class FusedAdamW:
         exchange in front of each slice's update on the same events; its 1/world scale is applied here.
 
         ``ema`` (an ``ArenaEMA``): the moving average of the weights is updated in the same pass whenever the callback's schedule says so
-        for this step (the reference's EMA callback runs right after every optimizer step, mode/callbacks/ema.py:128-142)."""
+        for this step (the reference's EMA callback runs right after every optimizer step, mode/callbacks/ema.py:128-142).
+
+        With a ``GradClip`` (``FusedAdamW(model, clip=...)``) the step first measures the gradient norm on the device - after the data-parallel
+        exchange, with ``grad_scale`` (1/world included) folded into ``total_norm`` - and every AdamW launch reads the resulting scale there.
+        ``overlap=True`` then hides only the MEASUREMENT under the backward (stage 1 of block l's chunks behind block l's event); the update
+        itself can no longer start before the backward ends, because the global norm needs every gradient - that is inherent to global-norm
+        clipping.  As a member of a joint clip the step consumes the measurement ``clip.measure()`` took instead (class ``GradClip``)."""
         eng = self.model.engine
         ar = eng.arena
         if ar is not self.arena:
@@ -377,10 +619,18 @@ class FusedAdamW:
                 # decay - the schedule's first step - the average equals the new weights either way and nothing is lost)
                 deferred = RuntimeError("fuse_expert_step: register the EMA as opt.fused_ema (or call ema.ensure(arena)) BEFORE the first backward - it is "
                                         "initialised from the pre-update weights" + done_msg)
-        if grad_scale is None:
-            grad_scale = 1.0
+        clip = self.clip
+        if clip is not None and fused:
+            raise NotImplementedError("fuse_expert_step with a GradClip")        # (unreachable through the public switches: both refuse the combination)
         if use_zero1:
             self._validate_zero1(reducer, zero1, ema)
+        joint = clip is not None and clip.joint
+        if joint:
+            if reducer is not None and reducer.world > 1:
+                raise NotImplementedError("a member of a joint GradClip steps without a reducer: exchange the gradients, then clip.measure(grad_scale=1/world)")
+            grad_scale = clip._consume_check(self, grad_scale)
+        if grad_scale is None:
+            grad_scale = 1.0
         self.step_count += 1
         self._frozen = self._frozen_ranges()
         if fused:                                               # the expert matrices are done: the passes below skip them exactly like frozen tensors
@@ -414,6 +664,10 @@ class FusedAdamW:
         elif not overlap or events is None:
             if reducer is not None:
                 reducer.reduce()
+            if clip is not None and not joint:                  # the whole (exchanged) gradient is there: stage 1, finish, then the launches read the state
+                clip._ensure()
+                clip._stage1(clip._segs[id(self)][0])
+                clip._finish(grad_scale)
             self._launch(0, ar.bounds["decay"], gd, lp, grad_scale)
             self._launch(ar.bounds["decay"], ar.bounds["no_decay"], gn, lp, grad_scale)
         else:
@@ -427,14 +681,32 @@ class FusedAdamW:
             cur = torch.cuda.current_stream()
             blocks, rest = self._block_slices()
             done = reducer.reduce_async() if (reducer is not None and reducer.world > 1) else None    # {(lo, hi): event after the exchange}
+            seg = None
+            if clip is not None and not joint:
+                clip._ensure()
+                seg = clip._segs[id(self)][0]
+                per_block, other = clip._block_ranges(seg, [(lo, hi) for lo, hi, _ in blocks])
+                if clip._uploaded is not None:                                 # a table (re)built just now was uploaded on the current stream
+                    self._side.wait_event(clip._uploaded)
+                    clip._uploaded = None
             with torch.cuda.stream(self._side):
-                for lo, hi, i in blocks:
+                for bi, (lo, hi, i) in enumerate(blocks):
                     self._side.wait_event(done[(lo, hi)] if done is not None else events[i])
-                    self._launch(lo, hi, gd, lp, grad_scale)
+                    if clip is None:
+                        self._launch(lo, hi, gd, lp, grad_scale)
+                    elif seg is not None:
+                        clip._stage1(seg, *per_block[bi])                      # the measurement of block l runs underneath the backward of the earlier blocks
                 self._side.wait_stream(cur)                                    # everything else needs the whole backward
                 if done is not None:
                     for ev in done.values():
                         self._side.wait_event(ev)
+                if clip is not None:
+                    if seg is not None:
+                        for first, count in other:
+                            clip._stage1(seg, first, count)
+                        clip._finish(grad_scale)
+                    for lo, hi, i in blocks:                                   # the global norm needs every gradient: no update before this point
+                        self._launch(lo, hi, gd, lp, grad_scale)
                 for lo, hi in rest:
                     self._launch(lo, hi, gd, lp, grad_scale)
                 self._launch(ar.bounds["decay"], ar.bounds["no_decay"], gn, lp, grad_scale)
@@ -454,6 +726,8 @@ class FusedAdamW:
                     L.check(eng.lib.mode_ema_update(ema_.flat[prev:lo_].data_ptr(), ar.flat[prev:lo_].data_ptr(), lo_ - prev, float(rate_), _stream()), "ema_update")
                 prev = hi_
             ema_.mark_applied(self.step_count)
+        if joint:
+            clip._consumed(self)
         eng.weights_updated(lp_synced=lp is not None)
         ar.grad_pending = False                                  # gradients consumed: the next backward starts a fresh sum
         if deferred is not None:
@@ -484,9 +758,14 @@ class FlatAdamW:
     Like torch, a parameter whose ``.grad`` is None in a step is SKIPPED (no decay, moments untouched: FiLM modules that saw no conditioning vector,
     parameters frozen later): the flat launch is cut into the runs of tensors that do have a gradient.  The update writes through raw pointers, so the
     parameters' version counters are bumped explicitly (cached bf16 weight shadows must notice); a parameter whose storage was re-pointed after
-    construction (``module.to()`` / ``.half()``) is refused in ``step()`` rather than silently left behind."""
+    construction (``module.to()`` / ``.half()``) is refused in ``step()`` rather than silently left behind.
 
-    def __init__(self, params, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2):
+    ``clip`` (a ``GradClip``): device-side gradient norms / global-norm clipping / non-finite-safe steps over this optimizer's tensors - alone, or
+    jointly with the denoiser's ``FusedAdamW`` (``clip.measure()``, then both ``step()``s); tensors whose ``.grad`` is None are not measured.  Its
+    ``names`` for this optimizer's tensors are ``g<group>.p<index>``."""
+
+    def __init__(self, params, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, clip=None):
+        self.clip = clip
         groups = list(params)
         if groups and not isinstance(groups[0], dict):
             groups = [dict(params=groups)]
@@ -524,6 +803,42 @@ class FlatAdamW:
                 offs.append((o, o + sz)); o += sz
             self._flat.append(dict(flat=flat, grad=grad, views=views, exp_avg=torch.zeros(n, device=dev), exp_avg_sq=torch.zeros(n, device=dev), n=n,
                                    spans=offs, ptrs=[p.data_ptr() for p in ps]))
+        if clip is not None:
+            clip._attach(self)
+
+    # ---- GradClip membership
+    def _clip_key(self):
+        return tuple((f["grad"].data_ptr(), tuple(p.grad is None for p in grp["params"])) for grp, f in zip(self.param_groups, self._flat))
+
+    def _clip_segments(self):
+        """One segment per parameter group: its flat gradient buffer and [(name, offset, TRUE numel)] of the tensors that have a gradient."""
+        return [(f["grad"], [(f"g{gi}.p{pi}", lo, p.numel()) for pi, (p, (lo, _)) in enumerate(zip(grp["params"], f["spans"])) if p.grad is not None])
+                for gi, (grp, f) in enumerate(zip(self.param_groups, self._flat))]
+
+    def _clip_prepare(self) -> None:
+        self._gather(copy=True)
+
+    def _gather(self, copy: bool):
+        """Per group the runs [lo, hi) of adjacent tensors that have a gradient; with ``copy`` the autograd-owned ``.grad``s are gathered into the flat
+        gradient buffer first (ONE multi-tensor copy per group) - what both ``step()`` and a joint ``GradClip.measure()`` need."""
+        out = []
+        for grp, f in zip(self.param_groups, self._flat):
+            src, dst, runs = [], [], []
+            for p, gv, (lo, hi), ptr in zip(grp["params"], f["views"], f["spans"], f["ptrs"]):
+                if p.data_ptr() != ptr:
+                    raise RuntimeError("FlatAdamW: a parameter's storage moved after construction (module.to() / .half()?): create a new FlatAdamW")
+                if p.grad is None:
+                    continue                                                    # torch skips a tensor without a gradient: no decay, moments untouched
+                if p.grad.data_ptr() != gv.data_ptr():
+                    src.append(p.grad); dst.append(gv)
+                if runs and runs[-1][1] == lo:
+                    runs[-1][1] = hi
+                else:
+                    runs.append([lo, hi])
+            if dst and copy:
+                torch._foreach_copy_(dst, src)                                  # all gradients into the flat buffer: one multi-tensor launch
+            out.append(runs)
+        return out
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         """``set_to_none=True`` (default, like torch): drop the gradients - the next backward hands autograd-owned tensors to ``.grad`` (no accumulation
@@ -540,29 +855,37 @@ class FlatAdamW:
                         p.grad = gv
 
     @torch.no_grad()
-    def step(self, grad_scale: float = 1.0) -> None:
+    def step(self, grad_scale=None) -> None:
+        """One AdamW update (``grad_scale`` None = 1.0).  With a ``GradClip`` of its own the step measures first; as a member of a joint clip it
+        consumes ``clip.measure()``'s measurement (which also gathered the gradients) and ``grad_scale`` defaults to the scale given there."""
+        clip = self.clip
+        joint = clip is not None and clip.joint
+        if joint:
+            grad_scale = clip._consume_check(self, grad_scale)
+        if grad_scale is None:
+            grad_scale = 1.0
         self.step_count += 1
-        for grp, f in zip(self.param_groups, self._flat):
-            src, dst, runs = [], [], []
-            for p, gv, (lo, hi), ptr in zip(grp["params"], f["views"], f["spans"], f["ptrs"]):
-                if p.data_ptr() != ptr:
-                    raise RuntimeError("FlatAdamW: a parameter's storage moved after construction (module.to() / .half()?): create a new FlatAdamW")
-                if p.grad is None:
-                    continue                                                    # torch skips a tensor without a gradient: no decay, moments untouched
-                if p.grad.data_ptr() != gv.data_ptr():
-                    src.append(p.grad); dst.append(gv)
-                if runs and runs[-1][1] == lo:
-                    runs[-1][1] = hi
-                else:
-                    runs.append([lo, hi])
-            if dst:
-                torch._foreach_copy_(dst, src)                                  # all gradients into the flat buffer: one multi-tensor launch
+        all_runs = self._gather(copy=not joint)
+        if clip is not None and not joint:
+            clip._ensure()
+            for seg in clip._segs[id(self)]:
+                clip._stage1(seg)
+            clip._finish(grad_scale)
+        for grp, f, runs in zip(self.param_groups, self._flat, all_runs):
             for lo, hi in runs:                                                 # ONE launch when every tensor has a gradient (the usual step)
+                if clip is not None:
+                    L.check(self.lib.mode_adamw_step_clipped(f["flat"][lo:hi].data_ptr(), f["grad"][lo:hi].data_ptr(), f["exp_avg"][lo:hi].data_ptr(),
+                                                             f["exp_avg_sq"][lo:hi].data_ptr(), hi - lo, float(grp["lr"]), float(grp["betas"][0]),
+                                                             float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]), self.step_count, None, None,
+                                                             0.0, clip._state.data_ptr(), _stream()), "adamw_step_clipped")
+                    continue
                 L.check(self.lib.mode_adamw_step(f["flat"][lo:hi].data_ptr(), f["grad"][lo:hi].data_ptr(), f["exp_avg"][lo:hi].data_ptr(),
                                                  f["exp_avg_sq"][lo:hi].data_ptr(), hi - lo, float(grp["lr"]), float(grp["betas"][0]), float(grp["betas"][1]),
                                                  float(grp["eps"]), float(grp["weight_decay"]), self.step_count, float(grad_scale), None, None, 0.0, _stream()),
                         "adamw_step")
             torch.autograd.graph.increment_version(grp["params"])                 # raw-pointer write: version-gated caches (conv weight shadows) must see it
+        if joint:
+            clip._consumed(self)
 
     def state_dict(self) -> Dict:
         return {"step": self.step_count, "exp_avg": [f["exp_avg"] for f in self._flat], "exp_avg_sq": [f["exp_avg_sq"] for f in self._flat],
