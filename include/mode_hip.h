@@ -84,7 +84,7 @@ const char* mode_hip_status_string(int status);
  * "conv_ns": LDS ring depth of the implicit-GEMM convolution kernel (csrc/conv_gemm.hip): 0 = auto (3 below two workgroups per CU), 2, 3.
  * "bwd_coexec": 1 = the caller runs other kernels beside the backward chain (FusedAdamW.step(overlap=True), ArenaGradReducer's collectives set it):
  *   the backward's large GEMMs keep the ring kernels, whose small workgroups leave CU resources to the co-running work; 0 (default) = the backward has
- *   the GPU to itself.  Same results either way (bit-identical kernels).  "adamw_blocks": workgroup cap of one AdamW launch (0 = 256, one streaming workgroup per CU).
+ *   the GPU to itself.  Same results either way (bit-identical kernels).  "adamw_blocks": workgroup cap of one AdamW launch (0 = 256, one streaming workgroup per CU; 512 for mode_adamw_step_lp).
  * "gemm_skinny_rows": bf16 GEMMs with M <= this many rows use the weight-streaming kernels, and mode_dit_forward runs a batch of at most this
  *   many TOKEN rows as the small-batch chain (MODE_GEMM_SMALL_ROWS) (default 32 = two environments, 0 = off).
  * "gemm_mid_rows": ungrouped bf16 GEMMs with K = 1024 and at most this many rows (more than "gemm_skinny_rows") keep their weights in registers
@@ -554,6 +554,35 @@ int mode_grad_clip_finish(const float* partial, const int32_t* tensor_chunk_begi
 int mode_adamw_step_clipped(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                             float weight_decay, int step, void* lp_bf16, float* ema, float ema_rate, const ModeGradClipState* st,
                             void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * AdamW with bf16 moments (an addition to ABI 13): mode_adamw_step / mode_adamw_step_clipped with exp_avg and exp_avg_sq held as bf16 -
+ * 22 instead of 30 bytes per parameter and step, half the moment memory.  m_bf16 / v_bf16: n bf16 values each, 8-byte aligned.
+ *
+ * One step: m and v are expanded to fp32 exactly (bits << 16), the update is mode_adamw_step's on the expanded values - same expression order,
+ * same bits - and p, ema and lp_bf16 are computed from this step's UNROUNDED fp32 m and v.  Only what is stored for the next step is rounded:
+ * stochastically, because at beta2 = 0.999 one step changes v by 0.1 %, less than half a bf16 ulp (2^-9) - round-to-nearest would hold v for ever.
+ *
+ * Random bits.  Element i of the launch is element e = elem_base + i of the optimizer's moment buffer (elem_base >= 0, a multiple of 4).  With
+ * lowbias32 = hash_u32 and mode_stream_seed of csrc/mode_common.h, all arithmetic modulo 2^32:
+ *   key = mode_stream_seed(round_seed, (uint32_t)step)
+ *   r   = lowbias32(lowbias32((uint32_t)e ^ key) + (uint32_t)(e >> 32) * 0x9e3779b9)
+ *   m is rounded with r16 = r & 0xffff, v with r16 = r >> 16.
+ * r is a function of (round_seed, step, e) only: the stored bits do not depend on the grid, on the "adamw_blocks" option, on how a range is cut
+ * into launches (as long as each launch passes its own elem_base) or on the run.
+ *
+ * Rounding of the fp32 bits u with the 16-bit field r16 to the 16 stored bits:
+ *   exponent of u all ones:  Inf -> u >> 16;  NaN -> (u >> 16) | 0x40        (a NaN stays a NaN)
+ *   otherwise                t = u + r16;  if the exponent of t is all ones, t = u;  store t >> 16
+ * i.e. the magnitude is truncated, or moved up one bf16 ulp with probability (low 16 bits of u) / 2^16: unbiased for either sign, exact for values
+ * that bf16 represents, and a finite value never becomes Inf (the largest finite magnitudes are truncated).
+ *
+ * grad_scale multiplies g as in mode_adamw_step; st (nullable, 4-byte aligned) overrides it with st->scale and honours st->skip as
+ * mode_adamw_step_clipped does: with st->skip != 0 the launch returns before its first store.  n % 4 == 0; p and g 16-byte aligned; n == 0
+ * returns MODE_OK; a bad argument returns MODE_ERR_BAD_ARG and launches nothing. */
+int mode_adamw_step_lp(float* p, const float* g, void* m_bf16, void* v_bf16, int64_t n, int64_t elem_base, float lr, float beta1, float beta2,
+                       float eps, float weight_decay, int step, uint32_t round_seed, float grad_scale, void* lp_bf16, float* ema, float ema_rate,
+                       const ModeGradClipState* st /* nullable: non-null overrides grad_scale, honours skip */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Whole-denoiser forward: the launch chain of one MoDeDiT.forward (modedit.py:741-821) [+ GCDenoiser.forward scalings

@@ -292,6 +292,9 @@ PROTOTYPES = {
     "mode_grad_clip_finish": (C.c_int, [c_vp, c_vp, c_i32, C.c_float, C.c_float, c_i32, c_vp, c_vp, c_vp]),
     "mode_adamw_step_clipped": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, c_i32, c_vp, c_vp,
                                           C.c_float, c_vp, c_vp]),
+    # (p, g, m_bf16, v_bf16, n, elem_base, lr, beta1, beta2, eps, weight_decay, step, round_seed, grad_scale, lp_bf16, ema, ema_rate, st, stream)
+    "mode_adamw_step_lp": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, c_i32, C.c_uint32,
+                                     C.c_float, c_vp, c_vp, C.c_float, c_vp, c_vp]),
     "mode_adamw_fuse_gsq_floats": (c_i64, [P(ModeDims)]),
     "mode_dit_backward": (C.c_int, [P(ModeDims), P(ModeModelWeights), P(ModeModelWeightsT), P(ModeTrainArgs), c_vp, c_vp, P(ModeModelGrads),
                                     c_vp, c_sz, c_vp]),

@@ -114,6 +114,22 @@ __device__ __forceinline__ bool drop_keep(uint32_t seed, uint64_t idx, uint32_t 
   return hash_u32(hash_u32((uint32_t)idx ^ seed) + (uint32_t)(idx >> 32) * 0x9e3779b9U) >= thresh;
 }
 
+// ---- bf16 AdamW moments (mode_adamw_step_lp; include/mode_hip.h states both functions bit for bit, tests/adamw_lp_refs.py restates them in numpy)
+// One 32-bit hash per element of the optimizer's moment buffer: a function of (key = mode_stream_seed(round_seed, step), element index) only - the
+// same mixing of a 64-bit index as drop_keep.
+__device__ __forceinline__ uint32_t sr_hash(uint32_t key, uint64_t idx) {
+  return hash_u32(hash_u32((uint32_t)idx ^ key) + (uint32_t)(idx >> 32) * 0x9e3779b9U);
+}
+// Stochastic rounding of the fp32 bits `u` to bf16 bits with the 16-bit random field r16: truncation of u + r16, i.e. the magnitude goes up one
+// bf16 ulp with probability (discarded bits) / 2^16 - unbiased for either sign, exact for bf16-representable values.  Inf passes through, NaN
+// stays NaN (quiet bit set: a payload that lives in the discarded bits only must not become Inf), a finite value never rounds to Inf.
+__host__ __device__ inline uint32_t sr_bf16_bits(uint32_t u, uint32_t r16) {
+  if ((u & 0x7f800000u) == 0x7f800000u) return (u >> 16) | ((u & 0x007fffffu) ? 0x40u : 0u);
+  uint32_t t = u + r16;
+  if ((t & 0x7f800000u) == 0x7f800000u) t = u;
+  return t >> 16;
+}
+
 // ---- model-size limits of the HIP path: tokens per sample (attention: attn.hip for T <= 16, attn_long.hip above) and action width (rowops.hip)
 constexpr int kMaxTokens = 64;
 constexpr int kMaxActionDim = 32;

@@ -952,10 +952,17 @@ extern "C" int mode_sigma_embed_bwd(const float* de1, const float* sigma, int B,
 // Fused AdamW over a flat fp32 arena slice (replaces torch.optim.AdamW's multi-tensor loop for mode_agent.py:365-384's two groups).
 // One pass: reads p, g, m, v (16 B/elem), writes p, m, v (12 B/elem) and, when asked, the bf16 compute shadow (2 B/elem) — so the
 // low-precision weights the next forward reads never need a separate cast pass.  Arithmetic follows torch's single-tensor AdamW order.
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+// MT = float: fp32 moments (mode_adamw_step / mode_adamw_step_clipped).  MT = uint16_t: bf16 moments (mode_adamw_step_lp, 22 instead of 30 B/elem) -
+// m / v travel as 8-byte groups of four bf16, are expanded exactly (bits << 16), the update runs on the expanded values as above and weight, EMA and
+// shadow come from this step's UNROUNDED fp32 moments; only what is stored for the next step is rounded, stochastically (sr_bf16_bits), with one
+// hash per element of the optimizer's moment buffer (sr_key, elem_base + position in the launch): the bits do not depend on the grid or on how a
+// range is cut into launches.
+template <typename MT>
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, MT* __restrict__ m, MT* __restrict__ v,
                                                     long n4, float decay, float b1, float b2, float eps, float step_size, float inv_bc2_sqrt,
                                                     float gscale, uint16_t* __restrict__ lp, float* __restrict__ ema, float ema_rate,
-                                                    const ModeGradClipState* __restrict__ clip) {
+                                                    const ModeGradClipState* __restrict__ clip, uint32_t sr_key, long elem_base) {
+  constexpr bool kLp = sizeof(MT) == 2;
   if (clip) {                                          // device-side clipping (grad_norm.hip): the scale comes from the measured state; a skipped step returns before any store
     if (clip->skip) return;
     gscale = clip->scale;
@@ -972,8 +979,17 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
       if (i < n4) {
         P[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p) + i);
         G[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(g) + i);
-        M[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(m) + i);
-        V[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(v) + i);
+        if constexpr (kLp) {
+          const u2 mb = __builtin_nontemporal_load(reinterpret_cast<const u2*>(m) + i), vb = __builtin_nontemporal_load(reinterpret_cast<const u2*>(v) + i);
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            M[u][2 * h] = __uint_as_float(mb[h] << 16); M[u][2 * h + 1] = __uint_as_float(mb[h] & 0xffff0000u);
+            V[u][2 * h] = __uint_as_float(vb[h] << 16); V[u][2 * h + 1] = __uint_as_float(vb[h] & 0xffff0000u);
+          }
+        } else {
+          M[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(m) + i);
+          V[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(v) + i);
+        }
       }
     }
 #pragma unroll
@@ -988,8 +1004,22 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
         P[u][j] = w; M[u][j] = m_; V[u][j] = v_;
       }
       __builtin_nontemporal_store(P[u], reinterpret_cast<f4*>(p) + i);
-      __builtin_nontemporal_store(M[u], reinterpret_cast<f4*>(m) + i);
-      __builtin_nontemporal_store(V[u], reinterpret_cast<f4*>(v) + i);
+      if constexpr (kLp) {
+        u2 mb, vb;
+        const uint64_t e0 = (uint64_t)elem_base + 4 * (uint64_t)i;          // a multiple of 4: the group's four indices share their high word
+        const uint32_t e_lo = (uint32_t)e0, e_hi = (uint32_t)(e0 >> 32) * 0x9e3779b9U;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {                                       // r0 / r1 = mode::sr_hash(sr_key, e0 + 2h / e0 + 2h + 1); m: low 16 bits, v: high 16 bits
+          const uint32_t r0 = mode::hash_u32(mode::hash_u32((e_lo | (2 * h)) ^ sr_key) + e_hi), r1 = mode::hash_u32(mode::hash_u32((e_lo | (2 * h + 1)) ^ sr_key) + e_hi);
+          mb[h] = mode::sr_bf16_bits(__float_as_uint(M[u][2 * h]), r0 & 0xffffu) | (mode::sr_bf16_bits(__float_as_uint(M[u][2 * h + 1]), r1 & 0xffffu) << 16);
+          vb[h] = mode::sr_bf16_bits(__float_as_uint(V[u][2 * h]), r0 >> 16) | (mode::sr_bf16_bits(__float_as_uint(V[u][2 * h + 1]), r1 >> 16) << 16);
+        }
+        __builtin_nontemporal_store(mb, reinterpret_cast<u2*>(m) + i);
+        __builtin_nontemporal_store(vb, reinterpret_cast<u2*>(v) + i);
+      } else {
+        __builtin_nontemporal_store(M[u], reinterpret_cast<f4*>(m) + i);
+        __builtin_nontemporal_store(V[u], reinterpret_cast<f4*>(v) + i);
+      }
       if (ema) {                                       // EMA of the weights (mode/callbacks/ema.py:119-126): e -= (1 - decay) * (e - w)
         f4 Ev = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ema) + i);
 #pragma unroll
@@ -1004,7 +1034,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   }
 }
 
-namespace mode { int g_adamw_blocks = 0; }   // "adamw_blocks" option: cap on the workgroups of one AdamW launch (0 = 256, one per CU: 15.4 vs 15.8 ms per step with 2048)
+namespace mode { int g_adamw_blocks = 0; }   // "adamw_blocks" option: cap on the workgroups of one AdamW launch (0 = 256, one per CU: 15.4 vs 15.8 ms per step with 2048; 0 = 512 for the bf16-moment launch)
 
 extern "C" int mode_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                                float weight_decay, int step, float grad_scale, void* lp_bf16, float* ema, float ema_rate, void* stream) {
@@ -1014,8 +1044,8 @@ extern "C" int mode_adamw_step(float* p, const float* g, float* m, float* v, int
   const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
   const long n4 = n / 4;
   const int blocks = (int)std::min<long>((n4 + 511) / 512, g_adamw_blocks > 0 ? g_adamw_blocks : 256);
-  hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, 1.f - lr * weight_decay, beta1, beta2, eps,
-                     (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), grad_scale, (uint16_t*)lp_bf16, ema, ema_rate, (const ModeGradClipState*)nullptr);
+  hipLaunchKernelGGL(adamw_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, 1.f - lr * weight_decay, beta1, beta2, eps,
+                     (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), grad_scale, (uint16_t*)lp_bf16, ema, ema_rate, (const ModeGradClipState*)nullptr, 0u, 0L);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }
@@ -1031,8 +1061,29 @@ extern "C" int mode_adamw_step_clipped(float* p, const float* g, float* m, float
   const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
   const long n4 = n / 4;
   const int blocks = (int)std::min<long>((n4 + 511) / 512, g_adamw_blocks > 0 ? g_adamw_blocks : 256);
-  hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, 1.f - lr * weight_decay, beta1, beta2, eps,
-                     (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), 1.f, (uint16_t*)lp_bf16, ema, ema_rate, st);
+  hipLaunchKernelGGL(adamw_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, 1.f - lr * weight_decay, beta1, beta2, eps,
+                     (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), 1.f, (uint16_t*)lp_bf16, ema, ema_rate, st, 0u, 0L);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
+// The AdamW step over bf16 moments (include/mode_hip.h): same launch geometry and arithmetic as the two calls above, m / v stored stochastically rounded
+extern "C" int mode_adamw_step_lp(float* p, const float* g, void* m_bf16, void* v_bf16, int64_t n, int64_t elem_base, float lr, float beta1, float beta2,
+                                  float eps, float weight_decay, int step, uint32_t round_seed, float grad_scale, void* lp_bf16, float* ema, float ema_rate,
+                                  const ModeGradClipState* st, void* stream) {
+  if (((uintptr_t)st & 3) || elem_base < 0 || elem_base % 4) return MODE_ERR_BAD_ARG;
+  if (n == 0) return MODE_OK;
+  if (!p || !g || !m_bf16 || !v_bf16 || n < 0 || n % 4 || step < 1 || (((uintptr_t)p | (uintptr_t)g) & 15) ||
+      (((uintptr_t)m_bf16 | (uintptr_t)v_bf16 | (uintptr_t)lp_bf16) & 7))
+    return MODE_ERR_BAD_ARG;
+  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+  const long n4 = n / 4;
+  // two workgroups per CU by default: with one wave per SIMD the rounding's integer arithmetic (two hashes per element) is not hidden behind the
+  // loads - isolated launch 3.78 ms at 256 workgroups (fp32 moments: 3.34), 2.61 ms at 512, 2.80 ms at 1024 (profiles/adamw_lp.txt)
+  const int blocks = (int)std::min<long>((n4 + 511) / 512, g_adamw_blocks > 0 ? g_adamw_blocks : 512);
+  hipLaunchKernelGGL(adamw_kernel<uint16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, (uint16_t*)m_bf16, (uint16_t*)v_bf16, n4,
+                     1.f - lr * weight_decay, beta1, beta2, eps, (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), grad_scale, (uint16_t*)lp_bf16, ema, ema_rate, st,
+                     mode_stream_seed(round_seed, (uint32_t)step), (long)elem_base);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }

@@ -72,6 +72,21 @@ def chunk_slices(table: Dict, slices):
     return per, rest
 
 
+MOMENT_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+
+
+def _moment_dtype(name) -> str:
+    if name not in MOMENT_DTYPES:
+        raise ValueError("moment_dtype must be 'fp32' or 'bf16'")
+    return name
+
+
+def _load_moments(dst, src) -> None:
+    """Checkpointed moments into this optimizer's buffers, either dtype: bf16 -> fp32 is exact; fp32 -> bf16 is a one-off round-to-nearest-even
+    conversion (the only place bf16 moments are ever rounded that way - every step rounds stochastically)."""
+    dst.copy_(src)
+
+
 class GradClip:
     """Gradient norms on the device: per-tensor squared norms (the reference's ``on_before_zero_grad`` log, mode_agent.py:304-363), global-norm
     clipping as ``torch.nn.utils.clip_grad_norm_`` defines it, and a step that changes NOTHING when the gradient is not finite.
@@ -232,10 +247,26 @@ class FusedAdamW:
     ``grad_scale``, a multi-rank reducer, an EMA that did not exist before the backward) it first COMPLETES the step with the backward's settings -
     remaining 12 % of the parameters, ``step_count``, shadow versions - and only then raises.  Skipping ``step()`` after a fused backward (e.g. a
     non-finite-loss guard) is unsupported - the experts have already moved; call ``finish_fused_step()`` to bring the rest of the arena to the same
-    step before continuing."""
+    step before continuing.
+
+    ``moment_dtype="bf16"`` (opt-in; default ``"fp32"``: same kernels, same bits as ever) keeps ``exp_avg`` / ``exp_avg_sq`` as ``torch.bfloat16``:
+    half the moment memory, and the two-pass stream moves 22 instead of 30 bytes per parameter (``mode_adamw_step_lp``, include/mode_hip.h).  Every
+    step expands the moments exactly, runs the unchanged fp32 arithmetic and computes weights, EMA and bf16 shadow from the UNROUNDED moments; only
+    what is stored is rounded - stochastically, with bits that are a function of ``(round_seed, step, element's position in the moment buffer)``
+    alone, so serial, ``overlap=True`` and frozen-slice launches store identical bits, run after run.  Works with ``overlap``, a plain reducer,
+    ``ema=``, frozen ranges, ``GradClip`` (alone or joint, skipped steps included) and ``reset_state()``.  Refused (``NotImplementedError``, before
+    anything changes): ``fuse_expert_step`` - the weight-gradient GEMM's AdamW epilogue reads fp32 moments - and ZeRO-1 - ``gather_state`` and the
+    shard collectives assume fp32.  ``state_dict()`` carries ``moment_dtype``, ``round_seed`` and the moments in their own dtype;
+    ``load_state_dict`` accepts either dtype (``_load_moments``), a dict without ``moment_dtype`` is fp32, and ``round_seed`` is adopted from a
+    bf16 checkpoint - a bf16 optimizer resumed from its own checkpoint continues bit-identically.  What bf16 moments do to convergence has not
+    been measured."""
 
     def __init__(self, model, lr: float = 1e-4, betas: Tuple[float, float] = (0.9, 0.95), eps: float = 1e-8, weight_decay: float = 0.05,
-                 fuse_expert_step: bool = False, fused_side_stream: bool = True, clip=None):
+                 fuse_expert_step: bool = False, fused_side_stream: bool = True, clip=None, moment_dtype: str = "fp32", round_seed: int = 0):
+        self.moment_dtype = _moment_dtype(moment_dtype)
+        self.round_seed = int(round_seed) & 0xFFFFFFFF
+        if self.moment_dtype == "bf16" and fuse_expert_step:
+            raise NotImplementedError("fuse_expert_step with moment_dtype='bf16': the weight-gradient GEMM's AdamW epilogue reads fp32 moments")
         if clip is not None and fuse_expert_step:
             raise NotImplementedError("fuse_expert_step with a GradClip: the expert gradients are never stored and their update happens inside the "
                                       "backward, before a norm could exist")
@@ -245,8 +276,8 @@ class FusedAdamW:
         self.eng, self.arena = eng, eng.arena
         model.grad_mode = "arena"                            # this optimizer reads the flat gradient arena: the backward chain writes there directly
         n = self.arena.bounds["no_decay"]                    # decay + no_decay regions (dead region excluded)
-        self.exp_avg = torch.zeros(n, dtype=torch.float32, device=eng.device)
-        self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=eng.device)
+        self.exp_avg = torch.zeros(n, dtype=MOMENT_DTYPES[self.moment_dtype], device=eng.device)
+        self.exp_avg_sq = torch.zeros(n, dtype=MOMENT_DTYPES[self.moment_dtype], device=eng.device)
         self.step_count = 0
         self._side = None
         self._ema_now = (None, 0.0)
@@ -284,6 +315,8 @@ class FusedAdamW:
             raise RuntimeError("set_fuse_expert_step(): a fused backward is pending - call step() / finish_fused_step() first")
         on = bool(on)
         if on:
+            if self.moment_dtype == "bf16":
+                raise NotImplementedError("fuse_expert_step with moment_dtype='bf16': the weight-gradient GEMM's AdamW epilogue reads fp32 moments")
             if self.clip is not None:
                 raise NotImplementedError("fuse_expert_step with a GradClip: the expert gradients are never stored and their update happens inside "
                                           "the backward, before a norm could exist")
@@ -436,6 +469,14 @@ class FusedAdamW:
     def _launch_raw(self, lo: int, hi: int, gp, lp, grad_scale: float) -> None:
         ar = self.arena
         ema, rate = self._ema_now
+        if self.moment_dtype == "bf16":                        # elem_base = lo: the rounding bits belong to the element's place in the moment buffer, not in the launch
+            L.check(self.eng.lib.mode_adamw_step_lp(ar.flat[lo:hi].data_ptr(), ar.grad[lo:hi].data_ptr(), self.exp_avg[lo:hi].data_ptr(),
+                                                    self.exp_avg_sq[lo:hi].data_ptr(), hi - lo, lo, float(gp["lr"]), float(gp["betas"][0]),
+                                                    float(gp["betas"][1]), float(gp["eps"]), float(gp["weight_decay"]), self.step_count, self.round_seed,
+                                                    float(grad_scale), None if lp is None else lp[lo:hi].data_ptr(),
+                                                    None if ema is None else ema.flat[lo:hi].data_ptr(), float(rate),
+                                                    None if self.clip is None else self.clip._state.data_ptr(), _stream()), "adamw_step_lp")
+            return
         if self.clip is not None:                              # the scale (and the skip flag) come from the device-side state of the measurement
             L.check(self.eng.lib.mode_adamw_step_clipped(ar.flat[lo:hi].data_ptr(), ar.grad[lo:hi].data_ptr(), self.exp_avg[lo:hi].data_ptr(),
                                                          self.exp_avg_sq[lo:hi].data_ptr(), hi - lo, float(gp["lr"]), float(gp["betas"][0]),
@@ -516,6 +557,8 @@ class FusedAdamW:
         the ranks with different step counts / partially updated slices)."""
         if zero1 not in ("fp32", "bf16"):
             raise ValueError("zero1 must be None, 'fp32' or 'bf16'")
+        if self.moment_dtype == "bf16":
+            raise NotImplementedError("ZeRO-1 with moment_dtype='bf16': gather_state() and the shard collectives assume fp32 moments")
         if self.clip is not None:
             raise NotImplementedError("ZeRO-1 with a GradClip: each rank holds only its shard of the reduced gradient (the global norm would need a "
                                       "scalar all-reduce)")
@@ -739,11 +782,14 @@ class FusedAdamW:
             raise RuntimeError("FusedAdamW.state_dict(): after ZeRO-1 steps the moments (and with zero1='bf16' the fp32 masters) are current on "
                                "each rank's own shards only - call opt.gather_state(reducer) on every rank first")
         return {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
-                "param_groups": [dict(g) for g in self.param_groups]}
+                "param_groups": [dict(g) for g in self.param_groups], "moment_dtype": self.moment_dtype, "round_seed": self.round_seed}
 
     def load_state_dict(self, sd: Dict) -> None:
+        src = _moment_dtype(sd.get("moment_dtype", "fp32"))      # a dict without the key predates bf16 moments
         self.step_count = int(sd["step"])
-        self.exp_avg.copy_(sd["exp_avg"]); self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        _load_moments(self.exp_avg, sd["exp_avg"]); _load_moments(self.exp_avg_sq, sd["exp_avg_sq"])
+        if src == "bf16" and self.moment_dtype == "bf16":
+            self.round_seed = int(sd.get("round_seed", self.round_seed)) & 0xFFFFFFFF
         for g, s in zip(self.param_groups, sd["param_groups"]):
             g.update(s)
 
@@ -762,9 +808,17 @@ class FlatAdamW:
 
     ``clip`` (a ``GradClip``): device-side gradient norms / global-norm clipping / non-finite-safe steps over this optimizer's tensors - alone, or
     jointly with the denoiser's ``FusedAdamW`` (``clip.measure()``, then both ``step()``s); tensors whose ``.grad`` is None are not measured.  Its
-    ``names`` for this optimizer's tensors are ``g<group>.p<index>``."""
+    ``names`` for this optimizer's tensors are ``g<group>.p<index>``.
 
-    def __init__(self, params, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, clip=None):
+    ``moment_dtype="bf16"`` / ``round_seed``: bf16 moments with stochastic rounding, as in ``FusedAdamW`` (its docstring; ``mode_adamw_step_lp``) - at
+    this class's default ``beta2 = 0.999`` round-to-nearest would never let ``exp_avg_sq`` decay.  The rounding bits belong to an element's position
+    in its group's moment buffer, so cutting a group into runs changes nothing.  Convergence with bf16 moments has not been measured."""
+
+    def __init__(self, params, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, clip=None,
+                 moment_dtype: str = "fp32", round_seed: int = 0):
+        self.moment_dtype = _moment_dtype(moment_dtype)
+        self.round_seed = int(round_seed) & 0xFFFFFFFF
+        mdt = MOMENT_DTYPES[self.moment_dtype]
         self.clip = clip
         groups = list(params)
         if groups and not isinstance(groups[0], dict):
@@ -801,7 +855,8 @@ class FlatAdamW:
             offs, o = [], 0
             for sz in sizes:
                 offs.append((o, o + sz)); o += sz
-            self._flat.append(dict(flat=flat, grad=grad, views=views, exp_avg=torch.zeros(n, device=dev), exp_avg_sq=torch.zeros(n, device=dev), n=n,
+            self._flat.append(dict(flat=flat, grad=grad, views=views, exp_avg=torch.zeros(n, dtype=mdt, device=dev),
+                                   exp_avg_sq=torch.zeros(n, dtype=mdt, device=dev), n=n,
                                    spans=offs, ptrs=[p.data_ptr() for p in ps]))
         if clip is not None:
             clip._attach(self)
@@ -873,6 +928,13 @@ class FlatAdamW:
             clip._finish(grad_scale)
         for grp, f, runs in zip(self.param_groups, self._flat, all_runs):
             for lo, hi in runs:                                                 # ONE launch when every tensor has a gradient (the usual step)
+                if self.moment_dtype == "bf16":
+                    L.check(self.lib.mode_adamw_step_lp(f["flat"][lo:hi].data_ptr(), f["grad"][lo:hi].data_ptr(), f["exp_avg"][lo:hi].data_ptr(),
+                                                        f["exp_avg_sq"][lo:hi].data_ptr(), hi - lo, lo, float(grp["lr"]), float(grp["betas"][0]),
+                                                        float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]), self.step_count,
+                                                        self.round_seed, float(grad_scale), None, None, 0.0,
+                                                        None if clip is None else clip._state.data_ptr(), _stream()), "adamw_step_lp")
+                    continue
                 if clip is not None:
                     L.check(self.lib.mode_adamw_step_clipped(f["flat"][lo:hi].data_ptr(), f["grad"][lo:hi].data_ptr(), f["exp_avg"][lo:hi].data_ptr(),
                                                              f["exp_avg_sq"][lo:hi].data_ptr(), hi - lo, float(grp["lr"]), float(grp["betas"][0]),
@@ -889,12 +951,16 @@ class FlatAdamW:
 
     def state_dict(self) -> Dict:
         return {"step": self.step_count, "exp_avg": [f["exp_avg"] for f in self._flat], "exp_avg_sq": [f["exp_avg_sq"] for f in self._flat],
-                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups], "moment_dtype": self.moment_dtype,
+                "round_seed": self.round_seed}
 
     def load_state_dict(self, sd: Dict) -> None:
+        src = _moment_dtype(sd.get("moment_dtype", "fp32"))      # a dict without the key predates bf16 moments
         self.step_count = int(sd["step"])
         for f, m_, v_ in zip(self._flat, sd["exp_avg"], sd["exp_avg_sq"]):
-            f["exp_avg"].copy_(m_); f["exp_avg_sq"].copy_(v_)
+            _load_moments(f["exp_avg"], m_); _load_moments(f["exp_avg_sq"], v_)
+        if src == "bf16" and self.moment_dtype == "bf16":
+            self.round_seed = int(sd.get("round_seed", self.round_seed)) & 0xFFFFFFFF
         for g, s_ in zip(self.param_groups, sd["param_groups"]):
             g.update(s_)
 
