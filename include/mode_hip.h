@@ -96,6 +96,9 @@ const char* mode_hip_status_string(int status);
  * "fuse_qkv_attn": 1 (default) = mode_dit_forward runs the QKV projection and the attention of a block as ONE launch (mode_qkv_attn_fwd) where that
  *   kernel applies, 0 = mode_gemm + mode_attn_block_fwd.  "fuse_qkv_attn_min_b": smallest batch it is taken for (default 56); "qkv_attn_w3": 1 (default) = its weight tiles ride a three-slot LDS ring
  *   (160 KiB per workgroup), 0 = two slots; "qkv_attn_waves": 8 (default) or 4 waves per workgroup.  Same results either way.
+ * "weight_runahead": 1 (default) = mode_dit_forward hands the expert down-projection of block l the QKV and c_proj weights of block l + 1 (the last block:
+ *   block 0's, for the next denoise step) as touch ranges (ModeGemmDesc::touch0 / touch1) in the bf16 chain above "gemm_skinny_rows", 0 = no touch (A/B
+ *   runs).  Byte-identical results; - 2.8 % per chunk at B = 128 (profiles/weight_runahead.txt).
  * Unknown keys return MODE_ERR_BAD_ARG. */
 int mode_set_option(const char* key, int value);
 
@@ -181,6 +184,14 @@ typedef struct ModeGemmDesc {
                                   /* weight memory read for the data gradient (ldw = taps * Cin, N = Cin).  a_tap_cols % 64 == 0.                            */
   const ModeAdamWFuse* adamw;     /* (ABI 11) non-NULL: weight-gradient GEMM with the AdamW update in its epilogue (see ModeAdamWFuse); C only locates the tile. */
                                   /* MODE_ERR_UNSUPPORTED unless bf16 operands, MODE_GEMM_A_KM | W_KN, fp32 out, epilogue NONE, N % 128 == 0, ldc == N row pitch of the parameter */
+  /* Weight run-ahead (an addition to ABI 13; csrc/runahead.h): up to two byte ranges - weight matrices of the kernels BEHIND this one - that the
+   * launch pulls from HBM into the Infinity Cache with loads whose data nobody uses, one dword per 128-byte line, never past the range.  A HINT:
+   * results are byte-identical with and without it.  Honoured by the persistent ping-pong kernel ("gemm_cfg" 17 / 18; epilogues NONE and SWIGLU):
+   * every workgroup issues its share once, behind its first operand fill (at most 16 x 64 lines per workgroup and range; a longer range is touched as
+   * a prefix); every other kernel ignores it.  NULL / 0 bytes / a base that is not 4-byte aligned = no touch (the default: a zero-initialised
+   * descriptor behaves as before).  Bases should be 128-byte aligned so that the lines are cache lines. */
+  const void* touch0; int64_t touch0_bytes;
+  const void* touch1; int64_t touch1_bytes;
 } ModeGemmDesc;
 #define MODE_GEMM_SKINNY_OK 1
 /* Backward-pass operand layouts (bf16, epilogue NONE; replace autograd's mm_backward for nn.Linear, i.e. the `grad @ W` and

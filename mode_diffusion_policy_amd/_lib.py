@@ -40,7 +40,8 @@ class ModeGemmDesc(C.Structure):
                 ("c_group_stride", c_i64), ("flags", c_i32), ("w_rows", c_vp),
                 ("C2", c_vp), ("ldc2", c_i64), ("gain", c_vp), ("row_ss_out", c_vp), ("row_ss", c_vp), ("row_ss_n", c_i32), ("row_eps", c_f32),
                 ("w_tap_cols", c_i32), ("w_rows_tap_stride", c_i64), ("a_tap_cols", c_i32), ("a_rows_tap_stride", c_i64),
-                ("adamw", C.POINTER(ModeAdamWFuse))]
+                ("adamw", C.POINTER(ModeAdamWFuse)),
+                ("touch0", c_vp), ("touch0_bytes", c_i64), ("touch1", c_vp), ("touch1_bytes", c_i64)]      # weight run-ahead ranges (a hint; zero = none)
 
 
 class ModeEmbedDesc(C.Structure):

@@ -66,6 +66,7 @@ static WsLayout ws_layout(const ModeDims& d, int B, int R, int dtype) {
 }
 
 int g_fuse_ln2 = 1;     // "fuse_ln2" option: 1 = ln_2 folded into the c_proj epilogue / up-projection epilogue / combine (bf16 path), 0 = its own kernel
+int g_weight_runahead = 1;   // "weight_runahead" option: 1 = the large-batch chain's expert down-projection touches the next block's attention weights into the Infinity Cache (runahead.h), 0 = off
 int g_dn_split_k = 0;   // "dn_split_k" option: K-slices of the inference-path expert down-projection (0 = default 4, 1 = off, <= 8)
 
 // The expert down-projection [NK, 4D] x [D, 4D]^T has few output tiles (16 x 4 tiles of 224 x 256 at B=128) and a long K, so the 256 CUs are
@@ -145,6 +146,7 @@ extern "C" int mode_set_option(const char* key, int value) {
   if (!strcmp(key, "qkv_attn_waves")) { if (value != 4 && value != 8) return MODE_ERR_BAD_ARG; g_qkv_attn_waves = value; return MODE_OK; }
   if (!strcmp(key, "qkv_attn_w3")) { g_qkv_attn_w3 = value != 0; return MODE_OK; }
   if (!strcmp(key, "fuse_qkv_attn_min_b")) { if (value < 0) return MODE_ERR_BAD_ARG; g_fuse_qkv_attn_min_b = value; return MODE_OK; }
+  if (!strcmp(key, "weight_runahead")) { g_weight_runahead = value != 0; return MODE_OK; }
   if (!strcmp(key, "dn_split_k")) { if (value < 0 || value > 8) return MODE_ERR_BAD_ARG; g_dn_split_k = value; return MODE_OK; }
   return MODE_ERR_UNSUPPORTED;
 }
@@ -306,6 +308,7 @@ static int dit_forward_chain(const ModeDims* dims, const ModeModelWeights* w, co
   const int ssn = small ? D / 16 : D / 64;
   const int small_flag = small ? MODE_GEMM_SMALL_ROWS : 0;
   const bool qa_fused = g_fuse_qkv_attn && !small && dt == MODE_BF16 && g_gemm_cfg == 0 && B >= g_fuse_qkv_attn_min_b;
+  const bool runahead = g_weight_runahead && !small && dt == MODE_BF16;   // the touches ride the persistent ping-pong kernel (ModeGemmDesc::touch0); other geometries ignore them
   ModeMetaLayout ml;
   mode_moe_meta_layout(N, d.E, d.k, &ml);
   const int ysplit = down_proj_split(dt, 4 * D);
@@ -327,6 +330,14 @@ static int dit_forward_chain(const ModeDims* dims, const ModeModelWeights* w, co
   else rc = mode_embed_tokens_fwd(&e, stream);
   if (rc) return rc;
 
+  // weight run-ahead: Wqkv and Wo of the NEXT block (the last block: block 0's, which the next denoise step begins with) come out of HBM while the
+  // expert down-projection of this block runs - MFMA-bound, HBM almost idle.  Between touch and use lie that launch and the combine: ~120 MB of
+  // traffic, well under the Infinity Cache's 256 MiB.  (From the up-projection it wins the same: profiles/weight_runahead.txt.)
+  auto touch_next_attn = [&](ModeGemmDesc& gd, int l) {
+    const ModeLayerWeights& nw = w->layers[(l + 1) % d.L];
+    gd.touch0 = nw.wqkv; gd.touch0_bytes = 3L * D * D * 2;
+    gd.touch1 = nw.wo; gd.touch1_bytes = (long)D * D * 2;
+  };
   for (int l = 0; l < d.L; ++l) {
     const ModeLayerWeights& lw = w->layers[l];
     const int32_t* meta = tok_route ? reinterpret_cast<const int32_t*>(ws + L.tr_meta) : a->meta + (long)l * a->meta_layer_stride;
@@ -394,6 +405,7 @@ static int dit_forward_chain(const ModeDims* dims, const ModeModelWeights* w, co
     g.split_k = ysplit; g.split_stride = (long)NK * D;
     g.flags = small_flag;
     if (uniform) g.flags |= MODE_GEMM_UNIFORM_GROUPS;
+    if (runahead) touch_next_attn(g, l);
     rc = mode_gemm(&g, stream);
     if (rc) return rc;
     if (l + 1 < d.L) {

@@ -28,6 +28,7 @@
 // Numerics: every output element is the same k-ordered fp32 MFMA accumulation chain and the same epilogue expression as gemm_bf16.hip, so
 // results are BIT-IDENTICAL to the 128x128 kernels (the batch-slice consistency tests of the sampler rely on it).
 #include "gemm_pp_common.h"
+#include "runahead.h"
 
 // (Round 5's L2 run-ahead variant of this kernel - built, bit-identical, measured, lost: profiles/r05_pp_l2touch.txt - lives in scripts/probe/gemm_bf16_pp_l2touch.hip.)
 
@@ -38,7 +39,9 @@ using namespace ppc;                                       // half-tile constant
 constexpr int LDS_BIAS = 8 * HALF_BYTES;                   // 8 x 1 KiB: one bias slot per wave (each wave DMAs and reads its own copy)
 constexpr int LDS_NRM = LDS_BIAS + 8 * 1024;               // 2 x 256 floats: inverse row norms of the fused ln_2 (double-buffered per restart)
 constexpr int LDS_SS = LDS_NRM + 2 * 1024;                 // 256 rows x 64 B: per-64-column partial sums of squares of the tile's rows (DMA'd at a restart)
-constexpr int LDS_TOTAL = LDS_SS + 256 * 64;               // 154 KiB of the CU's 160
+constexpr int LDS_TOUCH = LDS_SS + 256 * 64;               // 8 x 256 B: one landing strip per wave for the weight run-ahead's touches (runahead.h) - never read
+constexpr int LDS_RA_ID = LDS_TOUCH + 8 * 256;             // 8 x 4 B: each wave's copy of the run-ahead's (issuing workgroups, index) word - parked here, not in a register
+constexpr int LDS_TOTAL = LDS_RA_ID + 64;                  // 156 KiB of the CU's 160
 __device__ __forceinline__ void lds_read_f4(float4& dst, uint32_t addr) {
   asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr) : "memory");
 }
@@ -55,7 +58,7 @@ __device__ __forceinline__ void lds_read_u4(u32x4& dst, uint32_t addr) {
 }  // namespace pp
 
 template <int EPI, bool OUT_BF16, int FM1>
-__global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
+__global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p, const RaRanges ra) {
   using namespace pp;
   constexpr int BM = 128 + 32 * FM1;                         // rows of an output tile: half 0 = 2 x 64, half 1 = 2 x 16*FM1
   constexpr bool SWI = EPI == MODE_EPI_SWIGLU;
@@ -92,6 +95,13 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
   if ((int)blockIdx.x >= nwg) return;
   const int wg = xcd_remap(blockIdx.x, nwg);
   int L = wg * R;
+  // weight run-ahead (first operand fill, below): every workgroup that has work issues its share once.  What it needs then - (workgroups << 16 |
+  // index), non-zero until it has been used - waits in LDS, one copy per wave (the same wave writes and reads it: no barrier): a scalar kept live
+  // across the K loop costs the loop body spill reloads (the kernel has no SGPR to spare; seen: + 4 v_readlane per K-step pair).
+  if constexpr (EPI != MODE_EPI_BIAS) {
+    if ((ra.bytes[0] | ra.bytes[1]) != 0)
+      asm volatile("ds_write_b32 %0, %1" ::"v"((uint32_t)(uintptr_t)smem + LDS_RA_ID + wave * 4), "v"((nwg << 16) | wg) : "memory");
+  }
   const int Lend = min(T, L + R);
   const int nk = p.K / BKK / S;                                // K-steps per slice (even, >= 2: checked by the launcher)
 
@@ -259,6 +269,23 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
 #pragma unroll
           for (int q = 0; q < 2; ++q)
             dma16(p.ss_in + (long)nrow[q] * p.ss_n + chunk * 4, smem + LDS_SS + (wave * 2 + q) * 1024);
+        }
+      }
+      // Weight run-ahead (runahead.h), once per workgroup, behind its FIRST operand fill: every wave issues its share of the touches of the ranges
+      // this launch was handed (matrices of the kernels behind it) - dword LDS-DMA into a strip nobody reads.  Here they cost no wait of their own:
+      // the fill in front of them comes from cold HBM as well, and the vmcnt(0) below waits for both.  (Behind the stores of the epilogue between
+      // two tiles - the other place outside the MFMA blocks - the next tile's first counted wait caught them in flight: up-projection + 1.9 us,
+      // profiles/weight_runahead.txt.)  The BIAS epilogue ignores the hint: no launch of the chain uses it, and its 256-row bf16 instantiation is one
+      // register short of reloading a spill inside its peeled MFMA block (the same instantiation MODE_ST_PP_B stays plain for).
+      if constexpr (EPI != MODE_EPI_BIAS) {
+        if ((ra.bytes[0] | ra.bytes[1]) != 0) {
+          int ra_id;
+          asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(ra_id) : "v"(lds0 + LDS_RA_ID + wave * 4) : "memory");
+          ra_id = __builtin_amdgcn_readfirstlane(ra_id);
+          if (ra_id != 0) {
+            ra_touch_ranges<8>(ra, ra_id >> 16, ra_id & 0xffff, wave, smem + LDS_TOUCH + wave * 256);
+            asm volatile("ds_write_b32 %0, %1" ::"v"(lds0 + LDS_RA_ID + wave * 4), "v"(0) : "memory");
+          }
         }
       }
       // K-steps 0 and 1 complete and waited for: the state in which every output tile begins (see the epilogue)
@@ -512,7 +539,7 @@ static int pp_launch(GemmParams p, const ModeGemmDesc* d, hipStream_t s) {
     const int rc = lds_once.ensure(reinterpret_cast<const void*>(kern), pp::LDS_TOTAL);
     if (rc != MODE_OK) return rc;
   }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), pp::LDS_TOTAL, s, p);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), pp::LDS_TOTAL, s, p, ra_make(d->touch0, d->touch0_bytes, d->touch1, d->touch1_bytes));
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }
