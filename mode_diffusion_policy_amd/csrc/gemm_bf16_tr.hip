@@ -484,7 +484,7 @@ int gemm_bf16_tr_swiglu_bwd_launch(const ModeGemmDesc* d, const void* P, void* d
 // Weight gradient dW[M, N] (per K-group z: + z * c_group_stride) = A^T W whose epilogue applies AdamW to the parameter tile the C pointer locates
 // (ModeAdamWFuse, include/mode_hip.h).  Single-buffered 128 x 128 ring tile, three workgroups per CU: the 416 KiB of p / m / v / shadow traffic of one
 // workgroup's epilogue run under the other workgroups' K loops - these launches are HBM-bound (26 B per parameter against ~7 us of MFMA work per tile).
-// The scalars are derived exactly as mode_adamw_step derives them (train_ops.hip), so both paths round alike.
+// The scalars come from the function mode_adamw_step takes them from (mode::adamw_coef), so both paths round alike.
 // Round-6 probe (scripts/probe/gemm_bf16_trws.hip, linked only by scripts/probe/build_trws_variant.sh): the same launch as ONE persistent wave-specialised
 // workgroup per CU.  Measured and not shipped (profiles/r06_fused_adamw_ws.txt: 190 vs 195 us isolated, 11.12 vs 10.52 ms in the step) - a weak symbol, null here.
 __attribute__((weak)) int gemm_bf16_trws_adamw_launch(TrParams p, const ModeGemmDesc* d, long gsq_slots, hipStream_t s);
@@ -501,11 +501,11 @@ static int tr_adamw_launch(const ModeGemmDesc* d, hipStream_t s) {
   p.koffs = d->k_group_offsets; p.c_gstride = d->c_group_stride; p.w_rows = d->w_rows; p.tap_cols = 0; p.tap_stride = 0;
   p.M = d->M; p.N = d->N; p.K = d->K; p.split_k = 1; p.split_stride = 0; p.m_tiles = p.n_tiles = 0;
   p.P = nullptr; p.dP = nullptr; p.seed = p.thresh = 0; p.inv_keep = 1.f; p.bsum = nullptr; p.tile_offs = nullptr;
-  const double bc1 = 1.0 - pow((double)z->beta1, z->step), bc2 = 1.0 - pow((double)z->beta2, z->step);
+  const AdamWCoef co = adamw_coef(z->lr, z->beta1, z->beta2, z->weight_decay, z->step);
   p.ad_p = z->param_base + ofs; p.ad_m = z->exp_avg_base + ofs; p.ad_v = z->exp_avg_sq_base + ofs;
   p.ad_lp = z->lp_base ? z->lp_base + ofs : nullptr; p.ad_ema = z->ema_base ? z->ema_base + ofs : nullptr; p.ad_ema_rate = z->ema_rate;
-  p.ad_decay = 1.f - z->lr * z->weight_decay; p.ad_b1 = z->beta1; p.ad_b2 = z->beta2; p.ad_eps = z->eps;
-  p.ad_step_size = (float)(z->lr / bc1); p.ad_inv_bc2_sqrt = (float)(1.0 / sqrt(bc2)); p.ad_gscale = z->grad_scale;
+  p.ad_decay = co.decay; p.ad_b1 = z->beta1; p.ad_b2 = z->beta2; p.ad_eps = z->eps;
+  p.ad_step_size = co.step_size; p.ad_inv_bc2_sqrt = co.inv_bc2_sqrt; p.ad_gscale = z->grad_scale;
   const long groups = d->k_group_offsets ? d->num_k_groups : 1;
   const long wgs = groups * ((d->M + 127) / 128) * (d->N / 128);
   if (z->gsq && z->gsq_capacity < wgs) return MODE_ERR_WORKSPACE;

@@ -5,6 +5,7 @@
 
 #include <atomic>
 
+#include "adamw_coef.h"
 #include "mode_hip.h"
 
 namespace mode {
@@ -170,6 +171,7 @@ __device__ __forceinline__ float ss16_tree(const float* s) {          // s[j] = 
 // ONE definition with every product / sum spelled out (explicit fmas, explicitly un-fused multiplies): the streaming optimizer pass (train_ops.hip:
 // adamw_kernel) and the weight-gradient GEMM's fused epilogue (gemm_bf16_tr.hip, EPI = 2) must round alike - left to the compiler, `v * b2 + (1 - b2) * g * g`
 // was contracted differently in the two kernels (seen: ~0.5 % of the second moments one ulp apart after the second step).
+// Its host half - decay, step_size and inv_bc2_sqrt from (lr, betas, weight decay, step) - is mode::adamw_coef (adamw_coef.h), for the same reason.
 __device__ __forceinline__ void adamw_update_f(float& w, float& m, float& v, float gr, float decay, float b1, float b2, float eps, float step_size, float inv_bc2_sqrt) {
   const float wd = __fmul_rn(w, decay);
   m = __builtin_fmaf(__fsub_rn(gr, m), __fsub_rn(1.f, b1), m);

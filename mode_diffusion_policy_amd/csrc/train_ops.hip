@@ -1036,18 +1036,29 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 
 namespace mode { int g_adamw_blocks = 0; }   // "adamw_blocks" option: cap on the workgroups of one AdamW launch (0 = 256, one per CU: 15.4 vs 15.8 ms per step with 2048; 0 = 512 for the bf16-moment launch)
 
-extern "C" int mode_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
-                               float weight_decay, int step, float grad_scale, void* lp_bf16, float* ema, float ema_rate, void* stream) {
+// The ONE launch behind the three entry points below: the shared argument checks (p / g 16-byte aligned, m / v 16 bytes as fp32 and 8 bytes as groups of
+// four bf16, the shadow 8), the host coefficients (mode::adamw_coef), the grid - `wg_cap`: the entry's default workgroup cap, overridden by "adamw_blocks" -
+// and the kernel call.  What an entry point refuses BEFORE the n == 0 return stays with that entry point.
+template <typename MT>
+static int adamw_launch(float* p, const float* g, MT* m, MT* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                        float gscale, void* lp_bf16, float* ema, float ema_rate, const ModeGradClipState* clip, uint32_t sr_key, long elem_base, int wg_cap,
+                        void* stream) {
   if (n == 0) return MODE_OK;
-  if (!p || !g || !m || !v || n < 0 || n % 4 || step < 1 || (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) || ((uintptr_t)lp_bf16 & 7))
+  if (!p || !g || !m || !v || n < 0 || n % 4 || step < 1 || (((uintptr_t)p | (uintptr_t)g) & 15) || (((uintptr_t)m | (uintptr_t)v) & (4 * sizeof(MT) - 1)) ||
+      ((uintptr_t)lp_bf16 & 7))
     return MODE_ERR_BAD_ARG;
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+  const AdamWCoef co = adamw_coef(lr, beta1, beta2, weight_decay, step);
   const long n4 = n / 4;
-  const int blocks = (int)std::min<long>((n4 + 511) / 512, g_adamw_blocks > 0 ? g_adamw_blocks : 256);
-  hipLaunchKernelGGL(adamw_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, 1.f - lr * weight_decay, beta1, beta2, eps,
-                     (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), grad_scale, (uint16_t*)lp_bf16, ema, ema_rate, (const ModeGradClipState*)nullptr, 0u, 0L);
+  const int blocks = (int)std::min<long>((n4 + 511) / 512, g_adamw_blocks > 0 ? g_adamw_blocks : wg_cap);
+  hipLaunchKernelGGL(adamw_kernel<MT>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, co.decay, beta1, beta2, eps, co.step_size,
+                     co.inv_bc2_sqrt, gscale, (uint16_t*)lp_bf16, ema, ema_rate, clip, sr_key, elem_base);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
+}
+
+extern "C" int mode_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                               float weight_decay, int step, float grad_scale, void* lp_bf16, float* ema, float ema_rate, void* stream) {
+  return adamw_launch<float>(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, lp_bf16, ema, ema_rate, nullptr, 0u, 0L, 256, stream);
 }
 
 // mode_adamw_step with the gradient scale (and the skip flag) read from the device-side clip state: same launch geometry, same kernel, same multiply
@@ -1055,16 +1066,7 @@ extern "C" int mode_adamw_step_clipped(float* p, const float* g, float* m, float
                                        float weight_decay, int step, void* lp_bf16, float* ema, float ema_rate, const ModeGradClipState* st,
                                        void* stream) {
   if (!st || ((uintptr_t)st & 3)) return MODE_ERR_BAD_ARG;
-  if (n == 0) return MODE_OK;
-  if (!p || !g || !m || !v || n < 0 || n % 4 || step < 1 || (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) || ((uintptr_t)lp_bf16 & 7))
-    return MODE_ERR_BAD_ARG;
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  const long n4 = n / 4;
-  const int blocks = (int)std::min<long>((n4 + 511) / 512, g_adamw_blocks > 0 ? g_adamw_blocks : 256);
-  hipLaunchKernelGGL(adamw_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, 1.f - lr * weight_decay, beta1, beta2, eps,
-                     (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), 1.f, (uint16_t*)lp_bf16, ema, ema_rate, st, 0u, 0L);
-  MODE_LAUNCH_CHECK();
-  return MODE_OK;
+  return adamw_launch<float>(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, 1.f, lp_bf16, ema, ema_rate, st, 0u, 0L, 256, stream);
 }
 
 // The AdamW step over bf16 moments (include/mode_hip.h): same launch geometry and arithmetic as the two calls above, m / v stored stochastically rounded
@@ -1072,20 +1074,10 @@ extern "C" int mode_adamw_step_lp(float* p, const float* g, void* m_bf16, void* 
                                   float eps, float weight_decay, int step, uint32_t round_seed, float grad_scale, void* lp_bf16, float* ema, float ema_rate,
                                   const ModeGradClipState* st, void* stream) {
   if (((uintptr_t)st & 3) || elem_base < 0 || elem_base % 4) return MODE_ERR_BAD_ARG;
-  if (n == 0) return MODE_OK;
-  if (!p || !g || !m_bf16 || !v_bf16 || n < 0 || n % 4 || step < 1 || (((uintptr_t)p | (uintptr_t)g) & 15) ||
-      (((uintptr_t)m_bf16 | (uintptr_t)v_bf16 | (uintptr_t)lp_bf16) & 7))
-    return MODE_ERR_BAD_ARG;
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  const long n4 = n / 4;
   // two workgroups per CU by default: with one wave per SIMD the rounding's integer arithmetic (two hashes per element) is not hidden behind the
   // loads - isolated launch 3.78 ms at 256 workgroups (fp32 moments: 3.34), 2.61 ms at 512, 2.80 ms at 1024 (profiles/adamw_lp.txt)
-  const int blocks = (int)std::min<long>((n4 + 511) / 512, g_adamw_blocks > 0 ? g_adamw_blocks : 512);
-  hipLaunchKernelGGL(adamw_kernel<uint16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, (uint16_t*)m_bf16, (uint16_t*)v_bf16, n4,
-                     1.f - lr * weight_decay, beta1, beta2, eps, (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), grad_scale, (uint16_t*)lp_bf16, ema, ema_rate, st,
-                     mode_stream_seed(round_seed, (uint32_t)step), (long)elem_base);
-  MODE_LAUNCH_CHECK();
-  return MODE_OK;
+  return adamw_launch<uint16_t>(p, g, (uint16_t*)m_bf16, (uint16_t*)v_bf16, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, lp_bf16, ema, ema_rate,
+                                st, mode_stream_seed(round_seed, (uint32_t)step), (long)elem_base, 512, stream);
 }
 
 extern "C" int mode_router_mlp_bwd(const float* dlog, const float* r_pre, const float* w3, int L, int B, int E, int H2, float* dpre, float* dw3,

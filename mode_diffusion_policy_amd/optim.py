@@ -8,6 +8,7 @@ for the 685 M-parameter denoiser) and also emits the bf16 compute shadow, so the
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 from typing import Dict, Tuple
@@ -85,6 +86,49 @@ def _load_moments(dst, src) -> None:
     """Checkpointed moments into this optimizer's buffers, either dtype: bf16 -> fp32 is exact; fp32 -> bf16 is a one-off round-to-nearest-even
     conversion (the only place bf16 moments are ever rounded that way - every step rounds stochastically)."""
     dst.copy_(src)
+
+
+def _merge_spans(spans):
+    """Union of half-open element spans ``(lo, hi)``, any order: ascending ``[lo, hi]`` lists, overlapping, nested and touching spans merged."""
+    merged = []
+    for lo, hi in sorted(map(tuple, spans)):
+        if merged and lo <= merged[-1][1]:
+            merged[-1][1] = max(merged[-1][1], hi)
+        else:
+            merged.append([lo, hi])
+    return merged
+
+
+def _carve(lo: int, hi: int, holes):
+    """The pieces of ``[lo, hi)`` outside ``holes`` (ascending and disjoint, as ``_merge_spans`` returns them): ascending, none of them empty."""
+    for flo, fhi in holes:
+        if flo < hi and fhi > lo:
+            if lo < flo:
+                yield lo, flo
+            lo = max(lo, fhi)
+    if lo < hi:
+        yield lo, hi
+
+
+def _adamw_launch(lib, p, g, m, v, lo: int, hi: int, group, step: int, *, moment_dtype: str, round_seed: int, grad_scale: float, lp=None, ema=None,
+                  ema_rate: float = 0.0, clip=None) -> None:
+    """The ONE AdamW launch of this module: elements ``[lo, hi)`` of the flat buffers ``p`` / ``g`` / ``m`` / ``v`` (``lp`` / ``ema`` where given) with
+    ``group``'s hyper-parameters.  bf16 moments: ``mode_adamw_step_lp``, ``elem_base = lo`` (the rounding bits belong to the element's place in the moment
+    buffer, not in the launch); else with a ``GradClip``: ``mode_adamw_step_clipped`` (scale and skip flag from its device-side state); else ``mode_adamw_step``."""
+    ptrs = (p[lo:hi].data_ptr(), g[lo:hi].data_ptr(), m[lo:hi].data_ptr(), v[lo:hi].data_ptr(), hi - lo)
+    hyper = (float(group["lr"]), float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]), float(group["weight_decay"]), step)
+    tail = (None if lp is None else lp[lo:hi].data_ptr(), None if ema is None else ema[lo:hi].data_ptr(), float(ema_rate))
+    state = None if clip is None else clip._state.data_ptr()
+    if moment_dtype == "bf16":
+        L.check(lib.mode_adamw_step_lp(*ptrs, lo, *hyper, round_seed, float(grad_scale), *tail, state, _stream()), "adamw_step_lp")
+    elif clip is not None:
+        L.check(lib.mode_adamw_step_clipped(*ptrs, *hyper, *tail, state, _stream()), "adamw_step_clipped")
+    else:
+        L.check(lib.mode_adamw_step(*ptrs, *hyper, float(grad_scale), *tail, _stream()), "adamw_step")
+
+
+# One FusedAdamW.step() as its launches see it, built once per step.  holes: the arena ranges left alone (frozen tensors, after a fused backward the experts)
+_StepCtx = collections.namedtuple("_StepCtx", "holes ema ema_rate lp grad_scale decay no_decay")
 
 
 class GradClip:
@@ -280,8 +324,6 @@ class FusedAdamW:
         self.exp_avg_sq = torch.zeros(n, dtype=MOMENT_DTYPES[self.moment_dtype], device=eng.device)
         self.step_count = 0
         self._side = None
-        self._ema_now = (None, 0.0)
-        self._frozen = []
         self._master_sharded = self._state_sharded = False
         self._sharded_emas = []                                  # ArenaEMAs updated inside ZeRO-1 steps since the last gather_state(): current on each rank's shards only
         self.param_groups = [dict(name="decay", lr=lr, betas=betas, eps=eps, weight_decay=weight_decay),
@@ -422,15 +464,8 @@ class FusedAdamW:
     def _frozen_ranges(self):
         """Arena element ranges of parameters with ``requires_grad == False`` (``freeze_router()`` for fine-tuning, mode_agent.py:762-766):
         torch's AdamW skips tensors without a gradient, so these slices are left untouched."""
-        ar = self.arena
-        base = ar.flat.data_ptr()
-        spans = sorted(((p.data_ptr() - base) // 4, (p.data_ptr() - base) // 4 + p.numel()) for _, p in self.eng.named_params() if not p.requires_grad)
-        merged = []
-        for lo, hi in spans:
-            if merged and lo <= merged[-1][1]:
-                merged[-1][1] = max(merged[-1][1], hi)
-            else:
-                merged.append([lo, hi])
+        base = self.arena.flat.data_ptr()
+        merged = _merge_spans(((p.data_ptr() - base) // 4, (p.data_ptr() - base) // 4 + p.numel()) for _, p in self.eng.named_params() if not p.requires_grad)
         for lo, hi in merged:
             if lo % 4 or hi % 4:
                 raise NotImplementedError("frozen parameter ranges must start and end on 16-byte boundaries of the arena")
@@ -455,40 +490,24 @@ class FusedAdamW:
         if self.eng.arena is not self.arena or self.arena.grad is None:
             raise RuntimeError("GradClip.measure(): the FusedAdamW member has no gradients (or its arena was rebuilt)")
 
-    def _launch(self, lo: int, hi: int, gp, lp, grad_scale: float) -> None:
-        for flo, fhi in self._frozen:                          # carve frozen slices (and, after a fused backward, the expert matrices) out of [lo, hi)
-            if flo < hi and fhi > lo:
-                if lo < flo:
-                    self._launch_raw(lo, flo, gp, lp, grad_scale)
-                lo = max(lo, fhi)
-                if lo >= hi:
-                    return
-        if lo < hi:
-            self._launch_raw(lo, hi, gp, lp, grad_scale)
-
-    def _launch_raw(self, lo: int, hi: int, gp, lp, grad_scale: float) -> None:
+    def _launch(self, lo: int, hi: int, group, ctx) -> None:
+        """AdamW over ``[lo, hi)`` of the arena minus the step's holes (frozen slices and, after a fused backward, the expert matrices)."""
         ar = self.arena
-        ema, rate = self._ema_now
-        if self.moment_dtype == "bf16":                        # elem_base = lo: the rounding bits belong to the element's place in the moment buffer, not in the launch
-            L.check(self.eng.lib.mode_adamw_step_lp(ar.flat[lo:hi].data_ptr(), ar.grad[lo:hi].data_ptr(), self.exp_avg[lo:hi].data_ptr(),
-                                                    self.exp_avg_sq[lo:hi].data_ptr(), hi - lo, lo, float(gp["lr"]), float(gp["betas"][0]),
-                                                    float(gp["betas"][1]), float(gp["eps"]), float(gp["weight_decay"]), self.step_count, self.round_seed,
-                                                    float(grad_scale), None if lp is None else lp[lo:hi].data_ptr(),
-                                                    None if ema is None else ema.flat[lo:hi].data_ptr(), float(rate),
-                                                    None if self.clip is None else self.clip._state.data_ptr(), _stream()), "adamw_step_lp")
-            return
-        if self.clip is not None:                              # the scale (and the skip flag) come from the device-side state of the measurement
-            L.check(self.eng.lib.mode_adamw_step_clipped(ar.flat[lo:hi].data_ptr(), ar.grad[lo:hi].data_ptr(), self.exp_avg[lo:hi].data_ptr(),
-                                                         self.exp_avg_sq[lo:hi].data_ptr(), hi - lo, float(gp["lr"]), float(gp["betas"][0]),
-                                                         float(gp["betas"][1]), float(gp["eps"]), float(gp["weight_decay"]), self.step_count,
-                                                         None if lp is None else lp[lo:hi].data_ptr(), None if ema is None else ema.flat[lo:hi].data_ptr(),
-                                                         float(rate), self.clip._state.data_ptr(), _stream()), "adamw_step_clipped")
-            return
-        L.check(self.eng.lib.mode_adamw_step(ar.flat[lo:hi].data_ptr(), ar.grad[lo:hi].data_ptr(), self.exp_avg[lo:hi].data_ptr(),
-                                             self.exp_avg_sq[lo:hi].data_ptr(), hi - lo, float(gp["lr"]), float(gp["betas"][0]),
-                                             float(gp["betas"][1]), float(gp["eps"]), float(gp["weight_decay"]), self.step_count,
-                                             float(grad_scale), None if lp is None else lp[lo:hi].data_ptr(),
-                                             None if ema is None else ema.flat[lo:hi].data_ptr(), float(rate), _stream()), "adamw_step")
+        for a, b in _carve(lo, hi, ctx.holes):
+            _adamw_launch(self.eng.lib, ar.flat, ar.grad, self.exp_avg, self.exp_avg_sq, a, b, group, self.step_count, moment_dtype=self.moment_dtype,
+                          round_seed=self.round_seed, grad_scale=ctx.grad_scale, lp=ctx.lp, ema=None if ctx.ema is None else ctx.ema.flat,
+                          ema_rate=ctx.ema_rate, clip=self.clip)
+
+    def _side_stream(self, coexec: bool):
+        """The side stream, created on first use.  ``coexec`` (the overlapped path): the per-block passes run BESIDE the next backward chains - tell the
+        library, so that its large backward GEMMs keep the ring kernels that leave CU resources free (include/mode_hip.h "bwd_coexec", process-wide) - but
+        not with the experts updated inside the backward: the 4-M-parameter pass left per block (22 us) fits between the kernels.  A quirk, kept: only
+        the call that CREATES the stream sets the option, so an optimizer whose first side-stream step was a ZeRO-1 one never does."""
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.eng.device, priority=int(os.environ.get("MODE_OPT_PRIO", "0")))
+            if coexec and not self.fuse_expert_step:
+                self.eng.lib.mode_set_option(b"bwd_coexec", 1)
+        return self._side
 
     def _block_slices(self):
         """[(lo, hi, layer)] of the per-block weight slices (arena order = backward order) and the remaining decay-region ranges."""
@@ -501,7 +520,7 @@ class FusedAdamW:
         return blocks, rest
 
     @torch.no_grad()
-    def _step_zero1(self, grad_scale: float, reducer, gather: str, lp, gd, gn) -> None:
+    def _step_zero1(self, ctx, reducer, gather: str) -> None:
         """ZeRO-1 over the data-parallel ranks: per block slice {reduce-scatter of the gradients (behind the block's backward event) -> AdamW on
         THIS rank's 1/world shard only -> all-gather of the updated weights}, everything chained per slice on side streams.  The HBM-bound
         optimizer pass shrinks by the world size (20.5 GB -> 2.6 GB per rank at 8 GPUs: 3.4 -> ~0.45 ms) and the wire carries a reduce-scatter +
@@ -509,27 +528,24 @@ class FusedAdamW:
         the bf16 shadow is re-cast locally); ``gather='bf16'``: only the bf16 compute shadow is gathered (half the bytes again) - the fp32
         masters of the OTHER ranks' shards are then refreshed from it (bf16-rounded) and ``gather_master()`` restores exact masters everywhere
         before a checkpoint."""
-        eng, ar = self.eng, self.arena
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=eng.device, priority=int(os.environ.get("MODE_OPT_PRIO", "0")))
+        ar, lp = self.arena, ctx.lp
+        self._side_stream(coexec=False)
         cur = torch.cuda.current_stream()
-        n_red = ar.bounds["no_decay"]
         dec = ar.bounds["decay"]
-        parts, done = [], []
+        done = []
         with torch.cuda.stream(self._side):
             # collectives run in issue order: per slice reduce-scatter -> (shard update) -> all-gather, so that the all-gather of block l travels
             # while the earlier blocks are still back-propagating instead of queueing behind every reduce-scatter
             for si in range(len(reducer.slices)):
                 with torch.cuda.stream(cur):
                     (lo, hi, slo, shi, ev), = reducer.reduce_scatter_async(only=si)
-                parts.append((lo, hi, slo, shi, ev))
                 if ev is not None:
                     self._side.wait_event(ev)
                 # the shard may straddle the decay / no-decay boundary
                 if slo < min(shi, dec):
-                    self._launch(slo, min(shi, dec), gd, lp, grad_scale)
+                    self._launch(slo, min(shi, dec), ctx.decay, ctx)
                 if max(slo, dec) < shi:
-                    self._launch(max(slo, dec), shi, gn, lp, grad_scale)
+                    self._launch(max(slo, dec), shi, ctx.no_decay, ctx)
                 upd = torch.cuda.Event(); upd.record(self._side)
                 if gather == "bf16" and lp is not None:
                     done.append((lo, hi, slo, shi, reducer.all_gather_async(lp, lo, hi, after=upd)))
@@ -582,7 +598,7 @@ class FusedAdamW:
         All-gathers ``exp_avg`` / ``exp_avg_sq`` (and every EMA that was passed to those steps) per slice and the masters, so that ``state_dict()`` / a checkpoint written by any rank - or a
         stand-alone ``ArenaEMA.update`` - sees the complete, exact state.  Collective: all ranks call it."""
         self.gather_master(reducer)
-        if getattr(self, "_state_sharded", False):
+        if self._state_sharded:
             evs = []
             for sl in reducer.slices:
                 for buf in (self.exp_avg, self.exp_avg_sq):
@@ -601,13 +617,94 @@ class FusedAdamW:
     @torch.no_grad()
     def gather_master(self, reducer) -> None:
         """After ``zero1='bf16'`` steps: all-gather the exact fp32 masters of every shard (call before ``state_dict()`` / a checkpoint)."""
-        if not getattr(self, "_master_sharded", False):
+        if not self._master_sharded:
             return
-        ev = [reducer.all_gather_async(self.arena.flat, lo, hi, after=None) for lo, hi, *_ in [(s[0], s[1]) for s in reducer.slices]]
+        ev = [reducer.all_gather_async(self.arena.flat, sl[0], sl[1], after=None) for sl in reducer.slices]
         for e in ev:
             if e is not None:
                 torch.cuda.current_stream().wait_event(e)
         self._master_sharded = False
+
+    def _reconcile_fused(self, reducer, use_zero1, grad_scale, ema):
+        """A fused backward has applied this step's expert update: where ``step()``'s arguments disagree with it the backward's settings win, and the
+        disagreement is returned as a DEFERRED exception (class docstring).  ``(reducer, use_zero1, grad_scale, deferred)``; changes no state."""
+        deferred = None
+        done_msg = "; the step was completed with the backward's settings (parameters, moments and step count are consistent)"
+        if use_zero1 or (reducer is not None and reducer.world > 1):
+            deferred = NotImplementedError("fuse_expert_step is a single-process mode: the expert matrices were updated from this rank's gradients only" + done_msg)
+            reducer, use_zero1 = None, False
+        if grad_scale is not None and float(grad_scale) != float(self.fused_grad_scale):
+            deferred = ValueError(f"step(grad_scale={grad_scale}) differs from the scale the fused backward applied ({self.fused_grad_scale}): set "
+                                  "opt.fused_grad_scale before loss.backward()" + done_msg)
+        if ema is not None and ema is not self.fused_ema and ema.flat is None and ema.should_apply(self.step_count + 1) \
+                and ema.get_decay(self.step_count + 1) != 0.0:
+            # this EMA did not exist when the backward updated the experts: its first copy would start from post-update expert weights (with a zero
+            # decay - the schedule's first step - the average equals the new weights either way and nothing is lost)
+            deferred = RuntimeError("fuse_expert_step: register the EMA as opt.fused_ema (or call ema.ensure(arena)) BEFORE the first backward - it is "
+                                    "initialised from the pre-update weights" + done_msg)
+        return reducer, use_zero1, self.fused_grad_scale, deferred
+
+    def _step_serial(self, ctx, reducer, clip, joint: bool) -> None:
+        """(Gradient exchange, measurement of an own clip, then) two launches over the decay / no-decay regions on the current stream."""
+        ar = self.arena
+        if reducer is not None:
+            reducer.reduce()
+        if clip is not None and not joint:                      # the whole (exchanged) gradient is there: stage 1, finish, then the launches read the state
+            clip._ensure()
+            clip._stage1(clip._segs[id(self)][0])
+            clip._finish(ctx.grad_scale)
+        self._launch(0, ar.bounds["decay"], ctx.decay, ctx)
+        self._launch(ar.bounds["decay"], ar.bounds["no_decay"], ctx.no_decay, ctx)
+
+    def _step_overlap(self, ctx, reducer, clip, joint: bool, events) -> None:
+        """Block l's update (with a clip: its measurement) on the side stream behind the backward's event for block l (``events``), the rest afterwards."""
+        ar, side, cur = self.arena, self._side_stream(coexec=True), torch.cuda.current_stream()
+        blocks, rest = self._block_slices()
+        done = reducer.reduce_async() if (reducer is not None and reducer.world > 1) else None    # {(lo, hi): event after the exchange}
+        seg = None
+        if clip is not None and not joint:
+            clip._ensure()
+            seg = clip._segs[id(self)][0]
+            per_block, other = clip._block_ranges(seg, [(lo, hi) for lo, hi, _ in blocks])
+            if clip._uploaded is not None:                                 # a table (re)built just now was uploaded on the current stream
+                side.wait_event(clip._uploaded)
+                clip._uploaded = None
+        with torch.cuda.stream(side):
+            for bi, (lo, hi, i) in enumerate(blocks):
+                side.wait_event(done[(lo, hi)] if done is not None else events[i])
+                if clip is None:
+                    self._launch(lo, hi, ctx.decay, ctx)
+                elif seg is not None:
+                    clip._stage1(seg, *per_block[bi])                      # the measurement of block l runs underneath the backward of the earlier blocks
+            side.wait_stream(cur)                                          # everything else needs the whole backward
+            if done is not None:
+                for ev in done.values():
+                    side.wait_event(ev)
+            if clip is not None:
+                if seg is not None:
+                    for first, count in other:
+                        clip._stage1(seg, first, count)
+                    clip._finish(ctx.grad_scale)
+                for lo, hi, i in blocks:                                   # the global norm needs every gradient: no update before this point
+                    self._launch(lo, hi, ctx.decay, ctx)
+            for lo, hi in rest:
+                self._launch(lo, hi, ctx.decay, ctx)
+            self._launch(ar.bounds["decay"], ar.bounds["no_decay"], ctx.no_decay, ctx)
+        cur.wait_stream(side)
+
+    def _ema_after_fused(self, ctx, fused_ema_rest) -> None:
+        """The stand-alone EMA passes of a fused step: over the expert ranges for an ``ema=`` the fused epilogue did not know about (not the registered
+        one), and over the REST of the arena for ``fused_ema_rest`` - the registered EMA when the epilogue applied it and ``step()`` did not (else None)."""
+        ar, passes = self.arena, []                              # (_expert_ranges() walks the arena layout: only where a pass needs it)
+        if ctx.ema is not None and ctx.ema is not self.fused_ema:
+            passes += [(ctx.ema, ctx.ema_rate, lo, hi) for lo, hi in self._expert_ranges()]
+        if fused_ema_rest is not None:
+            rate = 1.0 - fused_ema_rest.get_decay(self.step_count)
+            passes += [(fused_ema_rest, rate, lo, hi) for lo, hi in _carve(0, ar.bounds["total"], self._expert_ranges())]
+        for em, rate, lo, hi in passes:
+            L.check(self.eng.lib.mode_ema_update(em.flat[lo:hi].data_ptr(), ar.flat[lo:hi].data_ptr(), hi - lo, float(rate), _stream()), "ema_update")
+        if fused_ema_rest is not None:
+            fused_ema_rest.mark_applied(self.step_count)
 
     @torch.no_grad()
     def step(self, grad_scale=None, overlap: bool = False, reducer=None, ema=None, zero1=None) -> None:
@@ -648,20 +745,7 @@ class FusedAdamW:
                                "through MoDeDiT in training mode?)")
         deferred = None                                         # fused mode: a disagreement with what the backward applied - the step is COMPLETED first (class docstring)
         if fused:
-            done_msg = "; the step was completed with the backward's settings (parameters, moments and step count are consistent)"
-            if use_zero1 or (reducer is not None and reducer.world > 1):
-                deferred = NotImplementedError("fuse_expert_step is a single-process mode: the expert matrices were updated from this rank's gradients only" + done_msg)
-                reducer, use_zero1 = None, False
-            if grad_scale is not None and float(grad_scale) != float(self.fused_grad_scale):
-                deferred = ValueError(f"step(grad_scale={grad_scale}) differs from the scale the fused backward applied ({self.fused_grad_scale}): set "
-                                      "opt.fused_grad_scale before loss.backward()" + done_msg)
-            grad_scale = self.fused_grad_scale
-            if ema is not None and ema is not self.fused_ema and ema.flat is None and ema.should_apply(self.step_count + 1) \
-                    and ema.get_decay(self.step_count + 1) != 0.0:
-                # this EMA did not exist when the backward updated the experts: its first copy would start from post-update expert weights (with a zero
-                # decay - the schedule's first step - the average equals the new weights either way and nothing is lost)
-                deferred = RuntimeError("fuse_expert_step: register the EMA as opt.fused_ema (or call ema.ensure(arena)) BEFORE the first backward - it is "
-                                        "initialised from the pre-update weights" + done_msg)
+            reducer, use_zero1, grad_scale, deferred = self._reconcile_fused(reducer, use_zero1, grad_scale, ema)
         clip = self.clip
         if clip is not None and fused:
             raise NotImplementedError("fuse_expert_step with a GradClip")        # (unreachable through the public switches: both refuse the combination)
@@ -674,101 +758,35 @@ class FusedAdamW:
             grad_scale = clip._consume_check(self, grad_scale)
         if grad_scale is None:
             grad_scale = 1.0
-        self.step_count += 1
-        self._frozen = self._frozen_ranges()
+        self.step_count += 1                                    # the refusals above leave the state untouched
+        holes = self._frozen_ranges()
         if fused:                                               # the expert matrices are done: the passes below skip them exactly like frozen tensors
-            spans = sorted([list(x) for x in self._frozen] + [list(x) for x in self._expert_ranges()])
-            merged = []
-            for lo_, hi_ in spans:
-                if merged and lo_ <= merged[-1][1]:
-                    merged[-1][1] = max(merged[-1][1], hi_)
-                else:
-                    merged.append([lo_, hi_])
-            self._frozen = merged
+            holes = _merge_spans(holes + self._expert_ranges())
             self._fused_pending = False
-        self._ema_now = (None, 0.0)
+        ema_now, ema_rate = None, 0.0
         fe = self.fused_ema if fused else None                   # the backward applied this EMA to the expert matrices iff its schedule says so for this step
         fe_rest = fe is not None and fe is not ema and fe.should_apply(self.step_count)
         if ema is not None and ema.should_apply(self.step_count):
             ema.ensure(ar)
-            self._ema_now = (ema, 1.0 - ema.get_decay(self.step_count))
+            ema_now, ema_rate = ema, 1.0 - ema.get_decay(self.step_count)
             ema.mark_applied(self.step_count)
             if use_zero1 and reducer.world > 1:
                 ema._sharded = True                              # current on this rank's shards only until gather_state()
                 self._sharded_emas = [e for e in self._sharded_emas if e is not ema] + [ema]
         lp = ar.lp if eng.compute_dtype == "bf16" else None
-        gd, gn = self.param_groups
         train = getattr(eng, "_train", None)
         events = train.events if (train is not None and train.events is not None) else None
         if reducer is not None and reducer.world > 1:
             grad_scale = grad_scale * (1.0 if reducer.average else 1.0 / reducer.world)
+        ctx = _StepCtx(holes, ema_now, ema_rate, lp, grad_scale, *self.param_groups)
         if use_zero1:
-            self._step_zero1(grad_scale, reducer, zero1, lp, gd, gn)
+            self._step_zero1(ctx, reducer, zero1)
         elif not overlap or events is None:
-            if reducer is not None:
-                reducer.reduce()
-            if clip is not None and not joint:                  # the whole (exchanged) gradient is there: stage 1, finish, then the launches read the state
-                clip._ensure()
-                clip._stage1(clip._segs[id(self)][0])
-                clip._finish(grad_scale)
-            self._launch(0, ar.bounds["decay"], gd, lp, grad_scale)
-            self._launch(ar.bounds["decay"], ar.bounds["no_decay"], gn, lp, grad_scale)
+            self._step_serial(ctx, reducer, clip, joint)
         else:
-            if self._side is None:
-                self._side = torch.cuda.Stream(device=eng.device, priority=int(os.environ.get("MODE_OPT_PRIO", "0")))
-                # the per-block passes run BESIDE the next backward chains: tell the library, so that its large backward GEMMs keep the ring
-                # kernels that leave CU resources free (include/mode_hip.h "bwd_coexec"; process-wide like every option).  Not with the expert
-                # matrices updated inside the backward: what is left per block is a 4-M-parameter pass (22 us) that fits between the kernels
-                if not self.fuse_expert_step:
-                    eng.lib.mode_set_option(b"bwd_coexec", 1)
-            cur = torch.cuda.current_stream()
-            blocks, rest = self._block_slices()
-            done = reducer.reduce_async() if (reducer is not None and reducer.world > 1) else None    # {(lo, hi): event after the exchange}
-            seg = None
-            if clip is not None and not joint:
-                clip._ensure()
-                seg = clip._segs[id(self)][0]
-                per_block, other = clip._block_ranges(seg, [(lo, hi) for lo, hi, _ in blocks])
-                if clip._uploaded is not None:                                 # a table (re)built just now was uploaded on the current stream
-                    self._side.wait_event(clip._uploaded)
-                    clip._uploaded = None
-            with torch.cuda.stream(self._side):
-                for bi, (lo, hi, i) in enumerate(blocks):
-                    self._side.wait_event(done[(lo, hi)] if done is not None else events[i])
-                    if clip is None:
-                        self._launch(lo, hi, gd, lp, grad_scale)
-                    elif seg is not None:
-                        clip._stage1(seg, *per_block[bi])                      # the measurement of block l runs underneath the backward of the earlier blocks
-                self._side.wait_stream(cur)                                    # everything else needs the whole backward
-                if done is not None:
-                    for ev in done.values():
-                        self._side.wait_event(ev)
-                if clip is not None:
-                    if seg is not None:
-                        for first, count in other:
-                            clip._stage1(seg, first, count)
-                        clip._finish(grad_scale)
-                    for lo, hi, i in blocks:                                   # the global norm needs every gradient: no update before this point
-                        self._launch(lo, hi, gd, lp, grad_scale)
-                for lo, hi in rest:
-                    self._launch(lo, hi, gd, lp, grad_scale)
-                self._launch(ar.bounds["decay"], ar.bounds["no_decay"], gn, lp, grad_scale)
-            cur.wait_stream(self._side)
-        if fused and self._ema_now[0] is not None and self.fused_ema is not self._ema_now[0]:
-            ema_, rate_ = self._ema_now                          # the fused epilogue did not know about this EMA: one stand-alone pass over the expert ranges
-            for lo_, hi_ in self._expert_ranges():
-                L.check(eng.lib.mode_ema_update(ema_.flat[lo_:hi_].data_ptr(), ar.flat[lo_:hi_].data_ptr(), hi_ - lo_, float(rate_), _stream()), "ema_update")
-        if fe_rest:
-            # the fused epilogue applied the registered EMA to the expert matrices; the rest of the arena follows here (step() got no ema=, or another one)
-            ema_ = fe
-            rate_ = 1.0 - ema_.get_decay(self.step_count)
-            n_all = ar.bounds["total"]
-            prev = 0
-            for lo_, hi_ in self._expert_ranges() + [(n_all, n_all)]:
-                if prev < lo_:
-                    L.check(eng.lib.mode_ema_update(ema_.flat[prev:lo_].data_ptr(), ar.flat[prev:lo_].data_ptr(), lo_ - prev, float(rate_), _stream()), "ema_update")
-                prev = hi_
-            ema_.mark_applied(self.step_count)
+            self._step_overlap(ctx, reducer, clip, joint, events)
+        if fused:
+            self._ema_after_fused(ctx, fe if fe_rest else None)
         if joint:
             clip._consumed(self)
         eng.weights_updated(lp_synced=lp is not None)
@@ -778,7 +796,7 @@ class FusedAdamW:
 
     # ---- checkpointing (same information as torch's optimizer state, flat)
     def state_dict(self) -> Dict:
-        if getattr(self, "_state_sharded", False) or getattr(self, "_master_sharded", False):
+        if self._state_sharded or self._master_sharded:
             raise RuntimeError("FusedAdamW.state_dict(): after ZeRO-1 steps the moments (and with zero1='bf16' the fp32 masters) are current on "
                                "each rank's own shards only - call opt.gather_state(reducer) on every rank first")
         return {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
@@ -928,23 +946,8 @@ class FlatAdamW:
             clip._finish(grad_scale)
         for grp, f, runs in zip(self.param_groups, self._flat, all_runs):
             for lo, hi in runs:                                                 # ONE launch when every tensor has a gradient (the usual step)
-                if self.moment_dtype == "bf16":
-                    L.check(self.lib.mode_adamw_step_lp(f["flat"][lo:hi].data_ptr(), f["grad"][lo:hi].data_ptr(), f["exp_avg"][lo:hi].data_ptr(),
-                                                        f["exp_avg_sq"][lo:hi].data_ptr(), hi - lo, lo, float(grp["lr"]), float(grp["betas"][0]),
-                                                        float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]), self.step_count,
-                                                        self.round_seed, float(grad_scale), None, None, 0.0,
-                                                        None if clip is None else clip._state.data_ptr(), _stream()), "adamw_step_lp")
-                    continue
-                if clip is not None:
-                    L.check(self.lib.mode_adamw_step_clipped(f["flat"][lo:hi].data_ptr(), f["grad"][lo:hi].data_ptr(), f["exp_avg"][lo:hi].data_ptr(),
-                                                             f["exp_avg_sq"][lo:hi].data_ptr(), hi - lo, float(grp["lr"]), float(grp["betas"][0]),
-                                                             float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]), self.step_count, None, None,
-                                                             0.0, clip._state.data_ptr(), _stream()), "adamw_step_clipped")
-                    continue
-                L.check(self.lib.mode_adamw_step(f["flat"][lo:hi].data_ptr(), f["grad"][lo:hi].data_ptr(), f["exp_avg"][lo:hi].data_ptr(),
-                                                 f["exp_avg_sq"][lo:hi].data_ptr(), hi - lo, float(grp["lr"]), float(grp["betas"][0]), float(grp["betas"][1]),
-                                                 float(grp["eps"]), float(grp["weight_decay"]), self.step_count, float(grad_scale), None, None, 0.0, _stream()),
-                        "adamw_step")
+                _adamw_launch(self.lib, f["flat"], f["grad"], f["exp_avg"], f["exp_avg_sq"], lo, hi, grp, self.step_count, moment_dtype=self.moment_dtype,
+                              round_seed=self.round_seed, grad_scale=grad_scale, clip=clip)
             torch.autograd.graph.increment_version(grp["params"])                 # raw-pointer write: version-gated caches (conv weight shadows) must see it
         if joint:
             clip._consumed(self)

@@ -15,7 +15,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 from mode_diffusion_policy_amd import _lib as L  # noqa: E402
-from mode_diffusion_policy_amd.optim import FusedAdamW  # noqa: E402
+from mode_diffusion_policy_amd.optim import FusedAdamW, _adamw_launch  # noqa: E402
 from mode_diffusion_policy_amd.utils import rand_log_logistic  # noqa: E402
 
 BLOCK, ROUNDS, WARM = 50, 3, 3
@@ -75,7 +75,8 @@ for rnd in range(LAUNCH_ROUNDS + 1):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(LAUNCHES):
-                opt._launch_raw(0, n, gp, ar.lp, 1.0)
+                _adamw_launch(lib, ar.flat, ar.grad, opt.exp_avg, opt.exp_avg_sq, 0, n, gp, opt.step_count, moment_dtype=opt.moment_dtype,
+                              round_seed=opt.round_seed, grad_scale=1.0, lp=ar.lp)
             e1.record()
             torch.cuda.synchronize()
             if rnd:                                                   # round 0 warms up
