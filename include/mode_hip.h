@@ -596,6 +596,46 @@ int mode_adamw_step_lp(float* p, const float* g, void* m_bf16, void* v_bf16, int
                        const ModeGradClipState* st /* nullable: non-null overrides grad_scale, honours skip */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * LoRA adapters (an addition to ABI 13): rank-r adapters W_eff = W + s B A on a frozen base, as two stand-alone launches around the
+ * unchanged chains.  In bf16 compute every chain reads the bf16 shadow of the weights only, and the backward chain writes the dense
+ * weight gradient dW of every matrix into a flat fp32 buffer - so the merge rewrites the shadow and the projection reads that buffer.
+ *
+ * One descriptor serves both.  A target is a batch of G matrices [rows, cols], fp32 row-major, w_stride elements apart (W, out and dW
+ * alike: the arena's expert stride; G = 1 for wqkv / wo).  A [G, r, cols] and B [G, rows, r] are dense fp32.  scale: ONE device fp32
+ * value s, read by the kernels - a captured launch follows a later change of it.
+ * Accepted: 1 <= r <= MODE_LORA_MAX_RANK, cols % 8 == 0, any rows >= 1, w_stride % 8 == 0 (and >= rows * cols when G > 1); W, out, dW,
+ * A, dA and the workspace 16-byte aligned.  A rank or column count outside that returns MODE_ERR_UNSUPPORTED, any other violation
+ * MODE_ERR_BAD_ARG, a short workspace MODE_ERR_WORKSPACE; nothing is launched then.
+ *
+ * mode_lora_merge: out[g][i][j] = W[g][i][j] + s * acc_r with acc_0 = 0, acc_(k+1) = acc_k + B[g][i][k] * A[g][k][j], k ascending - every
+ *   product and every sum rounded to fp32 on its own (no fused multiply-add: the expression written with separate fp32 tensor operations
+ *   yields the same bits), then (out_dtype MODE_BF16) one round-to-nearest-even.  out is bf16 (a slice of the shadow, same element offsets as W)
+ *   or fp32, where out == W folds the adapter into the master in place.  Streaming: W is read once, out written once, 16 bytes per access.
+ * mode_lora_grad: dA[g][k][j] = s * sum_i B[g][i][k] dW[g][i][j], dB[g][i][k] = s * sum_j dW[g][i][j] A[g][k][j] (the chain rule of W_eff);
+ *   with accumulate != 0 both are added to what dA / dB hold.  dW is read from HBM once for both products: a workgroup owns a block of 64
+ *   rows, walks its columns, completes its rows of dB (one fp32 fma chain over ascending j) and writes its share of dA (one fma chain over
+ *   the block's rows, ascending) to the workspace; a second launch adds the shares in ascending block order, multiplies by s and stores.
+ *   No atomics: the bits do not depend on the grid or the run.  Workspace: G * ceil(rows / 64) * r * cols floats. */
+#define MODE_LORA_MAX_RANK 64
+typedef struct ModeLoraDesc {
+  int32_t G, rows, cols, r;
+  int64_t w_stride;                      /* elements between consecutive matrices of W / out / dW */
+  const float* W;                        /* merge: the frozen fp32 base */
+  const float* A;
+  const float* B;
+  const float* scale;                    /* device, one fp32 value: s = alpha / r */
+  void* out;                             /* merge: bf16 or fp32 (may be W) */
+  int32_t out_dtype;                     /* ModeDType of out */
+  int32_t accumulate;                    /* grad: add to dA / dB instead of overwriting them */
+  const float* dW;                       /* grad: the backward chain's dense weight gradient */
+  float* dA;
+  float* dB;
+} ModeLoraDesc;
+int mode_lora_merge(const ModeLoraDesc* d, void* stream);
+size_t mode_lora_grad_workspace_bytes(const ModeLoraDesc* d);           /* 0 for a descriptor mode_lora_grad would refuse on its shape */
+int mode_lora_grad(const ModeLoraDesc* d, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Whole-denoiser forward: the launch chain of one MoDeDiT.forward (modedit.py:741-821) [+ GCDenoiser.forward scalings
  * + one sample_ddim update], issued from C++ so a 10-step sampler is ~100 back-to-back launches per step with no host
  * logic in between (and can be captured into a hipGraph by the caller).

@@ -222,6 +222,15 @@ class ModeGradClipState(C.Structure):
     _fields_ = [("total_norm", c_f32), ("coef", c_f32), ("scale", c_f32), ("nonfinite", c_i32), ("skip", c_i32), ("skipped", c_i32), ("pad", c_i32 * 2)]
 
 
+MODE_LORA_MAX_RANK = 64
+
+
+class ModeLoraDesc(C.Structure):
+    """One LoRA target of mode_lora_merge / mode_lora_grad (include/mode_hip.h, an addition to ABI 13): G matrices [rows, cols], w_stride elements apart."""
+    _fields_ = [("G", c_i32), ("rows", c_i32), ("cols", c_i32), ("r", c_i32), ("w_stride", c_i64), ("W", c_vp), ("A", c_vp), ("B", c_vp), ("scale", c_vp),
+                ("out", c_vp), ("out_dtype", c_i32), ("accumulate", c_i32), ("dW", c_vp), ("dA", c_vp), ("dB", c_vp)]
+
+
 P = C.POINTER
 # name -> (restype, argtypes): every symbol include/mode_hip.h declares
 PROTOTYPES = {
@@ -325,6 +334,9 @@ PROTOTYPES = {
     "mode_head_ddim_guided_fwd": (C.c_int, [P(ModeHeadGuidedDesc), c_vp]),
     "mode_dit_forward_guided": (C.c_int, [P(ModeDims), P(ModeModelWeights), P(ModeGuidedArgs), c_vp, c_sz, c_vp]),
     "mode_frames_preprocess": (C.c_int, [P(ModeFramePrepDesc), c_vp]),
+    "mode_lora_merge": (C.c_int, [P(ModeLoraDesc), c_vp]),
+    "mode_lora_grad_workspace_bytes": (c_sz, [P(ModeLoraDesc)]),
+    "mode_lora_grad": (C.c_int, [P(ModeLoraDesc), c_vp, c_sz, c_vp]),
 }
 
 _lib: Optional[C.CDLL] = None

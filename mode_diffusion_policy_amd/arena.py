@@ -107,6 +107,7 @@ class ParamArena:
         self.g_by_name: Dict[str, torch.Tensor] = {}
         self.lp_synced = False
         self.version = 0                                                        # bumped whenever the weights change
+        self.lora_merged = ()                                                   # target kinds whose shadow slices hold an adapter's merge (lora.py)
 
     def _views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
         return {key: flat[off: off + int(torch.Size(shp).numel())].view(shp) for key, shp, off in self.layout}

@@ -87,6 +87,7 @@ class DitEngine:
         self._structs_for = None
         self.arena = None
         self._ws: Optional[torch.Tensor] = None
+        self._lora_bufs: dict = {}                              # LoRA projection scratch shared by the model's adapters (lora.py: grad_scratch, project)
         self._ws_pin: Optional[torch.Tensor] = None            # workspace owned by a hipGraph being warmed up / captured (see pinned_workspace)
         m = model
         self.dims = L.ModeDims(D=m.embed_dim, H=m.n_heads, L=m.num_layers, E=m.num_experts, k=m.top_k, T=m.seq_len,
@@ -120,7 +121,8 @@ class DitEngine:
 
     def _key(self):
         ar = self.arena
-        return (id(ar), ar.version, tuple(p._version for _, _, p, _ in self.param_index()))
+        lora = self.model.__dict__.get("_lora")                     # an attached LoraAdapter (lora.py): its parameters' versions re-merge the shadow
+        return (id(ar), ar.version, tuple(p._version for _, _, p, _ in self.param_index()), None if lora is None else lora._key())
 
     def ensure_weights(self) -> None:
         """Adopt the module's parameters into the flat arena (once) and keep the compute shadow current.
@@ -144,8 +146,11 @@ class DitEngine:
             return
         if self._pv is not None and key[2] != self._pv:
             ar.lp_synced = False                                    # somebody wrote through the Parameter views
+        lora = m.__dict__.get("_lora")
         if self.compute_dtype == "bf16":
             ar.ensure_lp()
+        if lora is not None:
+            lora._merge_into(self)                                  # the targeted slices of the shadow = bf16(W + s B A), from the fp32 master
         if self._structs_for != (id(ar), ar.lp is not None):
             self._build_structs()
         self._wkey, self._pv = key, key[2]

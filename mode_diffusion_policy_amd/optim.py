@@ -316,6 +316,8 @@ class FusedAdamW:
                                       "backward, before a norm could exist")
         self.clip = clip                                     # a GradClip: device-side gradient norms / global-norm clipping / non-finite-safe steps (its docstring)
         self.model = model
+        from .lora import note_fused_adamw
+        note_fused_adamw(model, self)                        # refused on a model with a LoraAdapter attached (the base is frozen: FlatAdamW on the adapter)
         eng = model.engine                                   # adopts the parameters into the arena
         self.eng, self.arena = eng, eng.arena
         model.grad_mode = "arena"                            # this optimizer reads the flat gradient arena: the backward chain writes there directly
@@ -988,6 +990,9 @@ class ArenaEMA:
         self._sharded = False                                    # True between a ZeRO-1 step(ema=self) and FusedAdamW.gather_state(): own shards only
 
     def _need_complete(self, what: str) -> None:
+        if getattr(self.model, "_lora", None) is not None:
+            raise RuntimeError(f"ArenaEMA.{what}: a LoraAdapter is attached - the base weights are frozen and the shadow holds the merged weights; "
+                               "average the adapter's parameters instead")
         if self._sharded:
             raise RuntimeError(f"ArenaEMA.{what}: the average is current on each rank's own shards only after ZeRO-1 steps - call "
                                "optimizer.gather_state(reducer) on every rank first")

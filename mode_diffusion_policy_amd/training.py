@@ -155,7 +155,8 @@ class _Run:
 class _DitTrainFn(torch.autograd.Function):
     """Outputs: F (B, A_len, A), the load-balancing loss and the router z-loss of this forward (scalars).  One backward serves all three.
     Inputs: the (fp32, on-device) state_images and preprocessed goals - so that an upstream encoder trains through the denoiser like it does
-    in the reference (mode_agent.py:404-411, 548-567) - and every parameter that can receive a gradient."""
+    in the reference (mode_agent.py:404-411, 548-567) - and every parameter that can receive a gradient; with a LoraAdapter attached (lora.py) those
+    are the adapter's tensors, whose gradients mode_lora_grad projects out of the chain's dense weight gradients."""
 
     @staticmethod
     def forward(ctx, run, img, goals, *params):
@@ -333,6 +334,10 @@ def dit_forward_train(model, states, actions, goals, sigma, uncond=False):
     # so that DistributedDataParallel(find_unused_parameters=True) - how the reference trains, training_calvin.py:92-103 - sees it as unused.
     named = [(n, p) for n, p in eng.named_params() if p.requires_grad and n != "gripper_embed.weight"]
     names, params = [n for n, _ in named], [p for _, p in named]
+    # an attached LoraAdapter (lora.py): the base is frozen (params is empty then); its own tensors are the node's trainable inputs
+    lora = model.__dict__.get("_lora")
+    lparams = [p for p in lora.parameters() if p.requires_grad] if lora is not None else []
+    lkey = lora._key() if lora is not None else None            # the adapter this forward ran with: identity, scale, parameter versions
 
     def backward(dF: torch.Tensor, dlb=None, dz=None, want_img=False, want_goal=False):
         """Runs the backward chain.  ``model.grad_mode``:
@@ -370,8 +375,8 @@ def dit_forward_train(model, states, actions, goals, sigma, uncond=False):
         # the optimizer consumed the previous sum); otherwise into a buffer of its own: handed to autograd (autograd mode), or ADDED to the
         # arena - a second backward before the optimizer step must accumulate like autograd does (the reference's training_step sums the losses
         # of several modalities, mode_agent.py:386-440).
-        accumulate = grad_mode == "arena" and getattr(ar, "grad_pending", False) and any(p.grad is not None for p in all_params if p.requires_grad)
-        own = grad_mode != "arena" or accumulate
+        accumulate = lora is None and grad_mode == "arena" and getattr(ar, "grad_pending", False) and any(p.grad is not None for p in all_params if p.requires_grad)
+        own = lora is not None or grad_mode != "arena" or accumulate
         # (accumulate: zero-filled - the chain does not write the 256-byte alignment gaps between tensors, and whatever sits there would be added
         # into the arena's gaps; autograd mode only ever exposes per-tensor views)
         # Memory: in autograd mode every backward allocates one buffer of the arena's size (2.7 GB at C2) and the p.grad views AccumulateGrad keeps
@@ -379,7 +384,15 @@ def dit_forward_train(model, states, actions, goals, sigma, uncond=False):
         # (0.5 ms per backward at C2): the chain writes every element of every tensor it returns - MODE_DEBUG_GRAD_COVERAGE=1 checks exactly that
         # (NaN pre-fill, every returned view must come back finite; tests/test_gpu_train_dropin.py runs it over the shipped layouts).
         debug_cov = own and not accumulate and os.environ.get("MODE_DEBUG_GRAD_COVERAGE", "0") == "1"
-        flat = (torch.zeros if accumulate else torch.empty)(ar.bounds["total"], device=dev) if own else None
+        if lora is not None:
+            # the chain's dense gradients are scratch here: mode_lora_grad projects them onto the adapter below and nothing else reads them
+            if model.__dict__.get("_lora") is not lora or lora._key() != lkey:
+                # the projection reads A and B as they are NOW: refuse what autograd's version check would refuse for saved tensors
+                raise RuntimeError("the LoraAdapter was modified (optimizer step, load_state_dict, alpha) or replaced between this forward and its "
+                                   "backward: its gradients would belong to another point - run the forward again")
+            flat = lora.grad_scratch(eng)
+        else:
+            flat = (torch.zeros if accumulate else torch.empty)(ar.bounds["total"], device=dev) if own else None
         if debug_cov:
             flat.fill_(float("nan"))
         mg, gv = ts.grad_tables(flat)
@@ -400,6 +413,10 @@ def dit_forward_train(model, states, actions, goals, sigma, uncond=False):
             holes = [n for n in names if not bool(torch.isfinite(gv[n]).all())]
             if holes:
                 raise RuntimeError(f"backward chain left gradient elements unwritten (or non-finite) in: {holes[:8]}")
+        if lora is not None:
+            # dA = s B^T dW, dB = s dW A^T per layer, expert and target, handed to autograd (a second backward accumulates there); the base
+            # parameters are frozen: their .grad stays None
+            return d_img, d_goal, [None] * len(params) + lora.project(eng, flat, lparams)
         if grad_mode != "arena":
             return d_img, d_goal, [gv[n].view(p.shape) for n, p in zip(names, params)]
         if accumulate:
@@ -419,7 +436,7 @@ def dit_forward_train(model, states, actions, goals, sigma, uncond=False):
     run.backward, run.keep = backward, keep_alive
     run.F_shape, run.device = tuple(F.shape), dev
     run.outs = (F, lb_mean, zl_mean)                                        # taken out of `run` by the node (see _DitTrainFn.forward)
-    Fo, lb_o, z_o = _DitTrainFn.apply(run, img_in, goal_in, *params)
+    Fo, lb_o, z_o = _DitTrainFn.apply(run, img_in, goal_in, *params, *lparams)
     model._aux_losses = (lb_o, z_o)                                             # what load_balancing_loss() / compute_router_z_loss() return in training
     return Fo
 
