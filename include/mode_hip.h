@@ -635,6 +635,34 @@ int mode_lora_merge(const ModeLoraDesc* d, void* stream);
 size_t mode_lora_grad_workspace_bytes(const ModeLoraDesc* d);           /* 0 for a descriptor mode_lora_grad would refuse on its shape */
 int mode_lora_grad(const ModeLoraDesc* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Factored adapter gradients (an addition to ABI 13): dA and dB straight from the operands of the dense weight-gradient GEMM, without a
+ * rows x cols tensor.  With Y = X W_eff^T, X [M, cols] and dY [M, rows] (bf16, the operands mode_dit_backward's weight-gradient GEMMs read):
+ *   T = dY B [M, r],  U = X A^T [M, r],  dA = s T^T X [r, cols],  dB = s dY^T U [rows, r]
+ * per group g of rows group_offsets[g] .. group_offsets[g + 1] (offsets outside [0, M] are clamped).  bf16 operands expand exactly to fp32, A and
+ * B are used as fp32, every product is a k-ordered fp32 fma chain on v_mfma_f32_16x16x4_f32.  Order of summation, fixed by the shape and the
+ * offsets alone: T / U - the contraction in steps of 32, every fourth step to one of four chains, the four added in order; dA / dB - a group's
+ * rows in blocks of 128 counted from its first row, one chain per block, the blocks added in ascending order, then one multiplication by s.
+ * No atomics; a group without rows gets +0.0 everywhere; dA and dB are written, never accumulated.
+ * Accepted: 1 <= r <= MODE_LORA_MAX_RANK, rows % 8 == 0, cols % 8 == 0 (both >= 8), dtype MODE_BF16, M >= 0, G >= 1; X, dY, A, B, dA, dB and the
+ * workspace 16-byte aligned, ld_x and ld_dy multiples of 8 and at least cols / rows; group_offsets == NULL only with G == 1.  A rank, row count,
+ * column count or dtype outside that returns MODE_ERR_UNSUPPORTED, any other violation MODE_ERR_BAD_ARG, a short workspace
+ * MODE_ERR_WORKSPACE; nothing is launched and nothing written then.  Workspace: T and U [M, r] fp32 and (M / 128 + G + 1) block shares of
+ * r * (rows + cols) floats. */
+typedef struct ModeLoraFactDesc {
+  int32_t G, rows, cols, r;              /* G matrices [rows, cols]; A [G, r, cols], B [G, rows, r] dense fp32 */
+  int32_t M;                             /* rows of X and dY */
+  int32_t dtype;                         /* ModeDType of X and dY: MODE_BF16 only */
+  const void* X;  int64_t ld_x;          /* [M, cols] */
+  const int32_t* x_rows;                 /* optional: row m of X is X[x_rows[m]] (the up-projection's `perm` gather); NULL = m */
+  const void* dY; int64_t ld_dy;         /* [M, rows] */
+  const int32_t* group_offsets;          /* device, G + 1 ascending row offsets (the dispatch `offsets`); NULL: G == 1, all M rows */
+  const float* A; const float* B;
+  const float* scale;                    /* device, one fp32 value, read at run time like ModeLoraDesc.scale */
+  float* dA; float* dB;                  /* [G, r, cols], [G, rows, r] */
+} ModeLoraFactDesc;
+size_t mode_lora_fact_workspace_bytes(const ModeLoraFactDesc* d);       /* 0 for a descriptor that would be refused on its shape */
+int mode_lora_fact_grad(const ModeLoraFactDesc* d, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Whole-denoiser forward: the launch chain of one MoDeDiT.forward (modedit.py:741-821) [+ GCDenoiser.forward scalings
  * + one sample_ddim update], issued from C++ so a 10-step sampler is ~100 back-to-back launches per step with no host
@@ -825,6 +853,27 @@ typedef struct ModeModelWeightsT { const float* w_outT; /* [D, A] */ const ModeL
 int mode_dit_backward(const ModeDims* dims, const ModeModelWeights* w, const ModeModelWeightsT* wt, const ModeTrainArgs* a,
                       const void* stash, const float* dF, const ModeModelGrads* grads, void* workspace, size_t workspace_bytes,
                       void* stream);
+
+/* mode_dit_backward for a LoRA adapter on a frozen base (an addition to ABI 13).  The same chain, except that in every block NONE of the four
+ * weight-gradient GEMMs (dW2, dW1, dWo, dWqkv) is launched - nor the sorted copy of the u rows that feeds dW1 only - and the wqkv / wo / w1 / w2
+ * slots of ModeLayerGrads are neither read nor written (they may be NULL).  For an adapted kind one mode_lora_fact_grad takes the GEMM's place,
+ * on the same stream and over the same operands (w2: dYs and the stashed H by `offsets`; w1: dP and the stashed u rows through `perm`; wo: dx1 and
+ * yattn; wqkv: dqkv and h1), writing dA[kind][l] / dB[kind][l]; layer_events[l] is still recorded behind block l's launches.  Everything
+ * else - data gradients, bias, gain, router and embedding gradients, token routing, dropout, d_state_images, d_goals - is mode_dit_backward's.
+ * Tables are indexed [kind][layer], kind order wqkv, wo, w1, w2; a NULL A[kind] means the kind is not adapted.  A [G, r, cols] and B [G, rows, r]
+ * per layer as for ModeLoraFactDesc (G = E for w1 / w2, else 1).  bf16 compute only (else MODE_ERR_UNSUPPORTED); a->fuse_adamw must be NULL
+ * (else MODE_ERR_BAD_ARG); lora->workspace holds at least mode_dit_backward_lora_workspace_bytes(dims, B, r) bytes (else MODE_ERR_WORKSPACE). */
+typedef struct ModeLoraTrain {
+  int32_t r; int32_t reserved;
+  const float* scale;                    /* device, one fp32 value */
+  const float* const* A[4]; const float* const* B[4];
+  float* const* dA[4]; float* const* dB[4];
+  void* workspace; size_t workspace_bytes;
+} ModeLoraTrain;
+size_t mode_dit_backward_lora_workspace_bytes(const ModeDims* dims, int B, int r);      /* 0 for dims, B or r the chain would refuse */
+int mode_dit_backward_lora(const ModeDims* dims, const ModeModelWeights* w, const ModeModelWeightsT* wt, const ModeTrainArgs* a,
+                           const void* stash, const float* dF, const ModeModelGrads* grads, const ModeLoraTrain* lora, void* workspace,
+                           size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * FiLM-ResNet perceptual encoders (mode/models/perceptual_encoders/pretrained_resnets.py:5-60, resnets.py:27-200,

@@ -231,6 +231,23 @@ class ModeLoraDesc(C.Structure):
                 ("out", c_vp), ("out_dtype", c_i32), ("accumulate", c_i32), ("dW", c_vp), ("dA", c_vp), ("dB", c_vp)]
 
 
+class ModeLoraFactDesc(C.Structure):
+    """mode_lora_fact_grad (include/mode_hip.h, an addition to ABI 13): dA / dB of G matrices [rows, cols] from the bf16 operands X [M, cols] and
+    dY [M, rows] of the dense weight-gradient GEMM, grouped by row offsets."""
+    _fields_ = [("G", c_i32), ("rows", c_i32), ("cols", c_i32), ("r", c_i32), ("M", c_i32), ("dtype", c_i32), ("X", c_vp), ("ld_x", c_i64),
+                ("x_rows", c_vp), ("dY", c_vp), ("ld_dy", c_i64), ("group_offsets", c_vp), ("A", c_vp), ("B", c_vp), ("scale", c_vp),
+                ("dA", c_vp), ("dB", c_vp)]
+
+
+LORA_KINDS = ("wqkv", "wo", "w1", "w2")                          # the [kind] order of ModeLoraTrain's tables
+
+
+class ModeLoraTrain(C.Structure):
+    """mode_dit_backward_lora: per kind a table of per-layer A / B / dA / dB pointers (NULL table = kind not adapted) and the factored workspace."""
+    _fields_ = [("r", c_i32), ("reserved", c_i32), ("scale", c_vp), ("A", c_vp * 4), ("B", c_vp * 4), ("dA", c_vp * 4), ("dB", c_vp * 4),
+                ("workspace", c_vp), ("workspace_bytes", c_sz)]
+
+
 P = C.POINTER
 # name -> (restype, argtypes): every symbol include/mode_hip.h declares
 PROTOTYPES = {
@@ -337,6 +354,11 @@ PROTOTYPES = {
     "mode_lora_merge": (C.c_int, [P(ModeLoraDesc), c_vp]),
     "mode_lora_grad_workspace_bytes": (c_sz, [P(ModeLoraDesc)]),
     "mode_lora_grad": (C.c_int, [P(ModeLoraDesc), c_vp, c_sz, c_vp]),
+    "mode_lora_fact_workspace_bytes": (c_sz, [P(ModeLoraFactDesc)]),
+    "mode_lora_fact_grad": (C.c_int, [P(ModeLoraFactDesc), c_vp, c_sz, c_vp]),
+    "mode_dit_backward_lora_workspace_bytes": (c_sz, [P(ModeDims), C.c_int, C.c_int]),
+    "mode_dit_backward_lora": (C.c_int, [P(ModeDims), P(ModeModelWeights), P(ModeModelWeightsT), P(ModeTrainArgs), c_vp, c_vp, P(ModeModelGrads),
+                                         P(ModeLoraTrain), c_vp, c_sz, c_vp]),
 }
 
 _lib: Optional[C.CDLL] = None

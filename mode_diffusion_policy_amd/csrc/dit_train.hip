@@ -245,9 +245,10 @@ extern "C" int64_t mode_adamw_fuse_gsq_floats(const ModeDims* dims) {
   return (long)dims->L * dims->E * 12 * t * t;
 }
 
-extern "C" int mode_dit_backward(const ModeDims* dims, const ModeModelWeights* w, const ModeModelWeightsT* wt, const ModeTrainArgs* a,
-                                 const void* stash, const float* dF, const ModeModelGrads* gr, void* workspace, size_t workspace_bytes,
-                                 void* stream) {
+// The backward chain.  lora == nullptr: every launch as documented for mode_dit_backward.  lora != nullptr (mode_dit_backward_lora): the four weight-gradient
+// GEMMs of every block are not launched - the base is frozen - and an adapted kind gets one mode_lora_fact_grad over the very operands its GEMM would read.
+static int backward_impl(const ModeDims* dims, const ModeModelWeights* w, const ModeModelWeightsT* wt, const ModeTrainArgs* a, const void* stash,
+                         const float* dF, const ModeModelGrads* gr, const ModeLoraTrain* lora, void* workspace, size_t workspace_bytes, void* stream) {
   int rc = check_train_dims(dims);
   if (rc) return rc;
   if (!w || !w->layers || !wt || !wt->layers || !a || !stash || !dF || !gr || !gr->layers || !workspace) return MODE_ERR_BAD_ARG;
@@ -265,6 +266,19 @@ extern "C" int mode_dit_backward(const ModeDims* dims, const ModeModelWeights* w
   }
   const bool tr = dt == MODE_BF16 && D % 8 == 0;      // bf16: backward GEMMs read row-major operands directly (gemm_bf16_tr.hip); no transposed copies
   int du_split = (tr && (8 * D) % 128 == 0) ? 2 : 1;   // K-slices of the up-projection data gradient
+  if (lora) {
+    if (!tr) return MODE_ERR_UNSUPPORTED;                // bf16 compute only: the factored launches read the bf16 operands of the skipped GEMMs
+    if (a->fuse_adamw) return MODE_ERR_BAD_ARG;         // the fused step updates the base, which an adapter freezes
+    if (lora->r < 1 || lora->r > MODE_LORA_MAX_RANK) return MODE_ERR_UNSUPPORTED;
+    bool any = false;
+    for (int kd = 0; kd < 4; ++kd) {
+      if (!lora->A[kd]) continue;
+      if (!lora->B[kd] || !lora->dA[kd] || !lora->dB[kd]) return MODE_ERR_BAD_ARG;
+      any = true;
+    }
+    if (any && (!lora->scale || !lora->workspace)) return MODE_ERR_BAD_ARG;
+    if (any && lora->workspace_bytes < mode_dit_backward_lora_workspace_bytes(dims, B, lora->r)) return MODE_ERR_WORKSPACE;
+  }
   const bool bf = dt == MODE_BF16;
   const long NKp = ((long)NK + 63) / 64 * 64 + 64L * E, Np = ((long)N + 63) / 64 * 64;
   const int Ktok = bf ? (int)Np : N;                       // token-dim contraction length (bf16 kernel needs a multiple of 64: zero padded)
@@ -338,6 +352,16 @@ extern "C" int mode_dit_backward(const ModeDims* dims, const ModeModelWeights* w
     if (!ev_w2 || !ev_w1 || !ev_done[0] || !ev_done[1]) return MODE_ERR_BAD_ARG;
   }
   bool done_rec[2] = {false, false};
+  // kind: 0 wqkv, 1 wo, 2 w1, 3 w2 (the order of ModeLoraTrain's tables)
+  auto lora_fact = [&](int kind, int l, int G, int rows, int cols, int M, const void* X, long ld_x, const int32_t* x_rows, const void* dY, long ld_dy,
+                       const int32_t* group_offsets) -> int {
+    if (!lora->A[kind]) return MODE_OK;
+    ModeLoraFactDesc f{};
+    f.G = G; f.rows = rows; f.cols = cols; f.r = lora->r; f.M = M; f.dtype = MODE_BF16;
+    f.X = X; f.ld_x = ld_x; f.x_rows = x_rows; f.dY = dY; f.ld_dy = ld_dy; f.group_offsets = group_offsets;
+    f.A = lora->A[kind][l]; f.B = lora->B[kind][l]; f.scale = lora->scale; f.dA = lora->dA[kind][l]; f.dB = lora->dB[kind][l];
+    return mode_lora_fact_grad(&f, lora->workspace, lora->workspace_bytes, stream);
+  };
   for (int l = d.L - 1; l >= 0; --l) {
     const ModeLayerWeights& lw = w->layers[l];
     const ModeLayerWeightsT* lt = &wt->layers[l];
@@ -392,20 +416,28 @@ extern "C" int mode_dit_backward(const ModeDims* dims, const ModeModelWeights* w
       const uint32_t th = pd <= 0.f ? 0u : (uint32_t)((double)pd * 4294967296.0);
       if ((rc = mode::gemm_bf16_tr_swiglu_bwd_launch(&g, S + sl.P, dP, mode_stream_seed(a->seed, 2 * l + 1), th, 1.0f / (1.0f - pd), bsum, toff, hs))) return rc;
       if ((rc = mode_colsum(bsum, 8L * D, NK / 128 + E, 8 * D, MODE_F32, toff, 0, E, lg.b1, 0, (char*)csw + bsum_bytes + 4096, cswb - bsum_bytes - 4096, stream))) return rc;
-      g = gdesc(dt, MODE_EPI_NONE, MODE_F32, D, 4 * D, NK, dYs, D, S + sl.Hd, 4 * D, lg.w2, 4 * D);
-      g.k_group_offsets = offsets; g.num_k_groups = E; g.c_group_stride = 4L * D * D; g.flags = MODE_GEMM_W_KN | MODE_GEMM_A_KM;
-      if (a->fuse_adamw) { fz = *a->fuse_adamw; if (fz.gsq) { fz.gsq += (long)l * fz_per_layer; fz.gsq_capacity = fz_w2; } g.adamw = &fz; }   // W2 is updated here: no gradient is written
-      if (side) { MODE_HIP_OK(hipEventRecord(ev_w2, hs)); MODE_HIP_OK(hipStreamWaitEvent(ss, ev_w2, 0)); }   // ... after the data gradient above has read it
-      if ((rc = mode_gemm(&g, side ? (void*)ss : stream))) return rc;
+      if (lora) {                                       // dA / dB of W2 from dY and the stashed H, no dW2
+        if ((rc = lora_fact(3, l, E, D, 4 * D, NK, S + sl.Hd, 4 * D, nullptr, dYs, D, offsets))) return rc;
+      } else {
+        g = gdesc(dt, MODE_EPI_NONE, MODE_F32, D, 4 * D, NK, dYs, D, S + sl.Hd, 4 * D, lg.w2, 4 * D);
+        g.k_group_offsets = offsets; g.num_k_groups = E; g.c_group_stride = 4L * D * D; g.flags = MODE_GEMM_W_KN | MODE_GEMM_A_KM;
+        if (a->fuse_adamw) { fz = *a->fuse_adamw; if (fz.gsq) { fz.gsq += (long)l * fz_per_layer; fz.gsq_capacity = fz_w2; } g.adamw = &fz; }   // W2 is updated here: no gradient is written
+        if (side) { MODE_HIP_OK(hipEventRecord(ev_w2, hs)); MODE_HIP_OK(hipStreamWaitEvent(ss, ev_w2, 0)); }   // ... after the data gradient above has read it
+        if ((rc = mode_gemm(&g, side ? (void*)ss : stream))) return rc;
+      }
     } else if (tr) {                                 // bf16: operands as they lie in memory, fragments by LDS transpose reads
       g = gdesc(dt, MODE_EPI_NONE, dt, NK, 4 * D, D, dYs, D, lw.w2, 4 * D, dHd, 4 * D);
       g.w_expert_stride = 4L * D * D; g.expert_offsets = offsets; g.num_experts = E; g.flags = MODE_GEMM_W_KN;
       if ((rc = mode_gemm(&g, stream))) return rc;
-      g = gdesc(dt, MODE_EPI_NONE, MODE_F32, D, 4 * D, NK, dYs, D, S + sl.Hd, 4 * D, lg.w2, 4 * D);
-      g.k_group_offsets = offsets; g.num_k_groups = E; g.c_group_stride = 4L * D * D; g.flags = MODE_GEMM_W_KN | MODE_GEMM_A_KM;
-      if (a->fuse_adamw) { fz = *a->fuse_adamw; if (fz.gsq) { fz.gsq += (long)l * fz_per_layer; fz.gsq_capacity = fz_w2; } g.adamw = &fz; }   // W2 is updated here: no gradient is written
-      if (side) { MODE_HIP_OK(hipEventRecord(ev_w2, hs)); MODE_HIP_OK(hipStreamWaitEvent(ss, ev_w2, 0)); }   // ... after the data gradient above has read it
-      if ((rc = mode_gemm(&g, side ? (void*)ss : stream))) return rc;
+      if (lora) {                                       // dA / dB of W2 from dY and the stashed H, no dW2
+        if ((rc = lora_fact(3, l, E, D, 4 * D, NK, S + sl.Hd, 4 * D, nullptr, dYs, D, offsets))) return rc;
+      } else {
+        g = gdesc(dt, MODE_EPI_NONE, MODE_F32, D, 4 * D, NK, dYs, D, S + sl.Hd, 4 * D, lg.w2, 4 * D);
+        g.k_group_offsets = offsets; g.num_k_groups = E; g.c_group_stride = 4L * D * D; g.flags = MODE_GEMM_W_KN | MODE_GEMM_A_KM;
+        if (a->fuse_adamw) { fz = *a->fuse_adamw; if (fz.gsq) { fz.gsq += (long)l * fz_per_layer; fz.gsq_capacity = fz_w2; } g.adamw = &fz; }   // W2 is updated here: no gradient is written
+        if (side) { MODE_HIP_OK(hipEventRecord(ev_w2, hs)); MODE_HIP_OK(hipStreamWaitEvent(ss, ev_w2, 0)); }   // ... after the data gradient above has read it
+        if ((rc = mode_gemm(&g, side ? (void*)ss : stream))) return rc;
+      }
     } else {
       g = gdesc(dt, MODE_EPI_NONE, dt, NK, 4 * D, D, dYs, D, lt->w2T, D, dHd, 4 * D);
       g.w_expert_stride = 4L * D * D; g.expert_offsets = offsets; g.num_experts = E;
@@ -437,18 +469,22 @@ extern "C" int mode_dit_backward(const ModeDims* dims, const ModeModelWeights* w
       du_split = ((8 * D) % 512 == 0 && mode::gemm_bf16_pptr_accepts(&g)) ? 4 : du_split;
       g.split_k = du_split;
       if ((rc = mode_gemm(&g, stream))) return rc;
-      g = gdesc(dt, MODE_EPI_NONE, MODE_F32, 8 * D, D, NK, dP, 8 * D, Td2, D, lg.w1, D);
-      g.k_group_offsets = offsets; g.num_k_groups = E; g.c_group_stride = 8L * D * D;
-      g.flags = MODE_GEMM_W_KN | MODE_GEMM_A_KM;
-      if (a->fuse_adamw) { fz = *a->fuse_adamw; if (fz.gsq) { fz.gsq += (long)l * fz_per_layer + fz_w2; fz.gsq_capacity = fz_w1; } g.adamw = &fz; }   // W1 likewise (ring kernel: gathers u through perm)
-      if (!a->fuse_adamw && mode::gemm_bf16_pptr_accepts(&g)) { // it reads its K rows where they lie: sorted-order copy of the u rows first (7 MB)
-        if ((rc = mode::gather_rows_bf16(S + sl.ub, D, meta + ml.perm, NK, D, Td2, D, hs))) return rc;
+      if (lora) {                                       // dA / dB of W1 from dP and the u rows gathered through perm, no dW1 and no sorted copy of u
+        if ((rc = lora_fact(2, l, E, 8 * D, D, NK, S + sl.ub, D, meta + ml.perm, dP, 8 * D, offsets))) return rc;
       } else {
-        g.W = S + sl.ub; g.w_rows = meta + ml.perm;             // ring kernel: u rows gathered through perm inside the GEMM
+        g = gdesc(dt, MODE_EPI_NONE, MODE_F32, 8 * D, D, NK, dP, 8 * D, Td2, D, lg.w1, D);
+        g.k_group_offsets = offsets; g.num_k_groups = E; g.c_group_stride = 8L * D * D;
+        g.flags = MODE_GEMM_W_KN | MODE_GEMM_A_KM;
+        if (a->fuse_adamw) { fz = *a->fuse_adamw; if (fz.gsq) { fz.gsq += (long)l * fz_per_layer + fz_w2; fz.gsq_capacity = fz_w1; } g.adamw = &fz; }   // W1 likewise (ring kernel: gathers u through perm)
+        if (!a->fuse_adamw && mode::gemm_bf16_pptr_accepts(&g)) { // it reads its K rows where they lie: sorted-order copy of the u rows first (7 MB)
+          if ((rc = mode::gather_rows_bf16(S + sl.ub, D, meta + ml.perm, NK, D, Td2, D, hs))) return rc;
+        } else {
+          g.W = S + sl.ub; g.w_rows = meta + ml.perm;             // ring kernel: u rows gathered through perm inside the GEMM
+        }
+        if (side) { MODE_HIP_OK(hipEventRecord(ev_w1, hs)); MODE_HIP_OK(hipStreamWaitEvent(ss, ev_w1, 0)); }   // dU (reads W1) is on the chain: W1 may be updated behind it
+        if ((rc = mode_gemm(&g, side ? (void*)ss : stream))) return rc;
+        if (side) { MODE_HIP_OK(hipEventRecord(ev_done[par], ss)); done_rec[par] = true; }
       }
-      if (side) { MODE_HIP_OK(hipEventRecord(ev_w1, hs)); MODE_HIP_OK(hipStreamWaitEvent(ss, ev_w1, 0)); }   // dU (reads W1) is on the chain: W1 may be updated behind it
-      if ((rc = mode_gemm(&g, side ? (void*)ss : stream))) return rc;
-      if (side) { MODE_HIP_OK(hipEventRecord(ev_done[par], ss)); done_rec[par] = true; }
     } else {
       g = gdesc(dt, MODE_EPI_NONE, MODE_F32, NK, D, 8 * D, dP, 8 * D, lt->w1T, 8 * D, dUs, D);
       g.w_expert_stride = 8L * D * D; g.expert_offsets = offsets; g.num_experts = E;
@@ -472,9 +508,13 @@ extern "C" int mode_dit_backward(const ModeDims* dims, const ModeModelWeights* w
       g = gdesc(dt, MODE_EPI_NONE, dt, N, D, D, dx1lp, D, lw.wo, D, dyattn, D);
       g.flags = MODE_GEMM_W_KN;
       if ((rc = mode_gemm(&g, stream))) return rc;
-      g = gdesc(dt, MODE_EPI_NONE, MODE_F32, D, D, N, dx1lp, D, S + sl.yattn, D, lg.wo, D);
-      g.flags = MODE_GEMM_W_KN | MODE_GEMM_A_KM;
-      if ((rc = mode_gemm(&g, stream))) return rc;
+      if (lora) {
+        if ((rc = lora_fact(1, l, 1, D, D, N, S + sl.yattn, D, nullptr, dx1lp, D, nullptr))) return rc;
+      } else {
+        g = gdesc(dt, MODE_EPI_NONE, MODE_F32, D, D, N, dx1lp, D, S + sl.yattn, D, lg.wo, D);
+        g.flags = MODE_GEMM_W_KN | MODE_GEMM_A_KM;
+        if ((rc = mode_gemm(&g, stream))) return rc;
+      }
     } else {
       g = gdesc(dt, MODE_EPI_NONE, dt, N, D, D, dx1lp, D, lt->woT, D, dyattn, D);
       if ((rc = mode_gemm(&g, stream))) return rc;
@@ -495,9 +535,13 @@ extern "C" int mode_dit_backward(const ModeDims* dims, const ModeModelWeights* w
       g = gdesc(dt, MODE_EPI_NONE, MODE_F32, N, D, 3 * D, dqkv, 3 * D, lw.wqkv, D, dh1, D);
       g.flags = MODE_GEMM_W_KN;
       if ((rc = mode_gemm(&g, stream))) return rc;
-      g = gdesc(dt, MODE_EPI_NONE, MODE_F32, 3 * D, D, N, dqkv, 3 * D, S + sl.h1, D, lg.wqkv, D);
-      g.flags = MODE_GEMM_W_KN | MODE_GEMM_A_KM;
-      if ((rc = mode_gemm(&g, stream))) return rc;
+      if (lora) {
+        if ((rc = lora_fact(0, l, 1, 3 * D, D, N, S + sl.h1, D, nullptr, dqkv, 3 * D, nullptr))) return rc;
+      } else {
+        g = gdesc(dt, MODE_EPI_NONE, MODE_F32, 3 * D, D, N, dqkv, 3 * D, S + sl.h1, D, lg.wqkv, D);
+        g.flags = MODE_GEMM_W_KN | MODE_GEMM_A_KM;
+        if ((rc = mode_gemm(&g, stream))) return rc;
+      }
     } else {
       g = gdesc(dt, MODE_EPI_NONE, MODE_F32, N, D, 3 * D, dqkv, 3 * D, lt->wqkvT, 3 * D, dh1, D);
       if ((rc = mode_gemm(&g, stream))) return rc;
@@ -638,6 +682,34 @@ extern "C" int mode_dit_backward(const ModeDims* dims, const ModeModelWeights* w
   }
 #undef ZERO
   return MODE_OK;
+}
+
+extern "C" int mode_dit_backward(const ModeDims* dims, const ModeModelWeights* w, const ModeModelWeightsT* wt, const ModeTrainArgs* a,
+                                 const void* stash, const float* dF, const ModeModelGrads* gr, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+  return backward_impl(dims, w, wt, a, stash, dF, gr, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t mode_dit_backward_lora_workspace_bytes(const ModeDims* dims, int B, int r) {
+  if (check_train_dims(dims) || B <= 0) return 0;
+  const int D = dims->D, N = B * dims->T, NK = N * dims->k, E = dims->E;
+  const int shape[4][4] = {{1, 3 * D, D, N}, {1, D, D, N}, {E, 8 * D, D, NK}, {E, D, 4 * D, NK}};      // G, rows, cols, M per kind
+  size_t need = 0;
+  for (int kd = 0; kd < 4; ++kd) {
+    ModeLoraFactDesc f{};
+    f.G = shape[kd][0]; f.rows = shape[kd][1]; f.cols = shape[kd][2]; f.M = shape[kd][3]; f.r = r; f.dtype = MODE_BF16;
+    const size_t b = mode_lora_fact_workspace_bytes(&f);
+    if (!b) return 0;
+    need = b > need ? b : need;
+  }
+  return need;
+}
+
+extern "C" int mode_dit_backward_lora(const ModeDims* dims, const ModeModelWeights* w, const ModeModelWeightsT* wt, const ModeTrainArgs* a,
+                                      const void* stash, const float* dF, const ModeModelGrads* gr, const ModeLoraTrain* lora, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  if (!lora) return MODE_ERR_BAD_ARG;
+  return backward_impl(dims, w, wt, a, stash, dF, gr, lora, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -7,7 +7,11 @@ layout.  So an adapter needs no kernel of the chains changed:
 * ``mode_lora_merge`` writes ``bf16(W + s B A)`` from the frozen fp32 master into the shadow - same pointers, so captured graphs keep replaying;
 * ``mode_lora_grad`` projects the chain's ``dW`` onto the adapter, ``dA = s B^T dW`` and ``dB = s dW A^T`` (the chain rule of ``W + s B A``).
 
-The chain still computes and writes the dense ``dW`` of the adapted matrices; skipping those GEMMs would be a change to the backward chain.
+That is ``grad="dense"``: the chain still computes and writes the dense ``dW`` of all four matrices of every block into an arena-sized scratch.
+``grad="factored"`` runs ``mode_dit_backward_lora`` instead: the chain rule factors through the low rank - with ``Y = X W_eff^T``,
+``dA = s (dY B)^T X`` and ``dB = s dY^T (X A^T)`` - so the four weight-gradient GEMMs of every block are not launched at all, an adapted kind gets one
+``mode_lora_fact_grad`` over the very bf16 operands its GEMM would have read, no ``rows x cols`` tensor is written and the arena-sized scratch is not
+allocated (the chain's remaining small gradients go to a buffer of their own size).
 """
 from __future__ import annotations
 
@@ -22,6 +26,7 @@ from . import _lib as L
 from .engine import _stream
 
 TARGETS = ("wqkv", "wo", "w1", "w2")
+GRAD_MODES = ("dense", "factored")
 
 
 def target_shapes(model) -> Dict[str, Tuple[int, int, int]]:
@@ -31,7 +36,7 @@ def target_shapes(model) -> Dict[str, Tuple[int, int, int]]:
 
 
 class LoraAdapter(nn.Module):
-    """``LoraAdapter(model, rank=16, alpha=None, targets=("wqkv", "wo", "w1", "w2"), seed=0)``: per target kind ``A_<kind> [L, G, r, cols]`` ~
+    """``LoraAdapter(model, rank=16, alpha=None, targets=("wqkv", "wo", "w1", "w2"), seed=0, grad="dense")``: per target kind ``A_<kind> [L, G, r, cols]`` ~
     N(0, 1/r) from ``seed`` and ``B_<kind> [L, G, rows, r]`` = 0, ordinary parameters of THIS module (G = experts for ``w1`` / ``w2``, else 1);
     ``s = alpha / rank``, ``alpha`` defaults to ``rank``.  The adapter is not a submodule of the model: ``model.named_parameters()`` and
     ``model.state_dict()`` keep the reference's layout.
@@ -45,12 +50,18 @@ class LoraAdapter(nn.Module):
     saves in the reference's ``state_dict`` layout.  ``forward`` is the model's, so a wrapper that drives a module (torch DDP over the adapter
     alone) exchanges the adapter's gradients only.
 
+    ``grad`` says how ``dA`` / ``dB`` are computed, not what the adapter is: ``"dense"`` projects the chain's dense weight gradients
+    (``mode_lora_grad``, an arena-sized scratch per model), ``"factored"`` computes them from the GEMM operands inside the backward chain
+    (``mode_dit_backward_lora``: no dense weight gradient, no such scratch).  A plain attribute, validated, that may change between steps; it is
+    not part of ``state_dict()`` or of the merge key, and a file saved in one mode loads in the other.
+
     Refused with an error before anything changes: ``compute_dtype="fp32"`` (its GEMMs read the master), a ``FusedAdamW`` of the model (either
     order) and an ``ArenaEMA`` of the base.  Adapters on routers, embeddings or encoders, several adapters at once and the ZeRO-1 /
     ``fuse_expert_step`` combinations are out of scope."""
 
-    def __init__(self, model, rank: int = 16, alpha=None, targets=TARGETS, seed: int = 0):
+    def __init__(self, model, rank: int = 16, alpha=None, targets=TARGETS, seed: int = 0, grad: str = "dense"):
         super().__init__()
+        self.grad = grad
         rank = int(rank)
         if not 1 <= rank <= L.MODE_LORA_MAX_RANK:
             raise ValueError(f"LoraAdapter: rank must be in 1..{L.MODE_LORA_MAX_RANK}, got {rank}")
@@ -77,6 +88,17 @@ class LoraAdapter(nn.Module):
         self._gen = 0                                            # bumped by what changes the merge without touching a parameter (alpha)
         self._attached = False
         self._saved_flags: List[Tuple[nn.Parameter, bool]] = []
+
+    # ------------------------------------------------------------------ gradient mode
+    @property
+    def grad(self) -> str:
+        return self._grad
+
+    @grad.setter
+    def grad(self, value) -> None:
+        if value not in GRAD_MODES:
+            raise ValueError(f"LoraAdapter: grad must be one of {GRAD_MODES}, got {value!r}")
+        self._grad = value
 
     # ------------------------------------------------------------------ scale
     @property
@@ -224,6 +246,7 @@ class LoraAdapter(nn.Module):
         """The flat buffer the backward chain writes its dense gradients into while an adapter is attached.  One per MODEL (held by its engine, shared
         by every adapter of the model, released when the last one detaches): it is as large as the arena, an adapter is not."""
         n, dev = eng.arena.bounds["total"], eng.device
+        eng._lora_bufs.pop("small", None); eng._lora_bufs.pop("fact_ws", None)         # left by grad="factored"
         flat = eng._lora_bufs.get("flat")
         if flat is None or flat.numel() != n or flat.device != dev:
             flat = eng._lora_bufs["flat"] = torch.empty(n, dtype=torch.float32, device=dev)
@@ -248,6 +271,53 @@ class LoraAdapter(nn.Module):
             d.dB = grads[id(getattr(self, f"B_{t}"))][i].data_ptr()
             L.check(eng.lib.mode_lora_grad(C.byref(d), ws.data_ptr(), ws.numel(), _stream()), f"lora_grad {key}")
         return [grads.get(id(p)) for p in params]
+
+    # ------------------------------------------------------------------ grad="factored"
+    @staticmethod
+    def small_grad_scratch(eng) -> torch.Tensor:
+        """The buffer of the chain's remaining gradients (biases, gains, routers, embeddings, head) in factored mode: ``small_grad_layout``, a few
+        MB.  Per model like the dense scratch, which is dropped here - a model that switches to factored mode gives its 2.7 GB back."""
+        eng._lora_bufs.pop("flat", None); eng._lora_bufs.pop("ws", None)
+        n, dev = small_grad_layout(eng.arena)[1], eng.device
+        buf = eng._lora_bufs.get("small")
+        if buf is None or buf.numel() != n or buf.device != dev:
+            buf = eng._lora_bufs["small"] = torch.empty(n, dtype=torch.float32, device=dev)
+        return buf
+
+    def fact_tables(self, eng, B: int, params):
+        """(ModeLoraTrain for one backward at batch size B, the gradients of ``params`` it will write, what must stay alive over the call).  The A / B
+        pointer tables are built once per set of adapter tensors (keyed by their ``data_ptr()``), the dA / dB tables per backward: the gradients are
+        fresh ``empty_like`` tensors handed to autograd, as ``project()``'s are."""
+        m, dev = self.model, eng.device
+        Ly = m.num_layers
+        key = tuple(p.data_ptr() for _, a, b in self.pairs() for p in (a, b))
+        hit = self.__dict__.get("_fact_cache")
+        if hit is None or hit[0] != key:
+            tabs = {}
+            for t, a, b in self.pairs():
+                if a.device != dev or b.device != dev:
+                    raise RuntimeError(f"LoraAdapter: A_{t} / B_{t} live on {a.device}, the model on {dev} - move the adapter with .to()")
+                tabs[t] = ((C.c_void_p * Ly)(*[a[i].data_ptr() for i in range(Ly)]), (C.c_void_p * Ly)(*[b[i].data_ptr() for i in range(Ly)]))
+            hit = self.__dict__["_fact_cache"] = (key, tabs)
+        tabs = hit[1]
+        need = eng.lib.mode_dit_backward_lora_workspace_bytes(C.byref(eng.dims), B, self.rank)
+        if need == 0:
+            raise ValueError("LoraAdapter(grad='factored'): the backward chain refuses this model geometry (embed_dim must be a multiple of 8)")
+        ws = eng._lora_bufs.get("fact_ws")
+        if ws is None or ws.numel() < need or ws.device != dev:
+            ws = eng._lora_bufs["fact_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        lt = L.ModeLoraTrain(r=self.rank, scale=self._scale_dev(dev).data_ptr(), workspace=ws.data_ptr(), workspace_bytes=ws.numel())
+        grads, keep = {}, [tabs]
+        for t, a, b in self.pairs():
+            ga, gb = torch.empty_like(a), torch.empty_like(b)
+            grads[id(a)], grads[id(b)] = ga, gb
+            da = (C.c_void_p * Ly)(*[ga[i].data_ptr() for i in range(Ly)])
+            db = (C.c_void_p * Ly)(*[gb[i].data_ptr() for i in range(Ly)])
+            keep += [da, db]
+            kd = L.LORA_KINDS.index(t)
+            lt.A[kd], lt.B[kd] = C.cast(tabs[t][0], C.c_void_p), C.cast(tabs[t][1], C.c_void_p)
+            lt.dA[kd], lt.dB[kd] = C.cast(da, C.c_void_p), C.cast(db, C.c_void_p)
+        return lt, [grads.get(id(p)) for p in params], (keep, list(grads.values()))
 
     # ------------------------------------------------------------------ serialisation
     def get_extra_state(self):
@@ -274,6 +344,18 @@ class LoraAdapter(nn.Module):
 # model -> weak reference to its FusedAdamW: a registry beside the models, so that a model carries nothing for a feature it does not use (a copy
 # of a model is not in it, and the model pickles as before)
 _FUSED_ADAMW = weakref.WeakKeyDictionary()
+
+
+def small_grad_layout(ar):
+    """([(key, shape, offset)], total): the arena's gradient layout without the four matrices of every block (and the dead gripper embedding) -
+    what the backward chain still writes when ``mode_dit_backward_lora`` skips the weight-gradient GEMMs.  Offsets in elements, 256-byte aligned."""
+    out, off = [], 0
+    for key, shp, _ in ar.layout:
+        if key == "gripper" or (key.startswith("l") and key.split(".")[-1] in TARGETS):
+            continue
+        out.append((key, shp, off))
+        off += (int(torch.Size(shp).numel()) + 63) // 64 * 64
+    return out, off
 
 
 def adapter_of(model):

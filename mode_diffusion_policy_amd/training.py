@@ -133,13 +133,23 @@ class TrainState:
             hit = cache[flat.data_ptr()] = self._tables(g)
         return hit[0], param_views(m, g)
 
+    def compact_grad_tables(self, buf):
+        """Tables over ``buf`` with ``lora.small_grad_layout``: the factored LoRA backward writes no dense weight gradient, so the four matrix slots
+        of every block are NULL and the buffer holds the chain's small gradients only.  Cached per base pointer.  Returns (tables, views by key)."""
+        from .lora import small_grad_layout
+        hit = self.__dict__.get("_compact_tables")
+        if hit is None or hit[0] != buf.data_ptr() or hit[1] != buf.numel():
+            views = {key: buf[off: off + int(torch.Size(shp).numel())].view(shp) for key, shp, off in small_grad_layout(self.eng.arena)[0]}
+            hit = self.__dict__["_compact_tables"] = (buf.data_ptr(), buf.numel(), self._tables(views), views)
+        return hit[2][0], hit[3]
+
     def _tables(self, g):
         m = self.eng.model
         lgr = (L.ModeLayerGrads * m.num_layers)()
         for i in range(m.num_layers):
             for fld, _ in L.ModeLayerGrads._fields_:
-                t = g[fld][i] if fld in g else g[f"l{i}.{fld}"]              # routers / norm gains are stacked over layers
-                setattr(lgr[i], fld, t.data_ptr())
+                t = g[fld][i] if fld in g else g.get(f"l{i}.{fld}")         # routers / norm gains are stacked over layers; None: not computed (factored LoRA)
+                setattr(lgr[i], fld, t.data_ptr() if t is not None else None)
         mg = L.ModeModelGrads()
         for fld in ("pos", "w_se", "b_se", "w_sl", "w_tok", "w_goal", "w_act", "ln_g", "w_out", "b_out"):
             setattr(mg, fld, g[fld].data_ptr())
@@ -156,7 +166,8 @@ class _DitTrainFn(torch.autograd.Function):
     """Outputs: F (B, A_len, A), the load-balancing loss and the router z-loss of this forward (scalars).  One backward serves all three.
     Inputs: the (fp32, on-device) state_images and preprocessed goals - so that an upstream encoder trains through the denoiser like it does
     in the reference (mode_agent.py:404-411, 548-567) - and every parameter that can receive a gradient; with a LoraAdapter attached (lora.py) those
-    are the adapter's tensors, whose gradients mode_lora_grad projects out of the chain's dense weight gradients."""
+    are the adapter's tensors, whose gradients mode_lora_grad projects out of the chain's dense weight gradients (grad="dense") or
+    mode_dit_backward_lora computes from the GEMM operands without forming them (grad="factored")."""
 
     @staticmethod
     def forward(ctx, run, img, goals, *params):
@@ -384,18 +395,20 @@ def dit_forward_train(model, states, actions, goals, sigma, uncond=False):
         # (0.5 ms per backward at C2): the chain writes every element of every tensor it returns - MODE_DEBUG_GRAD_COVERAGE=1 checks exactly that
         # (NaN pre-fill, every returned view must come back finite; tests/test_gpu_train_dropin.py runs it over the shipped layouts).
         debug_cov = own and not accumulate and os.environ.get("MODE_DEBUG_GRAD_COVERAGE", "0") == "1"
+        factored = lora is not None and lora.grad == "factored"
         if lora is not None:
             # the chain's dense gradients are scratch here: mode_lora_grad projects them onto the adapter below and nothing else reads them
             if model.__dict__.get("_lora") is not lora or lora._key() != lkey:
                 # the projection reads A and B as they are NOW: refuse what autograd's version check would refuse for saved tensors
                 raise RuntimeError("the LoraAdapter was modified (optimizer step, load_state_dict, alpha) or replaced between this forward and its "
                                    "backward: its gradients would belong to another point - run the forward again")
-            flat = lora.grad_scratch(eng)
+            # grad="factored": no dense gradient exists - the chain's small gradients go to a buffer of their own size
+            flat = lora.small_grad_scratch(eng) if factored else lora.grad_scratch(eng)
         else:
             flat = (torch.zeros if accumulate else torch.empty)(ar.bounds["total"], device=dev) if own else None
         if debug_cov:
             flat.fill_(float("nan"))
-        mg, gv = ts.grad_tables(flat)
+        mg, gv = ts.compact_grad_tables(flat) if factored else ts.grad_tables(flat)
         # (ABI 11) FusedAdamW(fuse_expert_step=True): the expert matrices are UPDATED by their weight-gradient GEMMs - arena mode, first backward of the
         # step only (the optimizer object refuses accumulation); their slices of the gradient arena are not written
         fopt = getattr(model, "_fused_optimizer", None)
@@ -405,6 +418,21 @@ def dit_forward_train(model, states, actions, goals, sigma, uncond=False):
                 raise RuntimeError("FusedAdamW(fuse_expert_step=True) needs model.grad_mode == 'arena' (it was changed after the optimizer was built)")
             fz = fopt.fused_step_struct(accumulate)
         args.fuse_adamw = C.pointer(fz) if fz is not None else None
+        if factored:
+            # dA / dB come out of the chain itself (mode_lora_fact_grad in place of every adapted weight-gradient GEMM) and go to autograd like
+            # project()'s; the base parameters are frozen: their .grad stays None
+            lt, lgrads, lkeep = lora.fact_tables(eng, B, lparams)
+            if debug_cov:
+                for t in lkeep[1]:
+                    t.fill_(float("nan"))
+            L.check(lib.mode_dit_backward_lora(C.byref(d), C.byref(eng._mw), C.byref(ts.wt), C.byref(args), stash.data_ptr(), dF.data_ptr(), C.byref(mg),
+                                               C.byref(lt), ts._ws.data_ptr(), ts._ws.numel(), _stream()), "backward_lora")
+            if debug_cov:
+                holes = [k for k, v in gv.items() if not bool(torch.isfinite(v).all())]
+                holes += [f"adapter gradient {i}" for i, t in enumerate(lkeep[1]) if not bool(torch.isfinite(t).all())]
+                if holes:
+                    raise RuntimeError(f"factored LoRA backward left gradient elements unwritten (or non-finite) in: {holes[:8]}")
+            return d_img, d_goal, [None] * len(params) + lgrads
         L.check(lib.mode_dit_backward(C.byref(d), C.byref(eng._mw), C.byref(ts.wt), C.byref(args), stash.data_ptr(), dF.data_ptr(), C.byref(mg),
                                       ts._ws.data_ptr(), ts._ws.numel(), _stream()), "backward")
         if fz is not None:
