@@ -136,12 +136,13 @@ class GuardedCols(Guarded):
 
 def gemm_into(A, W, out, M, N, K, epilogue=L.EPI_NONE, bias=None, resid=None, a_rows=None, offsets=None, num_experts=0, w_estride=0, b_estride=0,
               split_k=0, split_stride=0, flags=0, C2=None, gain=None, row_ss_out=None, row_ss=None, row_eps=0.0, lda=None, ldw=None,
-              k_group_offsets=None, num_k_groups=0, c_group_stride=0, w_rows=None, w_tap_cols=0, w_rows_tap_stride=0):
+              k_group_offsets=None, num_k_groups=0, c_group_stride=0, w_rows=None, w_tap_cols=0, w_rows_tap_stride=0, a_tap_cols=0, a_rows_tap_stride=0):
     """mode_gemm through a full descriptor into GuardedCols outputs; returns the status (the caller decides what it means).  A / W / resid may be column
     slices of wider buffers (their row strides are the leading dimensions; W is the first expert's [Nw, K] view, or its [K, N] view under MODE_GEMM_W_KN);
     out / C2: GuardedCols (ldc / ldc2 are their widths); row_ss_out: a Guarded [M, N / group]; row_ss: [tokens, row_ss_n].  The backward layouts'
     fields: k_group_offsets int32 [num_k_groups + 1] with group z written c_group_stride elements after group z - 1 (`out` holds them all); w_rows int32
-    index tables, w_rows_tap_stride apart when w_tap_cols > 0."""
+    index tables, w_rows_tap_stride apart when w_tap_cols > 0; a_rows in taps (the implicit-GEMM convolution): a_tap_cols columns per tap, the tables
+    a_rows_tap_stride apart."""
     lib = L.load()
     d = L.ModeGemmDesc(dtype=dt_of(A), epilogue=epilogue, out_dtype=dt_of(out.out), M=M, N=N, K=K, A=p(A), lda=lda if lda is not None else A.stride(0),
                        W=p(W), ldw=ldw if ldw is not None else W.stride(0), w_expert_stride=w_estride, bias=p(bias), bias_expert_stride=b_estride,
@@ -149,7 +150,7 @@ def gemm_into(A, W, out, M, N, K, epilogue=L.EPI_NONE, bias=None, resid=None, a_
                        num_experts=num_experts, split_k=split_k, split_stride=split_stride, flags=flags, C2=p(C2 and C2.out), ldc2=C2.ld if C2 else 0,
                        gain=p(gain), row_ss_out=p(row_ss_out and row_ss_out.t), row_ss=p(row_ss), row_ss_n=0 if row_ss is None else row_ss.shape[1],
                        row_eps=row_eps, k_group_offsets=p(k_group_offsets), num_k_groups=num_k_groups, c_group_stride=c_group_stride, w_rows=p(w_rows),
-                       w_tap_cols=w_tap_cols, w_rows_tap_stride=w_rows_tap_stride)
+                       w_tap_cols=w_tap_cols, w_rows_tap_stride=w_rows_tap_stride, a_tap_cols=a_tap_cols, a_rows_tap_stride=a_rows_tap_stride)
     return lib.mode_gemm(C.byref(d), stream())
 
 
