@@ -1000,6 +1000,30 @@ int mode_maxpool_nhwc_bwd(const void* dy, const uint8_t* argmax, int dtype, int 
  * added pairwise by wave shuffles.  The selected candidate has the smallest score; the lowest index wins ties; a NaN score never beats a
  * non-NaN one; if every score is NaN candidate 0 is selected.  An environment whose has-previous-plan bit is clear scores exactly 0 for every
  * candidate and so selects candidate 0.
+ *
+ * Forward contrast (mode_env_gather_*_bid, mode_env_select_bid; rollout.VectorEnvPolicy(candidates=N, contrast=M); an addition to ABI 13: a new
+ * struct and new exports, nothing existing changes).  The second criterion of Bidirectional Decoding: a replanning environment r runs N STRONG
+ * and M WEAK candidates, N >= 1, M >= 1, N + M <= 64.  The chunk batch is m_b * (N + M), environment-major: chunk row j * (N + M) + c is candidate
+ * c of rows[j]; c < N is strong (the environment's goal row), c >= N is weak (a zero goal row: the unconditional branch of classifier-free
+ * guidance; where weak rows come from is the caller's business, the rule below does not depend on it).  The latent of candidate c is the stream
+ * element z(seeds[r], draws[r] * (N + M) + c, e), the index in uint32 arithmetic; a replan still advances draws[r] by one.  With shift, L and
+ * weights[L] as above:
+ *   bc_c   for all N + M candidates: score_c above against plan[r] - the same device function as mode_env_select, so bc[:N] has the bits of its
+ *          scores for the same strong rows -, exactly 0 when the has-previous-plan bit is clear
+ *   d(x, y) = sum_{w < W} sum_a (x[w][a] - y[w][a])^2 over the WHOLE chunk, unweighted: fp32, each term accumulated as fma(diff, diff, acc) by
+ *          the lane that owns element w * A + a (elements 64 apart), the 64 partial sums then added pairwise by wave shuffles in the order of
+ *          the score above (lane distances 32, 16, 8, 4, 2, 1)
+ *   S+     the Ks = min(K, N) strong candidates with the smallest bc, S- the Kw = min(K, M) weak ones with the smallest bc among the weak; the
+ *          lower index wins ties, a NaN ranks after every non-NaN (NaNs among themselves by index).  With no previous plan these are the first
+ *          Ks strong and the first Kw weak candidates.  p_0 .. p_{Ks-1} and q_0 .. q_{Kw-1} are the sets in rank order.
+ *   fc_c   for c < N, in fp32 exactly
+ *            pos = (..((0 + d(c, p_0)) + d(c, p_1)) + ..) + d(c, p_{Ks-1}),   neg likewise over q_0 .. q_{Kw-1}
+ *            fc_c = pos / (float)Ks - neg / (float)Kw                           (two IEEE divisions, one subtraction)
+ *          d(c, c) is evaluated like any other pair (0 for finite rows).
+ *   total_c = fma(lambda, fc_c, bc_c)                                           (one rounding; lambda = 0 and fc_c finite: bc_c bit for bit)
+ * Selection is the rule above over c < N on total: the smallest wins, the lowest index wins ties, a NaN never beats a non-NaN, all NaN selects
+ * candidate 0.  A weak candidate is never selected.  lambda is read from a device float at run time (as the guidance scale is), so a new value
+ * never recaptures a graph.
  * ------------------------------------------------------------------------------------------------------------------ */
 #define MODE_ENV_MAX 1024
 
@@ -1120,6 +1144,43 @@ typedef struct ModeEnvSelectDesc {
   int32_t m_b, num_envs, W, A, shift, N;
 } ModeEnvSelectDesc;
 int mode_env_select(const ModeEnvSelectDesc* d, void* stream);
+
+/* The two gathers with N strong and M weak candidates per environment (forward contrast above; one launch each, grid (m_b, N + M)): the `_cand`
+ * gathers at N + M rows per environment - chunk row j * (N + M) + c, draw index draws[r] * (N + M) + c, img_out written for every candidate -
+ * except that goal_out rows of the weak candidates c >= N are written as zeros.  MODE_ERR_BAD_ARG as their siblings, and for N < 1, M < 1 or
+ * N + M > 64. */
+int mode_env_gather_noise_bid(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
+                              const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
+                              float* img_out, float* goal_out, float* x0, int noise_floats, float sigma_max, int N, int M, void* stream);
+int mode_env_gather_warm_bid(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
+                             const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
+                             float* img_out, float* goal_out, float* x0, const float* plan, int W, int A, int shift, float sigma_start, int N,
+                             int M, void* stream);
+
+/* Selection with forward contrast among the N strong candidates of every replanning row (one launch, one workgroup per row j < m_b; the
+ * formulas and the rule: forward contrast above).  rows entries outside [0, num_envs), `count`, padding rows and plan (only read) are treated as
+ * by mode_env_select.  For r = rows[j]:
+ *   bc[r][c], c < N + M;  fc[r][c] and scores[r][c] = total_c, c < N;  selected[r] in [0, N);  chosen[j] = chunk[j * (N + M) + selected[r]],
+ *   W * A floats, bit for bit.
+ * No atomics; the summation order depends on the shape alone, so the output bits repeat from run to run.  MODE_ERR_BAD_ARG, before any launch: a
+ * NULL desc or pointer (count may be NULL), N < 1, M < 1, N + M > 64, K < 1, W <= 0, A <= 0, W * A > 4096, shift outside [1, W - 1], m_b <= 0,
+ * num_envs <= 0. */
+typedef struct ModeEnvBidDesc {
+  const int32_t* rows;                   /* [m_b] device */
+  const uint32_t* has_prev;              /* [ceil(num_envs / 32)] device bitmask */
+  const int32_t* count;                  /* device, or NULL */
+  const float* chunk;                    /* [m_b * (N + M), W, A] the chain's result */
+  const float* plan;                     /* [num_envs, W, A] the previous plans */
+  const float* weights;                  /* [W - shift] device */
+  float* chosen;                         /* [m_b, W, A] */
+  int32_t* selected;                     /* [num_envs] */
+  float* scores;                         /* [num_envs, N] total */
+  const float* lambda;                   /* device scalar: the weight of the contrast term */
+  float* bc;                             /* [num_envs, N + M] backward coherence */
+  float* fc;                             /* [num_envs, N] forward contrast */
+  int32_t m_b, num_envs, W, A, shift, N, M, K;
+} ModeEnvBidDesc;
+int mode_env_select_bid(const ModeEnvBidDesc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Classifier-free guidance (GCDenoiser(guidance_scale=w)).  An addition to ABI 13: new structs that wrap the old ones and new exports, nothing

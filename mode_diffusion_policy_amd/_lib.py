@@ -188,6 +188,13 @@ class ModeEnvSelectDesc(C.Structure):
                 ("selected", c_vp), ("scores", c_vp), ("m_b", c_i32), ("num_envs", c_i32), ("W", c_i32), ("A", c_i32), ("shift", c_i32), ("N", c_i32)]
 
 
+class ModeEnvBidDesc(C.Structure):
+    """Selection with forward contrast among N strong candidates, against M weak ones (include/mode_hip.h, an addition to ABI 13)."""
+    _fields_ = [("rows", c_vp), ("has_prev", c_vp), ("count", c_vp), ("chunk", c_vp), ("plan", c_vp), ("weights", c_vp), ("chosen", c_vp),
+                ("selected", c_vp), ("scores", c_vp), ("lambda_", c_vp), ("bc", c_vp), ("fc", c_vp), ("m_b", c_i32), ("num_envs", c_i32),
+                ("W", c_i32), ("A", c_i32), ("shift", c_i32), ("N", c_i32), ("M", c_i32), ("K", c_i32)]
+
+
 class ModeEnvFramesCam(C.Structure):
     """One camera of mode_env_gather_frames (include/mode_hip.h, ABI 13)."""
     _fields_ = [("src", c_vp), ("src_stride", c_i64), ("row_elems", c_i64), ("dst", c_vp), ("src_dtype", c_i32), ("dst_dtype", c_i32)]
@@ -344,6 +351,10 @@ PROTOTYPES = {
     "mode_env_gather_warm_cand": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32,
                                             c_i32, c_vp]),
     "mode_env_select": (C.c_int, [P(ModeEnvSelectDesc), c_vp]),
+    "mode_env_gather_noise_bid": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_f32, c_i32, c_i32, c_vp]),
+    "mode_env_gather_warm_bid": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32,
+                                           c_i32, c_i32, c_vp]),
+    "mode_env_select_bid": (C.c_int, [P(ModeEnvBidDesc), c_vp]),
     "mode_env_commit_emit": (C.c_int, [P(ModeEnvPoolDesc), c_vp]),
     "mode_env_gather_frames": (C.c_int, [P(ModeEnvFramesDesc), c_vp]),
     "mode_env_commit_emit_ens": (C.c_int, [P(ModeEnvEnsDesc), c_vp]),

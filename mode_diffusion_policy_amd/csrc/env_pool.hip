@@ -3,6 +3,8 @@
 // chunk's input buffers, and the commit of the chunk's plans + the emission of one action per active environment - the newest plan's row, or with temporal ensembling the weighted mean of the rows that the environment's last K
 // plans predict for the step (env_commit_emit_ens_kernel).  With candidate selection (rollout.VectorEnvPolicy(candidates=N)) the gathers fill N
 // rows per environment and env_select_kernel picks, between the chain and the commit, the candidate closest to the previous plan's tail (staged in LDS).
+// With forward contrast (candidates=N, contrast=M) the gathers fill N + M rows, the last M with a zero goal row, and env_select_bid_kernel adds to
+// each strong candidate's score its distance to the best strong candidates minus that to the best weak ones.
 // All move a few hundred KB at most: one launch each, plain coalesced loops, no LDS beside that tail.  The gather of the
 // replanning environments' camera frames into the encoders' input (mode_env_gather_frames) moves ~1.2 MB per fp32 row at 224 x 224: HBM-bound,
 // 16-byte loads and stores.
@@ -22,7 +24,7 @@ __device__ __forceinline__ float env_normal(uint32_t k, uint32_t e) {
 // Observation and goal rows of environment r -> row j of a chunk's inputs (256 threads; either pair may be absent)
 __device__ __forceinline__ void env_gather_obs(const int r, const int j, const float* __restrict__ img, const long img_floats,
                                                const float* __restrict__ goals, const long goal_floats, float* __restrict__ img_out,
-                                               float* __restrict__ goal_out) {
+                                               float* __restrict__ goal_out, const bool zero_goal) {
   if (img && img_out) {
     const float* src = img + (long)r * img_floats;
     float* dst = img_out + (long)j * img_floats;
@@ -31,20 +33,22 @@ __device__ __forceinline__ void env_gather_obs(const int r, const int j, const f
   if (goals && goal_out) {
     const float* src = goals + (long)r * goal_floats;
     float* dst = goal_out + (long)j * goal_floats;
-    for (long i = threadIdx.x; i < goal_floats; i += 256) dst[i] = src[i];
+    for (long i = threadIdx.x; i < goal_floats; i += 256) dst[i] = zero_goal ? 0.f : src[i];
   }
 }
 
 // Both gathers run on grid (m_b, N): block (j, c) fills chunk row j * N + c, candidate c of environment rows[j], from draw draws[r] * N + c of
-// its stream (uint32 arithmetic).  N = 1 - a replan without candidate selection - is row j from draw draws[r].
+// its stream (uint32 arithmetic).  N = 1 - a replan without candidate selection - is row j from draw draws[r].  The first `strong` candidates
+// carry the environment's goal row, the others (forward contrast: the weak candidates of the _bid gathers) a zero goal row.
 __global__ __launch_bounds__(256) void env_gather_noise_kernel(const int32_t* __restrict__ rows, int num_envs, const uint32_t* __restrict__ seeds,
                                                                const uint32_t* __restrict__ draws, const float* __restrict__ img, long img_floats,
                                                                const float* __restrict__ goals, long goal_floats, float* __restrict__ img_out,
-                                                               float* __restrict__ goal_out, float* __restrict__ x0, int noise_floats, float sigma_max) {
+                                                               float* __restrict__ goal_out, float* __restrict__ x0, int noise_floats, float sigma_max,
+                                                               int strong) {
   const int r = rows[blockIdx.x];
   if (r < 0 || r >= num_envs) return;
   const int j = blockIdx.x * gridDim.y + blockIdx.y;
-  env_gather_obs(r, j, img, img_floats, goals, goal_floats, img_out, goal_out);
+  env_gather_obs(r, j, img, img_floats, goals, goal_floats, img_out, goal_out, (int)blockIdx.y >= strong);
   const uint32_t k = mode_stream_seed(seeds[r], draws[r] * gridDim.y + blockIdx.y);
   float* dst = x0 + (long)j * noise_floats;
   for (int e = threadIdx.x; e < noise_floats; e += 256) dst[e] = sigma_max * env_normal(k, (uint32_t)e);
@@ -57,11 +61,11 @@ __global__ __launch_bounds__(256) void env_gather_warm_kernel(const int32_t* __r
                                                               const uint32_t* __restrict__ draws, const float* __restrict__ img, long img_floats,
                                                               const float* __restrict__ goals, long goal_floats, float* __restrict__ img_out,
                                                               float* __restrict__ goal_out, float* __restrict__ x0, const float* __restrict__ plan, int W,
-                                                              int A, int shift, float sigma_start) {
+                                                              int A, int shift, float sigma_start, int strong) {
   const int r = rows[blockIdx.x];
   if (r < 0 || r >= num_envs) return;
   const int j = blockIdx.x * gridDim.y + blockIdx.y;
-  env_gather_obs(r, j, img, img_floats, goals, goal_floats, img_out, goal_out);
+  env_gather_obs(r, j, img, img_floats, goals, goal_floats, img_out, goal_out, (int)blockIdx.y >= strong);
   const uint32_t k = mode_stream_seed(seeds[r], draws[r] * gridDim.y + blockIdx.y);
   const int WA = W * A;
   const float* old = plan + (long)r * WA;
@@ -261,6 +265,35 @@ __global__ __launch_bounds__(64) void env_commit_emit_ens_kernel(ModeEnvEnsDesc 
 // previous plan's tail - the L * A floats from row `shift` on, at most 16 KB - is staged in LDS once; the waves take the N candidates round-robin,
 // a wave's lanes run the L * A elements coalesced and add their partial sums by shuffles; thread 0 takes the argmin of the <= 64 scores; then
 // every thread copies the winner's W * A floats.  At most N * 16 KB read per row: latency-bound, plain loops.
+// The coherence scores of a row's first n candidates against the staged tail, by the four waves of the workgroup (both selection kernels)
+__device__ __forceinline__ void env_coherence_scores(const float* __restrict__ cands, const int n, const int WA, const int LA, const int A,
+                                                     const float* __restrict__ weights, const float* tail, const bool has_prev, float* score) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int c = wave; c < n; c += 4) {
+    float acc = 0.f;
+    if (has_prev) {
+      const float* x = cands + (long)c * WA;
+      for (int e = lane; e < LA; e += 64) {
+        const float df = x[e] - tail[e];
+        acc = fmaf(weights[e / A], df * df, acc);
+      }
+      for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    }
+    if (lane == 0) score[c] = acc;
+  }
+}
+
+// The rule on n scores (one thread): the smallest, strictly - the lowest index wins ties; a NaN only loses; all NaN -> 0
+__device__ __forceinline__ int env_select_min(const float* score, const int n) {
+  int best = 0;
+  float bs = score[0];
+  for (int c = 1; c < n; ++c) {
+    const float v = score[c];
+    if (v < bs || (bs != bs && v == v)) { best = c; bs = v; }
+  }
+  return best;
+}
+
 __global__ __launch_bounds__(256) void env_select_kernel(ModeEnvSelectDesc d) {
   __shared__ float tail[4096];
   __shared__ float score[64];
@@ -273,27 +306,10 @@ __global__ __launch_bounds__(256) void env_select_kernel(ModeEnvSelectDesc d) {
   const float* prev = d.plan + (long)r * WA + d.shift * d.A;
   for (int e = tid; e < LA; e += 256) tail[e] = prev[e];
   __syncthreads();
-  const int wave = tid >> 6, lane = tid & 63;
-  for (int c = wave; c < N; c += 4) {
-    float acc = 0.f;
-    if (has_prev) {
-      const float* x = d.chunk + ((long)j * N + c) * WA;
-      for (int e = lane; e < LA; e += 64) {
-        const float df = x[e] - tail[e];
-        acc = fmaf(d.weights[e / d.A], df * df, acc);
-      }
-      for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    }
-    if (lane == 0) score[c] = acc;
-  }
+  env_coherence_scores(d.chunk + (long)j * N * WA, N, WA, LA, d.A, d.weights, tail, has_prev, score);
   __syncthreads();
   if (tid == 0) {
-    int best = 0;
-    float bs = score[0];
-    for (int c = 1; c < N; ++c) {
-      const float v = score[c];
-      if (v < bs || (bs != bs && v == v)) { best = c; bs = v; }                 // strict: the lowest index wins ties; a NaN only loses
-    }
+    const int best = env_select_min(score, N);
     winner = best;
     d.selected[r] = best;
   }
@@ -304,19 +320,113 @@ __global__ __launch_bounds__(256) void env_select_kernel(ModeEnvSelectDesc d) {
   for (int e = tid; e < WA; e += 256) dst[e] = src[e];
 }
 
+// Unweighted squared distance of two whole chunk rows by one wave (every lane returns the sum): the lane owns elements 64 apart, the partial
+// sums are added in the order of the coherence score
+__device__ __forceinline__ float env_row_distance(const float* __restrict__ x, const float* __restrict__ y, const int WA, const int lane) {
+  float acc = 0.f;
+  for (int e = lane; e < WA; e += 64) {
+    const float df = x[e] - y[e];
+    acc = fmaf(df, df, acc);
+  }
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  return acc;
+}
+
+// Selection with forward contrast (ModeEnvBidDesc; the formulas and the rule: include/mode_hip.h).  The workgroup of env_select_kernel per
+// replanning row j, in four steps with a barrier between them: the coherence scores bc of the N + M candidates (the function above, the tail in
+// LDS); thread c ranks candidate c within its kind - <= 63 compares on the LDS scores - and the first Ks / Kw ranks enter S+ / S-; the waves
+// take the N strong candidates round-robin and add, in rank order, the distances to S+ and to S- (Ks + Kw wave-wide passes over two rows read
+// from global memory: a chunk is L2-resident, and no row is staged); thread 0 takes the argmin of total.  Nothing is added across waves and no
+// atomic is used, so the bits depend on the shape alone.
+__global__ __launch_bounds__(256) void env_select_bid_kernel(ModeEnvBidDesc d) {
+  __shared__ float tail[4096];
+  __shared__ float bc[64], total[64];
+  __shared__ int sp[64], sn[64];
+  __shared__ int winner;
+  const int j = blockIdx.x, tid = threadIdx.x;
+  const int r = d.rows[j];
+  if (r < 0 || r >= d.num_envs || (d.count && j >= d.count[0])) return;          // (uniform over the workgroup)
+  const int N = d.N, NT = d.N + d.M, WA = d.W * d.A, LA = (d.W - d.shift) * d.A;
+  const int Ks = min(d.K, N), Kw = min(d.K, d.M);
+  const bool has_prev = (d.has_prev[r >> 5] >> (r & 31)) & 1u;
+  const float* prev = d.plan + (long)r * WA + d.shift * d.A;
+  const float* cands = d.chunk + (long)j * NT * WA;
+  for (int e = tid; e < LA; e += 256) tail[e] = prev[e];
+  __syncthreads();
+  env_coherence_scores(cands, NT, WA, LA, d.A, d.weights, tail, has_prev, bc);
+  __syncthreads();
+  if (tid < NT) {
+    const bool strong = tid < N;
+    const int lo = strong ? 0 : N, hi = strong ? N : NT;
+    const float v = bc[tid];
+    int rank = 0;
+    for (int c = lo; c < hi; ++c) {
+      const float u = bc[c];
+      // u ranks before v: smaller; equal (or both NaN) and of the lower index; any number before a NaN
+      const bool before = (u < v) || (c < tid && (u == v || (u != u && v != v))) || (u == u && v != v);
+      rank += before ? 1 : 0;
+    }
+    if (strong) { if (rank < Ks) sp[rank] = tid; }
+    else if (rank < Kw) sn[rank] = tid;
+    d.bc[(long)r * NT + tid] = v;
+  }
+  __syncthreads();
+  const float lambda = d.lambda[0];
+  const int wave = tid >> 6, lane = tid & 63;
+  for (int c = wave; c < N; c += 4) {
+    const float* x = cands + (long)c * WA;
+    float pos = 0.f, neg = 0.f;
+    for (int k = 0; k < Ks; ++k) pos += env_row_distance(x, cands + (long)sp[k] * WA, WA, lane);
+    for (int k = 0; k < Kw; ++k) neg += env_row_distance(x, cands + (long)sn[k] * WA, WA, lane);
+    if (lane == 0) {
+      const float f = __fdiv_rn(pos, (float)Ks) - __fdiv_rn(neg, (float)Kw);
+      const float t = fmaf(lambda, f, bc[c]);
+      total[c] = t;
+      d.fc[(long)r * N + c] = f;
+      d.scores[(long)r * N + c] = t;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const int best = env_select_min(total, N);
+    winner = best;
+    d.selected[r] = best;
+  }
+  __syncthreads();
+  const float* src = cands + (long)winner * WA;
+  float* dst = d.chosen + (long)j * WA;
+  for (int e = tid; e < WA; e += 256) dst[e] = src[e];
+}
+
 }  // namespace mode
 
 using namespace mode;
 
+// N strong + M weak candidates per environment (M = 0: the _cand gathers)
+static int env_gather_noise_launch(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws, const float* state_images,
+                                   int64_t img_floats, const float* goals, int64_t goal_floats, float* img_out, float* goal_out, float* x0,
+                                   int noise_floats, float sigma_max, int N, int M, void* stream) {
+  if (!rows || !seeds || !draws || !x0 || m_b <= 0 || num_envs <= 0 || noise_floats <= 0 || img_floats < 0 || goal_floats < 0) return MODE_ERR_BAD_ARG;
+  if (N < 1 || N > 64 || M < 0 || M > 64 - N) return MODE_ERR_BAD_ARG;
+  hipLaunchKernelGGL(env_gather_noise_kernel, dim3(m_b, N + M), dim3(256), 0, (hipStream_t)stream, rows, num_envs, seeds, draws, state_images,
+                     (long)img_floats, goals, (long)goal_floats, img_out, goal_out, x0, noise_floats, sigma_max, N);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
 extern "C" int mode_env_gather_noise_cand(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
                                           const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
                                           float* img_out, float* goal_out, float* x0, int noise_floats, float sigma_max, int N, void* stream) {
-  if (!rows || !seeds || !draws || !x0 || m_b <= 0 || num_envs <= 0 || noise_floats <= 0 || img_floats < 0 || goal_floats < 0) return MODE_ERR_BAD_ARG;
-  if (N < 1 || N > 64) return MODE_ERR_BAD_ARG;
-  hipLaunchKernelGGL(env_gather_noise_kernel, dim3(m_b, N), dim3(256), 0, (hipStream_t)stream, rows, num_envs, seeds, draws, state_images, (long)img_floats,
-                     goals, (long)goal_floats, img_out, goal_out, x0, noise_floats, sigma_max);
-  MODE_LAUNCH_CHECK();
-  return MODE_OK;
+  return env_gather_noise_launch(rows, m_b, num_envs, seeds, draws, state_images, img_floats, goals, goal_floats, img_out, goal_out, x0, noise_floats,
+                                 sigma_max, N, 0, stream);
+}
+
+extern "C" int mode_env_gather_noise_bid(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
+                                         const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
+                                         float* img_out, float* goal_out, float* x0, int noise_floats, float sigma_max, int N, int M, void* stream) {
+  if (M < 1) return MODE_ERR_BAD_ARG;
+  return env_gather_noise_launch(rows, m_b, num_envs, seeds, draws, state_images, img_floats, goals, goal_floats, img_out, goal_out, x0, noise_floats,
+                                 sigma_max, N, M, stream);
 }
 
 extern "C" int mode_env_gather_noise(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
@@ -326,17 +436,33 @@ extern "C" int mode_env_gather_noise(const int32_t* rows, int m_b, int num_envs,
                                     sigma_max, 1, stream);
 }
 
+static int env_gather_warm_launch(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws, const float* state_images,
+                                  int64_t img_floats, const float* goals, int64_t goal_floats, float* img_out, float* goal_out, float* x0,
+                                  const float* plan, int W, int A, int shift, float sigma_start, int N, int M, void* stream) {
+  if (!rows || !seeds || !draws || !x0 || !plan || m_b <= 0 || num_envs <= 0 || img_floats < 0 || goal_floats < 0) return MODE_ERR_BAD_ARG;
+  if (W <= 0 || A <= 0 || (long)W * A > 4096 || shift < 1 || shift >= W || !(sigma_start >= 0.f) || !(sigma_start <= FLT_MAX)) return MODE_ERR_BAD_ARG;
+  if (N < 1 || N > 64 || M < 0 || M > 64 - N) return MODE_ERR_BAD_ARG;
+  hipLaunchKernelGGL(env_gather_warm_kernel, dim3(m_b, N + M), dim3(256), 0, (hipStream_t)stream, rows, num_envs, seeds, draws, state_images,
+                     (long)img_floats, goals, (long)goal_floats, img_out, goal_out, x0, plan, W, A, shift, sigma_start, N);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
 extern "C" int mode_env_gather_warm_cand(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
                                          const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
                                          float* img_out, float* goal_out, float* x0, const float* plan, int W, int A, int shift, float sigma_start,
                                          int N, void* stream) {
-  if (!rows || !seeds || !draws || !x0 || !plan || m_b <= 0 || num_envs <= 0 || img_floats < 0 || goal_floats < 0) return MODE_ERR_BAD_ARG;
-  if (W <= 0 || A <= 0 || (long)W * A > 4096 || shift < 1 || shift >= W || !(sigma_start >= 0.f) || !(sigma_start <= FLT_MAX)) return MODE_ERR_BAD_ARG;
-  if (N < 1 || N > 64) return MODE_ERR_BAD_ARG;
-  hipLaunchKernelGGL(env_gather_warm_kernel, dim3(m_b, N), dim3(256), 0, (hipStream_t)stream, rows, num_envs, seeds, draws, state_images, (long)img_floats,
-                     goals, (long)goal_floats, img_out, goal_out, x0, plan, W, A, shift, sigma_start);
-  MODE_LAUNCH_CHECK();
-  return MODE_OK;
+  return env_gather_warm_launch(rows, m_b, num_envs, seeds, draws, state_images, img_floats, goals, goal_floats, img_out, goal_out, x0, plan, W, A, shift,
+                                sigma_start, N, 0, stream);
+}
+
+extern "C" int mode_env_gather_warm_bid(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
+                                        const float* state_images, int64_t img_floats, const float* goals, int64_t goal_floats,
+                                        float* img_out, float* goal_out, float* x0, const float* plan, int W, int A, int shift, float sigma_start,
+                                        int N, int M, void* stream) {
+  if (M < 1) return MODE_ERR_BAD_ARG;
+  return env_gather_warm_launch(rows, m_b, num_envs, seeds, draws, state_images, img_floats, goals, goal_floats, img_out, goal_out, x0, plan, W, A, shift,
+                                sigma_start, N, M, stream);
 }
 
 extern "C" int mode_env_gather_warm(const int32_t* rows, int m_b, int num_envs, const uint32_t* seeds, const uint32_t* draws,
@@ -352,6 +478,17 @@ extern "C" int mode_env_select(const ModeEnvSelectDesc* d, void* stream) {
   if (d->N < 1 || d->N > 64 || d->W <= 0 || d->A <= 0 || (long)d->W * d->A > 4096 || d->shift < 1 || d->shift >= d->W || d->m_b <= 0 || d->num_envs <= 0)
     return MODE_ERR_BAD_ARG;
   hipLaunchKernelGGL(env_select_kernel, dim3(d->m_b), dim3(256), 0, (hipStream_t)stream, *d);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
+extern "C" int mode_env_select_bid(const ModeEnvBidDesc* d, void* stream) {
+  if (!d || !d->rows || !d->has_prev || !d->chunk || !d->plan || !d->weights || !d->chosen || !d->selected || !d->scores || !d->lambda || !d->bc || !d->fc)
+    return MODE_ERR_BAD_ARG;
+  if (d->N < 1 || d->N > 64 || d->M < 1 || d->M > 64 - d->N || d->K < 1 || d->W <= 0 || d->A <= 0 || (long)d->W * d->A > 4096 || d->shift < 1 ||
+      d->shift >= d->W || d->m_b <= 0 || d->num_envs <= 0)
+    return MODE_ERR_BAD_ARG;
+  hipLaunchKernelGGL(env_select_bid_kernel, dim3(d->m_b), dim3(256), 0, (hipStream_t)stream, *d);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }

@@ -396,6 +396,67 @@ def select_coherent(chunk: torch.Tensor, prev: torch.Tensor, has_prev, shift: in
     return chosen, selected, scores
 
 
+@torch.no_grad()
+def select_bidirectional(chunk: torch.Tensor, prev: torch.Tensor, has_prev, shift: int, weights, n_weak: int, topk: int, contrast_weight: float):
+    """The selection of ``VectorEnvPolicy(candidates=N, contrast=M)`` on explicit rows (csrc/env_pool.hip; formulas: include/mode_hip.h): ``chunk``
+    (n, N + M, W, A) holds per row N strong candidates followed by ``n_weak`` = M weak ones; ``prev``, ``has_prev``, ``shift`` and ``weights`` as
+    for ``select_coherent``.  ``bc`` is ``select_coherent``'s score of all N + M candidates; S+ / S- are the min(topk, N) strong / min(topk, M)
+    weak candidates of smallest ``bc`` (lower index on ties, NaN last); ``fc[c] = mean_{p in S+} d(c, p) - mean_{q in S-} d(c, q)`` with d the
+    unweighted squared distance over the whole chunk; ``total = bc + contrast_weight * fc``, and the strong candidate of smallest total is
+    selected by ``select_coherent``'s rule.  Returns ``(chosen (n, W, A) fp32, selected (n,) int32 in [0, N), total (n, N), bc (n, N + M),
+    fc (n, N))`` on the inputs' device."""
+    from . import _lib as L
+    from .engine import _stream
+    if not torch.is_tensor(chunk) or chunk.dim() != 4 or chunk.numel() == 0:
+        raise ValueError(f"select_bidirectional: chunk must be a non-empty (n, N + M, W, A) tensor, got {tuple(getattr(chunk, 'shape', ()))}")
+    n, NT, W, A = chunk.shape
+    if isinstance(n_weak, bool) or not isinstance(n_weak, (int, np.integer)) or not 1 <= int(n_weak) <= NT - 1:
+        raise ValueError(f"select_bidirectional: n_weak must be an int in [1, {NT - 1}] (of the {NT} candidates at least one is strong), got {n_weak!r}")
+    if NT > 64:
+        raise ValueError(f"select_bidirectional: the number of candidates N + M must be at most 64, got {NT}")
+    if isinstance(topk, bool) or not isinstance(topk, (int, np.integer)) or int(topk) < 1:
+        raise ValueError(f"select_bidirectional: topk must be an int >= 1, got {topk!r}")
+    try:
+        lam = float(contrast_weight)
+    except (TypeError, ValueError):
+        lam = float("nan")
+    if isinstance(contrast_weight, bool) or not (np.isfinite(lam) and lam >= 0.0):
+        raise ValueError(f"select_bidirectional: contrast_weight must be a finite float >= 0, got {contrast_weight!r}")
+    if W * A > 4096:
+        raise ValueError(f"select_bidirectional: W * A must be at most 4096, got {W} * {A}")
+    if not torch.is_tensor(prev) or tuple(prev.shape) != (n, W, A):
+        raise ValueError(f"select_bidirectional: prev must be ({n}, {W}, {A}), one previous plan per row, got {tuple(getattr(prev, 'shape', ()))}")
+    has = np.asarray(has_prev.cpu() if torch.is_tensor(has_prev) else has_prev)
+    if has.dtype != np.bool_ or has.shape != (n,):
+        raise ValueError(f"select_bidirectional: has_prev must be {n} host bools, got {has.dtype} {has.shape}")
+    if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not 1 <= int(shift) <= W - 1:
+        raise ValueError(f"select_bidirectional: shift must be an int in [1, W - 1] = [1, {W - 1}], got {shift!r}")
+    wt = np.asarray(weights.cpu() if torch.is_tensor(weights) else weights, dtype=np.float32).reshape(-1)
+    if wt.size != W - int(shift):
+        raise ValueError(f"select_bidirectional: weights must have W - shift = {W - int(shift)} entries, got {wt.size}")
+    if chunk.device.type != "cuda" or prev.device != chunk.device:
+        raise ValueError("select_bidirectional: chunk and prev must be on one ROCm device")
+    dev, M = chunk.device, int(n_weak)
+    N = NT - M
+    x, old = chunk.to(torch.float32).contiguous(), prev.to(torch.float32).contiguous()
+    nw = (n + 31) // 32
+    rows = torch.arange(n, dtype=torch.int32, device=dev)
+    mask = torch.from_numpy(_mask_words(has, nw).view("<i4").copy()).to(dev)
+    wdev = torch.from_numpy(wt.copy()).to(dev)
+    lam_dev = torch.tensor([lam], dtype=torch.float32).to(dev)
+    chosen = torch.empty(n, W, A, dtype=torch.float32, device=dev)
+    selected = torch.empty(n, dtype=torch.int32, device=dev)
+    total, fc = torch.empty(n, N, dtype=torch.float32, device=dev), torch.empty(n, N, dtype=torch.float32, device=dev)
+    bc = torch.empty(n, NT, dtype=torch.float32, device=dev)
+    d = L.ModeEnvBidDesc(rows=rows.data_ptr(), has_prev=mask.data_ptr(), count=None, chunk=x.data_ptr(), plan=old.data_ptr(),
+                         weights=wdev.data_ptr(), chosen=chosen.data_ptr(), selected=selected.data_ptr(), scores=total.data_ptr(),
+                         lambda_=lam_dev.data_ptr(), bc=bc.data_ptr(), fc=fc.data_ptr(), m_b=n, num_envs=n, W=W, A=A, shift=int(shift), N=N, M=M,
+                         K=min(int(topk), 64))
+    with torch.cuda.device(dev):
+        L.check(L.load().mode_env_select_bid(C.byref(d), _stream()), "env_select_bid")
+    return chosen, selected, total, bc, fc
+
+
 class VectorEnvPolicy(ChunkedRolloutPolicy):
     """``MoDEAgent.reset`` / ``step`` (mode_agent.py:584-637) for each of ``num_envs`` environments of a batch on its own: every environment keeps
     its own plan, its own position in it and its own noise stream, so a batch behaves like ``num_envs`` independent agents whose episodes start,
@@ -473,11 +534,36 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
     (num_envs, N) expose the last replan's choice.  With ``warm_start=k`` a warm replan's candidates are ``env_warm_latents(plans[b], seed,
     draws[b] * N + c, s, sigmas[k])`` through the sub-schedule; with raw frames the encoders still run once per environment at batch mb * T and
     their rows are broadcast to the N candidate rows inside the encoder graph.  Known cost: a cold replan (an episode's first) also runs N
-    candidates and keeps the first - running cold chunks at N = 1 would need a second family of graphs.  What candidate selection does to task
-    success is NOT measured in this repository: only the mechanics and the cost (profiles/vector_env_candidates.txt) are pinned."""
+    candidates and, without ``contrast``, keeps the first - running cold chunks at N = 1 would need a second family of graphs; with
+    ``contrast`` a cold replan selects among its N candidates by the contrast term alone (below).  What candidate selection does to task
+    success is NOT measured in this repository: only the mechanics and the cost (profiles/vector_env_candidates.txt) are pinned.
+
+    ``contrast=M`` (an int >= 1, with ``candidates=N >= 2``, ``N + M <= 64`` and ``num_envs * (N + M) <= MODE_ENV_MAX``; None, the default, is
+    everything above unchanged: the same entry points, draw indices, graphs and bits) adds the forward-contrast criterion of Bidirectional
+    Decoding.  A replanning environment runs N STRONG candidates - its own goal row - and M WEAK ones - a zero goal row, the unconditional
+    branch that classifier-free guidance defines, so the weak policy needs no weights of its own.  The chunk, its buffers and its bucket
+    templates are sized by N + M: chunk row j * (N + M) + c is candidate c of the j-th replanner, strong ones first, its latent the stream
+    element ``z(seed, draws[b] * (N + M) + c)``; a replan still advances ``draws[b]`` by one.  With ``bc_c`` the coherence score above for all
+    N + M candidates (0 without a previous plan), S+ / S- the ``min(contrast_topk, N)`` strong / ``min(contrast_topk, M)`` weak candidates of
+    smallest ``bc`` (lower index on ties, NaN last; with no previous plan the first by index; ``contrast_topk`` an int >= 1, default min(N, M))
+    and ``d`` the unweighted squared distance over the whole chunk, a strong candidate gets ``fc_c = mean_{p in S+} d(c, p) - mean_{q in S-}
+    d(c, q)`` and ``total_c = bc_c + contrast_weight * fc_c`` (fp32; exact expressions: include/mode_hip.h); the strong candidate of smallest
+    total is selected by the rule above and a weak one never is.  ``contrast_weight`` (a finite float >= 0, default 1.0) is a settable
+    attribute backed by a device scalar the kernel reads: a new value is used by the next replan, recaptures no graph and is in no graph key.
+    ``contrast_weight`` and ``contrast_topk`` are only legal with ``contrast``.  Commit, ring, ``plans`` and ``selected`` are as above;
+    ``candidate_scores`` holds ``total``, and ``coherence_scores`` (num_envs, N + M) and ``contrast_scores`` (num_envs, N) hold ``bc`` and
+    ``fc`` of the last replan (``select_bidirectional`` runs the kernel on explicit rows).  Raw frames: the encoder towers still run once per
+    environment, FiLM-conditioned on the environment's goal, taken from the first (strong) row; weak candidates share those observation
+    embeddings, only the denoiser's goal row is zero.  ``warm_start``: weak candidates are warm-started from the same previous plan, like the
+    strong ones.  ``guidance_scale`` needs nothing special - a zero-goal row's guided prediction is its unconditional one - but costs: the
+    chain then runs 2 * mb * (N + M) rows and evaluates every weak row twice for the same result.  Cost: (N, M) costs what ``candidates=N + M``
+    costs, the chain batch being the same (profiles/vector_env_contrast.txt).  A second, separately loaded weak model (an earlier checkpoint,
+    the base model under a LoRA adapter) is out of scope; the selection does not depend on where weak rows come from.  What forward contrast
+    does to task success is NOT measured in this repository (no trained checkpoint, no simulator): only the mechanics and the cost are pinned."""
 
     def __init__(self, denoiser, num_envs: int, seed: int = 0, extra_args: Optional[dict] = None, temporal_ensemble: Optional[float] = None,
-                 warm_start: Optional[int] = None, candidates: Optional[int] = None, coherence_decay: Optional[float] = None, **kw):
+                 warm_start: Optional[int] = None, candidates: Optional[int] = None, coherence_decay: Optional[float] = None,
+                 contrast: Optional[int] = None, contrast_weight: Optional[float] = None, contrast_topk: Optional[int] = None, **kw):
         from . import _lib as L
         from .modedit import MoDeDiT
         sampler = kw.get("sampler_type", "ddim")
@@ -507,6 +593,28 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
             self.coherence_decay = rho
         elif candidates is not None:
             self.coherence_decay = 0.5
+        self.contrast, self.contrast_topk, self._contrast_weight, self._nweak, self._lambda = None, None, None, 0, None
+        if contrast is not None:
+            if isinstance(contrast, bool) or not isinstance(contrast, (int, np.integer)) or int(contrast) < 1:
+                raise ValueError(f"contrast must be None or an int >= 1, the number of weak (zero-goal) candidates, got {contrast!r}")
+            if self._ncand < 2:
+                raise ValueError(f"contrast compares the strong candidates with each other and with the weak ones: it needs candidates >= 2, got "
+                                 f"candidates={candidates!r}")
+            if self._ncand + int(contrast) > 64:
+                raise ValueError(f"candidates + contrast must be at most 64, got {self._ncand} + {int(contrast)}")
+            if isinstance(num_envs, (int, np.integer)) and int(num_envs) * (self._ncand + int(contrast)) > L.MODE_ENV_MAX:
+                raise ValueError(f"num_envs * (candidates + contrast) must be at most {L.MODE_ENV_MAX} (the largest batch a chunk runs at), got "
+                                 f"{int(num_envs)} * ({self._ncand} + {int(contrast)})")
+            self.contrast = self._nweak = int(contrast)
+            self.contrast_topk = min(self._ncand, self._nweak)
+            if contrast_topk is not None:
+                if isinstance(contrast_topk, bool) or not isinstance(contrast_topk, (int, np.integer)) or int(contrast_topk) < 1:
+                    raise ValueError(f"contrast_topk must be None or an int >= 1, got {contrast_topk!r}")
+                self.contrast_topk = int(contrast_topk)
+            self._contrast_weight = self._checked_contrast_weight(1.0 if contrast_weight is None else contrast_weight)
+        elif contrast_weight is not None or contrast_topk is not None:
+            raise ValueError("contrast_weight and contrast_topk shape the forward-contrast term: they are only legal with contrast=M")
+        self._nper = self._ncand + self._nweak                               # chunk rows per replanning environment
         self.warm_start = None
         if warm_start is not None:
             n_steps, W, s = int(kw.get("num_sampling_steps", 10)), int(kw.get("act_window_size", 10)), int(kw.get("multistep", 10))
@@ -561,6 +669,11 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
             self._selected = torch.full((n,), -1, dtype=torch.int32, device=dev)
             self._cand_scores = torch.zeros(n, self._ncand, dtype=torch.float32, device=dev)
             self._coh_w = torch.from_numpy(coherence_weights(self.coherence_decay, W - self.multistep)).to(dev)
+            if self._nweak:
+                # forward contrast: both terms of the last selection per environment, and the weight as the device scalar the kernel reads
+                self._bc_scores = torch.zeros(n, self._nper, dtype=torch.float32, device=dev)
+                self._fc_scores = torch.zeros(n, self._ncand, dtype=torch.float32, device=dev)
+                self._lambda = torch.full((1,), self._contrast_weight, dtype=torch.float32, device=dev)
         self._ctrl = torch.zeros(nctrl, dtype=torch.int32, device=dev)
         # pinned staging of the control block, a ring: a slot is rewritten only after the copy that read it has run (its event)
         self._ring = [torch.zeros(nctrl, dtype=torch.int32, pin_memory=True) for _ in range(4)]
@@ -569,7 +682,13 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         self._scratch_out = torch.zeros(n, A, dtype=torch.float32, device=dev)
         self._desc = L.ModeEnvPoolDesc(num_envs=n, W=W, A=A, multistep=self.multistep, plan=self._plan.data_ptr(),
                                        counter=self._counter_dev.data_ptr(), draws=self._draws.data_ptr())
-        if self._ncand > 1:
+        if self._nweak:
+            self._sel = L.ModeEnvBidDesc(rows=self._rows_ptr(), has_prev=self._rows_ptr() + 4 * n, count=self._ctrl.data_ptr(),
+                                         plan=self._plan.data_ptr(), weights=self._coh_w.data_ptr(), selected=self._selected.data_ptr(),
+                                         scores=self._cand_scores.data_ptr(), lambda_=self._lambda.data_ptr(), bc=self._bc_scores.data_ptr(),
+                                         fc=self._fc_scores.data_ptr(), num_envs=n, W=W, A=A, shift=self.multistep, N=self._ncand, M=self._nweak,
+                                         K=min(self.contrast_topk, 64))
+        elif self._ncand > 1:
             self._sel = L.ModeEnvSelectDesc(rows=self._rows_ptr(), has_prev=self._rows_ptr() + 4 * n, count=self._ctrl.data_ptr(),
                                             plan=self._plan.data_ptr(), weights=self._coh_w.data_ptr(), selected=self._selected.data_ptr(),
                                             scores=self._cand_scores.data_ptr(), num_envs=n, W=W, A=A, shift=self.multistep, N=self._ncand)
@@ -674,8 +793,49 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
 
     @property
     def candidate_scores(self) -> torch.Tensor:
-        """[num_envs, candidates] fp32: the scores of every environment's last replan (device, ``candidates`` only)."""
+        """[num_envs, candidates] fp32: the scores of every environment's last replan (device, ``candidates`` only); with ``contrast`` the totals
+        ``bc + contrast_weight * fc`` the selection minimised."""
         return self._cand_state("_cand_scores")
+
+    def _contrast_state(self, name: str) -> torch.Tensor:
+        if not self._nweak:
+            raise AttributeError("this policy was built without contrast: its selection has the backward-coherence term only (candidate_scores)")
+        return getattr(self, name)
+
+    @property
+    def coherence_scores(self) -> torch.Tensor:
+        """[num_envs, candidates + contrast] fp32: the backward-coherence term of every candidate, strong ones first, at every environment's last
+        replan (device, ``contrast`` only; ``candidate_scores`` then holds the total)."""
+        return self._contrast_state("_bc_scores")
+
+    @property
+    def contrast_scores(self) -> torch.Tensor:
+        """[num_envs, candidates] fp32: the forward-contrast term of the strong candidates at every environment's last replan (device, ``contrast``
+        only)."""
+        return self._contrast_state("_fc_scores")
+
+    @staticmethod
+    def _checked_contrast_weight(value) -> float:
+        try:
+            lam = float(value)
+        except (TypeError, ValueError):
+            lam = float("nan")
+        if isinstance(value, bool) or not (np.isfinite(lam) and lam >= 0.0):
+            raise ValueError(f"contrast_weight must be a finite float >= 0, got {value!r}")
+        return lam
+
+    @property
+    def contrast_weight(self) -> Optional[float]:
+        """The weight lambda of the forward-contrast term in ``total = bc + lambda * fc`` (None without ``contrast``).  Settable: the new value is
+        written into the device scalar the selection kernel reads, so the next replan uses it - no graph is captured again, no graph key holds it."""
+        return self._contrast_weight
+
+    @contrast_weight.setter
+    def contrast_weight(self, value) -> None:
+        if not self._nweak:
+            raise AttributeError("this policy was built without contrast: there is no forward-contrast term to weigh")
+        self._contrast_weight = self._checked_contrast_weight(value)
+        self._lambda.fill_(self._contrast_weight)
 
     def _ens_state(self, name: str) -> torch.Tensor:
         if self._ens is None:
@@ -789,14 +949,22 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         img, gl, frames = self._inputs
         inner = self.model.inner_model
         x = ent["bufs"][0]
-        N = self._ncand
+        N = self._nper
         rows = (self._rows_ptr(), x.shape[0] // N, self.num_envs, self._seeds.data_ptr(), self._draws.data_ptr(),
                 None if img is None else img.data_ptr(), inner.n_img_tokens * inner.obs_dim, gl.data_ptr(), inner.goal_dim,
                 None if img is None else ent["img"].data_ptr(), ent["goals"].data_ptr(), x.data_ptr())
         if N > 1:                                                            # candidates: N rows per environment, draw index draws * N + c
             if "chosen" not in ent:                                          # (a new entry: this call is ahead of its capture)
                 ent["chosen"] = torch.zeros(x.shape[0] // N, *x.shape[1:], dtype=torch.float32, device=x.device)
-            if warm:
+            if self._nweak:                                                  # forward contrast: the last M of the N rows with a zero goal row
+                if warm:
+                    L.check(self._lib.mode_env_gather_warm_bid(*rows, self._plan.data_ptr(), self.act_window_size, self.action_dim, self.multistep,
+                                                               self._warm_schedule(x.device)[1], self._ncand, self._nweak, _stream()),
+                            "env_gather_warm_bid")
+                else:
+                    L.check(self._lib.mode_env_gather_noise_bid(*rows, self.act_window_size * self.action_dim, float(self.sigma_max), self._ncand,
+                                                                self._nweak, _stream()), "env_gather_noise_bid")
+            elif warm:
                 L.check(self._lib.mode_env_gather_warm_cand(*rows, self._plan.data_ptr(), self.act_window_size, self.action_dim, self.multistep,
                                                             self._warm_schedule(x.device)[1], N, _stream()), "env_gather_warm_cand")
             else:
@@ -851,7 +1019,7 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         encoder graph (captured on first use, and again when the frame geometry, the weights' storage or the chunk entry's buffers moved), or
         the eager towers when the encoders are in training mode / MODE_HIP_GRAPH=0.  ``store``: the encoder store of the chunk's kind."""
         enc = self.encoders
-        N = self._ncand
+        N = self._nper                                                      # (forward contrast: the weak rows share the embeddings too)
         mb, n_img = ent["goals"].shape[0] // N, self.model.inner_model.n_img_tokens
         dts = self._frame_dtypes(frames)
         shapes = [tuple(f.shape[1:]) for f in frames]                      # of one environment's gathered frames
@@ -897,7 +1065,10 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
             from .engine import _stream
             sel = type(self._sel).from_buffer_copy(self._sel)
             sel.chunk, sel.chosen, sel.m_b = d.chunk, ent["chosen"].data_ptr(), ent["chosen"].shape[0]
-            L.check(self._lib.mode_env_select(C.byref(sel), _stream()), "env_select")
+            if self._nweak:
+                L.check(self._lib.mode_env_select_bid(C.byref(sel), _stream()), "env_select_bid")
+            else:
+                L.check(self._lib.mode_env_select(C.byref(sel), _stream()), "env_select")
             d.chunk = sel.chosen
         if capturing:
             d.ctrl = self._ctrl.data_ptr()
@@ -927,13 +1098,13 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         sig = self._warm_schedule(eng.device)[0] if warm else self._schedule(eng.device)
         tpl = self._templates.get(mb)
         if tpl is None:
-            dev, B = eng.device, mb * self._ncand                           # (candidates: N chunk rows per environment)
+            dev, B = eng.device, mb * self._nper                            # (candidates: N (+ M weak) chunk rows per environment)
             tpl = self._templates[mb] = ({"state_images": torch.zeros(B, inner.n_img_tokens, inner.obs_dim, device=dev)},
                                          torch.zeros(B, self.act_window_size, self.action_dim, device=dev), torch.zeros(B, inner.goal_dim, device=dev))
         w = getattr(self.model, "guidance_scale", None)                  # classifier-free guidance: the bucket's mb rows run as 2·mb inside the chain
         gkey, plan = inner._chunk_plan(eng, self._solver, sig.numel() - 1, w is not None)
         inner._sample_chunk(eng, gkey, plan, tpl[0], tpl[1], tpl[2], sig, float(self.model.sigma_data),
-                            hooks=self._hooks_warm if warm else self._hooks, rows=m * self._ncand, guidance=w)
+                            hooks=self._hooks_warm if warm else self._hooks, rows=m * self._nper, guidance=w)
 
     @staticmethod
     def _prepared(img, gl, frames):
