@@ -37,6 +37,9 @@ __device__ __forceinline__ void env_gather_obs(const int r, const int j, const f
   }
 }
 
+// Bit b of a little-endian bitmask of uint32 words (the active and has-previous-plan masks), given its word, words[b >> 5]
+__device__ __forceinline__ bool env_bit(const uint32_t word, const int b) { return (word >> (b & 31)) & 1u; }
+
 // Both gathers run on grid (m_b, N): block (j, c) fills chunk row j * N + c, candidate c of environment rows[j], from draw draws[r] * N + c of
 // its stream (uint32 arithmetic).  N = 1 - a replan without candidate selection - is row j from draw draws[r].  The first `strong` candidates
 // carry the environment's goal row, the others (forward contrast: the weak candidates of the _bid gathers) a zero goal row.
@@ -130,15 +133,12 @@ __global__ __launch_bounds__(256) void env_gather_frames_kernel(ModeEnvFramesDes
   frames_copy_row(c, r, j);
 }
 
-// One wave per environment b: find b among the chunk's m real rows (rows are distinct), commit that row, then emit.  The emitted row of a
-// just-committed plan is read from the chunk itself (counter 0), so no thread reads plan memory another thread of this launch wrote.
-__global__ __launch_bounds__(64) void env_commit_emit_kernel(ModeEnvPoolDesc d) {
-  const int b = blockIdx.x, lane = threadIdx.x;
+// Head of both commit kernels, one wave per environment b: the step's output and the word of its active mask that holds b's bit from the control block (d.ctrl) or, without
+// one, from the descriptor (then no row replans), and the row j of b among the chunk's m real rows (-1: b does not replan), known to every lane
+__device__ __forceinline__ int env_commit_head(const ModeEnvPoolDesc& d, const int b, const int lane, float*& out, uint32_t& act_word) {
   const int NW = (d.num_envs + 31) >> 5;
   const int32_t* ctrl = d.ctrl;
   int m = 0;
-  uint32_t act_word;
-  float* out;
   if (ctrl) {
     m = min(max(ctrl[0], 0), d.num_envs);
     out = reinterpret_cast<float*>((uint64_t)(uint32_t)ctrl[2] | ((uint64_t)(uint32_t)ctrl[3] << 32));
@@ -147,13 +147,23 @@ __global__ __launch_bounds__(64) void env_commit_emit_kernel(ModeEnvPoolDesc d) 
     out = d.out;
     act_word = d.active[b >> 5];
   }
-  const bool active = (act_word >> (b & 31)) & 1u;
   const int32_t* rows = ctrl ? ctrl + 4 + NW : nullptr;
   int j = -1;
   for (int i = lane; i < m; i += 64)
     if (rows[i] == b) j = i;
   // every lane learns the (unique) row: the largest index found by any lane
   for (int o = 32; o > 0; o >>= 1) j = max(j, __shfl_xor(j, o, 64));
+  return j;
+}
+
+// One wave per environment b: find b among the chunk's m real rows (rows are distinct), commit that row, then emit.  The emitted row of a
+// just-committed plan is read from the chunk itself (counter 0), so no thread reads plan memory another thread of this launch wrote.
+__global__ __launch_bounds__(64) void env_commit_emit_kernel(ModeEnvPoolDesc d) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  float* out;
+  uint32_t act_word;
+  const int j = env_commit_head(d, b, lane, out, act_word);
+  const bool active = env_bit(act_word, b);
   const int WA = d.W * d.A;
   float* plan = d.plan + (long)b * WA;
   int c;
@@ -184,25 +194,10 @@ __global__ __launch_bounds__(64) void env_commit_emit_kernel(ModeEnvPoolDesc d) 
 __global__ __launch_bounds__(64) void env_commit_emit_ens_kernel(ModeEnvEnsDesc e) {
   const ModeEnvPoolDesc& d = e.pool;
   const int b = blockIdx.x, lane = threadIdx.x;
-  const int NW = (d.num_envs + 31) >> 5;
-  const int32_t* ctrl = d.ctrl;
-  int m = 0;
-  uint32_t act_word;
   float* out;
-  if (ctrl) {
-    m = min(max(ctrl[0], 0), d.num_envs);
-    out = reinterpret_cast<float*>((uint64_t)(uint32_t)ctrl[2] | ((uint64_t)(uint32_t)ctrl[3] << 32));
-    act_word = (uint32_t)ctrl[4 + (b >> 5)];
-  } else {
-    out = d.out;
-    act_word = d.active[b >> 5];
-  }
-  const bool active = (act_word >> (b & 31)) & 1u;
-  const int32_t* rows = ctrl ? ctrl + 4 + NW : nullptr;
-  int j = -1;
-  for (int i = lane; i < m; i += 64)
-    if (rows[i] == b) j = i;
-  for (int o = 32; o > 0; o >>= 1) j = max(j, __shfl_xor(j, o, 64));
+  uint32_t act_word;
+  const int j = env_commit_head(d, b, lane, out, act_word);
+  const bool active = env_bit(act_word, b);
   const int s = d.multistep, K = e.K, W = d.W, A = d.A, WA = W * A;
   const int t = max(e.t[b], 0);
   const int q = (t / s) % K;                   // slot of the newest plan, born at tn
@@ -302,7 +297,7 @@ __global__ __launch_bounds__(256) void env_select_kernel(ModeEnvSelectDesc d) {
   const int r = d.rows[j];
   if (r < 0 || r >= d.num_envs || (d.count && j >= d.count[0])) return;          // (uniform over the workgroup)
   const int N = d.N, WA = d.W * d.A, LA = (d.W - d.shift) * d.A;
-  const bool has_prev = (d.has_prev[r >> 5] >> (r & 31)) & 1u;
+  const bool has_prev = env_bit(d.has_prev[r >> 5], r);
   const float* prev = d.plan + (long)r * WA + d.shift * d.A;
   for (int e = tid; e < LA; e += 256) tail[e] = prev[e];
   __syncthreads();
@@ -348,7 +343,7 @@ __global__ __launch_bounds__(256) void env_select_bid_kernel(ModeEnvBidDesc d) {
   if (r < 0 || r >= d.num_envs || (d.count && j >= d.count[0])) return;          // (uniform over the workgroup)
   const int N = d.N, NT = d.N + d.M, WA = d.W * d.A, LA = (d.W - d.shift) * d.A;
   const int Ks = min(d.K, N), Kw = min(d.K, d.M);
-  const bool has_prev = (d.has_prev[r >> 5] >> (r & 31)) & 1u;
+  const bool has_prev = env_bit(d.has_prev[r >> 5], r);
   const float* prev = d.plan + (long)r * WA + d.shift * d.A;
   const float* cands = d.chunk + (long)j * NT * WA;
   for (int e = tid; e < LA; e += 256) tail[e] = prev[e];
@@ -473,43 +468,43 @@ extern "C" int mode_env_gather_warm(const int32_t* rows, int m_b, int num_envs, 
                                    shift, sigma_start, 1, stream);
 }
 
+// What both selection descriptors (D) share: the pointers every selection needs and the geometry
+template <class D>
+static bool env_select_desc_ok(const D* d) {
+  return d && d->rows && d->has_prev && d->chunk && d->plan && d->weights && d->chosen && d->selected && d->scores && d->N >= 1 && d->N <= 64 &&
+         d->W > 0 && d->A > 0 && (long)d->W * d->A <= 4096 && d->shift >= 1 && d->shift < d->W && d->m_b > 0 && d->num_envs > 0;
+}
+
 extern "C" int mode_env_select(const ModeEnvSelectDesc* d, void* stream) {
-  if (!d || !d->rows || !d->has_prev || !d->chunk || !d->plan || !d->weights || !d->chosen || !d->selected || !d->scores) return MODE_ERR_BAD_ARG;
-  if (d->N < 1 || d->N > 64 || d->W <= 0 || d->A <= 0 || (long)d->W * d->A > 4096 || d->shift < 1 || d->shift >= d->W || d->m_b <= 0 || d->num_envs <= 0)
-    return MODE_ERR_BAD_ARG;
+  if (!env_select_desc_ok(d)) return MODE_ERR_BAD_ARG;
   hipLaunchKernelGGL(env_select_kernel, dim3(d->m_b), dim3(256), 0, (hipStream_t)stream, *d);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }
 
 extern "C" int mode_env_select_bid(const ModeEnvBidDesc* d, void* stream) {
-  if (!d || !d->rows || !d->has_prev || !d->chunk || !d->plan || !d->weights || !d->chosen || !d->selected || !d->scores || !d->lambda || !d->bc || !d->fc)
-    return MODE_ERR_BAD_ARG;
-  if (d->N < 1 || d->N > 64 || d->M < 1 || d->M > 64 - d->N || d->K < 1 || d->W <= 0 || d->A <= 0 || (long)d->W * d->A > 4096 || d->shift < 1 ||
-      d->shift >= d->W || d->m_b <= 0 || d->num_envs <= 0)
-    return MODE_ERR_BAD_ARG;
+  if (!env_select_desc_ok(d) || !d->lambda || !d->bc || !d->fc || d->M < 1 || d->M > 64 - d->N || d->K < 1) return MODE_ERR_BAD_ARG;
   hipLaunchKernelGGL(env_select_bid_kernel, dim3(d->m_b), dim3(256), 0, (hipStream_t)stream, *d);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }
 
+// The pool descriptor of both commit exports: geometry, state pointers, and the chunk (control-block form) or the output (descriptor form)
+static bool env_pool_desc_ok(const ModeEnvPoolDesc* d) {
+  return d->num_envs > 0 && d->num_envs <= MODE_ENV_MAX && d->W > 0 && d->A > 0 && d->A <= 64 && d->W * d->A <= 4096 && d->multistep > 0 &&
+         d->multistep <= d->W && d->plan && d->counter && d->draws && (d->ctrl ? d->chunk != nullptr : d->out != nullptr);
+}
+
 extern "C" int mode_env_commit_emit(const ModeEnvPoolDesc* d, void* stream) {
-  if (!d || d->num_envs <= 0 || d->num_envs > MODE_ENV_MAX || d->W <= 0 || d->A <= 0 || d->A > 64 || d->W * d->A > 4096 || d->multistep <= 0 ||
-      d->multistep > d->W || !d->plan || !d->counter || !d->draws)
-    return MODE_ERR_BAD_ARG;
-  if (d->ctrl ? !d->chunk : !d->out) return MODE_ERR_BAD_ARG;
+  if (!d || !env_pool_desc_ok(d)) return MODE_ERR_BAD_ARG;
   hipLaunchKernelGGL(env_commit_emit_kernel, dim3(d->num_envs), dim3(64), 0, (hipStream_t)stream, *d);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }
 
 extern "C" int mode_env_commit_emit_ens(const ModeEnvEnsDesc* e, void* stream) {
-  if (!e) return MODE_ERR_BAD_ARG;
+  if (!e || !env_pool_desc_ok(&e->pool)) return MODE_ERR_BAD_ARG;
   const ModeEnvPoolDesc* d = &e->pool;
-  if (d->num_envs <= 0 || d->num_envs > MODE_ENV_MAX || d->W <= 0 || d->A <= 0 || d->A > 64 || d->W * d->A > 4096 || d->multistep <= 0 ||
-      d->multistep > d->W || !d->plan || !d->counter || !d->draws)
-    return MODE_ERR_BAD_ARG;
-  if (d->ctrl ? !d->chunk : !d->out) return MODE_ERR_BAD_ARG;
   if (!e->ring || !e->birth || !e->t || !e->weights || e->K < 1 || e->K > 64 || e->K != (d->W + d->multistep - 1) / d->multistep) return MODE_ERR_BAD_ARG;
   hipLaunchKernelGGL(env_commit_emit_ens_kernel, dim3(d->num_envs), dim3(64), 0, (hipStream_t)stream, *e);
   MODE_LAUNCH_CHECK();

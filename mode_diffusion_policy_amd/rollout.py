@@ -143,12 +143,8 @@ class ChunkedRolloutPolicy:
         """The raw observation's contract of a policy built with ``camera_transforms``: both cameras, uint8 (n, T, H, W, 3) each with one T,
         2 T = n_img_tokens, on the policy's device, at most 8 source pixels per output pixel; a row's frames one contiguous block (made so here)."""
         from .camera import check_frames_u8
-        n_img = self.model.inner_model.n_img_tokens
-        if not isinstance(rgb, dict) or set(rgb) != set(self._CAMERAS):
-            raise ValueError(f"rgb_obs must hold exactly the cameras {list(self._CAMERAS)}, got {sorted(rgb) if isinstance(rgb, dict) else type(rgb).__name__}")
-        out = []
-        for name in self._CAMERAS:
-            f = rgb[name]
+
+        def camera(name, f):
             if torch.is_tensor(f) and f.dtype != torch.uint8:
                 raise ValueError(f"{name}: a policy built with camera_transforms takes the camera's uint8 (n, T, H, W, 3) frames, got {f.dtype} "
                                  f"{tuple(f.shape)}; float frames go to a policy without camera_transforms")
@@ -156,13 +152,21 @@ class ChunkedRolloutPolicy:
                 raise ValueError(f"{name} must be uint8 ({'n' if n is None else n}, T, H, W, 3) (one row per environment), got {tuple(getattr(f, 'shape', ()))}")
             f = check_frames_u8(f, name, self._frames_device())
             self.camera_transforms[name].check_source(f.shape[2], f.shape[3], name)
-            out.append(f)
-        if out[1].shape[:2] != out[0].shape[:2]:
-            raise ValueError(f"both cameras must carry the same rows and number of frames T, got {tuple(out[0].shape[:2])} and {tuple(out[1].shape[:2])}")
-        T = out[0].shape[1]
+            return f
+        return self._check_cameras(rgb, camera, "rows and number of frames T", lambda f: tuple(f.shape[:2]))
+
+    def _check_cameras(self, rgb, camera, same: str, key):
+        """What every raw observation has to meet: exactly the two cameras, each passing ``camera(name, frames) -> frames`` (the caller's own
+        contract), both with one ``key(frames)`` - named ``same`` in the refusal - and 2 T = n_img_tokens.  Returns the two checked tensors."""
+        if not isinstance(rgb, dict) or set(rgb) != set(self._CAMERAS):
+            raise ValueError(f"rgb_obs must hold exactly the cameras {list(self._CAMERAS)}, got {sorted(rgb) if isinstance(rgb, dict) else type(rgb).__name__}")
+        out = tuple(camera(name, rgb[name]) for name in self._CAMERAS)
+        if key(out[1]) != key(out[0]):
+            raise ValueError(f"both cameras must carry the same {same}, got {key(out[0])} and {key(out[1])}")
+        T, n_img = out[0].shape[1], self.model.inner_model.n_img_tokens
         if 2 * T != n_img:
             raise ValueError(f"2 * T frames (T = {T}) must equal the model's n_img_tokens = {n_img}")
-        return tuple(out)
+        return out
 
     def _transform_pair(self):
         return tuple(self.camera_transforms[name] for name in self._CAMERAS)
@@ -297,24 +301,49 @@ def coherence_weights(rho: float, length: int) -> np.ndarray:
     return (float(rho) ** np.arange(length, dtype=np.float64)).astype(np.float32)
 
 
+def _checked_int(value, lo: int, hi: Optional[int], message: str) -> int:
+    """``value`` as an int when it is one (no bool) in [lo, hi] (``hi`` None: no upper bound); ValueError(message) otherwise."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or int(value) < lo or (hi is not None and int(value) > hi):
+        raise ValueError(message)
+    return int(value)
+
+
+def _checked_float(value, lo: float, hi: float, message: str, lo_open: bool = False) -> float:
+    """``float(value)`` when it is finite and in [lo, hi] ((lo, hi] with ``lo_open``); ValueError(message) otherwise, also for a bool and for
+    what float() does not take."""
+    try:
+        x = float(value)
+    except (TypeError, ValueError):
+        x = float("nan")
+    if isinstance(value, bool) or not (np.isfinite(x) and lo <= x <= hi and not (lo_open and x == lo)):
+        raise ValueError(message)
+    return x
+
+
+def _env_latents(what: str, seeds, draws, dev, shape, *tail) -> torch.Tensor:
+    """One row per (seed, draw) from the single-row gather ``mode_<what>`` without observations: ``shape`` fp32 on ``dev``."""
+    from . import _lib as L
+    from .engine import _stream
+    n = len(seeds)
+    s, d = _u32_as_i32(seeds).to(dev), _u32_as_i32(draws).to(dev)
+    rows = torch.arange(n, dtype=torch.int32, device=dev)
+    x = torch.empty(shape, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(getattr(L.load(), "mode_" + what)(rows.data_ptr(), n, n, s.data_ptr(), d.data_ptr(), None, 0, None, 0, None, None, x.data_ptr(), *tail,
+                                                  _stream()), what)
+    return x
+
+
 @torch.no_grad()
 def env_noise(seeds, draws, act_window_size: int, action_dim: int, sigma_max: float, device="cuda") -> torch.Tensor:
     """The initial latents ``VectorEnvPolicy`` plans from: row i = draw ``draws[i]`` of the noise stream with seed ``seeds[i]`` times ``sigma_max``,
     (len(seeds), act_window_size, action_dim) fp32 on ``device``.  The stream is counter-based (formula: include/mode_hip.h, ABI 13), so any
     environment's replan can be reproduced from its seed and draw index alone."""
-    from . import _lib as L
-    from .engine import _stream
     seeds, draws = list(seeds), list(draws)
     if not seeds or len(seeds) != len(draws):
         raise ValueError("env_noise: one draw index per seed, at least one")
-    dev, n = torch.device(device), len(seeds)
-    s, d = _u32_as_i32(seeds).to(dev), _u32_as_i32(draws).to(dev)
-    rows = torch.arange(n, dtype=torch.int32, device=dev)
-    x = torch.empty(n, act_window_size, action_dim, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        L.check(L.load().mode_env_gather_noise(rows.data_ptr(), n, n, s.data_ptr(), d.data_ptr(), None, 0, None, 0, None, None, x.data_ptr(),
-                                               act_window_size * action_dim, float(sigma_max), _stream()), "env_gather_noise")
-    return x
+    return _env_latents("env_gather_noise", seeds, draws, torch.device(device), (len(seeds), act_window_size, action_dim),
+                        act_window_size * action_dim, float(sigma_max))
 
 
 @torch.no_grad()
@@ -323,8 +352,6 @@ def env_warm_latents(plans: torch.Tensor, seeds, draws, shift: int, sigma_start:
     row held beyond the end, plus ``sigma_start`` times draw ``draws[i]`` of the noise stream with seed ``seeds[i]`` - the stream element
     ``env_noise`` scales by ``sigma_max``:  ``x0[i, w, a] = plans[i, min(w + shift, W - 1), a] + sigma_start * z_i[w, a]`` (fp32; formula:
     include/mode_hip.h).  ``plans`` (n, W, A) on a ROCm device, 1 <= shift < W, sigma_start finite and >= 0; returns (n, W, A) fp32 there."""
-    from . import _lib as L
-    from .engine import _stream
     seeds, draws = list(seeds), list(draws)
     if not torch.is_tensor(plans) or plans.dim() != 3 or plans.shape[0] == 0:
         raise ValueError(f"env_warm_latents: plans must be a (n, W, A) tensor, got {tuple(getattr(plans, 'shape', ()))}")
@@ -333,21 +360,53 @@ def env_warm_latents(plans: torch.Tensor, seeds, draws, shift: int, sigma_start:
         raise ValueError("env_warm_latents: one seed and one draw index per plan")
     if plans.device.type != "cuda":
         raise ValueError("env_warm_latents: plans must be on a ROCm device")
-    dev = plans.device
     old = plans.to(torch.float32).contiguous()
-    s, d = _u32_as_i32(seeds).to(dev), _u32_as_i32(draws).to(dev)
-    rows = torch.arange(n, dtype=torch.int32, device=dev)
-    x = torch.empty(n, W, A, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        L.check(L.load().mode_env_gather_warm(rows.data_ptr(), n, n, s.data_ptr(), d.data_ptr(), None, 0, None, 0, None, None, x.data_ptr(),
-                                              old.data_ptr(), W, A, int(shift), float(sigma_start), _stream()), "env_gather_warm")
-    return x
+    return _env_latents("env_gather_warm", seeds, draws, plans.device, (n, W, A), old.data_ptr(), W, A, int(shift), float(sigma_start))
 
 
 def _mask_words(mask: np.ndarray, nw: int) -> np.ndarray:
     """A host bool vector as ``nw`` little-endian uint32 words, bit b % 32 of word b // 32 = entry b (the control block's bitmasks)."""
     bits = np.packbits(mask, bitorder="little")
     return np.pad(bits, (0, 4 * nw - bits.size)).view("<u4")
+
+
+def _select_desc(contrast: Optional[dict] = None, **common):
+    """``ModeEnvSelectDesc`` from the fields both selections share; with ``contrast`` - ``lambda_``, ``bc``, ``fc``, ``M`` and ``K`` -
+    ``ModeEnvBidDesc``.  A tensor stands for its address."""
+    from . import _lib as L
+    fields = {k: v.data_ptr() if torch.is_tensor(v) else v for k, v in {**common, **(contrast or {})}.items()}
+    return (L.ModeEnvBidDesc if contrast else L.ModeEnvSelectDesc)(**fields)
+
+
+def _candidate_dims(name: str, dims: str, chunk):
+    if not torch.is_tensor(chunk) or chunk.dim() != 4 or chunk.numel() == 0:
+        raise ValueError(f"{name}: chunk must be a non-empty {dims} tensor, got {tuple(getattr(chunk, 'shape', ()))}")
+    return chunk.shape
+
+
+def _select_rows(name: str, chunk, prev, has_prev, shift, weights) -> dict:
+    """What ``select_coherent`` and ``select_bidirectional`` share behind their own checks: ``prev``, ``has_prev``, ``shift`` and ``weights``
+    checked against ``chunk``, and the descriptor fields of n explicit rows - identity rows, the mask words, fp32 contiguous inputs, the
+    ``chosen`` and ``selected`` outputs - as tensors on the chunk's device."""
+    n, _, W, A = chunk.shape
+    if W * A > 4096:
+        raise ValueError(f"{name}: W * A must be at most 4096, got {W} * {A}")
+    if not torch.is_tensor(prev) or tuple(prev.shape) != (n, W, A):
+        raise ValueError(f"{name}: prev must be ({n}, {W}, {A}), one previous plan per row, got {tuple(getattr(prev, 'shape', ()))}")
+    has = np.asarray(has_prev.cpu() if torch.is_tensor(has_prev) else has_prev)
+    if has.dtype != np.bool_ or has.shape != (n,):
+        raise ValueError(f"{name}: has_prev must be {n} host bools, got {has.dtype} {has.shape}")
+    shift = _checked_int(shift, 1, W - 1, f"{name}: shift must be an int in [1, W - 1] = [1, {W - 1}], got {shift!r}")
+    wt = np.asarray(weights.cpu() if torch.is_tensor(weights) else weights, dtype=np.float32).reshape(-1)
+    if wt.size != W - shift:
+        raise ValueError(f"{name}: weights must have W - shift = {W - shift} entries, got {wt.size}")
+    if chunk.device.type != "cuda" or prev.device != chunk.device:
+        raise ValueError(f"{name}: chunk and prev must be on one ROCm device")
+    dev = chunk.device
+    return dict(rows=torch.arange(n, dtype=torch.int32, device=dev), count=None, m_b=n, num_envs=n, W=W, A=A, shift=shift,
+                has_prev=torch.from_numpy(_mask_words(has, (n + 31) // 32).view("<i4").copy()).to(dev),
+                chunk=chunk.to(torch.float32).contiguous(), plan=prev.to(torch.float32).contiguous(), weights=torch.from_numpy(wt.copy()).to(dev),
+                chosen=torch.empty(n, W, A, dtype=torch.float32, device=dev), selected=torch.empty(n, dtype=torch.int32, device=dev))
 
 
 @torch.no_grad()
@@ -360,40 +419,15 @@ def select_coherent(chunk: torch.Tensor, prev: torch.Tensor, has_prev, shift: in
     selected (n,) int32, scores (n, N) fp32)`` on the inputs' device."""
     from . import _lib as L
     from .engine import _stream
-    if not torch.is_tensor(chunk) or chunk.dim() != 4 or chunk.numel() == 0:
-        raise ValueError(f"select_coherent: chunk must be a non-empty (n, N, W, A) tensor, got {tuple(getattr(chunk, 'shape', ()))}")
-    n, N, W, A = chunk.shape
+    n, N, W, A = _candidate_dims("select_coherent", "(n, N, W, A)", chunk)
     if not 1 <= N <= 64:
         raise ValueError(f"select_coherent: the number of candidates N must be in [1, 64], got {N}")
-    if W * A > 4096:
-        raise ValueError(f"select_coherent: W * A must be at most 4096, got {W} * {A}")
-    if not torch.is_tensor(prev) or tuple(prev.shape) != (n, W, A):
-        raise ValueError(f"select_coherent: prev must be ({n}, {W}, {A}), one previous plan per row, got {tuple(getattr(prev, 'shape', ()))}")
-    has = np.asarray(has_prev.cpu() if torch.is_tensor(has_prev) else has_prev)
-    if has.dtype != np.bool_ or has.shape != (n,):
-        raise ValueError(f"select_coherent: has_prev must be {n} host bools, got {has.dtype} {has.shape}")
-    if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not 1 <= int(shift) <= W - 1:
-        raise ValueError(f"select_coherent: shift must be an int in [1, W - 1] = [1, {W - 1}], got {shift!r}")
-    wt = np.asarray(weights.cpu() if torch.is_tensor(weights) else weights, dtype=np.float32).reshape(-1)
-    if wt.size != W - int(shift):
-        raise ValueError(f"select_coherent: weights must have W - shift = {W - int(shift)} entries, got {wt.size}")
-    if chunk.device.type != "cuda" or prev.device != chunk.device:
-        raise ValueError("select_coherent: chunk and prev must be on one ROCm device")
-    dev = chunk.device
-    x, old = chunk.to(torch.float32).contiguous(), prev.to(torch.float32).contiguous()
-    nw = (n + 31) // 32
-    rows = torch.arange(n, dtype=torch.int32, device=dev)
-    mask = torch.from_numpy(_mask_words(has, nw).view("<i4").copy()).to(dev)
-    wdev = torch.from_numpy(wt.copy()).to(dev)
-    chosen = torch.empty(n, W, A, dtype=torch.float32, device=dev)
-    selected = torch.empty(n, dtype=torch.int32, device=dev)
-    scores = torch.empty(n, N, dtype=torch.float32, device=dev)
-    d = L.ModeEnvSelectDesc(rows=rows.data_ptr(), has_prev=mask.data_ptr(), count=None, chunk=x.data_ptr(), plan=old.data_ptr(),
-                            weights=wdev.data_ptr(), chosen=chosen.data_ptr(), selected=selected.data_ptr(), scores=scores.data_ptr(), m_b=n,
-                            num_envs=n, W=W, A=A, shift=int(shift), N=N)
-    with torch.cuda.device(dev):
+    f = _select_rows("select_coherent", chunk, prev, has_prev, shift, weights)
+    scores = torch.empty(n, N, dtype=torch.float32, device=chunk.device)
+    d = _select_desc(scores=scores, N=N, **f)
+    with torch.cuda.device(chunk.device):
         L.check(L.load().mode_env_select(C.byref(d), _stream()), "env_select")
-    return chosen, selected, scores
+    return f["chosen"], f["selected"], scores
 
 
 @torch.no_grad()
@@ -407,54 +441,22 @@ def select_bidirectional(chunk: torch.Tensor, prev: torch.Tensor, has_prev, shif
     fc (n, N))`` on the inputs' device."""
     from . import _lib as L
     from .engine import _stream
-    if not torch.is_tensor(chunk) or chunk.dim() != 4 or chunk.numel() == 0:
-        raise ValueError(f"select_bidirectional: chunk must be a non-empty (n, N + M, W, A) tensor, got {tuple(getattr(chunk, 'shape', ()))}")
-    n, NT, W, A = chunk.shape
-    if isinstance(n_weak, bool) or not isinstance(n_weak, (int, np.integer)) or not 1 <= int(n_weak) <= NT - 1:
-        raise ValueError(f"select_bidirectional: n_weak must be an int in [1, {NT - 1}] (of the {NT} candidates at least one is strong), got {n_weak!r}")
+    name = "select_bidirectional"
+    n, NT, W, A = _candidate_dims(name, "(n, N + M, W, A)", chunk)
+    M = _checked_int(n_weak, 1, NT - 1, f"{name}: n_weak must be an int in [1, {NT - 1}] (of the {NT} candidates at least one is strong), got {n_weak!r}")
     if NT > 64:
-        raise ValueError(f"select_bidirectional: the number of candidates N + M must be at most 64, got {NT}")
-    if isinstance(topk, bool) or not isinstance(topk, (int, np.integer)) or int(topk) < 1:
-        raise ValueError(f"select_bidirectional: topk must be an int >= 1, got {topk!r}")
-    try:
-        lam = float(contrast_weight)
-    except (TypeError, ValueError):
-        lam = float("nan")
-    if isinstance(contrast_weight, bool) or not (np.isfinite(lam) and lam >= 0.0):
-        raise ValueError(f"select_bidirectional: contrast_weight must be a finite float >= 0, got {contrast_weight!r}")
-    if W * A > 4096:
-        raise ValueError(f"select_bidirectional: W * A must be at most 4096, got {W} * {A}")
-    if not torch.is_tensor(prev) or tuple(prev.shape) != (n, W, A):
-        raise ValueError(f"select_bidirectional: prev must be ({n}, {W}, {A}), one previous plan per row, got {tuple(getattr(prev, 'shape', ()))}")
-    has = np.asarray(has_prev.cpu() if torch.is_tensor(has_prev) else has_prev)
-    if has.dtype != np.bool_ or has.shape != (n,):
-        raise ValueError(f"select_bidirectional: has_prev must be {n} host bools, got {has.dtype} {has.shape}")
-    if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not 1 <= int(shift) <= W - 1:
-        raise ValueError(f"select_bidirectional: shift must be an int in [1, W - 1] = [1, {W - 1}], got {shift!r}")
-    wt = np.asarray(weights.cpu() if torch.is_tensor(weights) else weights, dtype=np.float32).reshape(-1)
-    if wt.size != W - int(shift):
-        raise ValueError(f"select_bidirectional: weights must have W - shift = {W - int(shift)} entries, got {wt.size}")
-    if chunk.device.type != "cuda" or prev.device != chunk.device:
-        raise ValueError("select_bidirectional: chunk and prev must be on one ROCm device")
-    dev, M = chunk.device, int(n_weak)
-    N = NT - M
-    x, old = chunk.to(torch.float32).contiguous(), prev.to(torch.float32).contiguous()
-    nw = (n + 31) // 32
-    rows = torch.arange(n, dtype=torch.int32, device=dev)
-    mask = torch.from_numpy(_mask_words(has, nw).view("<i4").copy()).to(dev)
-    wdev = torch.from_numpy(wt.copy()).to(dev)
-    lam_dev = torch.tensor([lam], dtype=torch.float32).to(dev)
-    chosen = torch.empty(n, W, A, dtype=torch.float32, device=dev)
-    selected = torch.empty(n, dtype=torch.int32, device=dev)
+        raise ValueError(f"{name}: the number of candidates N + M must be at most 64, got {NT}")
+    K = _checked_int(topk, 1, None, f"{name}: topk must be an int >= 1, got {topk!r}")
+    lam = _checked_float(contrast_weight, 0.0, float("inf"), f"{name}: contrast_weight must be a finite float >= 0, got {contrast_weight!r}")
+    f = _select_rows(name, chunk, prev, has_prev, shift, weights)
+    dev, N = chunk.device, NT - M
     total, fc = torch.empty(n, N, dtype=torch.float32, device=dev), torch.empty(n, N, dtype=torch.float32, device=dev)
     bc = torch.empty(n, NT, dtype=torch.float32, device=dev)
-    d = L.ModeEnvBidDesc(rows=rows.data_ptr(), has_prev=mask.data_ptr(), count=None, chunk=x.data_ptr(), plan=old.data_ptr(),
-                         weights=wdev.data_ptr(), chosen=chosen.data_ptr(), selected=selected.data_ptr(), scores=total.data_ptr(),
-                         lambda_=lam_dev.data_ptr(), bc=bc.data_ptr(), fc=fc.data_ptr(), m_b=n, num_envs=n, W=W, A=A, shift=int(shift), N=N, M=M,
-                         K=min(int(topk), 64))
+    lam_dev = torch.tensor([lam], dtype=torch.float32).to(dev)
+    d = _select_desc(dict(lambda_=lam_dev, bc=bc, fc=fc, M=M, K=min(K, 64)), scores=total, N=N, **f)
     with torch.cuda.device(dev):
         L.check(L.load().mode_env_select_bid(C.byref(d), _stream()), "env_select_bid")
-    return chosen, selected, total, bc, fc
+    return f["chosen"], f["selected"], total, bc, fc
 
 
 class VectorEnvPolicy(ChunkedRolloutPolicy):
@@ -567,73 +569,60 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         from . import _lib as L
         from .modedit import MoDeDiT
         sampler = kw.get("sampler_type", "ddim")
+        n_steps, W, s = int(kw.get("num_sampling_steps", 10)), int(kw.get("act_window_size", 10)), int(kw.get("multistep", 10))
+
+        def need_tail(what: str) -> None:                                    # the options that read the previous plan's unexecuted tail
+            if not s < W:
+                raise ValueError(f"{what} the unexecuted tail of the previous plan: it needs multistep < act_window_size, got multistep={s}, "
+                                 f"act_window_size={W}")
+
+        def need_room(rows_per_env: int, factor: str, got: str) -> None:     # a chunk runs num_envs * rows_per_env rows at most
+            if isinstance(num_envs, (int, np.integer)) and int(num_envs) * rows_per_env > L.MODE_ENV_MAX:
+                raise ValueError(f"num_envs * {factor} must be at most {L.MODE_ENV_MAX} (the largest batch a chunk runs at), got {int(num_envs)} * {got}")
+
         self.candidates, self.coherence_decay, self._ncand = None, None, 1
         if candidates is not None:
-            W, s = int(kw.get("act_window_size", 10)), int(kw.get("multistep", 10))
-            if isinstance(candidates, bool) or not isinstance(candidates, (int, np.integer)) or not 1 <= int(candidates) <= 64:
-                raise ValueError(f"candidates must be None or an int in [1, 64], got {candidates!r}")
-            self.candidates = int(candidates)
+            self.candidates = _checked_int(candidates, 1, 64, f"candidates must be None or an int in [1, 64], got {candidates!r}")
+            self.coherence_decay = 0.5
             if self.candidates > 1:
-                if not s < W:
-                    raise ValueError(f"candidates scores each candidate against the unexecuted tail of the previous plan: it needs multistep < "
-                                     f"act_window_size, got multistep={s}, act_window_size={W}")
-                if isinstance(num_envs, (int, np.integer)) and int(num_envs) * self.candidates > L.MODE_ENV_MAX:
-                    raise ValueError(f"num_envs * candidates must be at most {L.MODE_ENV_MAX} (the largest batch a chunk runs at), got "
-                                     f"{int(num_envs)} * {self.candidates}")
+                need_tail("candidates scores each candidate against")
+                need_room(self.candidates, "candidates", f"{self.candidates}")
                 self._ncand = self.candidates
         if coherence_decay is not None:
             if candidates is None:
                 raise ValueError("coherence_decay weighs the candidates' scores: it is only legal with candidates=N")
-            try:
-                rho = float(coherence_decay)
-            except (TypeError, ValueError):
-                rho = float("nan")
-            if isinstance(coherence_decay, bool) or not (np.isfinite(rho) and 0.0 < rho <= 1.0):
-                raise ValueError(f"coherence_decay must be a finite float in (0, 1], got {coherence_decay!r}")
-            self.coherence_decay = rho
-        elif candidates is not None:
-            self.coherence_decay = 0.5
+            self.coherence_decay = _checked_float(coherence_decay, 0.0, 1.0, f"coherence_decay must be a finite float in (0, 1], got {coherence_decay!r}",
+                                                  lo_open=True)
         self.contrast, self.contrast_topk, self._contrast_weight, self._nweak, self._lambda = None, None, None, 0, None
         if contrast is not None:
-            if isinstance(contrast, bool) or not isinstance(contrast, (int, np.integer)) or int(contrast) < 1:
-                raise ValueError(f"contrast must be None or an int >= 1, the number of weak (zero-goal) candidates, got {contrast!r}")
+            M = _checked_int(contrast, 1, None, f"contrast must be None or an int >= 1, the number of weak (zero-goal) candidates, got {contrast!r}")
             if self._ncand < 2:
                 raise ValueError(f"contrast compares the strong candidates with each other and with the weak ones: it needs candidates >= 2, got "
                                  f"candidates={candidates!r}")
-            if self._ncand + int(contrast) > 64:
-                raise ValueError(f"candidates + contrast must be at most 64, got {self._ncand} + {int(contrast)}")
-            if isinstance(num_envs, (int, np.integer)) and int(num_envs) * (self._ncand + int(contrast)) > L.MODE_ENV_MAX:
-                raise ValueError(f"num_envs * (candidates + contrast) must be at most {L.MODE_ENV_MAX} (the largest batch a chunk runs at), got "
-                                 f"{int(num_envs)} * ({self._ncand} + {int(contrast)})")
-            self.contrast = self._nweak = int(contrast)
-            self.contrast_topk = min(self._ncand, self._nweak)
+            if self._ncand + M > 64:
+                raise ValueError(f"candidates + contrast must be at most 64, got {self._ncand} + {M}")
+            need_room(self._ncand + M, "(candidates + contrast)", f"({self._ncand} + {M})")
+            self.contrast = self._nweak = M
+            self.contrast_topk = min(self._ncand, M)
             if contrast_topk is not None:
-                if isinstance(contrast_topk, bool) or not isinstance(contrast_topk, (int, np.integer)) or int(contrast_topk) < 1:
-                    raise ValueError(f"contrast_topk must be None or an int >= 1, got {contrast_topk!r}")
-                self.contrast_topk = int(contrast_topk)
+                self.contrast_topk = _checked_int(contrast_topk, 1, None, f"contrast_topk must be None or an int >= 1, got {contrast_topk!r}")
             self._contrast_weight = self._checked_contrast_weight(1.0 if contrast_weight is None else contrast_weight)
         elif contrast_weight is not None or contrast_topk is not None:
             raise ValueError("contrast_weight and contrast_topk shape the forward-contrast term: they are only legal with contrast=M")
         self._nper = self._ncand + self._nweak                               # chunk rows per replanning environment
         self.warm_start = None
         if warm_start is not None:
-            n_steps, W, s = int(kw.get("num_sampling_steps", 10)), int(kw.get("act_window_size", 10)), int(kw.get("multistep", 10))
-            if isinstance(warm_start, bool) or not isinstance(warm_start, (int, np.integer)) or not 1 <= int(warm_start) <= n_steps - 1:
-                raise ValueError(f"warm_start must be None or an int in [1, num_sampling_steps - 1] = [1, {n_steps - 1}], got {warm_start!r}")
-            if not s < W:
-                raise ValueError(f"warm_start resumes from the unexecuted tail of the previous plan: it needs multistep < act_window_size, got "
-                                 f"multistep={s}, act_window_size={W}")
-            self.warm_start = int(warm_start)
+            self.warm_start = _checked_int(warm_start, 1, n_steps - 1, f"warm_start must be None or an int in [1, num_sampling_steps - 1] = "
+                                           f"[1, {n_steps - 1}], got {warm_start!r}")
+            need_tail("warm_start resumes from")
         self._checked_transforms(kw.get("camera_transforms"), kw.get("static_resnet") is not None and kw.get("gripper_resnet") is not None)
         self.temporal_ensemble, self.ensemble_depth, self._ens = None, None, None   # (the base constructor calls reset)
         if temporal_ensemble is not None:
-            m_ens = float(temporal_ensemble)
-            if not (np.isfinite(m_ens) and m_ens >= 0.0):
-                raise ValueError(f"temporal_ensemble must be None or a finite float >= 0, got {temporal_ensemble!r}")
-            W, s = int(kw.get("act_window_size", 10)), int(kw.get("multistep", 10))
+            # (float() first: a bool or a numeric string is taken for its value, anything else float() refuses in its own words)
+            self.temporal_ensemble = _checked_float(float(temporal_ensemble), 0.0, float("inf"), f"temporal_ensemble must be None or a finite float "
+                                                    f">= 0, got {temporal_ensemble!r}")
             if 1 <= s <= W and -(-W // s) > 64:
                 raise ValueError(f"temporal_ensemble keeps ceil(act_window_size / multistep) = {-(-W // s)} plans per environment; at most 64")
-            self.temporal_ensemble = m_ens
         if sampler not in _VECTOR_SAMPLERS or extra_args:
             raise ValueError(f"VectorEnvPolicy supports the deterministic fused samplers {sorted(_VECTOR_SAMPLERS)} without extra_args; got "
                              f"sampler_type={sampler!r}, extra_args={extra_args!r}")
@@ -662,7 +651,7 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         self._draws = torch.zeros(n, dtype=torch.int32, device=dev)          # uint32 bit patterns
         self._seeds = _u32_as_i32(range(seed, seed + n)).to(dev)
         nctrl = 4 + self._nw + n                                             # control block: include/mode_hip.h (ABI 13)
-        self._sel = None
+        self._sel, bid = None, None
         if self._ncand > 1:
             # candidate selection: the control block grows by the has-previous-plan bitmask behind the rows; the last selection per environment
             nctrl += self._nw
@@ -674,6 +663,7 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
                 self._bc_scores = torch.zeros(n, self._nper, dtype=torch.float32, device=dev)
                 self._fc_scores = torch.zeros(n, self._ncand, dtype=torch.float32, device=dev)
                 self._lambda = torch.full((1,), self._contrast_weight, dtype=torch.float32, device=dev)
+                bid = dict(lambda_=self._lambda, bc=self._bc_scores, fc=self._fc_scores, M=self._nweak, K=min(self.contrast_topk, 64))
         self._ctrl = torch.zeros(nctrl, dtype=torch.int32, device=dev)
         # pinned staging of the control block, a ring: a slot is rewritten only after the copy that read it has run (its event)
         self._ring = [torch.zeros(nctrl, dtype=torch.int32, pin_memory=True) for _ in range(4)]
@@ -682,16 +672,9 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         self._scratch_out = torch.zeros(n, A, dtype=torch.float32, device=dev)
         self._desc = L.ModeEnvPoolDesc(num_envs=n, W=W, A=A, multistep=self.multistep, plan=self._plan.data_ptr(),
                                        counter=self._counter_dev.data_ptr(), draws=self._draws.data_ptr())
-        if self._nweak:
-            self._sel = L.ModeEnvBidDesc(rows=self._rows_ptr(), has_prev=self._rows_ptr() + 4 * n, count=self._ctrl.data_ptr(),
-                                         plan=self._plan.data_ptr(), weights=self._coh_w.data_ptr(), selected=self._selected.data_ptr(),
-                                         scores=self._cand_scores.data_ptr(), lambda_=self._lambda.data_ptr(), bc=self._bc_scores.data_ptr(),
-                                         fc=self._fc_scores.data_ptr(), num_envs=n, W=W, A=A, shift=self.multistep, N=self._ncand, M=self._nweak,
-                                         K=min(self.contrast_topk, 64))
-        elif self._ncand > 1:
-            self._sel = L.ModeEnvSelectDesc(rows=self._rows_ptr(), has_prev=self._rows_ptr() + 4 * n, count=self._ctrl.data_ptr(),
-                                            plan=self._plan.data_ptr(), weights=self._coh_w.data_ptr(), selected=self._selected.data_ptr(),
-                                            scores=self._cand_scores.data_ptr(), num_envs=n, W=W, A=A, shift=self.multistep, N=self._ncand)
+        if self._ncand > 1:
+            self._sel = _select_desc(bid, rows=self._rows_ptr(), has_prev=self._rows_ptr() + 4 * n, count=self._ctrl, plan=self._plan, weights=self._coh_w,
+                                     selected=self._selected, scores=self._cand_scores, num_envs=n, W=W, A=A, shift=self.multistep, N=self._ncand)
         self._ens = None
         if self.temporal_ensemble is not None:
             # the ring of each environment's last K plans with their birth times, the local times and the weight table: allocated here, once
@@ -706,6 +689,14 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
             self._ens = L.ModeEnvEnsDesc(ring=self._ens_ring.data_ptr(), birth=self._ens_birth.data_ptr(), t=self._ens_t.data_ptr(),
                                          weights=self._ens_w.data_ptr(), K=K)
         self._lib = L.load()
+        # the exports of this configuration, fixed here: (export, its name in an error) and, for the gathers, the arguments behind the common head
+        # - those before a warm gather's sigma_start, those after it
+        kind, per = ("_bid", (self._ncand, self._nweak)) if self._nweak else ("_cand", (self._ncand,)) if self._ncand > 1 else ("", ())
+        self._gather_call = {False: ("mode_env_gather_noise" + kind, "env_gather_noise" + kind, (W * A, float(self.sigma_max)), per),
+                             True: ("mode_env_gather_warm" + kind, "env_gather_warm" + kind, (self._plan.data_ptr(), W, A, self.multistep), per)}
+        self._select_export, self._select_what = ("mode_env_select_bid", "env_select_bid") if self._nweak else ("mode_env_select", "env_select")
+        self._commit_export, self._commit_what = ("mode_env_commit_emit", "env_commit_emit") if self._ens is None else \
+            ("mode_env_commit_emit_ens", "env_commit_emit_ens")
         self._buckets = _buckets(n)
         self._templates = {}
         self._inputs = None
@@ -816,13 +807,7 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
 
     @staticmethod
     def _checked_contrast_weight(value) -> float:
-        try:
-            lam = float(value)
-        except (TypeError, ValueError):
-            lam = float("nan")
-        if isinstance(value, bool) or not (np.isfinite(lam) and lam >= 0.0):
-            raise ValueError(f"contrast_weight must be a finite float >= 0, got {value!r}")
-        return lam
+        return _checked_float(value, 0.0, float("inf"), f"contrast_weight must be a finite float >= 0, got {value!r}")
 
     @property
     def contrast_weight(self) -> Optional[float]:
@@ -902,24 +887,17 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         made so here."""
         if getattr(self, "camera_transforms", None) is not None:
             return self._check_u8_frames(rgb, self.num_envs)
-        n, n_img = self.num_envs, self.model.inner_model.n_img_tokens
-        if not isinstance(rgb, dict) or set(rgb) != set(self._CAMERAS):
-            raise ValueError(f"rgb_obs must hold exactly the cameras {list(self._CAMERAS)}, got {sorted(rgb) if isinstance(rgb, dict) else type(rgb).__name__}")
-        out = []
-        for name in self._CAMERAS:
-            f = rgb[name]
+        n = self.num_envs
+
+        def camera(name, f):
             if not torch.is_tensor(f) or f.dim() != 5 or f.shape[0] != n or f.shape[2] != 3 or f.numel() == 0:
                 raise ValueError(f"{name} must be ({n}, T, 3, H, W) (one row per environment), got {tuple(getattr(f, 'shape', ()))}")
             if f.dtype not in (torch.float32, torch.bfloat16):
                 raise ValueError(f"{name} must be float32 or bfloat16, got {f.dtype}")
             if f.device != self._plan.device:
                 raise ValueError(f"{name} must be on {self._plan.device}, got {f.device}")
-            out.append(f)
-        T = out[0].shape[1]
-        if out[1].shape[1] != T:
-            raise ValueError(f"both cameras must carry the same number of frames T, got {out[0].shape[1]} and {out[1].shape[1]}")
-        if 2 * T != n_img:
-            raise ValueError(f"2 * T frames (T = {T}) must equal the model's n_img_tokens = {n_img}")
+            return f
+        out = self._check_cameras(rgb, camera, "number of frames T", lambda f: f.shape[1])
         return tuple(f if f[0].is_contiguous() and (n == 1 or f.stride(0) >= f[0].numel()) else f.contiguous() for f in out)
 
     # ---------------------------------------------------------------------------------------------------------------- device side
@@ -953,29 +931,11 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
         rows = (self._rows_ptr(), x.shape[0] // N, self.num_envs, self._seeds.data_ptr(), self._draws.data_ptr(),
                 None if img is None else img.data_ptr(), inner.n_img_tokens * inner.obs_dim, gl.data_ptr(), inner.goal_dim,
                 None if img is None else ent["img"].data_ptr(), ent["goals"].data_ptr(), x.data_ptr())
-        if N > 1:                                                            # candidates: N rows per environment, draw index draws * N + c
-            if "chosen" not in ent:                                          # (a new entry: this call is ahead of its capture)
-                ent["chosen"] = torch.zeros(x.shape[0] // N, *x.shape[1:], dtype=torch.float32, device=x.device)
-            if self._nweak:                                                  # forward contrast: the last M of the N rows with a zero goal row
-                if warm:
-                    L.check(self._lib.mode_env_gather_warm_bid(*rows, self._plan.data_ptr(), self.act_window_size, self.action_dim, self.multistep,
-                                                               self._warm_schedule(x.device)[1], self._ncand, self._nweak, _stream()),
-                            "env_gather_warm_bid")
-                else:
-                    L.check(self._lib.mode_env_gather_noise_bid(*rows, self.act_window_size * self.action_dim, float(self.sigma_max), self._ncand,
-                                                                self._nweak, _stream()), "env_gather_noise_bid")
-            elif warm:
-                L.check(self._lib.mode_env_gather_warm_cand(*rows, self._plan.data_ptr(), self.act_window_size, self.action_dim, self.multistep,
-                                                            self._warm_schedule(x.device)[1], N, _stream()), "env_gather_warm_cand")
-            else:
-                L.check(self._lib.mode_env_gather_noise_cand(*rows, self.act_window_size * self.action_dim, float(self.sigma_max), N, _stream()),
-                        "env_gather_noise_cand")
-        elif warm:
-            L.check(self._lib.mode_env_gather_warm(*rows, self._plan.data_ptr(), self.act_window_size, self.action_dim, self.multistep,
-                                                   self._warm_schedule(x.device)[1], _stream()), "env_gather_warm")
-        else:
-            L.check(self._lib.mode_env_gather_noise(*rows, self.act_window_size * self.action_dim, float(self.sigma_max), _stream()),
-                    "env_gather_noise")
+        if N > 1 and "chosen" not in ent:                                    # (candidates, a new entry: this call is ahead of its capture)
+            ent["chosen"] = torch.zeros(x.shape[0] // N, *x.shape[1:], dtype=torch.float32, device=x.device)
+        export, what, pre, post = self._gather_call[warm]
+        mid = (self._warm_schedule(x.device)[1],) if warm else ()
+        L.check(getattr(self._lib, export)(*rows, *pre, *mid, *post, _stream()), what)
         if frames is not None:
             self._encode(ent, frames, (self._hooks_warm if warm else self._hooks).enc)
 
@@ -1065,10 +1025,7 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
             from .engine import _stream
             sel = type(self._sel).from_buffer_copy(self._sel)
             sel.chunk, sel.chosen, sel.m_b = d.chunk, ent["chosen"].data_ptr(), ent["chosen"].shape[0]
-            if self._nweak:
-                L.check(self._lib.mode_env_select_bid(C.byref(sel), _stream()), "env_select_bid")
-            else:
-                L.check(self._lib.mode_env_select(C.byref(sel), _stream()), "env_select")
+            L.check(getattr(self._lib, self._select_export)(C.byref(sel), _stream()), self._select_what)
             d.chunk = sel.chosen
         if capturing:
             d.ctrl = self._ctrl.data_ptr()
@@ -1079,12 +1036,11 @@ class VectorEnvPolicy(ChunkedRolloutPolicy):
     def _launch(self, d) -> None:
         from . import _lib as L
         from .engine import _stream
-        if self._ens is None:
-            L.check(self._lib.mode_env_commit_emit(C.byref(d), _stream()), "env_commit_emit")
-            return
-        e = type(self._ens).from_buffer_copy(self._ens)                      # temporal ensembling: the same step on the ring of plans
-        e.pool = d
-        L.check(self._lib.mode_env_commit_emit_ens(C.byref(e), _stream()), "env_commit_emit_ens")
+        if self._ens is not None:                                            # temporal ensembling: the same step on the ring of plans
+            e = type(self._ens).from_buffer_copy(self._ens)
+            e.pool = d
+            d = e
+        L.check(getattr(self._lib, self._commit_export)(C.byref(d), _stream()), self._commit_what)
 
     def _run_chunk(self, mb: int, m: int, warm: bool = False) -> None:
         """One replanning chunk at bucket ``mb`` with ``m`` real rows (the control block is staged): gather launch + one replay.  ``warm``: the
