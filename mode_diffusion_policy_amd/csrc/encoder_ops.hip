@@ -124,10 +124,10 @@ __global__ __launch_bounds__(256) void bn_row_sums_kernel(const T* __restrict__ 
   s = wave_sum(s); q = wave_sum(q);
   if (lane == 0) { psum[row] = s; psq[row] = q; }
 }
-// Per-channel fold of per-row partials: a 1024-thread workgroup owns 64 channels, its 16 waves split the N rows (coalesced 256-byte reads of 64
-// neighbouring channels), partials meet in LDS as doubles and are added in wave order: deterministic.  (One thread per channel walking all N rows,
-// the first version, took 17 us per BatchNorm - a serial chain of N strided loads - and there are 106 BatchNorms per ResNet-50 pair.)
-// per-channel folds of [rows][C] partials: a 1024-thread workgroup owns FC = 16 channels, its 64 row lanes split the rows (a wave reads 4 rows x 64 bytes),
+// Per-channel folds of [rows][C] partials (rows = N for NCHW, N * pixel splits for channels_last), shared by bn_finalize_kernel, bn_prepare_kernel and
+// bn_film_bwd_fold_kernel.  (One thread per channel walking all the rows, the first version, took 17 us per BatchNorm - a serial chain of strided
+// loads - and there are 106 BatchNorms per ResNet-50 pair.)  The shape in use:
+// a 1024-thread workgroup owns FC = 16 channels, its FR = 64 row lanes split the rows (row lane rl takes rows rl, rl + 64, ...; a wave reads 4 rows x 64 bytes),
 // partials meet in LDS as doubles and are added in row-lane order: deterministic; C / 16 workgroups keep even a 64-channel layer on four CUs' worth of
 // memory pipes (64 channels per workgroup - the previous shape - left a 256-channel fold on 4 workgroups: 9 us per launch, 212 launches per step)
 constexpr int FC = 16, FR = 64;
@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256) void bn_film_act_bwd_sums_kernel(const ModeBnF
     o[0] = a0; o[1] = a1; o[2] = a2; o[3] = a3; o[4] = a4; o[5] = a5;
   }
 }
-// per-channel fold of the row sums (double; 64 channels per 1024-thread workgroup, the 16 waves split the rows), FiLM gradients are the row sums themselves
+// per-channel fold of the row sums (double; FC = 16 channels per 1024-thread workgroup, its 64 row lanes split the rows), FiLM gradients are the row sums themselves
 __global__ __launch_bounds__(1024) void bn_film_bwd_fold_kernel(const float* __restrict__ sums, int NS, int S, int C, float* __restrict__ dweight,
                                                                 float* __restrict__ dbias, float* __restrict__ dpg, float* __restrict__ dpb, float* __restrict__ dqg,
                                                                 float* __restrict__ dqb) {

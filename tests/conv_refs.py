@@ -377,13 +377,15 @@ def conv_as_tables(cv):
 
 
 # ------------------------------------------------------------------------------------------------------------------ mode_bn_prepare_partials
-def bn_partials_ref(psum, psq, count, w, b, eps, momentum, running_mean, running_var, nbt):
+def bn_partials_ref(psum, psq, count, w, b, eps, momentum, running_mean, running_var, nbt, e_sum=0.0, e_sq=0.0):
     """The fold of partial sums [rows, C] and nn.BatchNorm2d's bookkeeping in fp64 (include/mode_hip.h: mode_bn_prepare / mode_bn_prepare_partials).
     Returns (ref dict, bound dict).  Bounds, u = 2^-23 (a rounding to fp32 errs by at most u / 2 of the value; `n u` stands for up to 2 n roundings):
       mean, var      the kernel folds in double: one rounding to fp32 each -> u |mean|, u |var| + 2^-40 (sum sq / count) for the cancellation in double
       invstd         from the fp32 var (u |var| through d invstd / d var = invstd / (2 (var + eps))), + the sum, the square root, the division
       scale          + one product; shift: the fp32 mean times scale's error, + the product and the difference
-      running stats  (1 - f) rounds, two products (three for the unbiased variance), one sum, on top of the fp32 mean / var."""
+      running stats  (1 - f) rounds, two products (three for the unbiased variance), one sum, on top of the fp32 mean / var.
+    e_sum / e_sq [C]: what the column totals of the partials the kernel folds may be off by (0: the partials are given, as here; bn_refs.stats_ref: the
+    fp32 row sums of mode_bn_prepare's own pass); they enter mean as e_sum / count and var as e_sq / count + (2 |mean| + e_sum / count) e_sum / count."""
     ps, pq = f64(psum), f64(psq)
     m = ps.sum(0) / count
     ex2 = pq.sum(0) / count
@@ -398,7 +400,8 @@ def bn_partials_ref(psum, psq, count, w, b, eps, momentum, running_mean, running
     unbias = count / max(count - 1.0, 1.0)
     rm, rv = f64(running_mean), f64(running_var)
     ref = dict(mean=m, var=v, invstd=inv, scale=sc, shift=sh, running_mean=rm * (1 - f) + m * f, running_var=rv * (1 - f) + v * unbias * f)
-    b_m, b_v = U * m.abs(), U * v + 2.0 ** -40 * (ex2 + m * m)
+    e_m = e_sum / count
+    b_m, b_v = U * m.abs() + e_m, U * v + 2.0 ** -40 * (ex2 + m * m) + e_sq / count + (2 * m.abs() + e_m) * e_m
     b_inv = inv * (0.5 * b_v / (v + epsd)) + 2 * U * inv
     b_sc = wd.abs() * b_inv + U * sc.abs()
     b_sh = b_m * sc.abs() + m.abs() * b_sc + 2 * U * (bd.abs() + (m * sc).abs())
