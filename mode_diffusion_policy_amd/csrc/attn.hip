@@ -6,8 +6,9 @@
 //   * the probabilities are already laid out as the B operand of  O^T = V^T P^T  (k-slots 4..7 of each lane group are zero
 //     padding), so P never moves between lanes; each lane then owns 4 consecutive head-dim outputs of one query -> 8-byte stores.
 // fp32 parity mode: a plain VALU kernel with the same math (one wave per (sample, head), LDS-staged q/k/v).
-#include <type_traits>
-
+// Backward (training, both dtypes): attn_bwd_kernel below, one 256-thread workgroup per (sample, head), in an MFMA and a VALU form of its matrix products.
+// Both entry points hand T > 16 to attn_long.hip.  attn_core.h holds the bf16 forward's wave body (shared with qkv_attn.hip), the LDS layouts of the backward kernels and
+// the backward phases shared with attn_long.hip (staging, gain partials, norm backward, write-out).
 #include "mode_common.h"
 #include "attn_core.h"
 
@@ -95,72 +96,27 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_kernel(const T2* __restrict__
                                                        float* __restrict__ dgk_part, int B, int T, int H, int HD, float eps, uint32_t seed,
                                                        uint32_t thresh, float inv_keep, float* __restrict__ dbias_part) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int HP = HD + 1;                               // padded row (bank-conflict-free column walks)
-  // v / dO (and dV, which replaces v) are kept in the INPUT dtype: for bf16 that is exact (the inputs are bf16, dV is rounded to bf16 on
-  // its way out anyway) and brings the workgroup under 40 KB of LDS — four workgroups per CU, the whole grid of B*H = 1024 in one round
-  typedef typename std::conditional<sizeof(T2) == 2, uint16_t, float>::type TV;
-  const int HV = sizeof(T2) == 2 ? HD + 8 : HD + 1;     // row stride of the TV tiles (bf16: 16-byte aligned rows, 4 banks of skew)
-  float* sq = reinterpret_cast<float*>(smem);          // raw q  [T][HP]
-  float* sk = sq + T * HP;                             // raw k
-  float* sqh = sk + T * HP;                            // q_hat, later d q_hat
-  float* skh = sqh + T * HP;                           // k_hat, later d k_hat
-  // probability-sized tiles are zero-padded to 16 x 16 (row stride 16): branch-free 16-term dot products, float4 broadcast reads
-  float* sp = skh + T * HP + ((4 - ((4 * T * HP) & 3)) & 3);   // P [query][key]                    (16-byte aligned)
-  float* sds = sp + 256;                               // dPd, then dS   [query][key]
-  float* spdT = sds + 256;                             // dropped probabilities, transposed [key][query]   (VALU form only: the MFMA form keeps them in sp)
-  float* sdsT = MF ? sds + 256 : spdT + 256;           // dS transposed                     [key][query]
-  float* srq = sdsT + 256;                             // 1/norm per token (q)              [T]
-  float* srk = srq + T;                                // (k)
-  float* sgq = srk + T + ((4 - ((2 * T) & 3)) & 3);    // qk-norm gains [HD] (read per element in three phases: from LDS, not through the vector cache)
-  float* sgk = sgq + HD;
-  TV* sv = reinterpret_cast<TV*>(sgk + HD);            // v, later dV   [T][HV]   (16-byte aligned: HD % 4 == 0)
-  TV* sdo = sv + T * HV;                               // dO
-  auto tvf = [](TV x) -> float { if constexpr (sizeof(TV) == 2) return bf16_bits_to_f32(x); else return x; };
+  // v / dO (and dV, which replaces v) in the INPUT dtype: for bf16 that is exact (the inputs are bf16, dV is rounded to bf16 on its way out anyway) and
+  // brings the workgroup under 40 KB of LDS (attn_core.h: AttnBwdLds)
+  typedef attn_tv_t<T2> TV;
+  const AttnBwdLds L(T, HD, sizeof(T2), MF);
+  const int HP = L.HP, HV = L.HV;
+  float *sq = lds_at<float>(smem, L.q), *sk = lds_at<float>(smem, L.k), *sqh = lds_at<float>(smem, L.qh), *skh = lds_at<float>(smem, L.kh);
+  float *sp = lds_at<float>(smem, L.p), *sds = lds_at<float>(smem, L.ds), *spdT = lds_at<float>(smem, L.pdT), *sdsT = lds_at<float>(smem, L.dsT);
+  float *srq = lds_at<float>(smem, L.rq), *srk = lds_at<float>(smem, L.rk), *sgq = lds_at<float>(smem, L.gq), *sgk = lds_at<float>(smem, L.gk);
+  TV *sv = lds_at<TV>(smem, L.v), *sdo = lds_at<TV>(smem, L.dO);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int prob = blockIdx.x, b = prob / H, h = prob % H, D = H * HD;
   const long ld = 3L * D;
-  // 16-byte global loads, all four tensors of a thread's chunk requested before the first use (one memory round trip per workgroup —
-  // a per-element loop serialises T*HD/256 dependent round trips and was 80 % of this kernel's time)
-  constexpr int VE = 16 / (int)sizeof(T2);              // elements per 16-byte chunk
-  const int cpr = HD / VE;                              // chunks per token row
-  auto unpack = [&](const uint4& u, float* dst) {
-    if constexpr (sizeof(T2) == 2) {
-      const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { dst[2 * j] = bf16_bits_to_f32(w[j] & 0xffff); dst[2 * j + 1] = bf16_bits_to_f32(w[j] >> 16); }
-    } else {
-      dst[0] = __uint_as_float(u.x); dst[1] = __uint_as_float(u.y); dst[2] = __uint_as_float(u.z); dst[3] = __uint_as_float(u.w);
-    }
-  };
-  for (int i = tid; i < (MF ? 3 : 4) * 256; i += 256) sp[i] = 0.f;   // zero padding of the 16x16 tiles (written sparsely below)
+  for (int i = tid; i < L.ntile * 256; i += 256) sp[i] = 0.f;   // zero padding of the 16x16 tiles (written sparsely below)
   for (int d = tid; d < HD; d += 256) { sgq[d] = qg[d]; sgk[d] = kg[d]; }
-  for (int i = tid; i < T * cpr; i += 256) {
-    const int t = i / cpr, d = (i % cpr) * VE;
-    const T2* r = qkv + ((long)b * T + t) * ld + h * HD + d;
-    const uint4 uq = *reinterpret_cast<const uint4*>(r), uk = *reinterpret_cast<const uint4*>(r + D), uv = *reinterpret_cast<const uint4*>(r + 2 * D);
-    const uint4 ud = *reinterpret_cast<const uint4*>(dY + ((long)b * T + t) * D + h * HD + d);
-    float fq_[VE], fk_[VE];
-    unpack(uq, fq_); unpack(uk, fk_);
-#pragma unroll
-    for (int j = 0; j < VE; ++j) { sq[t * HP + d + j] = fq_[j]; sk[t * HP + d + j] = fk_[j]; }
-    if constexpr (sizeof(T2) == 2) {                    // bf16: the 16-byte chunks go to LDS as they are
-      *reinterpret_cast<uint4*>(sv + t * HV + d) = uv; *reinterpret_cast<uint4*>(sdo + t * HV + d) = ud;
-    } else {
-      float fv_[VE], fd_[VE];
-      unpack(uv, fv_); unpack(ud, fd_);
-#pragma unroll
-      for (int j = 0; j < VE; ++j) { sv[t * HV + d + j] = fv_[j]; sdo[t * HV + d + j] = fd_[j]; }
-    }
-  }
+  attn_bwd_stage<T2>(qkv + (long)b * T * ld + h * HD, dY + (long)b * T * D + h * HD, ld, D, T, HD, sq, sk, HP, sv, sdo, HV, tid);
   __syncthreads();
   for (int t = wave; t < T; t += 4) {                  // one wave per token: row norms
     float a = 0.f, c = 0.f;
     for (int d = lane; d < HD; d += 64) { a += sq[t * HP + d] * sq[t * HP + d]; c += sk[t * HP + d] * sk[t * HP + d]; }
     a = wave_sum(a); c = wave_sum(c);
-    if (lane == 0) {
-      srq[t] = 1.0f / fmaxf(sqrtf(a) * rsqrtf((float)HD), eps);
-      srk[t] = 1.0f / fmaxf(sqrtf(c) * rsqrtf((float)HD), eps);
-    }
+    if (lane == 0) { srq[t] = attn_bwd_rnorm(a, HD, eps); srk[t] = attn_bwd_rnorm(c, HD, eps); }
   }
   __syncthreads();
   for (int i = tid; i < T * HD; i += 256) {
@@ -190,7 +146,7 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_kernel(const T2* __restrict__
         for (int d0 = 0; d0 < HD; d0 += 16) {
           float a[4], bv[4];
 #pragma unroll
-          for (int u = 0; u < 4; ++u) { a[u] = tvf(oa[d0 + 4 * u]); bv[u] = tvf(vb[d0 + 4 * u]); }
+          for (int u = 0; u < 4; ++u) { a[u] = attn_tvf(oa[d0 + 4 * u]); bv[u] = attn_tvf(vb[d0 + 4 * u]); }
 #pragma unroll
           for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], bv[u], acc, 0, 0, 0);
         }
@@ -221,9 +177,9 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_kernel(const T2* __restrict__
       for (int j = 0; j < 4; ++j) { const int kk = min(k0 + j, T - 1); kr[j] = skh + kk * HP; vr[j] = sv + kk * HV; }
 #pragma unroll 4
       for (int d = part; d < HD; d += 4) {                  // lanes interleave d: consecutive banks; unrolled: 40 LDS reads in flight
-        const float qv = qr[d], ov = tvf(orow[d]);
+        const float qv = qr[d], ov = attn_tvf(orow[d]);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { sa[j] = fmaf(qv, kr[j][d], sa[j]); pa[j] = fmaf(ov, tvf(vr[j][d]), pa[j]); }
+        for (int j = 0; j < 4; ++j) { sa[j] = fmaf(qv, kr[j][d], sa[j]); pa[j] = fmaf(ov, attn_tvf(vr[j][d]), pa[j]); }
       }
     }
 #pragma unroll
@@ -286,7 +242,7 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_kernel(const T2* __restrict__
         for (int k0 = 0; k0 < 16; k0 += 4) {
           const int k = k0 + fq, kc = min(k, T - 1);
           const float a_dq = sdsT[k * 16 + fr], a_dk = sds[k * 16 + fr], a_dv = sp[k * 16 + fr];
-          const float b_k = skh[kc * HP + d], b_q = sqh[kc * HP + d], b_o = tvf(sdo[kc * HV + d]);
+          const float b_k = skh[kc * HP + d], b_q = sqh[kc * HP + d], b_o = attn_tvf(sdo[kc * HV + d]);
           rq[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_dq, b_k, rq[u], 0, 0, 0);
           rk[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_dk, b_q, rk[u], 0, 0, 0);
           rv[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_dv, b_o, rv[u], 0, 0, 0);
@@ -335,7 +291,7 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_kernel(const T2* __restrict__
     } else if (act) {
       float oc[TMAX], qc[TMAX];
 #pragma unroll
-      for (int u = 0; u < TMAX; ++u) { oc[u] = u < T ? tvf(sdo[u * HV + d]) : 0.f; qc[u] = u < T ? sqh[u * HP + d] : 0.f; }
+      for (int u = 0; u < TMAX; ++u) { oc[u] = u < T ? attn_tvf(sdo[u * HV + d]) : 0.f; qc[u] = u < T ? sqh[u * HP + d] : 0.f; }
 #pragma unroll
       for (int j = 0; j < TMAX; ++j) { o0[j] = dot16(spdT + j * 16, oc); o1[j] = dot16(sdsT + j * 16, qc); }
     }
@@ -352,75 +308,14 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_kernel(const T2* __restrict__
     }
   }
   __syncthreads();
-  for (int d = tid; d < HD; d += 256) {                 // gain-gradient partials of this (sample, head)
-    float a = 0.f, c = 0.f;
-    for (int t = 0; t < T; ++t) { a += sqh[t * HP + d] * sq[t * HP + d] * srq[t]; c += skh[t * HP + d] * sk[t * HP + d] * srk[t]; }
-    dgq_part[(long)prob * HD + d] = a; dgk_part[(long)prob * HD + d] = c;
-  }
+  const AttnRawLds raw{sq, sk, sgq, sgk, HP};
+  attn_bwd_gain_partials(raw, sqh, skh, HP, srq, srk, dgq_part + (long)prob * HD, dgk_part + (long)prob * HD, T, HD, tid);
   __syncthreads();
-  // qk-RMSNorm backward (x_hat = x * r * g): dx = g*dxh*r - x * <g*dxh, x> * r^3 / HD  (clamped rows: dx = g*dxh/eps); in place over d x_hat
-  {                                                     // 16 lanes per token: all T tokens in one pass, 4-step xor-shuffle reductions
-    const int t = tid >> 4, l16 = tid & 15;
-    float cq = 0.f, ck = 0.f;
-    if (t < T) {
-#pragma unroll 4
-      for (int d = l16; d < HD; d += 16) { cq += sgq[d] * sqh[t * HP + d] * sq[t * HP + d]; ck += sgk[d] * skh[t * HP + d] * sk[t * HP + d]; }
-    }
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) { cq += __shfl_xor(cq, o, 64); ck += __shfl_xor(ck, o, 64); }
-    if (t < T) {
-      const float rq = srq[t], rk = srk[t];
-      const bool clq = rq >= 1.0f / eps, clk = rk >= 1.0f / eps;
-      const float cqs = clq ? 0.f : cq * rq * rq * rq / (float)HD, cks = clk ? 0.f : ck * rk * rk * rk / (float)HD;   // per token, not per element (a division each)
-#pragma unroll 4
-      for (int d = l16; d < HD; d += 16) {
-        sqh[t * HP + d] = sgq[d] * sqh[t * HP + d] * rq - sq[t * HP + d] * cqs;
-        skh[t * HP + d] = sgk[d] * skh[t * HP + d] * rk - sk[t * HP + d] * cks;
-      }
-    }
-  }
+  attn_bwd_norm_token(raw, sqh, skh, HP, srq, srk, tid >> 4, tid & 15, T, HD, eps);   // all T <= 16 tokens in one pass
   __syncthreads();
-  auto pack = [&](const float* src) -> uint4 {
-    uint4 u;
-    if constexpr (sizeof(T2) == 2) {
-      u.x = pack_bf16x2(src[0], src[1]); u.y = pack_bf16x2(src[2], src[3]); u.z = pack_bf16x2(src[4], src[5]); u.w = pack_bf16x2(src[6], src[7]);
-    } else {
-      u.x = __float_as_uint(src[0]); u.y = __float_as_uint(src[1]); u.z = __float_as_uint(src[2]); u.w = __float_as_uint(src[3]);
-    }
-    return u;
-  };
-  if (dbias_part) {
-    // bias gradient of the packed QKV projection = column sums of dqkv: this sample's share [3 D] (summed over its T tokens, from the values AS STORED - bf16-
-    // rounded on the bf16 path, like the separate column sum over dqkv did); the caller adds the B rows with one small column sum instead of re-reading dqkv
-    for (int c = tid; c < 3 * HD; c += 256) {
-      const int which = c / HD, d = c - which * HD;
-      float sacc = 0.f;
-      for (int t = 0; t < T; ++t) {
-        float v = which == 0 ? sqh[t * HP + d] : which == 1 ? skh[t * HP + d] : tvf(sv[t * HV + d]);
-        if constexpr (sizeof(T2) == 2) v = bf16_bits_to_f32(f32_to_bf16_bits(v));
-        sacc += v;
-      }
-      dbias_part[(long)b * 3 * D + (long)which * D + h * HD + d] = sacc;
-    }
-  }
-  for (int i = tid; i < T * cpr; i += 256) {            // 16-byte stores of dq | dk | dv
-    const int t = i / cpr, d = (i % cpr) * VE;
-    T2* o = dqkv + ((long)b * T + t) * ld + h * HD + d;
-    *reinterpret_cast<uint4*>(o) = pack(sqh + t * HP + d);
-    *reinterpret_cast<uint4*>(o + D) = pack(skh + t * HP + d);
-    if constexpr (sizeof(T2) == 2) *reinterpret_cast<uint4*>(o + 2 * D) = *reinterpret_cast<const uint4*>(sv + t * HV + d);
-    else *reinterpret_cast<uint4*>(o + 2 * D) = pack(reinterpret_cast<const float*>(sv) + t * HV + d);
-  }
+  attn_bwd_write<T2>(sqh, skh, HP, sv, HV, dqkv + (long)b * T * ld + h * HD, dbias_part ? dbias_part + (long)b * 3 * D + h * HD : nullptr, ld, D, T, HD, tid);
 }
 
-}  // namespace mode
-
-namespace mode {
-// attn_long.hip: the kernels for 16 < T <= 64 (taken by both entry points below when T > 16)
-int attn_long_fwd_launch(const void* qkv, const float* qg, const float* kg, void* y, int dtype, int B, int T, int H, int HD, float eps, uint32_t seed,
-                         uint32_t thresh, float inv_keep, hipStream_t s);
-int attn_long_bwd_launch(const void* qkv, const float* qg, const float* kg, const void* dy, void* dqkv, float* dgq_partial, float* dgk_partial, int dtype,
-                         int B, int T, int H, int HD, float eps, uint32_t seed, uint32_t thresh, float inv_keep, float* dbias_partial, hipStream_t s);
 }  // namespace mode
 
 using namespace mode;
@@ -434,18 +329,14 @@ extern "C" int mode_attn_block_fwd(const void* qkv, const float* q_gain, const f
   hipStream_t s = (hipStream_t)stream;
   if (T > 16) return attn_long_fwd_launch(qkv, q_gain, k_gain, y, dtype, B, T, H, head_dim, eps, seed, th, ik, s);
   if (dtype == MODE_BF16) {
-    if (T > 16 || head_dim % 16 != 0 || head_dim > 128) return MODE_ERR_UNSUPPORTED;
+    if (head_dim <= 0 || head_dim % 16 != 0 || head_dim > 128) return MODE_ERR_UNSUPPORTED;
     const dim3 grid((B * H + 3) / 4), blk(256);
     const uint16_t* in = (const uint16_t*)qkv; uint16_t* out = (uint16_t*)y;
-    switch ((head_dim + 31) / 32) {
-      case 1: hipLaunchKernelGGL(attn_bf16_kernel<1>, grid, blk, 0, s, in, q_gain, k_gain, out, B, T, H, head_dim, eps, seed, th, ik); break;
-      case 2: hipLaunchKernelGGL(attn_bf16_kernel<2>, grid, blk, 0, s, in, q_gain, k_gain, out, B, T, H, head_dim, eps, seed, th, ik); break;
-      case 3: hipLaunchKernelGGL(attn_bf16_kernel<3>, grid, blk, 0, s, in, q_gain, k_gain, out, B, T, H, head_dim, eps, seed, th, ik); break;
-      case 4: hipLaunchKernelGGL(attn_bf16_kernel<4>, grid, blk, 0, s, in, q_gain, k_gain, out, B, T, H, head_dim, eps, seed, th, ik); break;
-      default: return MODE_ERR_UNSUPPORTED;
-    }
+#define MODE_ASF(NK) hipLaunchKernelGGL(attn_bf16_kernel<NK>, grid, blk, 0, s, in, q_gain, k_gain, out, B, T, H, head_dim, eps, seed, th, ik)
+    MODE_ATTN_NKS_DISPATCH(head_dim, MODE_ASF)
+#undef MODE_ASF
   } else {
-    const size_t lds = ((size_t)3 * T * head_dim + (size_t)T * T) * 4;
+    const size_t lds = ((size_t)3 * T * head_dim + (size_t)T * T) * 4;   // attn_f32_kernel's carve-up (kept by hand: see the LDS layouts in attn_core.h)
     if (lds > 64 * 1024) return MODE_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(attn_f32_kernel, dim3(B * H), dim3(64), lds, s, (const float*)qkv, q_gain, k_gain, (float*)y, B, T, H, head_dim, eps, seed, th, ik);
   }
@@ -454,8 +345,7 @@ extern "C" int mode_attn_block_fwd(const void* qkv, const float* q_gain, const f
 }
 
 namespace mode {
-int g_attn_bwd_mfma = 1;   // "attn_bwd_mfma" option: 1 = the attention backward's matrix products on fp32 MFMA (head_dim % 16 == 0), 0 = the VALU form
-// dbias_partial (optional): [B][3 D] fp32, row b = sample b's share of the packed QKV bias gradient (dit_train.hip adds the rows)
+int g_attn_bwd_mfma = 1;
 int attn_block_bwd_launch(const void* qkv, const float* q_gain, const float* k_gain, const void* dy, void* dqkv, float* dgq_partial,
                           float* dgk_partial, int dtype, int B, int T, int H, int head_dim, float eps, uint32_t seed, float p_drop, float* dbias_partial,
                           void* stream) {
@@ -466,10 +356,9 @@ int attn_block_bwd_launch(const void* qkv, const float* q_gain, const float* k_g
     return attn_long_bwd_launch(qkv, q_gain, k_gain, dy, dqkv, dgq_partial, dgk_partial, dtype, B, T, H, head_dim, eps, seed, dropout_thresh(p_drop),
                                 1.0f / (1.0f - p_drop), dbias_partial, (hipStream_t)stream);
   const bool mf = head_dim % 16 == 0 && g_attn_bwd_mfma;
-  const size_t tiles = mf ? 3 : 4;                             // 16 x 16 coefficient tiles (the MFMA form needs no transposed copy of the dropped probabilities)
-  const size_t lds = dtype == MODE_BF16 ? ((size_t)4 * T * (head_dim + 1) + 4 + tiles * 256 + 2 * T + 4 + 2 * head_dim) * 4 + (size_t)2 * T * (head_dim + 8) * 2
-                                        : ((size_t)6 * T * (head_dim + 1) + 4 + tiles * 256 + 2 * T + 4 + 2 * head_dim) * 4;
-  if (lds > 64 * 1024 || head_dim > 128 || T > 16 || head_dim % (dtype == MODE_BF16 ? 8 : 4)) return MODE_ERR_UNSUPPORTED;
+  if (head_dim > 128 || head_dim % (dtype == MODE_BF16 ? 8 : 4)) return MODE_ERR_UNSUPPORTED;
+  const size_t lds = AttnBwdLds(T, head_dim, dtype == MODE_BF16 ? 2 : 4, mf).bytes;   // at most 54,784 bytes (fp32, T = 16, head_dim 128, VALU form)
+  if (lds > 64 * 1024) return MODE_ERR_UNSUPPORTED;
   const uint32_t th = dropout_thresh(p_drop); const float ik = 1.0f / (1.0f - p_drop);
   hipStream_t s = (hipStream_t)stream;
 #define MODE_ATTN_BWD(T2, MF) hipLaunchKernelGGL((attn_bwd_kernel<T2, MF>), dim3(B * H), dim3(256), lds, s, (const T2*)qkv, q_gain, k_gain, (const T2*)dy, (T2*)dqkv, \

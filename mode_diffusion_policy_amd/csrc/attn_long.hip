@@ -1,5 +1,6 @@
 // Causal attention for 16 < T <= 64 tokens per sample (action chunks longer than the 14-token default): selected inside mode_attn_block_fwd /
-// mode_attn_block_bwd / attn_block_bwd_launch when T > 16.  The tiny-T kernels (attn.hip, attn_core.h) stay as they are for T <= 16.
+// mode_attn_block_bwd / attn_block_bwd_launch when T > 16.  The tiny-T kernels (attn.hip, attn_core.h) stay as they are for T <= 16.  attn_core.h also
+// holds the LDS layouts of this file's fp32 forward and backward and the backward phases this file shares with attn.hip (staging, gain partials, norm backward, write-out).
 //
 // bf16 forward: one workgroup per (sample, head), one wave per 16-query tile (ceil(T/16) waves).  Wave w normalises rows 16w .. 16w+15 of q and k
 // exactly like attn_core.h's body (fragment loads, 4-lane-group shuffle reduction, one reciprocal per row), keeps its q_hat fragments in registers and
@@ -8,8 +9,6 @@
 // tile 2m+1 of the lane group's 4 keys): each lane ends up with 8 consecutive head dims of its query per accumulator register -> 16-byte stores.
 // fp32 parity forward and the backward (both dtypes): one 256-thread workgroup per (sample, head), everything staged in LDS, fp32 VALU math; the
 // backward keeps P and dS as lower triangles so that T = 64, head_dim = 128 in fp32 fits one CU's LDS.
-#include <type_traits>
-
 #include "mode_common.h"
 #include "attn_core.h"
 
@@ -52,7 +51,8 @@ __global__ __launch_bounds__(256) void attn_long_bf16_kernel(const uint16_t* __r
     tq_[ks] = *reinterpret_cast<const uint4*>(base + (long)rrow * ld + dg);
     tk_[ks] = *reinterpret_cast<const uint4*>(base + (long)rrow * ld + D + dg);
   }
-  // qk-RMSNorm on the fragments (attn_core.h's arithmetic: rows past T and dims past head_dim are zeros)
+  // qk-RMSNorm on the fragments: a copy of attn_wave_bf16's (attn_core.h) arithmetic, rows past T and dims past head_dim zeros.  Kept as a copy on purpose:
+  // sharing the body changed the register allocation of attn_bf16_kernel and of all qkv_attn_kernel instantiations
   float qf[NKS][8], kf[NKS][8];
   float qss = 0.f, kss = 0.f;
 #pragma unroll
@@ -172,11 +172,9 @@ __global__ __launch_bounds__(256) void attn_long_f32_kernel(const float* __restr
                                                             float* __restrict__ y, int T, int H, int HD, float eps, uint32_t seed, uint32_t thresh,
                                                             float inv_keep) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int HP = HD + 1, TP = T + 1;
-  float* sq = reinterpret_cast<float*>(smem);          // [T][HP]
-  float* sk = sq + T * HP;
-  float* sv = sk + T * HP;
-  float* sp = sv + T * HP;                             // [T][TP]
+  const AttnLongF32Lds L(T, HD);
+  const int HP = L.HP, TP = L.TP;
+  float *sq = lds_at<float>(smem, L.q), *sk = lds_at<float>(smem, L.k), *sv = lds_at<float>(smem, L.v), *sp = lds_at<float>(smem, L.p);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int prob = blockIdx.x, b = prob / H, h = prob % H, D = H * HD;
   const long ld = 3L * D;
@@ -234,61 +232,24 @@ __global__ __launch_bounds__(256) void attn_long_bwd_kernel(const T2* __restrict
                                                             float* __restrict__ dgk_part, int T, int H, int HD, float eps, uint32_t seed, uint32_t thresh,
                                                             float inv_keep, float* __restrict__ dbias_part) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef typename std::conditional<sizeof(T2) == 2, uint16_t, float>::type TV;
+  typedef attn_tv_t<T2> TV;
   constexpr int MAXE = kLongTMax * 128 / 256;           // outputs per thread and tensor at T = 64, head_dim = 128
-  const int HP = HD + 1;
-  const int HV = sizeof(T2) == 2 ? HD + 8 : HD + 1;
-  const int NTRI = T * (T + 1) / 2;
-  float* sqh = reinterpret_cast<float*>(smem);          // q_hat, later d q_hat, later dq       [T][HP]
-  float* skh = sqh + T * HP;                            // k_hat, later d k_hat, later dk
-  float* sP = skh + T * HP;                             // P, later Pd                          [tri]
-  float* sdS = sP + NTRI;                               // dPd, later dS                        [tri]
-  float* srq = sdS + NTRI;                              // 1/norm per token                     [T]
-  float* srk = srq + T;
-  const size_t tv_off = ((size_t)(2 * T * HP + 2 * NTRI + 2 * T) * 4 + 15) / 16 * 16;
-  TV* sv = reinterpret_cast<TV*>(smem + tv_off);        // v, later dV                          [T][HV]
-  TV* sdo = sv + T * HV;                                // dO
-  auto tvf = [](TV x) -> float { if constexpr (sizeof(TV) == 2) return bf16_bits_to_f32(x); else return x; };
-  auto ld2 = [](const T2* p_) -> float { if constexpr (sizeof(T2) == 2) return bf16_bits_to_f32(*p_); else return *p_; };
+  const AttnLongBwdLds L(T, HD, sizeof(T2));
+  const int HP = L.HP, HV = L.HV, NTRI = L.ntri;
+  float *sqh = lds_at<float>(smem, L.qh), *skh = lds_at<float>(smem, L.kh), *sP = lds_at<float>(smem, L.p), *sdS = lds_at<float>(smem, L.ds);
+  float *srq = lds_at<float>(smem, L.rq), *srk = lds_at<float>(smem, L.rk);
+  TV *sv = lds_at<TV>(smem, L.v), *sdo = lds_at<TV>(smem, L.dO);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int prob = blockIdx.x, b = prob / H, h = prob % H, D = H * HD;
   const long ld = 3L * D;
   const T2* qrow0 = qkv + (long)b * T * ld + h * HD;    // raw q of token t at qrow0 + t*ld, k at + D, v at + 2D
-  constexpr int VE = 16 / (int)sizeof(T2);
-  const int cpr = HD / VE;
-  auto unpack = [&](const uint4& u, float* dst) {
-    if constexpr (sizeof(T2) == 2) {
-      const uint32_t wd[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { dst[2 * j] = bf16_bits_to_f32(wd[j] & 0xffff); dst[2 * j + 1] = bf16_bits_to_f32(wd[j] >> 16); }
-    } else {
-      dst[0] = __uint_as_float(u.x); dst[1] = __uint_as_float(u.y); dst[2] = __uint_as_float(u.z); dst[3] = __uint_as_float(u.w);
-    }
-  };
-  for (int i = tid; i < T * cpr; i += 256) {
-    const int t = i / cpr, d = (i % cpr) * VE;
-    const T2* r = qrow0 + (long)t * ld + d;
-    const uint4 uq = *reinterpret_cast<const uint4*>(r), uk = *reinterpret_cast<const uint4*>(r + D), uv = *reinterpret_cast<const uint4*>(r + 2 * D);
-    const uint4 ud = *reinterpret_cast<const uint4*>(dY + ((long)b * T + t) * D + h * HD + d);
-    float fq_[VE], fk_[VE];
-    unpack(uq, fq_); unpack(uk, fk_);
-#pragma unroll
-    for (int j = 0; j < VE; ++j) { sqh[t * HP + d + j] = fq_[j]; skh[t * HP + d + j] = fk_[j]; }
-    if constexpr (sizeof(T2) == 2) {
-      *reinterpret_cast<uint4*>(sv + t * HV + d) = uv; *reinterpret_cast<uint4*>(sdo + t * HV + d) = ud;
-    } else {
-      float fv_[VE], fd_[VE];
-      unpack(uv, fv_); unpack(ud, fd_);
-#pragma unroll
-      for (int j = 0; j < VE; ++j) { sv[t * HV + d + j] = fv_[j]; sdo[t * HV + d + j] = fd_[j]; }
-    }
-  }
+  attn_bwd_stage<T2>(qrow0, dY + (long)b * T * D + h * HD, ld, D, T, HD, sqh, skh, HP, sv, sdo, HV, tid);   // raw q / k where q_hat / k_hat replace them
   __syncthreads();
   for (int t = wave; t < T; t += 4) {                   // row norms, then q_hat / k_hat in place
     float a = 0.f, c = 0.f;
     for (int d = lane; d < HD; d += 64) { a += sqh[t * HP + d] * sqh[t * HP + d]; c += skh[t * HP + d] * skh[t * HP + d]; }
     a = wave_sum(a); c = wave_sum(c);
-    const float rq = 1.0f / fmaxf(sqrtf(a) * rsqrtf((float)HD), eps), rk = 1.0f / fmaxf(sqrtf(c) * rsqrtf((float)HD), eps);
+    const float rq = attn_bwd_rnorm(a, HD, eps), rk = attn_bwd_rnorm(c, HD, eps);
     if (lane == 0) { srq[t] = rq; srk[t] = rk; }
     for (int d = lane; d < HD; d += 64) { sqh[t * HP + d] = sqh[t * HP + d] * rq * qg[d]; skh[t * HP + d] = skh[t * HP + d] * rk * kg[d]; }
   }
@@ -302,7 +263,7 @@ __global__ __launch_bounds__(256) void attn_long_bwd_kernel(const T2* __restrict
     float s = 0.f, dp = 0.f;
     for (int d = 0; d < HD; ++d) {
       s = fmaf(sqh[qi * HP + d], skh[ki * HP + d], s);
-      dp = fmaf(tvf(sdo[qi * HV + d]), tvf(sv[ki * HV + d]), dp);
+      dp = fmaf(attn_tvf(sdo[qi * HV + d]), attn_tvf(sv[ki * HV + d]), dp);
     }
     sP[i] = s * scale; sdS[i] = dp;
   }
@@ -339,7 +300,7 @@ __global__ __launch_bounds__(256) void attn_long_bwd_kernel(const T2* __restrict
         for (int i = t; i < T; ++i) {
           const int ti = tri_idx(i, t);
           c = fmaf(sdS[ti], sqh[i * HP + d], c);
-          v = fmaf(sP[ti], tvf(sdo[i * HV + d]), v);
+          v = fmaf(sP[ti], attn_tvf(sdo[i * HV + d]), v);
         }
         aq[u] = a; ak[u] = c;
         if constexpr (sizeof(TV) == 2) sv[t * HV + d] = f32_to_bf16_bits(v); else sv[t * HV + d] = v;
@@ -356,68 +317,12 @@ __global__ __launch_bounds__(256) void attn_long_bwd_kernel(const T2* __restrict
     }
   }
   __syncthreads();
-  for (int d = tid; d < HD; d += 256) {                 // gain-gradient partials of this (sample, head)
-    float a = 0.f, c = 0.f;
-    for (int t = 0; t < T; ++t) {
-      const T2* r = qrow0 + (long)t * ld + d;
-      a += sqh[t * HP + d] * ld2(r) * srq[t]; c += skh[t * HP + d] * ld2(r + D) * srk[t];
-    }
-    dgq_part[(long)prob * HD + d] = a; dgk_part[(long)prob * HD + d] = c;
-  }
+  const AttnRawGlobal<T2> raw{qrow0, ld, D, qg, kg};
+  attn_bwd_gain_partials(raw, sqh, skh, HP, srq, srk, dgq_part + (long)prob * HD, dgk_part + (long)prob * HD, T, HD, tid);
   __syncthreads();
-  // qk-RMSNorm backward (x_hat = x * r * g): dx = g*dxh*r - x * <g*dxh, x> * r^3 / HD  (clamped rows: dx = g*dxh*r); 16 lanes per token
-  for (int t0 = 0; t0 < T; t0 += 16) {
-    const int t = t0 + (tid >> 4), l16 = tid & 15;
-    float cq = 0.f, ck = 0.f;
-    if (t < T) {
-      for (int d = l16; d < HD; d += 16) {
-        const T2* r = qrow0 + (long)t * ld + d;
-        cq += qg[d] * sqh[t * HP + d] * ld2(r); ck += kg[d] * skh[t * HP + d] * ld2(r + D);
-      }
-    }
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) { cq += __shfl_xor(cq, o, 64); ck += __shfl_xor(ck, o, 64); }
-    if (t < T) {
-      const float rq = srq[t], rk = srk[t];
-      const bool clq = rq >= 1.0f / eps, clk = rk >= 1.0f / eps;
-      const float cqs = clq ? 0.f : cq * rq * rq * rq / (float)HD, cks = clk ? 0.f : ck * rk * rk * rk / (float)HD;
-      for (int d = l16; d < HD; d += 16) {
-        const T2* r = qrow0 + (long)t * ld + d;
-        sqh[t * HP + d] = qg[d] * sqh[t * HP + d] * rq - ld2(r) * cqs;
-        skh[t * HP + d] = kg[d] * skh[t * HP + d] * rk - ld2(r + D) * cks;
-      }
-    }
-  }
+  for (int t0 = 0; t0 < T; t0 += 16) attn_bwd_norm_token(raw, sqh, skh, HP, srq, srk, t0 + (tid >> 4), tid & 15, T, HD, eps);   // 16 tokens per pass
   __syncthreads();
-  auto pack = [&](const float* src) -> uint4 {
-    uint4 u;
-    if constexpr (sizeof(T2) == 2) {
-      u.x = pack_bf16x2(src[0], src[1]); u.y = pack_bf16x2(src[2], src[3]); u.z = pack_bf16x2(src[4], src[5]); u.w = pack_bf16x2(src[6], src[7]);
-    } else {
-      u.x = __float_as_uint(src[0]); u.y = __float_as_uint(src[1]); u.z = __float_as_uint(src[2]); u.w = __float_as_uint(src[3]);
-    }
-    return u;
-  };
-  if (dbias_part) {                                     // this sample's share of the packed QKV bias gradient, from the values as stored
-    for (int c = tid; c < 3 * HD; c += 256) {
-      const int which = c / HD, d = c - which * HD;
-      float sacc = 0.f;
-      for (int t = 0; t < T; ++t) {
-        float v = which == 0 ? sqh[t * HP + d] : which == 1 ? skh[t * HP + d] : tvf(sv[t * HV + d]);
-        if constexpr (sizeof(T2) == 2) v = bf16_bits_to_f32(f32_to_bf16_bits(v));
-        sacc += v;
-      }
-      dbias_part[(long)b * 3 * D + (long)which * D + h * HD + d] = sacc;
-    }
-  }
-  for (int i = tid; i < T * cpr; i += 256) {            // 16-byte stores of dq | dk | dv
-    const int t = i / cpr, d = (i % cpr) * VE;
-    T2* o = dqkv + ((long)b * T + t) * ld + h * HD + d;
-    *reinterpret_cast<uint4*>(o) = pack(sqh + t * HP + d);
-    *reinterpret_cast<uint4*>(o + D) = pack(skh + t * HP + d);
-    if constexpr (sizeof(T2) == 2) *reinterpret_cast<uint4*>(o + 2 * D) = *reinterpret_cast<const uint4*>(sv + t * HV + d);
-    else *reinterpret_cast<uint4*>(o + 2 * D) = pack(reinterpret_cast<const float*>(sv) + t * HV + d);
-  }
+  attn_bwd_write<T2>(sqh, skh, HP, sv, HV, dqkv + (long)b * T * ld + h * HD, dbias_part ? dbias_part + (long)b * 3 * D + h * HD : nullptr, ld, D, T, HD, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
@@ -435,19 +340,14 @@ int attn_long_fwd_launch(const void* qkv, const float* qg, const float* kg, void
   if (dtype == MODE_BF16) {
     if (HD % 16) return MODE_ERR_UNSUPPORTED;
     const int nt = (T + 15) / 16;
-    const int nks = (HD + 31) / 32;
-    const size_t lds = (size_t)nt * 16 * ((nks * 32 + 8) + (128 + 8)) * 2;
     const uint16_t* in = (const uint16_t*)qkv; uint16_t* out = (uint16_t*)y;
-#define MODE_ALF(NK) hipLaunchKernelGGL(attn_long_bf16_kernel<NK>, grid, dim3(64 * nt), lds, s, in, qg, kg, out, T, H, HD, eps, seed, thresh, inv_keep)
-    switch (nks) {
-      case 1: MODE_ALF(1); break;
-      case 2: MODE_ALF(2); break;
-      case 3: MODE_ALF(3); break;
-      default: MODE_ALF(4); break;
-    }
+    // attn_long_bf16_kernel<NK>'s carve-up (kept by hand: see the LDS layouts in attn_core.h)
+#define MODE_ALF(NK) \
+  hipLaunchKernelGGL(attn_long_bf16_kernel<NK>, grid, dim3(64 * nt), (size_t)nt * 16 * ((NK * 32 + 8) + (128 + 8)) * 2, s, in, qg, kg, out, T, H, HD, eps, seed, thresh, inv_keep)
+    MODE_ATTN_NKS_DISPATCH(HD, MODE_ALF)
 #undef MODE_ALF
   } else {
-    const size_t lds = ((size_t)3 * T * (HD + 1) + (size_t)T * (T + 1)) * 4;
+    const size_t lds = AttnLongF32Lds(T, HD).bytes;
     int rc = ensure_lds(reinterpret_cast<const void*>(attn_long_f32_kernel), lds, g_lds_f32_fwd);
     if (rc) return rc;
     hipLaunchKernelGGL(attn_long_f32_kernel, grid, dim3(256), lds, s, (const float*)qkv, qg, kg, (float*)y, T, H, HD, eps, seed, thresh, inv_keep);
@@ -459,9 +359,7 @@ int attn_long_fwd_launch(const void* qkv, const float* qg, const float* kg, void
 int attn_long_bwd_launch(const void* qkv, const float* qg, const float* kg, const void* dy, void* dqkv, float* dgq_partial, float* dgk_partial, int dtype,
                          int B, int T, int H, int HD, float eps, uint32_t seed, uint32_t thresh, float inv_keep, float* dbias_partial, hipStream_t s) {
   if (T > kLongTMax || HD <= 0 || HD > 128 || HD % (dtype == MODE_BF16 ? 8 : 4)) return MODE_ERR_UNSUPPORTED;
-  const size_t tri = (size_t)T * (T + 1) / 2;
-  const size_t f32b = ((size_t)2 * T * (HD + 1) + 2 * tri + 2 * T) * 4;
-  const size_t lds = (f32b + 15) / 16 * 16 + (dtype == MODE_BF16 ? (size_t)2 * T * (HD + 8) * 2 : (size_t)2 * T * (HD + 1) * 4);
+  const size_t lds = AttnLongBwdLds(T, HD, dtype == MODE_BF16 ? 2 : 4).bytes;   // at most 149,248 bytes (fp32, T = 64, head_dim 128)
   if (lds > (size_t)kLdsMax) return MODE_ERR_UNSUPPORTED;
   int rc;
 #define MODE_ALB(T2, ONCE)                                                                                                                                  \

@@ -2,6 +2,7 @@
 // 1 + 7*L kernels per denoise step, zero host synchronisation (the reference crosses device->host ~120 times per forward,
 // SURVEY.md §3.1), hipGraph-capture safe.
 #include "mode_common.h"
+#include "attn_core.h"   // g_attn_bwd_mfma
 
 #include <string.h>
 
@@ -27,7 +28,6 @@ extern int g_gemm_mid_rows;
 extern int g_gemm_mid_rows_rn;
 extern int g_tr_cfg;
 extern int g_bwd_coexec;
-extern int g_attn_bwd_mfma;   // attn.hip
 int g_train_dn_split = -1;   // "train_dn_split" option: 1 = the training forward cuts the expert down-projection into the inference chain's K-slices (bf16 slabs), 0 = one slab, -1 = by batch size (dit_train.hip: train_dn_split)
 int g_fuse_swiglu_bwd = 1;   // "fuse_swiglu_bwd" option: 1 = the training backward runs dH = dY W2 and the SwishGLU backward as one launch
 extern int g_conv_ns;

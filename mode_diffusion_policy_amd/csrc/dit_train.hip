@@ -6,6 +6,7 @@
 // dW = dy^T x as GEMM(A = dy^T, "W" = x^T) on operands produced by mode_transpose (per-expert 64-padded for the grouped GEMMs,
 // contracted with the K-group mode so one launch covers all experts; experts without tokens get exact zeros).
 #include "mode_common.h"
+#include "attn_core.h"   // attn_block_bwd_launch
 
 #include <string.h>
 
@@ -18,8 +19,6 @@ int rmsnorm_bwd_launch(const float* x, const float* g, const float* dy_a, const 
 int gemm_bf16_tr_swiglu_bwd_launch(const ModeGemmDesc* d, const void* P, void* dP, uint32_t seed, uint32_t thresh, float inv_keep, float* bsum, int* tile_offs,
                                    hipStream_t s);                                       // gemm_bf16_tr.hip
 extern int g_fuse_swiglu_bwd;                                                            // "fuse_swiglu_bwd" option (dit.hip)
-int attn_block_bwd_launch(const void* qkv, const float* q_gain, const float* k_gain, const void* dy, void* dqkv, float* dgq_partial, float* dgk_partial, int dtype, int B,
-                          int T, int H, int head_dim, float eps, uint32_t seed, float p_drop, float* dbias_partial, void* stream);   // attn.hip
 bool gemm_bf16_pptr_accepts(const ModeGemmDesc* d);                                      // gemm_bf16_pptr.hip: would mode_gemm take the ping-pong kernel?
 int gather_rows_bf16(const void* in, long ld_in, const int* rows, int n, int cols, void* out, long ld_out, hipStream_t s);   // gemm_bf16_pptr.hip
 int down_proj_split(int dt, int K);                                                      // dit.hip: K-slices of the expert down-projection (bf16 slabs)
