@@ -1281,6 +1281,75 @@ typedef struct ModeFramePrepDesc {
 } ModeFramePrepDesc;
 int mode_frames_preprocess(const ModeFramePrepDesc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Device-resident episode store -> the training batch of step t (csrc/data_stream.hip; data.EpisodeStore, data.WindowStream).
+ * An addition to ABI 13: new structs and exports, nothing existing changes.
+ *
+ * Store (read-only): E episodes, episode e the rows [ep_begin[e], ep_begin[e + 1]) of actions [S, A] fp32, L_e >= 1 of them; goals [E, G] fp32.
+ * A window is W consecutive action rows starting at step p of episode e.  The starts are numbered episode by episode:
+ *   n_e = L_e (pad="hold": every step starts a window) | max(0, L_e - W + 1) (pad="none": only windows inside the episode), the caller's choice
+ *   starts [E + 1] int32 = the prefix sums of n_e, starts[0] = 0, starts[E] = n_total (1 <= n_total <= S < 2^31)
+ * Sample j (0 <= j < B) of step t with stream seed s, every product and sum of the keys in uint32 arithmetic modulo 2^32 (lowbias32 = hash_u32
+ * and mode_stream_seed of csrc/mode_common.h):
+ *   k  = mode_stream_seed(s, t)            g = ((uint64) lowbias32(k ^ j) * n_total) >> 32                 i.i.d. uniform over the starts,
+ *                                                                                                          with replacement
+ *   e  = the largest index with starts[e] <= g (binary search: lo = 0, hi = E; mid = (lo + hi) / 2; starts[mid] <= g ? lo = mid : hi = mid,
+ *        while hi - lo > 1; an episode without starts is never found), p = g - starts[e]
+ *   index[j] = ep_begin[e] + p,  episode[j] = e,  last = ep_begin[e + 1] - 1
+ *   row w < W reads store row r_w = min(index[j] + w, last);  action_mask[j][w] = index[j] + w <= last ? 1.0f : 0.0f
+ *   actions[j][w][a]  = (x - lo[a]) * scale[a] - 1 with x = actions[r_w][a]: one difference, one product, one difference, each rounded to fp32,
+ *                       unfused; lo == scale == NULL: the bits of x
+ *   latent_goal[j][i] = goals[e][i], bits copied
+ *   noise[j][w * A + a] = z(s_j, t, w * A + a), the noise stream of mode_env_gather_noise above (ABI 13) with s_j = s + 1 + j * 0x9E3779B9
+ *   u[j]  (fp64)      = ((lowbias32(k2 ^ j) >> 8) + 0.5) * 2^-24, k2 = mode_stream_seed(s + 2, t): exact in fp64, strictly inside (0, 1)
+ *   shifts[q][j][c]   = ((uint64) lowbias32(k3 ^ (4 j + 2 q + c)) * (2 shift_pad[q] + 1)) >> 32, k3 = mode_stream_seed(s + 3, t); camera q, c = 0: sx,
+ *                       c = 1: sy - the [B, 2] table mode_frames_preprocess takes for T = 1
+ * Before it is used as an address every index is clamped into its table: g into [0, n_total), e into [0, E), ep_begin[e] and last into [0, S),
+ * index[j] into [ep_begin[e], last] (an index never reads outside the store, whatever the tables hold).  Row j is a function of (s, t, j) and the
+ * store only: not of B, the grid, or the order in which steps are asked for.  One launch, B workgroups, plain vector stores, no atomics.
+ * noise, u and either shifts table may be NULL (not written).  With frames, index is the `rows` of mode_frames_preprocess on the store's
+ * [S, H, W, 3] uint8 frames (T = 1, src_stride = H * W * 3, num_envs = S), so a batch is two launches with cameras and one without.
+ *
+ * Before any launch, outputs untouched: MODE_ERR_BAD_ARG for a NULL descriptor or required pointer (actions, ep_begin, starts, goals, out_actions,
+ * action_mask, latent_goal, index, episode), lo without scale or scale without lo, a non-positive S, E, A, G, W, B or n_total, n_total > S, E > S,
+ * shift_pad[q] outside 0..16384, a shifts table with shift_pad[q] == 0; MODE_ERR_UNSUPPORTED for B > 65535, W * A > 4096, G > 4096.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct ModeDataStreamDesc {
+  const float* actions;                  /* [S, A] */
+  const int32_t* ep_begin;               /* [E + 1] */
+  const int32_t* starts;                 /* [E + 1] prefix sums of n_e */
+  const float* goals;                    /* [E, G] */
+  const float* lo; const float* scale;   /* [A] each, or both NULL: no normalisation */
+  int32_t S, E, A, G, W, B;
+  int32_t n_total;                       /* = starts[E]; which n_e the caller summed decides the padding mode, the mask follows from ep_begin */  uint32_t seed, step;
+  float* out_actions;                    /* [B, W, A] */
+  float* action_mask;                    /* [B, W] */
+  float* latent_goal;                    /* [B, G] */
+  int32_t* index; int32_t* episode;      /* [B] each */
+  float* noise;                          /* [B, W, A] or NULL */
+  double* u;                             /* [B] or NULL */
+  int32_t* shifts[2];                    /* [B, 2] each or NULL */
+  int32_t shift_pad[2];
+} ModeDataStreamDesc;
+int mode_data_sample_windows(const ModeDataStreamDesc* d, void* stream);
+
+/* mode_edm_loss with a step mask and sample weights (GCDenoiser.loss(action_mask=, sample_weight=)).  An addition to ABI 13: a new export, nothing
+ * existing changes.  F, action, noise [B, W, A], sigma [B]; d[b][w][a] = F - target with mode_edm_loss's target and scalings (the same
+ * expressions).  mask [B, W] or NULL, weight [B] or NULL, an absent factor is 1; a value that is not > 0 (zero, negative, NaN) counts as 0:
+ *   m[b][w] = mask > 0 ? mask : 0,  wt[b] = weight > 0 ? weight : 0,  c[b][w] = wt[b] * m[b][w],  den = A * sum_b wt[b] * M_b,  M_b = sum_w m[b][w]
+ *   loss          = sum_b wt[b] * S_b / den,   S_b = sum_w m[b][w] * sum_a d^2          (den == 0: loss = 0)
+ *   dF[b][w][a]   = c > 0 && den > 0 ? ((2 * c) / den) * d : +0.0f                      (so F may be non-finite wherever c = 0)
+ *   per_sample[b] = M_b > 0 ? S_b / (A * M_b) : 0                                       (NULL = not written; the sample's own masked mean, no weight)
+ * Summation order, fixed by (B, W, A); one workgroup of 16 waves, wave v owns the samples b = v, v + 16, ... in ascending order:
+ *   M_b: lane l adds m[b][w] for w = l, l + 64, ... ascending, then the 64 lane sums are added by the xor butterfly 32, 16, 8, 4, 2, 1
+ *   S_b: lane l accumulates acc = fma(m[b][w], d * d, acc) (d * d rounded first) over the elements i = w * A + a = l, l + 64, ... ascending with
+ *        m > 0 (others are skipped, not multiplied), then the same butterfly
+ *   wave v: cs_v = fma(wt[b], M_b, cs_v) and t_v = fma(wt[b], S_b, t_v) over its samples with wt[b] > 0, ascending; sum of c = cs_0 + ... + cs_15 and
+ *   sum of wt S = t_0 + ... + t_15, each added ascending v; den = (float) A * (sum of c); loss = (sum of wt S) / den.
+ * MODE_ERR_BAD_ARG before any launch for a NULL F, action, noise, sigma, loss or dF or non-positive B, W, A. */
+int mode_edm_loss_masked(const float* F, const float* action, const float* noise, const float* sigma, float sigma_data, int B, int W, int A,
+                         const float* mask, const float* weight, float* loss, float* dF, float* per_sample, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

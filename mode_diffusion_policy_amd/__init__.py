@@ -8,7 +8,9 @@ from .perceptual_encoders import (FiLMResNet18Policy, FiLMResNet34Policy, FiLMRe
                                   embed_visual_obs)
 from .lora import LoraAdapter  # noqa: F401
 from .camera import CLIP_MEAN, CLIP_STD, CameraTransform, preprocess_cameras  # noqa: F401
+from . import data  # noqa: F401
+from .data import EpisodeStore, WindowStream  # noqa: F401
 
 __all__ = ["MoDeDiT", "NoiseBlockMoE", "GCDenoiser", "sample_ddim", "get_sigmas_exponential", "diffusion_loss", "training_step", "AdvancedLangEmbeddingBuffer",
            "FiLMResNet18Policy", "FiLMResNet34Policy", "FiLMResNet50Policy", "ResNetEncoderWithFiLM", "embed_visual_obs",
-           "CameraTransform", "preprocess_cameras", "CLIP_MEAN", "CLIP_STD", "LoraAdapter"]
+           "CameraTransform", "preprocess_cameras", "CLIP_MEAN", "CLIP_STD", "LoraAdapter", "data", "EpisodeStore", "WindowStream"]

@@ -216,6 +216,14 @@ class ModeFramePrepDesc(C.Structure):
     _fields_ = [("rows", c_vp), ("m_b", c_i32), ("num_envs", c_i32), ("cam", ModeFramePrepCam * 2)]
 
 
+class ModeDataStreamDesc(C.Structure):
+    """mode_data_sample_windows (include/mode_hip.h, an addition to ABI 13): the store's tables, the draw's (seed, step) and the batch's outputs."""
+    _fields_ = [("actions", c_vp), ("ep_begin", c_vp), ("starts", c_vp), ("goals", c_vp), ("lo", c_vp), ("scale", c_vp), ("S", c_i32), ("E", c_i32),
+                ("A", c_i32), ("G", c_i32), ("W", c_i32), ("B", c_i32), ("n_total", c_i32), ("seed", c_u32), ("step", c_u32), ("out_actions", c_vp),
+                ("action_mask", c_vp), ("latent_goal", c_vp), ("index", c_vp), ("episode", c_vp), ("noise", c_vp), ("u", c_vp), ("shifts", c_vp * 2),
+                ("shift_pad", c_i32 * 2)]
+
+
 MODE_GRAD_CHUNK = 16384
 
 
@@ -362,6 +370,8 @@ PROTOTYPES = {
     "mode_head_ddim_guided_fwd": (C.c_int, [P(ModeHeadGuidedDesc), c_vp]),
     "mode_dit_forward_guided": (C.c_int, [P(ModeDims), P(ModeModelWeights), P(ModeGuidedArgs), c_vp, c_sz, c_vp]),
     "mode_frames_preprocess": (C.c_int, [P(ModeFramePrepDesc), c_vp]),
+    "mode_data_sample_windows": (C.c_int, [P(ModeDataStreamDesc), c_vp]),
+    "mode_edm_loss_masked": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_f32, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mode_lora_merge": (C.c_int, [P(ModeLoraDesc), c_vp]),
     "mode_lora_grad_workspace_bytes": (c_sz, [P(ModeLoraDesc)]),
     "mode_lora_grad": (C.c_int, [P(ModeLoraDesc), c_vp, c_sz, c_vp]),

@@ -14,12 +14,7 @@
 
 namespace mode {
 
-// Box-Muller sample of the environment noise stream (the formula of include/mode_hip.h): element e of the draw keyed by k = mode_stream_seed(seed, draw)
-__device__ __forceinline__ float env_normal(uint32_t k, uint32_t e) {
-  const float u1 = (float)((hash_u32(k ^ (2u * e)) >> 8) + 1u) * 0x1p-24f;      // (0, 1]: exact in fp32
-  const float u2 = (float)(hash_u32(k ^ (2u * e + 1u)) >> 8) * 0x1p-24f;        // [0, 1)
-  return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);                            // cospi: no rounding of 2 pi u2 before the cosine
-}
+// (env_normal, the Box-Muller sample of the environment noise stream, is defined in mode_common.h: the training batch stream draws from it too)
 
 // Observation and goal rows of environment r -> row j of a chunk's inputs (256 threads; either pair may be absent)
 __device__ __forceinline__ void env_gather_obs(const int r, const int j, const float* __restrict__ img, const long img_floats,

@@ -110,6 +110,13 @@ __device__ __forceinline__ uint32_t hash_u32(uint32_t x) {
   x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
   return x;
 }
+// Box-Muller sample of the environment noise stream (the formula of include/mode_hip.h): element e of the draw keyed by k = mode_stream_seed(seed, draw).
+// ONE definition for the rollout gathers (env_pool.hip) and the training batch stream (data_stream.hip): the two document the same stream.
+__device__ __forceinline__ float env_normal(uint32_t k, uint32_t e) {
+  const float u1 = (float)((hash_u32(k ^ (2u * e)) >> 8) + 1u) * 0x1p-24f;      // (0, 1]: exact in fp32
+  const float u2 = (float)(hash_u32(k ^ (2u * e + 1u)) >> 8) * 0x1p-24f;        // [0, 1)
+  return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);                            // cospi: no rounding of 2 pi u2 before the cosine
+}
 // keep-mask: element `idx` of stream `seed` survives with probability 1-p (thresh = p * 2^32)
 __device__ __forceinline__ bool drop_keep(uint32_t seed, uint64_t idx, uint32_t thresh) {
   return hash_u32(hash_u32((uint32_t)idx ^ seed) + (uint32_t)(idx >> 32) * 0x9e3779b9U) >= thresh;

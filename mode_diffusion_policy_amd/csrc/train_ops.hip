@@ -596,6 +596,15 @@ __global__ __launch_bounds__(256) void edm_noise_scale_kernel(const float* __res
   const float c_in = 1.0f / __fsqrt_rn(s * s + sd * sd);
   xs[i] = (action[i] + noise[i] * s) * c_in;
 }
+// F - target of one element at noise level s, target = (action - c_skip * noised) / c_out: the expressions of edm_loss_kernel below, for the masked
+// loss (that kernel keeps its own copy: called through this function its compiled loop is scheduled differently, and its bits are a contract)
+__device__ __forceinline__ float edm_residual(float F, float action, float noise, float s, float sd) {
+  const float s2 = s * s + sd * sd;
+  const float c_skip = sd * sd / s2, c_out = s * sd / __fsqrt_rn(s2);
+  const float noised = action + noise * s;
+  const float target = (action - c_skip * noised) / c_out;
+  return F - target;
+}
 // one workgroup, fixed summation order (deterministic): B * n is a few thousand elements
 __global__ __launch_bounds__(1024) void edm_loss_kernel(const float* __restrict__ F, const float* __restrict__ action, const float* __restrict__ noise,
                                                         const float* __restrict__ sigma, float sd, int B, int n, float* __restrict__ loss, float* __restrict__ dF) {
@@ -621,6 +630,65 @@ __global__ __launch_bounds__(1024) void edm_loss_kernel(const float* __restrict_
 #pragma unroll
     for (int w = 0; w < 16; ++w) t += red[w];
     loss[0] = t * inv;
+  }
+}
+// The same loss with a step mask and sample weights (include/mode_hip.h: mode_edm_loss_masked states the formulas and the summation order).  One
+// workgroup of 16 waves, wave v owns the samples v, v + 16, ...: a sample's mask sum and masked sum of squares are wave reductions, a wave adds its
+// samples in ascending order, and the 16 wave sums are added in ascending order - twice, first the coefficients (dF needs den), then the squares.
+// A few thousand elements: latency-bound, like the kernel above.
+__global__ __launch_bounds__(1024) void edm_loss_masked_kernel(const float* __restrict__ F, const float* __restrict__ action, const float* __restrict__ noise,
+                                                               const float* __restrict__ sigma, float sd, int B, int W, int A, const float* __restrict__ mask,
+                                                               const float* __restrict__ weight, float* __restrict__ loss, float* __restrict__ dF,
+                                                               float* __restrict__ per_sample) {
+  __shared__ float red[16];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, n = W * A;
+  float cs = 0.f;
+  for (int b = wave; b < B; b += 16) {
+    float mb = 0.f;
+    for (int w = lane; w < W; w += 64) {
+      const float m = mask ? mask[(long)b * W + w] : 1.f;
+      mb += m > 0.f ? m : 0.f;
+    }
+    mb = wave_sum(mb);
+    const float wt = weight ? weight[b] : 1.f;
+    if (wt > 0.f) cs = __builtin_fmaf(wt, mb, cs);
+  }
+  if (lane == 0) red[wave] = cs;
+  __syncthreads();
+  float csum = 0.f;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) csum += red[v];
+  const float den = __fmul_rn((float)A, csum);
+  __syncthreads();
+  float tv = 0.f;
+  for (int b = wave; b < B; b += 16) {
+    const float wr = weight ? weight[b] : 1.f, wt = wr > 0.f ? wr : 0.f;
+    const float s = sigma[b];
+    float acc = 0.f, mb = 0.f;
+    for (int w = lane; w < W; w += 64) {
+      const float m = mask ? mask[(long)b * W + w] : 1.f;
+      mb += m > 0.f ? m : 0.f;
+    }
+    mb = wave_sum(mb);
+    for (int i = lane; i < n; i += 64) {
+      const long at = (long)b * n + i;
+      const float mr = mask ? mask[(long)b * W + i / A] : 1.f, m = mr > 0.f ? mr : 0.f;
+      const float c = __fmul_rn(wt, m);
+      const float d = edm_residual(F[at], action[at], noise[at], s, sd);
+      if (m > 0.f) acc = __builtin_fmaf(m, __fmul_rn(d, d), acc);
+      dF[at] = (c > 0.f && den > 0.f) ? __fmul_rn(__fdiv_rn(__fmul_rn(2.0f, c), den), d) : 0.0f;
+    }
+    acc = wave_sum(acc);
+    if (wt > 0.f) tv = __builtin_fmaf(wt, acc, tv);
+    if (per_sample && lane == 0) per_sample[b] = mb > 0.f ? __fdiv_rn(acc, __fmul_rn((float)A, mb)) : 0.f;
+  }
+  if (lane == 0) red[wave] = tv;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) t += red[v];
+    loss[0] = den > 0.f ? __fdiv_rn(t, den) : 0.f;
   }
 }
 
@@ -936,6 +1004,15 @@ extern "C" int mode_edm_loss(const float* F, const float* action, const float* n
                              float* dF, void* stream) {
   if (!F || !action || !noise || !sigma || !loss || !dF || B <= 0 || n <= 0) return MODE_ERR_BAD_ARG;
   hipLaunchKernelGGL(edm_loss_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, F, action, noise, sigma, sigma_data, B, n, loss, dF);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
+extern "C" int mode_edm_loss_masked(const float* F, const float* action, const float* noise, const float* sigma, float sigma_data, int B, int W, int A,
+                                    const float* mask, const float* weight, float* loss, float* dF, float* per_sample, void* stream) {
+  if (!F || !action || !noise || !sigma || !loss || !dF || B <= 0 || W <= 0 || A <= 0 || (long)W * A > 0x7fffffffL) return MODE_ERR_BAD_ARG;
+  hipLaunchKernelGGL(edm_loss_masked_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, F, action, noise, sigma, sigma_data, B, W, A, mask, weight, loss, dF,
+                     per_sample);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }

@@ -63,19 +63,36 @@ class GCDenoiser(nn.Module):
         c_in = 1 / (sigma ** 2 + self.sigma_data ** 2) ** 0.5
         return c_skip, c_out, c_in
 
-    def loss(self, state, action, goal, noise, sigma, **kwargs):
+    def loss(self, state, action, goal, noise, sigma, *, action_mask=None, sample_weight=None, **kwargs):
         """Score-matching loss (score_wrappers.py:45-63) -> (loss, model_output).  On a HIP MoDeDiT in training mode the scalings, the
         target, the MSE and their backward are two HIP launches around the training chain (training.edm_loss); the expression below is
-        the generic path (eval-mode loss, extra kwargs)."""
+        the generic path (eval-mode loss, extra kwargs).
+
+        ``action_mask`` (B, W) and ``sample_weight`` (B,), both optional: the loss becomes the mean over the elements weighted by
+        ``c[b, w] = sample_weight[b] * action_mask[b, w]`` (an absent factor is 1), ``sum(c * sq_err) / (A * sum(c))``, and 0 when every ``c`` is
+        0 - padded steps of a window (``data.WindowStream(pad="hold")``) then train nothing.  Without them nothing changes."""
         m = self.inner_model
         if isinstance(m, MoDeDiT) and m.training and not kwargs and torch.is_grad_enabled():
             from .training import edm_loss
-            return edm_loss(self, state, action, goal, noise, sigma)
+            if action_mask is None and sample_weight is None:
+                return edm_loss(self, state, action, goal, noise, sigma)
+            return edm_loss(self, state, action, goal, noise, sigma, action_mask=action_mask, sample_weight=sample_weight)
         c_skip, c_out, c_in = [append_dims(x, action.ndim) for x in self.get_scalings(sigma)]
         noised_input = action + noise * append_dims(sigma, action.ndim)
         model_output = self.inner_model(state, noised_input * c_in, goal, sigma, **kwargs)
         target = (action - c_skip * noised_input) / c_out
-        return (model_output - target).pow(2).flatten(1).mean(), model_output
+        if action_mask is None and sample_weight is None:
+            return (model_output - target).pow(2).flatten(1).mean(), model_output
+        if action.ndim != 3:
+            raise ValueError(f"action_mask / sample_weight need an action chunk of shape (B, W, A), got {tuple(action.shape)}")
+        c = torch.ones(action.shape[:2], dtype=model_output.dtype, device=model_output.device)
+        if action_mask is not None:
+            c = c * action_mask.to(c).clamp_min(0)
+        if sample_weight is not None:
+            c = c * sample_weight.to(c).clamp_min(0).unsqueeze(1)
+        den = action.shape[2] * c.sum()
+        resid = torch.where(c.unsqueeze(2) > 0, model_output - target, torch.zeros_like(model_output))     # an element with c = 0 trains nothing, finite or not
+        return (c.unsqueeze(2) * resid.pow(2)).sum() / den.clamp_min(torch.finfo(c.dtype).tiny) * (den > 0), model_output
 
     def forward(self, state, action, goal, sigma, **kwargs):
         """D(x; sigma) = F(x*c_in)*c_out + x*c_skip   (score_wrappers.py:65-80)."""

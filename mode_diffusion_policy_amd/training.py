@@ -469,9 +469,22 @@ def dit_forward_train(model, states, actions, goals, sigma, uncond=False):
     return Fo
 
 
-def edm_loss(denoiser, state, action, goal, noise, sigma):
+def _loss_factor(t, shape, name, dev):
+    """``action_mask`` [B, W] / ``sample_weight`` [B] as the masked loss kernel reads it (fp32, contiguous, on the device); None stays None."""
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or tuple(t.shape) != shape:
+        raise ValueError(f"{name} must be a {shape} tensor, got {tuple(getattr(t, 'shape', ()))}")
+    if torch.is_grad_enabled() and t.requires_grad:
+        raise NotImplementedError(f"GCDenoiser.loss (HIP): {name} requires grad, but the chain returns no input gradients")
+    return t.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+
+def edm_loss(denoiser, state, action, goal, noise, sigma, action_mask=None, sample_weight=None):
     """``GCDenoiser.loss`` (score_wrappers.py:45-63) on the HIP chain: noised input and c_in scaling in one launch, target / MSE / dF in
-    another; returns (loss, model_output) like the reference."""
+    another; returns (loss, model_output) like the reference.  With ``action_mask`` [B, W] and / or ``sample_weight`` [B] the second launch is
+    ``mode_edm_loss_masked``: the mean over the elements weighted by ``sample_weight[b] * action_mask[b, w]`` (include/mode_hip.h); with neither,
+    ``mode_edm_loss`` exactly as without the keywords."""
     m = denoiser.inner_model
     eng: DitEngine = m.engine
     lib, dev = eng.lib, eng.device
@@ -485,25 +498,41 @@ def edm_loss(denoiser, state, action, goal, noise, sigma):
     sig = f(sigma).reshape(-1)
     if sig.numel() == 1:
         sig = sig.expand(B).contiguous()
+    masked = action_mask is not None or sample_weight is not None
+    if masked:
+        if a.dim() != 3:
+            raise ValueError(f"action_mask / sample_weight need an action chunk of shape (B, W, A), got {tuple(a.shape)}")
+        mask, weight = _loss_factor(action_mask, (B, a.shape[1]), "action_mask", dev), _loss_factor(sample_weight, (B,), "sample_weight", dev)
     xs = torch.empty_like(a)
     sd = float(denoiser.sigma_data)
     L.check(lib.mode_edm_noise_scale(a.data_ptr(), nz.data_ptr(), sig.data_ptr(), sd, B, n, xs.data_ptr(), _stream()), "edm_noise_scale")
     F = m(state, xs, goal, sig)
     loss = torch.empty(1, device=dev)
     dF = torch.empty_like(a)
+    if masked:
+        p = lambda t: None if t is None else t.data_ptr()
+        L.check(lib.mode_edm_loss_masked(F.detach().contiguous().data_ptr(), a.data_ptr(), nz.data_ptr(), sig.data_ptr(), sd, B, a.shape[1], a.shape[2],
+                                         p(mask), p(weight), loss.data_ptr(), dF.data_ptr(), None, _stream()), "edm_loss_masked")
+        return _EdmLossFn.apply(F, loss, dF), F
     L.check(lib.mode_edm_loss(F.detach().contiguous().data_ptr(), a.data_ptr(), nz.data_ptr(), sig.data_ptr(), sd, B, n, loss.data_ptr(), dF.data_ptr(), _stream()),
             "edm_loss")
     return _EdmLossFn.apply(F, loss, dF), F
 
 
-def diffusion_loss(denoiser, perceptual_emb, latent_goal, actions, sample_density=None):
-    """``MoDEAgent.diffusion_loss`` (mode_agent.py:659-672): train mode, sigma ~ density (log-logistic by default), eps ~ N(0, 1)."""
+def diffusion_loss(denoiser, perceptual_emb, latent_goal, actions, sample_density=None, *, action_mask=None, sample_weight=None, noise=None,
+                   sigmas=None):
+    """``MoDEAgent.diffusion_loss`` (mode_agent.py:659-672): train mode, sigma ~ density (log-logistic by default), eps ~ N(0, 1).
+    ``noise`` / ``sigmas`` given (a ``data.WindowStream`` batch's, reproducible from the step counter) replace the two draws, which are then not
+    made; ``action_mask`` / ``sample_weight`` go to ``GCDenoiser.loss``.  With none of the four nothing differs from the call without them."""
     from .utils import make_sample_density
     denoiser.train()
-    density = sample_density or make_sample_density("loglogistic", sigma_data=float(denoiser.sigma_data))
-    sigmas = density(shape=(len(actions),), device=actions.device).to(actions.device)
-    noise = torch.randn_like(actions)
-    loss, _ = denoiser.loss(perceptual_emb, actions, latent_goal, noise, sigmas)
+    if sigmas is None:
+        density = sample_density or make_sample_density("loglogistic", sigma_data=float(denoiser.sigma_data))
+        sigmas = density(shape=(len(actions),), device=actions.device).to(actions.device)
+    if noise is None:
+        noise = torch.randn_like(actions)
+    kw = {k: v for k, v in (("action_mask", action_mask), ("sample_weight", sample_weight)) if v is not None}
+    loss, _ = denoiser.loss(perceptual_emb, actions, latent_goal, noise, sigmas, **kw)
     return loss
 
 
@@ -511,11 +540,13 @@ def training_step(denoiser, batch, entropy_gamma: float = 0.0, router_z_delta: f
     """``MoDEAgent.training_step`` (mode_agent.py:386-440) for precomputed embeddings: ``batch`` maps a modality name to
     ``{"perceptual_emb": {"state_images": ...}, "latent_goal": ..., "actions": ...}`` (what ``compute_input_embeddings`` hands over);
     per modality ``act_loss (+ entropy_gamma * LB) (+ router_z_delta * Z)``, summed, divided by the number of modalities.
-    Returns (total_loss, action_loss, aux) with aux = the last modality's LB / Z values (what the reference logs)."""
+    Returns (total_loss, action_loss, aux) with aux = the last modality's LB / Z values (what the reference logs).
+    Optional entries of a modality's dict, passed through to ``diffusion_loss``: ``action_mask``, ``sample_weight``, ``noise``, ``sigmas``."""
     inner = denoiser.inner_model
     total, action_loss, aux = None, None, {}
     for _, db in batch.items():
-        act = diffusion_loss(denoiser, db["perceptual_emb"], db["latent_goal"], db["actions"], sample_density)
+        extra = {k: db[k] for k in ("action_mask", "sample_weight", "noise", "sigmas") if db.get(k) is not None}
+        act = diffusion_loss(denoiser, db["perceptual_emb"], db["latent_goal"], db["actions"], sample_density, **extra)
         t = act
         if entropy_gamma > 0:
             aux["load_balancing_loss"] = inner.load_balancing_loss()

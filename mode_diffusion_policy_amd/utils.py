@@ -12,16 +12,24 @@ def append_dims(x: torch.Tensor, target_dims: int) -> torch.Tensor:
     return x[(...,) + (None,) * dims_to_append]
 
 
-def rand_log_logistic(shape, loc=0.0, scale=1.0, min_value=0.0, max_value=float("inf"), device="cpu", dtype=torch.float32):
+def rand_log_logistic(shape, loc=0.0, scale=1.0, min_value=0.0, max_value=float("inf"), device="cpu", dtype=torch.float32, u=None):
     """Truncated log-logistic draw, fp64 internally (edm_diffusion/utils.py:159-166) — the default sigma density
-    (mode_agent.py:703-708: loc = ln(sigma_data), scale = 0.5, [sigma_min, sigma_max])."""
+    (mode_agent.py:703-708: loc = ln(sigma_data), scale = 0.5, [sigma_min, sigma_max]).  ``u``: a tensor of uniforms in (0, 1) of ``shape`` (a
+    ``data.WindowStream`` batch's ``u``) used in place of this function's own ``torch.rand`` - the same fp64 arithmetic, on ``u``'s device, and
+    no draw from torch's generator."""
     # The two truncation bounds are scalars: evaluated on the host (fp64, the same torch kernels the reference's CPU path runs) and folded in as
     # Python floats.  `torch.as_tensor(scalar, device=cuda)` - the reference's form - is a blocking host-to-device copy: it drains the stream once
     # per training step, the GPU then idles while the host enqueues the next forward (measured: 7 ms of host wait per 14.5-ms step, and
     # 22-42 ms steps on a box with a slower launch path).
     min_cdf = float(torch.as_tensor(min_value, dtype=torch.float64).log().sub(loc).div(scale).sigmoid())
     max_cdf = float(torch.as_tensor(max_value, dtype=torch.float64).log().sub(loc).div(scale).sigmoid())
-    u = torch.rand(shape, device=device, dtype=torch.float64) * (max_cdf - min_cdf) + min_cdf
+    if u is None:
+        u = torch.rand(shape, device=device, dtype=torch.float64)
+    else:
+        if not torch.is_tensor(u) or tuple(u.shape) != tuple(torch.Size(shape)):
+            raise ValueError(f"u must be a tensor of shape {tuple(torch.Size(shape))}, got {tuple(getattr(u, 'shape', ()))}")
+        u = u.to(torch.float64)
+    u = u * (max_cdf - min_cdf) + min_cdf
     return u.logit().mul(scale).add(loc).exp().to(dtype)
 
 
