@@ -1350,6 +1350,78 @@ int mode_data_sample_windows(const ModeDataStreamDesc* d, void* stream);
 int mode_edm_loss_masked(const float* F, const float* action, const float* noise, const float* sigma, float sigma_data, int B, int W, int A,
                          const float* mask, const float* weight, float* loss, float* dF, float* per_sample, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Device-side validation: every window of a set of episodes exactly once (csrc/data_stream.hip; data.WindowSweep), and the masked error between a
+ * sampled chunk and the demonstrated one, accumulated on the device (validation.Validator).  An addition to ABI 13: new structs and exports,
+ * nothing existing changes.
+ *
+ * mode_data_sweep_windows: the store and the tables of mode_data_sample_windows above, with a fixed enumeration in place of the draw.  Windows
+ * are numbered episode by episode, `stride` steps apart:
+ *   n_e = ceil(L_e / stride) (pad="hold") | L_e >= W ? (L_e - W) / stride + 1 : 0 (pad="none") | 0 (an episode that is not selected), the
+ *   caller's choice; starts [E + 1] int32 = the prefix sums of n_e, starts[E] = n_total (1 <= n_total <= S)
+ * Row j (0 <= j < B) of the batch that begins at window `first` (batch i of a sweep: first = i * B):
+ *   valid[j] = first + j < n_total ? 1.0f : 0.0f,   g = min(first + j, n_total - 1),   window[j] = g
+ *                       (a row past the end of the enumeration repeats the last window, with valid = 0 and a zero action_mask)
+ *   e  = the largest index with starts[e] <= g - the binary search of mode_data_sample_windows, the same expression -, p = stride * (g - starts[e])
+ *   index[j] = ep_begin[e] + p, episode[j], last, the rows r_w, actions[j] (three unfused roundings) and latent_goal[j] exactly as above
+ *   action_mask[j][w] = valid[j] != 0 && index[j] + w <= last ? 1.0f : 0.0f
+ *   noise[j][w * A + a] = noise_scale * z(s_g, draw, w * A + a), one fp32 product, z the noise stream of mode_env_gather_noise (ABI 13) with
+ *                       s_g = seed + 1 + g * 0x9E3779B9 (uint32): the noise belongs to the WINDOW g, not to the row's place in a batch, and
+ *                       `draw` numbers independent repeats.  NULL = not written.  There is no u and there are no shifts.
+ * Every index is clamped into its table before it becomes an address, as above.  Row j is a function of (seed, draw, first + j) and the store
+ * only.  One launch, B workgroups, plain vector stores, no atomics.  With frames, index is the `rows` of mode_frames_preprocess (no shift table).
+ *
+ * Before any launch, outputs untouched: the refusals of mode_data_sample_windows (valid and window are required pointers too), and
+ * MODE_ERR_BAD_ARG for stride < 1, first < 0, first >= n_total.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct ModeDataSweepDesc {
+  const float* actions;                  /* [S, A] */
+  const int32_t* ep_begin;               /* [E + 1] */
+  const int32_t* starts;                 /* [E + 1] prefix sums of n_e */
+  const float* goals;                    /* [E, G] */
+  const float* lo; const float* scale;   /* [A] each, or both NULL: no normalisation */
+  int32_t S, E, A, G, W, B;
+  int32_t n_total;                       /* = starts[E] */
+  int32_t stride;                        /* >= 1: steps between two windows of an episode */
+  int32_t first;                         /* window number of row 0, 0 <= first < n_total */
+  uint32_t seed, draw;
+  float noise_scale;
+  float* out_actions;                    /* [B, W, A] */
+  float* action_mask;                    /* [B, W] */
+  float* latent_goal;                    /* [B, G] */
+  int32_t* index; int32_t* episode;      /* [B] each */
+  float* valid;                          /* [B] 1 | 0 */
+  int32_t* window;                       /* [B] */
+  float* noise;                          /* [B, W, A] or NULL */
+} ModeDataSweepDesc;
+int mode_data_sweep_windows(const ModeDataSweepDesc* d, void* stream);
+
+/* mode_action_error: pred, target [B, W, A] fp32; mask [B, W] or NULL, weight [B] or NULL, unit [A] fp64 or NULL (the factor that takes a
+ * normalised difference to raw action units); sq, ab [W * A] fp64, cnt [W] fp64.  m and wt as in mode_edm_loss_masked: an absent factor is 1, a
+ * value that is not > 0 (zero, negative, NaN) counts as 0.
+ *   c[b][w] = (double) (wt[b] * m[b][w])          one fp32 product
+ *   d = pred - target                             one fp32 difference
+ *   e = (double) d * unit[a]                      (double) d when unit == NULL
+ *   sq[w * A + a] = sum_b c (e * e),   ab[w * A + a] = sum_b c |e|,   cnt[w] = sum_b c
+ * Summation order, fixed by (B, W, A): one wave owns element i = w * A + a.  Lane l runs over b = l, l + 64, ... ascending and skips every term
+ * with c == 0 (pred and target may hold anything there); for the others t = c * (e * e) (t = c * |e|; t = c), acc = acc + t, every product and
+ * sum rounded to fp64 on its own (no contraction).  The 64 lane sums are added by the xor butterfly 32, 16, 8, 4, 2, 1; the wave with a == 0 sums
+ * cnt[w] the same way.  One lane stores the three sums (accumulate == 0) or adds each to what its accumulator holds, x = x + sum
+ * (accumulate == 1).  No atomics: the stored bits depend on (B, W, A) and the order of the calls only.
+ * MODE_ERR_BAD_ARG before any launch for a NULL descriptor, pred, target, sq, ab or cnt, or a non-positive B, W or A; MODE_ERR_UNSUPPORTED for
+ * B > 65535 or W * A > 4096. */
+typedef struct ModeActionErrorDesc {
+  const float* pred; const float* target;   /* [B, W, A] */
+  const float* mask;                        /* [B, W] or NULL */
+  const float* weight;                      /* [B] or NULL */
+  const double* unit;                       /* [A] or NULL */
+  double* sq; double* ab;                   /* [W * A] */
+  double* cnt;                              /* [W] */
+  int32_t B, W, A;
+  int32_t accumulate;                       /* 0: store, 1: add to what is there */
+} ModeActionErrorDesc;
+int mode_action_error(const ModeActionErrorDesc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -224,6 +224,22 @@ class ModeDataStreamDesc(C.Structure):
                 ("shift_pad", c_i32 * 2)]
 
 
+class ModeDataSweepDesc(C.Structure):
+    """mode_data_sweep_windows (include/mode_hip.h, an addition to ABI 13): the store's tables, the enumeration's (stride, first), the noise's
+    (seed, draw, noise_scale) and the batch's outputs."""
+    _fields_ = [("actions", c_vp), ("ep_begin", c_vp), ("starts", c_vp), ("goals", c_vp), ("lo", c_vp), ("scale", c_vp), ("S", c_i32), ("E", c_i32),
+                ("A", c_i32), ("G", c_i32), ("W", c_i32), ("B", c_i32), ("n_total", c_i32), ("stride", c_i32), ("first", c_i32), ("seed", c_u32),
+                ("draw", c_u32), ("noise_scale", c_f32), ("out_actions", c_vp), ("action_mask", c_vp), ("latent_goal", c_vp), ("index", c_vp),
+                ("episode", c_vp), ("valid", c_vp), ("window", c_vp), ("noise", c_vp)]
+
+
+class ModeActionErrorDesc(C.Structure):
+    """mode_action_error (include/mode_hip.h, an addition to ABI 13): two [B, W, A] chunks, the optional mask / weight / unit factors and the fp64
+    accumulators."""
+    _fields_ = [("pred", c_vp), ("target", c_vp), ("mask", c_vp), ("weight", c_vp), ("unit", c_vp), ("sq", c_vp), ("ab", c_vp), ("cnt", c_vp),
+                ("B", c_i32), ("W", c_i32), ("A", c_i32), ("accumulate", c_i32)]
+
+
 MODE_GRAD_CHUNK = 16384
 
 
@@ -371,6 +387,8 @@ PROTOTYPES = {
     "mode_dit_forward_guided": (C.c_int, [P(ModeDims), P(ModeModelWeights), P(ModeGuidedArgs), c_vp, c_sz, c_vp]),
     "mode_frames_preprocess": (C.c_int, [P(ModeFramePrepDesc), c_vp]),
     "mode_data_sample_windows": (C.c_int, [P(ModeDataStreamDesc), c_vp]),
+    "mode_data_sweep_windows": (C.c_int, [P(ModeDataSweepDesc), c_vp]),
+    "mode_action_error": (C.c_int, [P(ModeActionErrorDesc), c_vp]),
     "mode_edm_loss_masked": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_f32, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mode_lora_merge": (C.c_int, [P(ModeLoraDesc), c_vp]),
     "mode_lora_grad_workspace_bytes": (c_sz, [P(ModeLoraDesc)]),

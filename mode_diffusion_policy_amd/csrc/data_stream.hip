@@ -7,6 +7,10 @@
 // of a table that is L2-resident after the first workgroups - and the threads then share the row's W * A + G elements.  A batch moves
 // B * (2 W A + G) floats, ~300 KB at B = 128: latency-bound, plain loops, no LDS, no atomics.  Every index is clamped into its table before it
 // becomes an address.
+//
+// Validation reads the same store (include/mode_hip.h: mode_data_sweep_windows, mode_action_error; data.WindowSweep, validation.Validator): the sweep
+// kernel enumerates the windows instead of drawing them and shares the located-window row body with the kernel above, and the error kernel sums the
+// masked squared / absolute difference of two chunks into fp64 accumulators, one wave per element, in an order fixed by the shape.
 #include "mode_common.h"
 
 namespace mode {
@@ -19,49 +23,73 @@ __device__ __forceinline__ float normalise_unfused(float x, float lo, float scal
   return t - 1.0f;
 }
 
+// What a located window needs of either descriptor (ModeDataStreamDesc, ModeDataSweepDesc): the store's tables and the row outputs.
+struct WindowTables {
+  const float* actions; const int32_t* ep_begin; const float* goals; const float* lo; const float* scale;
+  int S, E, A, G, W;
+  float* out_actions; float* action_mask; float* latent_goal; int32_t* index; int32_t* episode;
+};
+template <class Desc>
+__device__ __forceinline__ WindowTables window_tables(const Desc& d) {
+  return {d.actions, d.ep_begin, d.goals, d.lo, d.scale, d.S, d.E, d.A, d.G, d.W, d.out_actions, d.action_mask, d.latent_goal, d.index, d.episode};
+}
+
+// The episode of window number g: the largest e with starts[e] <= g (the header's binary search), clamped into [0, E).
+__device__ __forceinline__ int locate_episode(const int32_t* starts, int E, uint32_t g) {
+  int lo = 0, hi = E;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if ((uint32_t)starts[mid] <= g) lo = mid; else hi = mid;
+  }
+  return min(max(lo, 0), E - 1);
+}
+
+// Output row j of a located window - step p of episode e: index / episode, the gather of W action rows (normalised, the last row held past the
+// episode's end), the step mask (all zero unless `live`) and the episode's goal row.  ONE body for the training stream and the sweep.
+__device__ __forceinline__ void window_row(const WindowTables& t, int j, int e, long p, bool live, int tid) {
+  const int first = min(max(t.ep_begin[e], 0), t.S - 1);
+  const int last = min(max(t.ep_begin[e + 1] - 1, first), t.S - 1);
+  const long want = (long)t.ep_begin[e] + p;
+  const int start = (int)min(max(want, (long)first), (long)last);
+
+  const int A = t.A, WA = t.W * t.A;
+  const bool norm = t.lo != nullptr;
+  float* oa = t.out_actions + (long)j * WA;
+  for (int i = tid; i < WA; i += 256) {
+    const int w = i / A, a = i - w * A;
+    const float x = t.actions[min((long)start + w, (long)last) * A + a];
+    oa[i] = norm ? normalise_unfused(x, t.lo[a], t.scale[a]) : x;
+  }
+  for (int w = tid; w < t.W; w += 256) t.action_mask[(long)j * t.W + w] = live && (long)start + w <= (long)last ? 1.0f : 0.0f;
+  {
+    const float* src = t.goals + (long)e * t.G;
+    float* dst = t.latent_goal + (long)j * t.G;
+    for (int i = tid; i < t.G; i += 256) dst[i] = src[i];
+  }
+  if (tid == 0) {
+    t.index[j] = start;
+    t.episode[j] = e;
+  }
+}
+
 __global__ __launch_bounds__(256) void data_sample_windows_kernel(ModeDataStreamDesc d) {
   const int j = blockIdx.x, tid = threadIdx.x;
   const uint32_t uj = (uint32_t)j;
   const uint32_t k = mode_stream_seed(d.seed, d.step);
   uint32_t g = (uint32_t)(((uint64_t)hash_u32(k ^ uj) * (uint64_t)(uint32_t)d.n_total) >> 32);
   g = min(g, (uint32_t)d.n_total - 1u);
-  int lo = 0, hi = d.E;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if ((uint32_t)d.starts[mid] <= g) lo = mid; else hi = mid;
-  }
-  const int e = min(max(lo, 0), d.E - 1);
-  const int first = min(max(d.ep_begin[e], 0), d.S - 1);
-  const int last = min(max(d.ep_begin[e + 1] - 1, first), d.S - 1);
-  const long want = (long)d.ep_begin[e] + ((long)g - (long)d.starts[e]);
-  const int start = (int)min(max(want, (long)first), (long)last);
+  const int e = locate_episode(d.starts, d.E, g);
+  window_row(window_tables(d), j, e, (long)g - (long)d.starts[e], true, tid);
 
-  const int A = d.A, WA = d.W * d.A;
-  const bool norm = d.lo != nullptr;
-  float* oa = d.out_actions + (long)j * WA;
-  for (int i = tid; i < WA; i += 256) {
-    const int w = i / A, a = i - w * A;
-    const float x = d.actions[min((long)start + w, (long)last) * A + a];
-    oa[i] = norm ? normalise_unfused(x, d.lo[a], d.scale[a]) : x;
-  }
-  for (int w = tid; w < d.W; w += 256) d.action_mask[(long)j * d.W + w] = (long)start + w <= (long)last ? 1.0f : 0.0f;
-  {
-    const float* src = d.goals + (long)e * d.G;
-    float* dst = d.latent_goal + (long)j * d.G;
-    for (int i = tid; i < d.G; i += 256) dst[i] = src[i];
-  }
+  const int WA = d.W * d.A;
   if (d.noise) {
     const uint32_t kn = mode_stream_seed(d.seed + 1u + uj * 0x9E3779B9u, d.step);
     float* dst = d.noise + (long)j * WA;
     for (int i = tid; i < WA; i += 256) dst[i] = env_normal(kn, (uint32_t)i);
   }
-  if (tid == 0) {
-    d.index[j] = start;
-    d.episode[j] = e;
-    if (d.u) {
-      const uint32_t k2 = mode_stream_seed(d.seed + 2u, d.step);
-      d.u[j] = ((double)(hash_u32(k2 ^ uj) >> 8) + 0.5) * 0x1p-24;
-    }
+  if (tid == 0 && d.u) {
+    const uint32_t k2 = mode_stream_seed(d.seed + 2u, d.step);
+    d.u[j] = ((double)(hash_u32(k2 ^ uj) >> 8) + 0.5) * 0x1p-24;
   }
   if (tid < 4) {
     const int q = tid >> 1, c = tid & 1;
@@ -71,6 +99,68 @@ __global__ __launch_bounds__(256) void data_sample_windows_kernel(ModeDataStream
       const uint32_t k3 = mode_stream_seed(d.seed + 3u, d.step);
       sh[2 * (long)j + c] = (int32_t)(((uint64_t)hash_u32(k3 ^ (4u * uj + 2u * (uint32_t)q + (uint32_t)c)) * (uint64_t)(2 * pad + 1)) >> 32);
     }
+  }
+}
+
+// The sweep (include/mode_hip.h: mode_data_sweep_windows; data.WindowSweep): row j is window first + j of the fixed enumeration instead of a
+// draw - the same grid, search and row body; a row past the end repeats the last window with valid = 0 and a zero mask.  The noise row is keyed
+// by the window's number, so a window carries its noise whatever batch size it is swept with.
+__global__ __launch_bounds__(256) void data_sweep_windows_kernel(ModeDataSweepDesc d) {
+  const int j = blockIdx.x, tid = threadIdx.x;
+  const long want = (long)d.first + j;
+  const bool live = want < (long)d.n_total;
+  const uint32_t g = (uint32_t)min(max(want, 0l), (long)d.n_total - 1);
+  const int e = locate_episode(d.starts, d.E, g);
+  window_row(window_tables(d), j, e, (long)d.stride * ((long)g - (long)d.starts[e]), live, tid);
+  if (tid == 0) {
+    d.valid[j] = live ? 1.0f : 0.0f;
+    d.window[j] = (int32_t)g;
+  }
+  if (d.noise) {
+    const int WA = d.W * d.A;
+    const uint32_t kn = mode_stream_seed(d.seed + 1u + g * 0x9E3779B9u, d.draw);
+    float* dst = d.noise + (long)j * WA;
+    for (int i = tid; i < WA; i += 256) dst[i] = d.noise_scale * env_normal(kn, (uint32_t)i);
+  }
+}
+
+// Masked error between two chunks, accumulated in fp64 (include/mode_hip.h: mode_action_error states the terms and the summation order).  256
+// threads = 4 waves, one wave per element i = w * A + a; its lanes stride the batch, so the loads of a wave are W * A floats apart - a validation
+// batch is a few thousand elements, latency-bound like the loss kernels.  No fused multiply-add anywhere: numpy fp64 reproduces every bit.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void action_error_kernel(ModeActionErrorDesc d) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6), WA = d.W * d.A;
+  if (i >= WA) return;                                                       // (wave-uniform)
+  const int w = i / d.A, a = i - w * d.A;
+  const double un = d.unit ? d.unit[a] : 1.0;
+  double sq = 0.0, ab = 0.0, cn = 0.0;
+  for (int b = lane; b < d.B; b += 64) {
+    const float mr = d.mask ? d.mask[(long)b * d.W + w] : 1.f, m = mr > 0.f ? mr : 0.f;
+    const float wr = d.weight ? d.weight[b] : 1.f, wt = wr > 0.f ? wr : 0.f;
+    const float cf = wt * m;
+    if (!(cf > 0.f)) continue;                                               // c == 0: the term is skipped, not multiplied
+    const long at = (long)b * WA + i;
+    const float df = d.pred[at] - d.target[at];
+    const double c = (double)cf;
+    const double e = d.unit ? (double)df * un : (double)df;
+    const double t2 = c * (e * e), t1 = c * fabs(e);
+    sq = sq + t2;
+    ab = ab + t1;
+    cn = cn + c;
+  }
+  sq = wave_sum_f64(sq);
+  ab = wave_sum_f64(ab);
+  cn = wave_sum_f64(cn);
+  if (lane == 0) {
+    d.sq[i] = d.accumulate ? d.sq[i] + sq : sq;
+    d.ab[i] = d.accumulate ? d.ab[i] + ab : ab;
+    if (a == 0) d.cnt[w] = d.accumulate ? d.cnt[w] + cn : cn;
   }
 }
 
@@ -87,6 +177,28 @@ extern "C" int mode_data_sample_windows(const ModeDataStreamDesc* d, void* strea
     if (d->shift_pad[q] < 0 || d->shift_pad[q] > 16384 || (d->shifts[q] && d->shift_pad[q] == 0)) return MODE_ERR_BAD_ARG;
   if (d->B > 65535 || (long)d->W * d->A > 4096 || d->G > 4096) return MODE_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(data_sample_windows_kernel, dim3(d->B), dim3(256), 0, (hipStream_t)stream, *d);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
+extern "C" int mode_data_sweep_windows(const ModeDataSweepDesc* d, void* stream) {
+  if (!d || !d->actions || !d->ep_begin || !d->starts || !d->goals || !d->out_actions || !d->action_mask || !d->latent_goal || !d->index || !d->episode ||
+      !d->valid || !d->window)
+    return MODE_ERR_BAD_ARG;
+  if ((d->lo == nullptr) != (d->scale == nullptr)) return MODE_ERR_BAD_ARG;
+  if (d->S <= 0 || d->E <= 0 || d->A <= 0 || d->G <= 0 || d->W <= 0 || d->B <= 0 || d->n_total <= 0 || d->n_total > d->S || d->E > d->S) return MODE_ERR_BAD_ARG;
+  if (d->stride < 1 || d->first < 0 || d->first >= d->n_total) return MODE_ERR_BAD_ARG;
+  if (d->B > 65535 || (long)d->W * d->A > 4096 || d->G > 4096) return MODE_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(data_sweep_windows_kernel, dim3(d->B), dim3(256), 0, (hipStream_t)stream, *d);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
+extern "C" int mode_action_error(const ModeActionErrorDesc* d, void* stream) {
+  if (!d || !d->pred || !d->target || !d->sq || !d->ab || !d->cnt) return MODE_ERR_BAD_ARG;
+  if (d->B <= 0 || d->W <= 0 || d->A <= 0) return MODE_ERR_BAD_ARG;
+  if (d->B > 65535 || (long)d->W * d->A > 4096) return MODE_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(action_error_kernel, dim3((unsigned)((d->W * d->A + 3) / 4)), dim3(256), 0, (hipStream_t)stream, *d);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }

@@ -9,6 +9,12 @@ no host sync and no state: a run resumed at step ``t`` with the same seed and st
 Windows are drawn i.i.d. uniformly over all window starts, WITH replacement - this is not an epoch permutation: within any stretch of steps
 some starts repeat and others are not seen.  Reading CALVIN / LIBERO files, goal images and sharding the store across ranks are not part of this
 module (rank ``r`` of a data-parallel run may simply use ``seed + 16 * r``: the stream's keys use ``seed .. seed + 3``).
+
+Holding episodes out: ``split_episodes`` names a training and a validation set of episode ids, ``WindowStream(episodes=train_ids)`` draws from
+the first only, and ``WindowSweep(episodes=val_ids)`` enumerates every window of the second exactly once, a batch per launch
+(``mode_data_sweep_windows``) - what ``validation.Validator`` runs the sampler on.  The normalisation stays the store's own: the bounds of
+``finalize("minmax")`` are taken over ALL episodes, the held-out ones included; ``finalize((lo, hi))`` with bounds of the training episodes
+avoids that.
 """
 from __future__ import annotations
 
@@ -157,6 +163,98 @@ class EpisodeStore:
         return self
 
 
+def split_episodes(store: EpisodeStore, val_fraction: Optional[float] = None, val_episodes=None, seed: int = 0):
+    """``(train_ids, val_ids)``: two sorted, disjoint int64 numpy arrays that together cover ``range(store.num_episodes)``.  ``val_fraction=f``
+    (0 < f < 1) holds out ``max(1, round(f * E))`` episodes, the first of ``numpy.random.default_rng(seed).permutation(E)``;
+    ``val_episodes=ids`` holds out the caller's.  ValueError for neither or both arguments, a fraction outside (0, 1), an id out of range, a
+    repeated id, or a side left empty."""
+    if not isinstance(store, EpisodeStore):
+        raise ValueError("split_episodes needs an EpisodeStore")
+    E = store.num_episodes
+    if (val_fraction is None) == (val_episodes is None):
+        raise ValueError("give exactly one of val_fraction and val_episodes")
+    if val_fraction is not None:
+        try:
+            f = float(val_fraction)
+        except (TypeError, ValueError):
+            f = float("nan")
+        if isinstance(val_fraction, bool) or not 0.0 < f < 1.0:
+            raise ValueError(f"val_fraction must lie strictly inside (0, 1), got {val_fraction!r}")
+        val = np.random.default_rng(seed).permutation(E)[: max(1, int(round(f * E)))]
+    else:
+        val = _episode_ids(val_episodes, E, "val_episodes")
+    val = np.sort(np.asarray(val, dtype=np.int64))
+    train = np.setdiff1d(np.arange(E, dtype=np.int64), val)
+    if len(val) == 0 or len(train) == 0:
+        raise ValueError(f"the split leaves a side empty: {len(train)} training and {len(val)} validation episodes of {E}")
+    return train, val
+
+
+def _episode_ids(ids, E: int, name: str) -> np.ndarray:
+    """``ids`` as a sorted int64 array of distinct episode numbers in [0, E); ValueError otherwise."""
+    try:
+        arr = np.asarray(_host(ids, name) if torch.is_tensor(ids) else ids)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a sequence of episode ids") from None
+    if arr.ndim != 1 or (arr.size and (arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer))):
+        raise ValueError(f"{name} must be a 1-d sequence of ints, got {arr.dtype} {arr.shape}")
+    arr = arr.astype(np.int64)
+    if arr.size and (arr.min() < 0 or arr.max() >= E):
+        raise ValueError(f"{name} holds an id outside 0..{E - 1}")
+    if len(np.unique(arr)) != len(arr):
+        raise ValueError(f"{name} repeats an id")
+    return np.sort(arr)
+
+
+def _start_table(n_e: np.ndarray, episodes, what: str):
+    """The ``starts`` table the kernels search: the prefix sums of ``n_e``, with ``n_e = 0`` for an episode that ``episodes`` (None = all) does
+    not list - the search never finds an episode without starts.  -> (int64 host table, n_total); ValueError when nothing is left."""
+    n_e = np.asarray(n_e, dtype=np.int64)
+    if episodes is not None:
+        keep = np.zeros(len(n_e), dtype=bool)
+        keep[_episode_ids(episodes, len(n_e), "episodes")] = True
+        n_e = np.where(keep, n_e, 0)
+    starts = np.concatenate([[0], np.cumsum(n_e)])
+    if starts[-1] == 0:
+        raise ValueError(what)
+    return starts, int(starts[-1])
+
+
+def _check_window_args(store, batch_size, window, seed, pad, camera_transforms, frame_dtype, who: str):
+    """The constructor checks WindowStream and WindowSweep share; returns the transforms as a tuple (or None)."""
+    if not isinstance(store, EpisodeStore) or not store.finalized:
+        raise ValueError(f"{who} needs a finalized EpisodeStore")
+    for name, v, hi in (("batch_size", batch_size, MAX_BATCH), ("window", window, MAX_WINDOW_FLOATS), ("seed", seed, 2 ** 32 - 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < (0 if name == "seed" else 1) or v > hi:
+            raise ValueError(f"{name} must be an int in {0 if name == 'seed' else 1}..{hi}, got {v!r}")
+    if window * store.action_dim > MAX_WINDOW_FLOATS:
+        raise ValueError(f"window * action_dim must be at most {MAX_WINDOW_FLOATS}, got {window} * {store.action_dim}")
+    if store.goal_dim > MAX_GOAL_DIM:
+        raise ValueError(f"goal_dim must be at most {MAX_GOAL_DIM}, got {store.goal_dim}")
+    if pad not in _PADS:
+        raise ValueError(f"pad must be one of {_PADS}, got {pad!r}")
+    if frame_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"frame_dtype must be torch.float32 or torch.bfloat16, got {frame_dtype}")
+    if camera_transforms is not None:
+        camera_transforms = tuple(camera_transforms)
+        if len(camera_transforms) != 2 or not all(isinstance(t, CameraTransform) for t in camera_transforms):
+            raise ValueError("camera_transforms must be (static, gripper) CameraTransforms")
+        if not store.has_cameras:
+            raise ValueError("camera_transforms given, but the store holds no frames")
+        for t, f, n in zip(camera_transforms, (store.frames_static, store.frames_gripper), ("rgb_static", "rgb_gripper")):
+            t.check_source(f.shape[1], f.shape[2], n)
+    return camera_transforms
+
+
+def _frames_of(store: EpisodeStore, tr, shifts, index: torch.Tensor, B: int, frame_dtype) -> dict:
+    """``rgb_obs`` of a batch: one ``mode_frames_preprocess`` launch that reads the store rows ``index`` (``shifts[q]`` None: no shift)."""
+    from . import camera
+    frames = (store.frames_static, store.frames_gripper)
+    dst = [torch.empty(tr[q].out_shape((B,) + tuple(frames[q].shape[1:])), dtype=frame_dtype, device=store.device) for q in range(2)]
+    camera.launch([(tr[q], frames[q], dst[q], shifts[q]) for q in range(2)], index.data_ptr(), B, frames[0].shape[0])
+    return {"rgb_static": dst[0], "rgb_gripper": dst[1]}
+
+
 class WindowStream:
     """``batch(step)`` -> the training batch of step ``step`` as a dict of device tensors, without a host sync:
 
@@ -169,43 +267,25 @@ class WindowStream:
     ``pad="none"`` draws only windows that lie inside an episode (episodes shorter than ``window`` are never drawn); ``pad="hold"`` lets a window
     start at every step, holds the episode's last action past its end and marks those rows with ``action_mask = 0``.  Draws are i.i.d. uniform
     over the starts, with replacement (not an epoch permutation).  Row ``j`` of step ``t`` depends on ``(seed, t, j)`` and the store only:
-    ``noise[j] == rollout.env_noise([(seed + 1 + j * 0x9E3779B9) % 2**32], [t], W, A, 1.0)[0]``."""
+    ``noise[j] == rollout.env_noise([(seed + 1 + j * 0x9E3779B9) % 2**32], [t], W, A, 1.0)[0]``.
+
+    ``episodes=ids`` (``split_episodes``) draws from the listed episodes only: an episode that is not listed gets no starts, and the kernel's search
+    never finds an episode without starts.  None, the default, builds the table of all episodes.  The normalisation stays the store's own - the
+    bounds of ``finalize("minmax")`` include the episodes left out here; ``finalize((lo, hi))`` avoids that."""
 
     def __init__(self, store: EpisodeStore, batch_size: int, window: int, seed: int = 0, pad: str = "hold",
-                 camera_transforms: Optional[Sequence[CameraTransform]] = None, noise: bool = True, frame_dtype=torch.float32):
-        if not isinstance(store, EpisodeStore) or not store.finalized:
-            raise ValueError("WindowStream needs a finalized EpisodeStore")
-        for name, v, hi in (("batch_size", batch_size, MAX_BATCH), ("window", window, MAX_WINDOW_FLOATS), ("seed", seed, 2 ** 32 - 1)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < (0 if name == "seed" else 1) or v > hi:
-                raise ValueError(f"{name} must be an int in {0 if name == 'seed' else 1}..{hi}, got {v!r}")
-        if window * store.action_dim > MAX_WINDOW_FLOATS:
-            raise ValueError(f"window * action_dim must be at most {MAX_WINDOW_FLOATS}, got {window} * {store.action_dim}")
-        if store.goal_dim > MAX_GOAL_DIM:
-            raise ValueError(f"goal_dim must be at most {MAX_GOAL_DIM}, got {store.goal_dim}")
-        if pad not in _PADS:
-            raise ValueError(f"pad must be one of {_PADS}, got {pad!r}")
-        if frame_dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError(f"frame_dtype must be torch.float32 or torch.bfloat16, got {frame_dtype}")
-        if camera_transforms is not None:
-            camera_transforms = tuple(camera_transforms)
-            if len(camera_transforms) != 2 or not all(isinstance(t, CameraTransform) for t in camera_transforms):
-                raise ValueError("camera_transforms must be (static, gripper) CameraTransforms")
-            if not store.has_cameras:
-                raise ValueError("camera_transforms given, but the store holds no frames")
-            for t, f, n in zip(camera_transforms, (store.frames_static, store.frames_gripper), ("rgb_static", "rgb_gripper")):
-                t.check_source(f.shape[1], f.shape[2], n)
+                 camera_transforms: Optional[Sequence[CameraTransform]] = None, noise: bool = True, frame_dtype=torch.float32, episodes=None):
+        camera_transforms = _check_window_args(store, batch_size, window, seed, pad, camera_transforms, frame_dtype, "WindowStream")
         n_e = store.lengths if pad == "hold" else np.maximum(0, store.lengths - window + 1)
-        starts = np.concatenate([[0], np.cumsum(n_e)])
-        if starts[-1] == 0:
-            raise ValueError(f"no window of {window} steps fits any episode (pad='none'): nothing to draw")
+        starts, n_total = _start_table(n_e, episodes, f"no window of {window} steps fits any "
+                                       f"{'episode' if episodes is None else 'selected episode'} (pad={pad!r}): nothing to draw")
         self.store, self.batch_size, self.window, self.seed, self.pad, self.noise = store, int(batch_size), int(window), int(seed), pad, bool(noise)
         self.camera_transforms, self.frame_dtype = camera_transforms, frame_dtype
-        self.n_total = int(starts[-1])
+        self.n_total = n_total
         self.starts = torch.from_numpy(starts.astype(np.int32)).to(store.device)            # the device table the kernel searches
 
     def batch(self, step: int) -> dict:
         from . import _lib as L
-        from . import camera
         from .engine import _stream
         if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or not 0 <= step < 2 ** 32:
             raise ValueError(f"step must be an int in 0..2^32 - 1, got {step!r}")
@@ -231,9 +311,77 @@ class WindowStream:
         with torch.cuda.device(dev):
             L.check(L.load().mode_data_sample_windows(C.byref(d), _stream()), "data_sample_windows")
         if tr is not None:
-            frames = (st.frames_static, st.frames_gripper)
-            dst = [torch.empty(tr[q].out_shape((B,) + tuple(frames[q].shape[1:])), dtype=self.frame_dtype, device=dev) for q in range(2)]
-            camera.launch([(tr[q], frames[q], dst[q], shifts[q]) for q in range(2)], out["index"].data_ptr(), B, frames[0].shape[0])
-            out["rgb_obs"] = {"rgb_static": dst[0], "rgb_gripper": dst[1]}
+            out["rgb_obs"] = _frames_of(st, tr, shifts, out["index"], B, self.frame_dtype)
             out["shifts"] = {"rgb_static": shifts[0], "rgb_gripper": shifts[1]}
+        return out
+
+
+class WindowSweep:
+    """Every window of the selected episodes exactly once, ``batch_size`` per launch: ``len(sweep) = ceil(n_total / B)`` batches, and
+    ``batch(i, draw=0)`` -> the windows numbered ``i * B .. i * B + B - 1`` of a fixed enumeration as a dict of device tensors, without a host sync
+    and without state (csrc/data_stream.hip; the expressions, bit for bit, are the comment of ``mode_data_sweep_windows`` in include/mode_hip.h):
+
+        actions, action_mask, latent_goal, index, episode: as ``WindowStream`` returns them for a window at that place,
+        valid [B] fp32 (1 = a window of the enumeration, 0 = a padding row of the last batch: it repeats the last window with a zero action_mask),
+        window [B] int32 (the window's number), noise [B, W, A] fp32 (unit normal times ``noise_scale``), and
+        rgb_obs {"rgb_static", "rgb_gripper"} [B, 3, OH, OW] with ``camera_transforms`` - no random shift: every transform is applied with its
+        shift table absent
+
+    Windows are numbered episode by episode, ``stride`` steps apart: with ``pad="hold"`` episode e has ``ceil(L_e / stride)`` windows (every
+    stride-th step starts one; the last action is held past the end under ``action_mask = 0``), with ``pad="none"`` ``(L_e - W) // stride + 1`` when
+    ``L_e >= W``, else none.  ``episodes=ids`` (``split_episodes``) sweeps the listed episodes only; None sweeps all.  ``B`` is fixed, so whatever
+    consumes the batches (a captured sampler graph) sees one shape; weigh the rows with ``valid``.
+
+    A row's noise belongs to its WINDOW, not to its place in a batch - ``noise[j] == rollout.env_noise([(seed + 1 + window[j] * 0x9E3779B9) %
+    2**32], [draw], W, A, noise_scale)[0]`` - so a sweep gives a window the same noise at every batch size, and ``draw`` numbers independent
+    repeats.  There is no ``u``.  The normalisation is the store's own (see ``WindowStream``)."""
+
+    def __init__(self, store: EpisodeStore, batch_size: int, window: int, stride: int = 1, pad: str = "hold", episodes=None, seed: int = 0,
+                 camera_transforms: Optional[Sequence[CameraTransform]] = None, frame_dtype=torch.float32, noise_scale: float = 1.0):
+        camera_transforms = _check_window_args(store, batch_size, window, seed, pad, camera_transforms, frame_dtype, "WindowSweep")
+        if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
+            raise ValueError(f"stride must be an int >= 1, got {stride!r}")
+        if isinstance(noise_scale, bool) or not np.isfinite(float(noise_scale)):
+            raise ValueError(f"noise_scale must be a finite number, got {noise_scale!r}")
+        L_e = store.lengths
+        n_e = -(-L_e // stride) if pad == "hold" else np.where(L_e >= window, (L_e - window) // stride + 1, 0)
+        starts, n_total = _start_table(n_e, episodes, f"no window of {window} steps fits any "
+                                       f"{'episode' if episodes is None else 'selected episode'} (pad={pad!r}): nothing to sweep")
+        self.store, self.batch_size, self.window, self.stride, self.pad, self.seed = store, int(batch_size), int(window), int(stride), pad, int(seed)
+        self.camera_transforms, self.frame_dtype, self.noise_scale = camera_transforms, frame_dtype, float(noise_scale)
+        self.n_total = n_total
+        self.starts = torch.from_numpy(starts.astype(np.int32)).to(store.device)            # the device table the kernel searches
+
+    def __len__(self) -> int:
+        return -(-self.n_total // self.batch_size)
+
+    def batch(self, i: int, draw: int = 0, noise_scale: Optional[float] = None) -> dict:
+        """``noise_scale``: this batch's factor in place of the sweep's own (``validation.Validator`` asks for its ``sigma_max``)."""
+        from . import _lib as L
+        from .engine import _stream
+        scale = self.noise_scale if noise_scale is None else float(noise_scale)
+        if not np.isfinite(scale):
+            raise ValueError(f"noise_scale must be a finite number, got {noise_scale!r}")
+        if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 0 <= i < len(self):
+            raise ValueError(f"batch index must be an int in 0..{len(self) - 1}, got {i!r}")
+        if isinstance(draw, bool) or not isinstance(draw, (int, np.integer)) or not 0 <= draw < 2 ** 32:
+            raise ValueError(f"draw must be an int in 0..2^32 - 1, got {draw!r}")
+        st, B, W = self.store, self.batch_size, self.window
+        A, G, dev = st.action_dim, st.goal_dim, st.device
+        if dev.type != "cuda":
+            raise ValueError(f"WindowSweep.batch: the store must be on a ROCm device (there is no CPU path), got {dev}")
+        f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+        i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
+        out = {"actions": f32(B, W, A), "action_mask": f32(B, W), "latent_goal": f32(B, G), "index": i32(B), "episode": i32(B), "valid": f32(B),
+               "window": i32(B), "noise": f32(B, W, A)}
+        p = lambda t: None if t is None else t.data_ptr()
+        d = L.ModeDataSweepDesc(actions=p(st.actions), ep_begin=p(st.ep_begin), starts=p(self.starts), goals=p(st.goals), lo=p(st.lo), scale=p(st.scale),
+                                S=st.actions.shape[0], E=st.goals.shape[0], A=A, G=G, W=W, B=B, n_total=self.n_total, stride=self.stride,
+                                first=int(i) * B, seed=self.seed, draw=int(draw), noise_scale=scale, out_actions=p(out["actions"]),
+                                action_mask=p(out["action_mask"]), latent_goal=p(out["latent_goal"]), index=p(out["index"]), episode=p(out["episode"]),
+                                valid=p(out["valid"]), window=p(out["window"]), noise=p(out["noise"]))
+        with torch.cuda.device(dev):
+            L.check(L.load().mode_data_sweep_windows(C.byref(d), _stream()), "data_sweep_windows")
+        if self.camera_transforms is not None:
+            out["rgb_obs"] = _frames_of(st, self.camera_transforms, (None, None), out["index"], B, self.frame_dtype)
         return out

@@ -191,7 +191,10 @@ class ChunkedRolloutPolicy:
             inner.precompute_experts_for_inference(sigma, goal)
 
     @torch.no_grad()
-    def denoise_actions(self, perceptual_emb: Dict[str, torch.Tensor], latent_goal: torch.Tensor, extra_args: Optional[dict] = None) -> torch.Tensor:
+    def denoise_actions(self, perceptual_emb: Dict[str, torch.Tensor], latent_goal: torch.Tensor, extra_args: Optional[dict] = None,
+                        x: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``x``: the initial latent, (B, act_window_size, action_dim) already at ``sigma_max`` (``validation.Validator`` plans from a window's own
+        noise); None, the default, draws it from the policy's generator."""
         self.model.eval()
         dev = perceptual_emb["state_images"].device
         if latent_goal.dim() < perceptual_emb["state_images"].dim():
@@ -200,7 +203,10 @@ class ChunkedRolloutPolicy:
             self.precompute_expert_for_inference(latent_goal[:1] if self.model.inner_model.use_goal_in_routing else None)
             self.need_precompute_experts_for_inference = False
         sigmas = self._schedule(dev)
-        x = torch.randn((len(latent_goal), self.act_window_size, self.action_dim), device=dev, generator=self.generator) * self.sigma_max
+        if x is None:
+            x = torch.randn((len(latent_goal), self.act_window_size, self.action_dim), device=dev, generator=self.generator) * self.sigma_max
+        elif tuple(x.shape) != (len(latent_goal), self.act_window_size, self.action_dim):
+            raise ValueError(f"x must be {(len(latent_goal), self.act_window_size, self.action_dim)}, got {tuple(x.shape)}")
         if self.sampler_type in _GRAPHABLE_SAMPLERS and not extra_args:
             out = self._sample_graphed(sigmas, x, perceptual_emb, latent_goal)
             if out is not None:
