@@ -1422,6 +1422,50 @@ typedef struct ModeActionErrorDesc {
 } ModeActionErrorDesc;
 int mode_action_error(const ModeActionErrorDesc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Hindsight goal relabelling (csrc/data_stream.hip; data.WindowStream / data.WindowSweep with goal="hindsight").  An addition to ABI 13: a new
+ * struct and export, nothing existing changes - ModeDataStreamDesc and ModeDataSweepDesc keep their layout and both sampling kernels their bits.
+ *
+ * Store: step_goals [S, G], one goal-space embedding per step (fp32 or bf16, goal_dtype), next to the tables of mode_data_sample_windows.  The
+ * launch runs after mode_data_sample_windows or mode_data_sweep_windows on the same stream and reads that launch's index [B] and episode [B]; it
+ * replaces the episode goal a row carries by the embedding of a step d steps after the window's first one, for the rows a second draw chooses.
+ * Row j (0 <= j < B) with id = ids ? (uint32) ids[j] : j, every product and sum of the keys in uint32 arithmetic modulo 2^32 (lowbias32 = hash_u32
+ * and mode_stream_seed of csrc/mode_common.h):
+ *   k4 = mode_stream_seed(seed + 4, step)      k5 = mode_stream_seed(seed + 5, step)        (the sampling kernels use seed .. seed + 3)
+ *   kind = (uint64) lowbias32(k5 ^ id) < thresh                                              thresh = 2^32: always; 0: never
+ *   d    = lo + (((uint64) lowbias32(k4 ^ id) * (uint64) (hi - lo + 1)) >> 32)               uniform over lo .. hi
+ *   e = episode[j],  last = ep_begin[e + 1] - 1
+ *   r    = min((int64) index[j] + d, last)      the episode's final step is the goal once the horizon passes its end
+ *   goal_index[j] = r,  goal_offset[j] = r - index[j],  goal_kind[j] = kind ? 1.0f : 0.0f    (each NULL = not written)
+ *   kind:  latent_goal[j][i] = step_goals[r][i]        MODE_F32: bits copied; MODE_BF16: expanded exactly, (uint32) bits << 16
+ *   !kind: latent_goal[j] is NOT written - it keeps the episode goal the sampling launch put there; goal_index / goal_offset are still written
+ * Before it is used as an address every index is clamped into its table, as in the sampling kernels: e into [0, E), ep_begin[e] and last into
+ * [0, S), index[j] into [ep_begin[e], last], r into [index[j], last].  Row j is a function of (seed, step, id, lo, hi, thresh) and the store only:
+ * not of B, the grid, or the order of the calls.  With ids = window [B] of a sweep and step = draw a goal belongs to the WINDOW, like its noise.
+ * One launch, B workgroups; 16-byte loads and stores where G % 4 == 0 (MODE_BF16: G % 8 == 0) and step_goals and latent_goal are 16-byte aligned,
+ * element by element otherwise; plain vector stores, no atomics.
+ *
+ * Before any launch, outputs untouched: MODE_ERR_BAD_ARG for a NULL descriptor or required pointer (step_goals, ep_begin, index, episode,
+ * latent_goal), a non-positive S, E, G or B, E > S, lo < 0, hi < lo, thresh > 2^32, a goal_dtype other than MODE_F32 / MODE_BF16;
+ * MODE_ERR_UNSUPPORTED for B > 65535 or G > 4096.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct ModeDataGoalDesc {
+  const void* step_goals;                /* [S, G] fp32 | bf16 */
+  const int32_t* ep_begin;               /* [E + 1] */
+  const int32_t* index; const int32_t* episode;   /* [B] each: what the sampling launch wrote */
+  const int32_t* ids;                    /* [B] or NULL: id = j */
+  uint64_t thresh;                       /* 0 .. 2^32: a row is relabelled with probability thresh / 2^32 */
+  int32_t goal_dtype;                    /* MODE_F32 | MODE_BF16 */
+  int32_t S, E, G, B;
+  uint32_t seed, step;
+  int32_t lo, hi;                        /* 0 <= lo <= hi: the horizon, in steps from the window's first step */
+  float* latent_goal;                    /* [B, G] fp32, updated in place */
+  int32_t* goal_index;                   /* [B] or NULL */
+  int32_t* goal_offset;                  /* [B] or NULL */
+  float* goal_kind;                      /* [B] or NULL */
+} ModeDataGoalDesc;
+int mode_data_relabel_goals(const ModeDataGoalDesc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

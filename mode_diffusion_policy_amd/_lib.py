@@ -240,6 +240,14 @@ class ModeActionErrorDesc(C.Structure):
                 ("B", c_i32), ("W", c_i32), ("A", c_i32), ("accumulate", c_i32)]
 
 
+class ModeDataGoalDesc(C.Structure):
+    """mode_data_relabel_goals (include/mode_hip.h, an addition to ABI 13): the store's per-step goal embeddings, the index / episode a sampling
+    launch wrote, the draws' (ids, seed, step, lo, hi, thresh) and the relabelled outputs."""
+    _fields_ = [("step_goals", c_vp), ("ep_begin", c_vp), ("index", c_vp), ("episode", c_vp), ("ids", c_vp), ("thresh", C.c_uint64),
+                ("goal_dtype", c_i32), ("S", c_i32), ("E", c_i32), ("G", c_i32), ("B", c_i32), ("seed", c_u32), ("step", c_u32), ("lo", c_i32),
+                ("hi", c_i32), ("latent_goal", c_vp), ("goal_index", c_vp), ("goal_offset", c_vp), ("goal_kind", c_vp)]
+
+
 MODE_GRAD_CHUNK = 16384
 
 
@@ -389,6 +397,7 @@ PROTOTYPES = {
     "mode_data_sample_windows": (C.c_int, [P(ModeDataStreamDesc), c_vp]),
     "mode_data_sweep_windows": (C.c_int, [P(ModeDataSweepDesc), c_vp]),
     "mode_action_error": (C.c_int, [P(ModeActionErrorDesc), c_vp]),
+    "mode_data_relabel_goals": (C.c_int, [P(ModeDataGoalDesc), c_vp]),
     "mode_edm_loss_masked": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_f32, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mode_lora_merge": (C.c_int, [P(ModeLoraDesc), c_vp]),
     "mode_lora_grad_workspace_bytes": (c_sz, [P(ModeLoraDesc)]),

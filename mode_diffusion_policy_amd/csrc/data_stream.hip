@@ -11,6 +11,9 @@
 // Validation reads the same store (include/mode_hip.h: mode_data_sweep_windows, mode_action_error; data.WindowSweep, validation.Validator): the sweep
 // kernel enumerates the windows instead of drawing them and shares the located-window row body with the kernel above, and the error kernel sums the
 // masked squared / absolute difference of two chunks into fp64 accumulators, one wave per element, in an order fixed by the shape.
+//
+// Hindsight goals (include/mode_hip.h: mode_data_relabel_goals): a second launch behind either sampling kernel replaces a drawn share of the rows'
+// episode goals by the stored embedding of a step a drawn number of steps ahead in the same episode.
 #include "mode_common.h"
 
 namespace mode {
@@ -124,6 +127,54 @@ __global__ __launch_bounds__(256) void data_sweep_windows_kernel(ModeDataSweepDe
   }
 }
 
+// Hindsight goal relabelling (include/mode_hip.h: mode_data_relabel_goals; data.WindowStream / data.WindowSweep with goal="hindsight"): runs after
+// either sampling kernel on its index / episode.  grid (B), 256 threads like them: every thread runs the row's two (uniform) draws and clamps, thread
+// 0 stores the three scalars, and a chosen row's G elements are shared - 16 bytes per thread where the row allows it (G = 512 fp32: 128 threads,
+// one load and one store each).  A row that is not chosen leaves latent_goal alone.  Latency-bound like the kernels above: no LDS, no atomics.
+__device__ __forceinline__ float bf16_bits_to_f32(uint32_t bits16) { return __builtin_bit_cast(float, bits16 << 16); }
+
+__global__ __launch_bounds__(256) void data_relabel_goals_kernel(ModeDataGoalDesc d) {
+  const int j = blockIdx.x, tid = threadIdx.x, G = d.G;
+  const uint32_t id = d.ids ? (uint32_t)d.ids[j] : (uint32_t)j;
+  const bool kind = (uint64_t)hash_u32(mode_stream_seed(d.seed + 5u, d.step) ^ id) < d.thresh;
+  const uint64_t span = (uint64_t)((long)d.hi - (long)d.lo + 1);
+  const long off = (long)d.lo + (long)(((uint64_t)hash_u32(mode_stream_seed(d.seed + 4u, d.step) ^ id) * span) >> 32);
+
+  const int e = min(max(d.episode[j], 0), d.E - 1);
+  const int first = min(max(d.ep_begin[e], 0), d.S - 1);
+  const int last = min(max(d.ep_begin[e + 1] - 1, first), d.S - 1);
+  const int start = min(max(d.index[j], first), last);
+  const int r = (int)min((long)start + off, (long)last);                      // off >= 0: start <= r <= last
+  if (tid == 0) {
+    if (d.goal_index) d.goal_index[j] = r;
+    if (d.goal_offset) d.goal_offset[j] = r - start;
+    if (d.goal_kind) d.goal_kind[j] = kind ? 1.0f : 0.0f;
+  }
+  if (!kind) return;                                                           // (uniform over the workgroup)
+
+  float* dst = d.latent_goal + (long)j * G;
+  const bool aligned = ((((uintptr_t)d.step_goals) | ((uintptr_t)d.latent_goal)) & 15u) == 0;
+  if (d.goal_dtype == MODE_F32) {
+    const uint32_t* src = (const uint32_t*)d.step_goals + (long)r * G;
+    if (aligned && (G & 3) == 0) {
+      for (int i = tid; i < (G >> 2); i += 256) ((uint4*)dst)[i] = ((const uint4*)src)[i];
+    } else {
+      for (int i = tid; i < G; i += 256) ((uint32_t*)dst)[i] = src[i];
+    }
+  } else {
+    const uint16_t* src = (const uint16_t*)d.step_goals + (long)r * G;
+    if (aligned && (G & 7) == 0) {
+      for (int i = tid; i < (G >> 3); i += 256) {
+        const uint4 v = ((const uint4*)src)[i];                                // 8 bf16, element 2 c in the low half of word c
+        ((float4*)dst)[2 * i] = make_float4(bf16_bits_to_f32(v.x & 0xffffu), bf16_bits_to_f32(v.x >> 16), bf16_bits_to_f32(v.y & 0xffffu), bf16_bits_to_f32(v.y >> 16));
+        ((float4*)dst)[2 * i + 1] = make_float4(bf16_bits_to_f32(v.z & 0xffffu), bf16_bits_to_f32(v.z >> 16), bf16_bits_to_f32(v.w & 0xffffu), bf16_bits_to_f32(v.w >> 16));
+      }
+    } else {
+      for (int i = tid; i < G; i += 256) dst[i] = bf16_bits_to_f32(src[i]);
+    }
+  }
+}
+
 // Masked error between two chunks, accumulated in fp64 (include/mode_hip.h: mode_action_error states the terms and the summation order).  256
 // threads = 4 waves, one wave per element i = w * A + a; its lanes stride the batch, so the loads of a wave are W * A floats apart - a validation
 // batch is a few thousand elements, latency-bound like the loss kernels.  No fused multiply-add anywhere: numpy fp64 reproduces every bit.
@@ -190,6 +241,17 @@ extern "C" int mode_data_sweep_windows(const ModeDataSweepDesc* d, void* stream)
   if (d->stride < 1 || d->first < 0 || d->first >= d->n_total) return MODE_ERR_BAD_ARG;
   if (d->B > 65535 || (long)d->W * d->A > 4096 || d->G > 4096) return MODE_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(data_sweep_windows_kernel, dim3(d->B), dim3(256), 0, (hipStream_t)stream, *d);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
+extern "C" int mode_data_relabel_goals(const ModeDataGoalDesc* d, void* stream) {
+  if (!d || !d->step_goals || !d->ep_begin || !d->index || !d->episode || !d->latent_goal) return MODE_ERR_BAD_ARG;
+  if (d->S <= 0 || d->E <= 0 || d->G <= 0 || d->B <= 0 || d->E > d->S) return MODE_ERR_BAD_ARG;
+  if (d->lo < 0 || d->hi < d->lo || d->thresh > (1ull << 32)) return MODE_ERR_BAD_ARG;
+  if (d->goal_dtype != MODE_F32 && d->goal_dtype != MODE_BF16) return MODE_ERR_BAD_ARG;
+  if (d->B > 65535 || d->G > 4096) return MODE_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(data_relabel_goals_kernel, dim3(d->B), dim3(256), 0, (hipStream_t)stream, *d);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }

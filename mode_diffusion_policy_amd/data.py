@@ -7,8 +7,16 @@ HIP launch (csrc/data_stream.hip; the expressions, bit for bit, are the comment 
 no host sync and no state: a run resumed at step ``t`` with the same seed and store sees the same windows, noise, sigma uniforms and shifts.
 
 Windows are drawn i.i.d. uniformly over all window starts, WITH replacement - this is not an epoch permutation: within any stretch of steps
-some starts repeat and others are not seen.  Reading CALVIN / LIBERO files, goal images and sharding the store across ranks are not part of this
-module (rank ``r`` of a data-parallel run may simply use ``seed + 16 * r``: the stream's keys use ``seed .. seed + 3``).
+some starts repeat and others are not seen.  Reading CALVIN / LIBERO files and sharding the store across ranks are not part of this module (rank
+``r`` of a data-parallel run may simply use ``seed + 16 * r``: the stream's keys use ``seed .. seed + 5``).
+
+Goal images (hindsight relabelling): a store that also holds one goal-space embedding per step (``add_episode(step_goals=[L, G])``, typically the
+image-goal encoder's output for that step's frame, computed offline) lets ``WindowStream`` / ``WindowSweep(goal="hindsight", goal_horizon=(lo,
+hi))`` replace a row's episode goal by the embedding of a step ``lo .. hi`` steps after the window's first one - the episode's final step once
+that passes its end - in ONE further launch (``mode_data_relabel_goals``) with counter-based draws: no host work, no sync, the same bits when
+step ``t`` is asked for again.  ``hindsight_prob`` mixes both kinds of goal row by row.  Not provided: encoding goal FRAMES inside the stream
+(``goal_index`` lets a caller gather ``store.frames_static[goal_index]`` and run an encoder of their own), fusing the relabel into the sampling
+launches, geometric or otherwise non-uniform horizon densities, disk formats, epoch permutations and a sharded store.
 
 Holding episodes out: ``split_episodes`` names a training and a validation set of episode ids, ``WindowStream(episodes=train_ids)`` draws from
 the first only, and ``WindowSweep(episodes=val_ids)`` enumerates every window of the second exactly once, a batch per launch
@@ -42,27 +50,33 @@ def _host(x, name: str) -> np.ndarray:
 
 
 class EpisodeStore:
-    """``add_episode(actions [L, A] float, goal [G] float, rgb_static=None, rgb_gripper=None)`` with frames uint8 ``[L, H, W, 3]`` /
-    ``[L, Hg, Wg, 3]``: either both cameras for every episode or for none, one geometry per camera.  ``finalize(normalize)`` uploads
+    """``add_episode(actions [L, A] float, goal [G] float, rgb_static=None, rgb_gripper=None, step_goals=None)`` with frames uint8
+    ``[L, H, W, 3]`` / ``[L, Hg, Wg, 3]``: either both cameras for every episode or for none, one geometry per camera; ``step_goals`` float
+    ``[L, G]``, the embedding of every step's observation in the goal space (finite), for every episode or for none.  ``finalize(normalize)`` uploads
 
         actions [S, A] fp32 (S = total steps), ep_begin [E + 1] int32, goals [E, G] fp32, frames_static / frames_gripper [S, H, W, 3] uint8,
-        lo / hi / scale [A] fp32 (None without normalisation)
+        lo / hi / scale [A] fp32 (None without normalisation), step_goals [S, G] in ``step_goal_dtype`` (None without them; torch.float32, or
+        torch.bfloat16 for half the memory: one round-to-nearest-even of the fp32 values, torch's, at upload)
 
     to ``device``; afterwards the store is read-only.  ``normalize="minmax"``: ``lo`` / ``hi`` per action dimension over all steps,
     ``scale = 2 / (hi - lo)`` computed in fp64 and rounded to fp32, 0 where ``hi == lo`` (such a dimension normalises to -1); ``(lo, hi)``: the
     caller's bounds, same formula; ``None``: the stream returns the stored bits.  Every refusal is a ``ValueError`` raised before anything is
     allocated on the device."""
 
-    def __init__(self, action_dim: int, goal_dim: int, device="cuda"):
+    def __init__(self, action_dim: int, goal_dim: int, device="cuda", step_goal_dtype=torch.float32):
         for name, v in (("action_dim", action_dim), ("goal_dim", goal_dim)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v <= 0:
                 raise ValueError(f"{name} must be a positive int, got {v!r}")
-        self.action_dim, self.goal_dim, self.device = int(action_dim), int(goal_dim), torch.device(device)
-        self._episodes = []                      # host side, until finalize(): (actions fp32, goal fp32, static u8 | None, gripper u8 | None)
+        if step_goal_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"step_goal_dtype must be torch.float32 or torch.bfloat16, got {step_goal_dtype}")
+        self.action_dim, self.goal_dim, self.device, self.step_goal_dtype = int(action_dim), int(goal_dim), torch.device(device), step_goal_dtype
+        # host side, until finalize(): (actions fp32, goal fp32, static u8 | None, gripper u8 | None, step goals fp32 | None)
+        self._episodes = []
         self._steps = 0
         self._cams: Optional[tuple] = None       # None until the first episode: then () or ((H, W), (Hg, Wg))
+        self._has_step_goals: Optional[bool] = None      # None until the first episode
         self.finalized = False
-        self.actions = self.ep_begin = self.goals = self.frames_static = self.frames_gripper = self.lo = self.hi = self.scale = None
+        self.actions = self.ep_begin = self.goals = self.frames_static = self.frames_gripper = self.lo = self.hi = self.scale = self.step_goals = None
         self.lengths: Optional[np.ndarray] = None
 
     @property
@@ -77,7 +91,7 @@ class EpisodeStore:
     def has_cameras(self) -> bool:
         return bool(self._cams)
 
-    def add_episode(self, actions, goal, rgb_static=None, rgb_gripper=None) -> None:
+    def add_episode(self, actions, goal, rgb_static=None, rgb_gripper=None, step_goals=None) -> None:
         if self.finalized:
             raise ValueError("the store is finalized: it is read-only")
         a, g = _host(actions, "actions"), _host(goal, "goal")
@@ -101,10 +115,23 @@ class EpisodeStore:
             cams = tuple(f.shape[1:3] for f in frames)
         if self._cams is not None and cams != self._cams:
             raise ValueError(f"camera presence and geometry must be the same for every episode: had {self._cams or 'no cameras'}, got {cams or 'no cameras'}")
+        sg = None
+        if step_goals is not None:
+            sg = _host(step_goals, "step_goals")
+            if sg.shape != (L, self.goal_dim) or not np.issubdtype(sg.dtype, np.floating):
+                raise ValueError(f"step_goals must be a float [{L}, {self.goal_dim}] array (one embedding per step), got {sg.dtype} {sg.shape}")
+            with np.errstate(over="ignore"):
+                sg = np.ascontiguousarray(sg, dtype=np.float32)
+            # bf16 rounds to nearest even: from 2^128 - 2^119 (halfway between the largest bf16 and 2^128) on, a finite fp32 becomes inf
+            if not np.isfinite(sg).all() or (self.step_goal_dtype == torch.bfloat16 and (np.abs(sg) >= np.float32(2.0 ** 128 - 2.0 ** 119)).any()):
+                raise ValueError(f"step_goals hold a non-finite value (or one that overflows {'bf16' if self.step_goal_dtype == torch.bfloat16 else 'fp32'})")
+        if self._has_step_goals is not None and (sg is not None) != self._has_step_goals:
+            raise ValueError(f"give step_goals for every episode or for none: had {'them' if self._has_step_goals else 'none'}, "
+                             f"got {'none' if sg is None else 'them'}")
         if self._steps + L >= 2 ** 31:
             raise ValueError(f"the store holds at most 2^31 - 1 steps, this episode would make {self._steps + L}")
-        self._cams = cams
-        self._episodes.append((a, np.ascontiguousarray(g, dtype=np.float32), *(None if f is None else np.ascontiguousarray(f) for f in frames)))
+        self._cams, self._has_step_goals = cams, sg is not None
+        self._episodes.append((a, np.ascontiguousarray(g, dtype=np.float32), *(None if f is None else np.ascontiguousarray(f) for f in frames), sg))
         self._steps += L
 
     def _bounds(self, normalize):
@@ -148,12 +175,16 @@ class EpisodeStore:
         fr = [None, None]
         for q in range(2 if self._cams else 0):
             fr[q] = torch.empty(S, *self._cams[q], 3, dtype=torch.uint8, device=dev)
+        if self._has_step_goals:
+            self.step_goals = torch.empty(S, self.goal_dim, dtype=self.step_goal_dtype, device=dev)
         for ep, b in zip(self._episodes, begin[:-1]):            # episode by episode: the host never holds a second copy of the frames
             n = ep[0].shape[0]
             self.actions[b: b + n].copy_(torch.from_numpy(ep[0]))
             for q in range(2):
                 if fr[q] is not None:
                     fr[q][b: b + n].copy_(torch.from_numpy(ep[2 + q]))
+            if self.step_goals is not None:                      # fp32 -> bf16: torch's round-to-nearest-even, wherever the copy converts
+                self.step_goals[b: b + n].copy_(torch.from_numpy(ep[4]))
         self.frames_static, self.frames_gripper = fr
         if bounds is not None:
             self.lo, self.hi, self.scale = (torch.from_numpy(v).to(dev) for v in bounds)
@@ -246,6 +277,62 @@ def _check_window_args(store, batch_size, window, seed, pad, camera_transforms, 
     return camera_transforms
 
 
+_GOALS = ("episode", "hindsight")
+MAX_HORIZON = 2 ** 31 - 1
+
+
+def _check_goal_args(store: EpisodeStore, goal, goal_horizon, hindsight_prob, who: str, sweep: bool):
+    """The goal keywords WindowStream and WindowSweep share -> None for ``goal="episode"``, else ``(lo, hi, thresh)`` of
+    ``mode_data_relabel_goals``.  A sweep's horizon may also be an int ``d`` (lo = hi = d) or ``"last"`` (the episode's final step)."""
+    if not isinstance(goal, str) or goal not in _GOALS:
+        raise ValueError(f"goal must be one of {_GOALS}, got {goal!r}")
+    try:
+        prob = float(hindsight_prob)
+    except (TypeError, ValueError):
+        prob = float("nan")
+    if isinstance(hindsight_prob, bool) or not 0.0 <= prob <= 1.0:
+        raise ValueError(f"hindsight_prob must lie in [0, 1], got {hindsight_prob!r}")
+    if goal == "episode":
+        if goal_horizon is not None:
+            raise ValueError(f"goal_horizon={goal_horizon!r} needs goal='hindsight': goal='episode' draws no goal step")
+        return None
+    if store.step_goals is None:
+        raise ValueError(f"{who}(goal='hindsight') needs a store with step_goals (EpisodeStore.add_episode(step_goals=))")
+    if goal_horizon is None:
+        raise ValueError(f"{who}(goal='hindsight') needs goal_horizon=(lo, hi), offsets in steps from the window's first step")
+    is_int = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))
+    if sweep and isinstance(goal_horizon, str) and goal_horizon == "last":
+        lo = hi = MAX_HORIZON
+    elif sweep and is_int(goal_horizon):
+        lo = hi = int(goal_horizon)
+    elif isinstance(goal_horizon, (tuple, list)) and len(goal_horizon) == 2 and all(is_int(v) for v in goal_horizon):
+        lo, hi = (int(v) for v in goal_horizon)
+    else:
+        raise ValueError(f"goal_horizon must be (lo, hi), two ints{', an int or last' if sweep else ''}, got {goal_horizon!r}")
+    if not 0 <= lo <= hi <= MAX_HORIZON:
+        raise ValueError(f"goal_horizon needs 0 <= lo <= hi <= 2^31 - 1, got {goal_horizon!r}")
+    return lo, hi, int(round(prob * 2.0 ** 32))
+
+
+def _relabel_goals(store: EpisodeStore, out: dict, ids: Optional[torch.Tensor], seed: int, step: int, plan) -> None:
+    """One ``mode_data_relabel_goals`` launch behind the sampling launch that filled ``out``: ``latent_goal`` updated in place, ``goal_index`` /
+    ``goal_offset`` / ``goal_kind`` added.  ``ids`` None: a row's draws are keyed by its place; a sweep passes its ``window``."""
+    from . import _lib as L
+    from .engine import _stream
+    lo, hi, thresh = plan
+    B, dev = out["index"].shape[0], store.device
+    out["goal_index"], out["goal_offset"] = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(2))
+    out["goal_kind"] = torch.empty(B, dtype=torch.float32, device=dev)
+    d = L.ModeDataGoalDesc(step_goals=store.step_goals.data_ptr(), ep_begin=store.ep_begin.data_ptr(), index=out["index"].data_ptr(),
+                           episode=out["episode"].data_ptr(), ids=None if ids is None else ids.data_ptr(), thresh=thresh,
+                           goal_dtype=L.MODE_BF16 if store.step_goals.dtype == torch.bfloat16 else L.MODE_F32, S=store.step_goals.shape[0],
+                           E=store.goals.shape[0], G=store.goal_dim, B=B, seed=seed, step=step, lo=lo, hi=hi,
+                           latent_goal=out["latent_goal"].data_ptr(), goal_index=out["goal_index"].data_ptr(),
+                           goal_offset=out["goal_offset"].data_ptr(), goal_kind=out["goal_kind"].data_ptr())
+    with torch.cuda.device(dev):
+        L.check(L.load().mode_data_relabel_goals(C.byref(d), _stream()), "data_relabel_goals")
+
+
 def _frames_of(store: EpisodeStore, tr, shifts, index: torch.Tensor, B: int, frame_dtype) -> dict:
     """``rgb_obs`` of a batch: one ``mode_frames_preprocess`` launch that reads the store rows ``index`` (``shifts[q]`` None: no shift)."""
     from . import camera
@@ -271,11 +358,21 @@ class WindowStream:
 
     ``episodes=ids`` (``split_episodes``) draws from the listed episodes only: an episode that is not listed gets no starts, and the kernel's search
     never finds an episode without starts.  None, the default, builds the table of all episodes.  The normalisation stays the store's own - the
-    bounds of ``finalize("minmax")`` include the episodes left out here; ``finalize((lo, hi))`` avoids that."""
+    bounds of ``finalize("minmax")`` include the episodes left out here; ``finalize((lo, hi))`` avoids that.
+
+    ``goal="hindsight", goal_horizon=(lo, hi)`` (ints, ``0 <= lo <= hi <= 2^31 - 1``; the store must hold ``step_goals``) relabels in one further
+    launch (``mode_data_relabel_goals`` in include/mode_hip.h states the draws bit for bit): row ``j`` is chosen with probability
+    ``hindsight_prob`` (``thresh = round(hindsight_prob * 2^32)``), draws an offset uniformly in ``lo .. hi`` and, if chosen, gets
+    ``latent_goal[j] = store.step_goals[goal_index[j]]`` with ``goal_index = min(index + offset, the episode's last row)``; a row that is not
+    chosen keeps its episode's goal - both modalities mixed row by row in one forward.  The batch gains ``goal_index``, ``goal_offset`` (int32
+    [B], written for every row) and ``goal_kind`` (fp32 [B], 1 = relabelled).  The draws use the keys ``seed + 4`` and ``seed + 5`` and depend on
+    ``(seed, t, j)`` only.  ``goal="episode"``, the default, is the stream without any of this: the same launches, keys and bits."""
 
     def __init__(self, store: EpisodeStore, batch_size: int, window: int, seed: int = 0, pad: str = "hold",
-                 camera_transforms: Optional[Sequence[CameraTransform]] = None, noise: bool = True, frame_dtype=torch.float32, episodes=None):
+                 camera_transforms: Optional[Sequence[CameraTransform]] = None, noise: bool = True, frame_dtype=torch.float32, episodes=None,
+                 goal: str = "episode", goal_horizon=None, hindsight_prob: float = 1.0):
         camera_transforms = _check_window_args(store, batch_size, window, seed, pad, camera_transforms, frame_dtype, "WindowStream")
+        self.goal, self._goal_plan = goal, _check_goal_args(store, goal, goal_horizon, hindsight_prob, "WindowStream", sweep=False)
         n_e = store.lengths if pad == "hold" else np.maximum(0, store.lengths - window + 1)
         starts, n_total = _start_table(n_e, episodes, f"no window of {window} steps fits any "
                                        f"{'episode' if episodes is None else 'selected episode'} (pad={pad!r}): nothing to draw")
@@ -310,6 +407,8 @@ class WindowStream:
             d.shift_pad[q] = tr[q].shift_pad if tr is not None else 0
         with torch.cuda.device(dev):
             L.check(L.load().mode_data_sample_windows(C.byref(d), _stream()), "data_sample_windows")
+        if self._goal_plan is not None:
+            _relabel_goals(st, out, None, self.seed, int(step), self._goal_plan)
         if tr is not None:
             out["rgb_obs"] = _frames_of(st, tr, shifts, out["index"], B, self.frame_dtype)
             out["shifts"] = {"rgb_static": shifts[0], "rgb_gripper": shifts[1]}
@@ -334,11 +433,18 @@ class WindowSweep:
 
     A row's noise belongs to its WINDOW, not to its place in a batch - ``noise[j] == rollout.env_noise([(seed + 1 + window[j] * 0x9E3779B9) %
     2**32], [draw], W, A, noise_scale)[0]`` - so a sweep gives a window the same noise at every batch size, and ``draw`` numbers independent
-    repeats.  There is no ``u``.  The normalisation is the store's own (see ``WindowStream``)."""
+    repeats.  There is no ``u``.  The normalisation is the store's own (see ``WindowStream``).
+
+    ``goal="hindsight"`` with ``goal_horizon=(lo, hi)``, an int ``d`` (``lo = hi = d``) or ``"last"`` (``lo = hi = 2^31 - 1``: the episode's final
+    step) and ``hindsight_prob`` relabel as in ``WindowStream``, with the draws keyed by ``(seed, draw, window[j])``: a window's goal belongs to
+    the window like its noise, the same at every batch size, and a padding row is relabelled like the window it repeats.  Such a sweep validates
+    the image-goal modality; ``goal="episode"``, the default, is the sweep without any of this."""
 
     def __init__(self, store: EpisodeStore, batch_size: int, window: int, stride: int = 1, pad: str = "hold", episodes=None, seed: int = 0,
-                 camera_transforms: Optional[Sequence[CameraTransform]] = None, frame_dtype=torch.float32, noise_scale: float = 1.0):
+                 camera_transforms: Optional[Sequence[CameraTransform]] = None, frame_dtype=torch.float32, noise_scale: float = 1.0,
+                 goal: str = "episode", goal_horizon=None, hindsight_prob: float = 1.0):
         camera_transforms = _check_window_args(store, batch_size, window, seed, pad, camera_transforms, frame_dtype, "WindowSweep")
+        self.goal, self._goal_plan = goal, _check_goal_args(store, goal, goal_horizon, hindsight_prob, "WindowSweep", sweep=True)
         if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
             raise ValueError(f"stride must be an int >= 1, got {stride!r}")
         if isinstance(noise_scale, bool) or not np.isfinite(float(noise_scale)):
@@ -382,6 +488,8 @@ class WindowSweep:
                                 valid=p(out["valid"]), window=p(out["window"]), noise=p(out["noise"]))
         with torch.cuda.device(dev):
             L.check(L.load().mode_data_sweep_windows(C.byref(d), _stream()), "data_sweep_windows")
+        if self._goal_plan is not None:
+            _relabel_goals(st, out, out["window"], self.seed, int(draw), self._goal_plan)
         if self.camera_transforms is not None:
             out["rgb_obs"] = _frames_of(st, self.camera_transforms, (None, None), out["index"], B, self.frame_dtype)
         return out

@@ -98,8 +98,13 @@ class Validator:
     the store's raw action units, ``unit[a] = 1 / (double) scale[a]``, 0 where ``scale[a] == 0``: a constant dimension (it normalises to -1 whatever
     the action) contributes NO error.  ``raw_units=False`` or a store without normalisation: the error of the values the model sees.
 
-    Not here: a held-out score-matching loss per noise level (``GCDenoiser.loss`` on ``WindowSweep`` batches gives one), goal images, disk formats,
-    and gathering results across ranks - rank ``r`` of ``n`` may run the batches ``r, r + n, ...`` itself and sum the returned accumulators
+    The goal is whatever the sweep puts into ``batch["latent_goal"]``: a ``WindowSweep(goal="hindsight", goal_horizon=...)`` on a store with
+    ``step_goals`` validates the image-goal modality (a future step's stored embedding as the goal; ``"last"``: the episode's final step), the
+    default sweep the episode's own goal.  Nothing here changes for it.
+
+    Not here: a held-out score-matching loss per noise level (``GCDenoiser.loss`` on ``WindowSweep`` batches gives one), encoding goal frames (the
+    sweep gathers stored embeddings; ``batch["goal_index"]`` names the frame for an encoder of the caller's), disk formats, and gathering results
+    across ranks - rank ``r`` of ``n`` may run the batches ``r, r + n, ...`` itself and sum the returned accumulators
     (``ValidationResult.from_sums``)."""
 
     def __init__(self, denoiser, sweep: WindowSweep, embed: Callable[[dict], dict], num_sampling_steps: int = 10, sigma_min: float = 0.001,
