@@ -1466,6 +1466,58 @@ typedef struct ModeDataGoalDesc {
 } ModeDataGoalDesc;
 int mode_data_relabel_goals(const ModeDataGoalDesc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Held-out denoising error per noise level (csrc/data_stream.hip; validation.LevelValidator).  An addition to ABI 13: two new structs and exports,
+ * nothing existing changes - no struct keeps another layout and mode_action_error keeps its bits (the two error kernels share ONE device function
+ * for the lane's terms and the butterfly).
+ *
+ * mode_val_noise_levels: the launch between mode_data_sweep_windows (noise_scale = 1) and the denoiser.  actions, noise [B, W, A] fp32, window [B]
+ * int32 (what the sweep wrote), sigmas [K] fp32 (a device table), draw (uint32).  Row j (0 <= j < B), element i (0 <= i < W * A):
+ *   level[j] = ((uint32) window[j] + draw) % K            the sum in uint32 arithmetic modulo 2^32
+ *   sigma[j] = sigmas[level[j]]
+ *   x[j][i]  = actions[j][i] + noise[j][i] * sigma[j]     one fp32 product and one fp32 sum, each rounded on its own (no contraction)
+ * x is the noised input as GCDenoiser.forward takes it - NOT multiplied by c_in (MoDeDiT.denoise applies c_in itself).  Row j is a function of
+ * (window[j], draw, sigmas) and the row's own actions and noise only: not of B, nor of the row's place in a batch.  Over K consecutive draws a
+ * window therefore meets every level exactly once, each time with that draw's own noise.  A padding row of the sweep (valid = 0) gets a level like
+ * any other row; its weight excludes it later.  One launch, B workgroups, plain vector stores, no atomics.
+ * Before any launch, outputs untouched: MODE_ERR_BAD_ARG for a NULL descriptor or pointer or a non-positive B, W, A or K; MODE_ERR_UNSUPPORTED for
+ * B > 65535, W * A > 4096 or K > 256. */
+typedef struct ModeValLevelsDesc {
+  const float* actions; const float* noise; /* [B, W, A] */
+  const int32_t* window;                    /* [B] */
+  const float* sigmas;                      /* [K] */
+  int32_t B, W, A, K;
+  uint32_t draw;
+  int32_t* level;                           /* [B] */
+  float* sigma;                             /* [B] */
+  float* x;                                 /* [B, W, A] */
+} ModeValLevelsDesc;
+int mode_val_noise_levels(const ModeValLevelsDesc* d, void* stream);
+
+/* mode_level_error: mode_action_error binned by a level per row.  pred, target [B, W, A] fp32; mask [B, W] or NULL, weight [B] or NULL; level [B]
+ * int32; sq [K, W * A] fp64, cnt [K, W] fp64.  c[b][w] = (double) (wt[b] * m[b][w]) and e = (double) (pred - target) are formed by exactly the
+ * expressions of mode_action_error (an absent factor is 1, a value that is not > 0 counts as 0); there is no unit factor and no absolute error.
+ *   sq[k][w * A + a] = sum over {b : level[b] == k} of c (e * e),   cnt[k][w] = sum over {b : level[b] == k} of c
+ * A row whose level lies outside [0, K) counts nowhere.  Summation order, fixed by (B, W, A, K): one wave owns the pair (k, i = w * A + a).  Lane l
+ * runs over b = l, l + 64, ... ascending and skips every row with level[b] != k or c == 0 (pred and target may hold anything there, NaN included);
+ * for the others t = c * (e * e) (t = c), acc = acc + t, every product and sum rounded to fp64 on its own.  The 64 lane sums are added by the xor
+ * butterfly 32, 16, 8, 4, 2, 1; the wave with a == 0 sums cnt[k][w] the same way.  accumulate as in mode_action_error.  No atomics: the stored
+ * bits depend on (B, W, A, K) and the order of the calls only.  Level k's slice of sq / cnt has exactly the bits mode_action_error gives with
+ * unit = NULL and weight'[b] = level[b] == k ? weight[b] : 0.
+ * MODE_ERR_BAD_ARG before any launch for a NULL descriptor, pred, target, level, sq or cnt or a non-positive B, W, A or K; MODE_ERR_UNSUPPORTED for
+ * B > 65535, W * A > 4096 or K > 256 (K outside 1 .. 256 is refused one way or the other). */
+typedef struct ModeLevelErrorDesc {
+  const float* pred; const float* target;   /* [B, W, A] */
+  const float* mask;                        /* [B, W] or NULL */
+  const float* weight;                      /* [B] or NULL */
+  const int32_t* level;                     /* [B] */
+  double* sq;                               /* [K, W * A] */
+  double* cnt;                              /* [K, W] */
+  int32_t B, W, A, K;
+  int32_t accumulate;                       /* 0: store, 1: add to what is there */
+} ModeLevelErrorDesc;
+int mode_level_error(const ModeLevelErrorDesc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

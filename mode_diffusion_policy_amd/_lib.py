@@ -248,6 +248,20 @@ class ModeDataGoalDesc(C.Structure):
                 ("hi", c_i32), ("latent_goal", c_vp), ("goal_index", c_vp), ("goal_offset", c_vp), ("goal_kind", c_vp)]
 
 
+class ModeValLevelsDesc(C.Structure):
+    """mode_val_noise_levels (include/mode_hip.h, an addition to ABI 13): a swept batch's actions / noise / window, the sigma table and the draw;
+    the rows' level, sigma and noised input."""
+    _fields_ = [("actions", c_vp), ("noise", c_vp), ("window", c_vp), ("sigmas", c_vp), ("B", c_i32), ("W", c_i32), ("A", c_i32), ("K", c_i32),
+                ("draw", c_u32), ("level", c_vp), ("sigma", c_vp), ("x", c_vp)]
+
+
+class ModeLevelErrorDesc(C.Structure):
+    """mode_level_error (include/mode_hip.h, an addition to ABI 13): mode_action_error's chunks and factors, a level per row and the fp64
+    accumulators per level."""
+    _fields_ = [("pred", c_vp), ("target", c_vp), ("mask", c_vp), ("weight", c_vp), ("level", c_vp), ("sq", c_vp), ("cnt", c_vp), ("B", c_i32),
+                ("W", c_i32), ("A", c_i32), ("K", c_i32), ("accumulate", c_i32)]
+
+
 MODE_GRAD_CHUNK = 16384
 
 
@@ -398,6 +412,8 @@ PROTOTYPES = {
     "mode_data_sweep_windows": (C.c_int, [P(ModeDataSweepDesc), c_vp]),
     "mode_action_error": (C.c_int, [P(ModeActionErrorDesc), c_vp]),
     "mode_data_relabel_goals": (C.c_int, [P(ModeDataGoalDesc), c_vp]),
+    "mode_val_noise_levels": (C.c_int, [P(ModeValLevelsDesc), c_vp]),
+    "mode_level_error": (C.c_int, [P(ModeLevelErrorDesc), c_vp]),
     "mode_edm_loss_masked": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_f32, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mode_lora_merge": (C.c_int, [P(ModeLoraDesc), c_vp]),
     "mode_lora_grad_workspace_bytes": (c_sz, [P(ModeLoraDesc)]),

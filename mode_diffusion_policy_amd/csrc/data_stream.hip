@@ -12,6 +12,9 @@
 // kernel enumerates the windows instead of drawing them and shares the located-window row body with the kernel above, and the error kernel sums the
 // masked squared / absolute difference of two chunks into fp64 accumulators, one wave per element, in an order fixed by the shape.
 //
+// The held-out denoising error per noise level (include/mode_hip.h: mode_val_noise_levels, mode_level_error; validation.LevelValidator): a prep
+// launch gives every swept window a level of a sigma table and its noised input, and the error kernel's body, shared, sums per level.
+//
 // Hindsight goals (include/mode_hip.h: mode_data_relabel_goals): a second launch behind either sampling kernel replaces a drawn share of the rows'
 // episode goals by the stored embedding of a step a drawn number of steps ahead in the same episode.
 #include "mode_common.h"
@@ -184,34 +187,83 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return v;
 }
 
-__global__ __launch_bounds__(256) void action_error_kernel(ModeActionErrorDesc d) {
+// One lane's share of element i = w * A + a and the butterfly over the wave: ONE body for mode_action_error and mode_level_error, so the two kernels
+// cannot drift apart in a rounding.  `level` (or nullptr: every row) restricts the rows to those of level k; `unit` (or nullptr) is mode_action_error's.
+struct ErrorSums { double sq, ab, cn; };
+__device__ __forceinline__ ErrorSums masked_error_sums(const float* pred, const float* target, const float* mask, const float* weight, const double* unit,
+                                                       const int32_t* level, int k, int B, int W, int A, int i, int lane) {
 #pragma clang fp contract(off)
-  const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6), WA = d.W * d.A;
-  if (i >= WA) return;                                                       // (wave-uniform)
-  const int w = i / d.A, a = i - w * d.A;
-  const double un = d.unit ? d.unit[a] : 1.0;
+  const int WA = W * A, w = i / A, a = i - w * A;
+  const double un = unit ? unit[a] : 1.0;
   double sq = 0.0, ab = 0.0, cn = 0.0;
-  for (int b = lane; b < d.B; b += 64) {
-    const float mr = d.mask ? d.mask[(long)b * d.W + w] : 1.f, m = mr > 0.f ? mr : 0.f;
-    const float wr = d.weight ? d.weight[b] : 1.f, wt = wr > 0.f ? wr : 0.f;
+  for (int b = lane; b < B; b += 64) {
+    if (level && level[b] != k) continue;                                    // another level's row: nothing of it is read
+    const float mr = mask ? mask[(long)b * W + w] : 1.f, m = mr > 0.f ? mr : 0.f;
+    const float wr = weight ? weight[b] : 1.f, wt = wr > 0.f ? wr : 0.f;
     const float cf = wt * m;
     if (!(cf > 0.f)) continue;                                               // c == 0: the term is skipped, not multiplied
     const long at = (long)b * WA + i;
-    const float df = d.pred[at] - d.target[at];
+    const float df = pred[at] - target[at];
     const double c = (double)cf;
-    const double e = d.unit ? (double)df * un : (double)df;
+    const double e = unit ? (double)df * un : (double)df;
     const double t2 = c * (e * e), t1 = c * fabs(e);
     sq = sq + t2;
     ab = ab + t1;
     cn = cn + c;
   }
-  sq = wave_sum_f64(sq);
-  ab = wave_sum_f64(ab);
-  cn = wave_sum_f64(cn);
+  return {wave_sum_f64(sq), wave_sum_f64(ab), wave_sum_f64(cn)};
+}
+
+__global__ __launch_bounds__(256) void action_error_kernel(ModeActionErrorDesc d) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6), WA = d.W * d.A;
+  if (i >= WA) return;                                                       // (wave-uniform)
+  const int w = i / d.A, a = i - w * d.A;
+  const ErrorSums s = masked_error_sums(d.pred, d.target, d.mask, d.weight, d.unit, nullptr, 0, d.B, d.W, d.A, i, lane);
   if (lane == 0) {
-    d.sq[i] = d.accumulate ? d.sq[i] + sq : sq;
-    d.ab[i] = d.accumulate ? d.ab[i] + ab : ab;
-    if (a == 0) d.cnt[w] = d.accumulate ? d.cnt[w] + cn : cn;
+    d.sq[i] = d.accumulate ? d.sq[i] + s.sq : s.sq;
+    d.ab[i] = d.accumulate ? d.ab[i] + s.ab : s.ab;
+    if (a == 0) d.cnt[w] = d.accumulate ? d.cnt[w] + s.cn : s.cn;
+  }
+}
+
+// The noised input of a held-out window at its level of this draw (include/mode_hip.h: mode_val_noise_levels).  grid (B), 256 threads like the sweep:
+// every thread forms the row's (uniform) level and reads its sigma - level < K by the modulus, so the table read is in bounds -, and the threads share
+// the row's W * A elements.  The pragma keeps the product and the sum two roundings (see normalise_unfused).
+__device__ __forceinline__ float noised_unfused(float a, float z, float sigma) {
+#pragma clang fp contract(off)
+  const float t = z * sigma;
+  return a + t;
+}
+
+__global__ __launch_bounds__(256) void val_noise_levels_kernel(ModeValLevelsDesc d) {
+  const int j = blockIdx.x, tid = threadIdx.x, WA = d.W * d.A;
+  const uint32_t lv = ((uint32_t)d.window[j] + d.draw) % (uint32_t)d.K;
+  const float sg = d.sigmas[lv];
+  if (tid == 0) {
+    d.level[j] = (int32_t)lv;
+    d.sigma[j] = sg;
+  }
+  const float* a = d.actions + (long)j * WA;
+  const float* z = d.noise + (long)j * WA;
+  float* x = d.x + (long)j * WA;
+  for (int i = tid; i < WA; i += 256) x[i] = noised_unfused(a[i], z[i], sg);
+}
+
+// mode_action_error binned by level (include/mode_hip.h: mode_level_error): the same 4 waves per workgroup, wave g of the grid owns the pair
+// (k, i) = (g / (W * A), g % (W * A)) and runs the shared body over the rows of level k.  K * W * A waves, each reading level [B] once: at K = 16,
+// W * A = 70, B = 128 that is 1120 waves over 72 KB - latency-bound like the kernel above.
+__global__ __launch_bounds__(256) void level_error_kernel(ModeLevelErrorDesc d) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63, g = blockIdx.x * 4 + (threadIdx.x >> 6), WA = d.W * d.A;
+  if (g >= d.K * WA) return;                                                 // (wave-uniform)
+  const int k = g / WA, i = g - k * WA, w = i / d.A, a = i - w * d.A;
+  const ErrorSums s = masked_error_sums(d.pred, d.target, d.mask, d.weight, nullptr, d.level, k, d.B, d.W, d.A, i, lane);
+  if (lane == 0) {
+    double* sq = d.sq + (long)k * WA + i;
+    double* cn = d.cnt + (long)k * d.W + w;
+    *sq = d.accumulate ? *sq + s.sq : s.sq;
+    if (a == 0) *cn = d.accumulate ? *cn + s.cn : s.cn;
   }
 }
 
@@ -261,6 +313,24 @@ extern "C" int mode_action_error(const ModeActionErrorDesc* d, void* stream) {
   if (d->B <= 0 || d->W <= 0 || d->A <= 0) return MODE_ERR_BAD_ARG;
   if (d->B > 65535 || (long)d->W * d->A > 4096) return MODE_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(action_error_kernel, dim3((unsigned)((d->W * d->A + 3) / 4)), dim3(256), 0, (hipStream_t)stream, *d);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
+extern "C" int mode_val_noise_levels(const ModeValLevelsDesc* d, void* stream) {
+  if (!d || !d->actions || !d->noise || !d->window || !d->sigmas || !d->level || !d->sigma || !d->x) return MODE_ERR_BAD_ARG;
+  if (d->B <= 0 || d->W <= 0 || d->A <= 0 || d->K <= 0) return MODE_ERR_BAD_ARG;
+  if (d->B > 65535 || (long)d->W * d->A > 4096 || d->K > 256) return MODE_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(val_noise_levels_kernel, dim3(d->B), dim3(256), 0, (hipStream_t)stream, *d);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
+extern "C" int mode_level_error(const ModeLevelErrorDesc* d, void* stream) {
+  if (!d || !d->pred || !d->target || !d->level || !d->sq || !d->cnt) return MODE_ERR_BAD_ARG;
+  if (d->B <= 0 || d->W <= 0 || d->A <= 0 || d->K <= 0) return MODE_ERR_BAD_ARG;
+  if (d->B > 65535 || (long)d->W * d->A > 4096 || d->K > 256) return MODE_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(level_error_kernel, dim3((unsigned)((d->K * d->W * d->A + 3) / 4)), dim3(256), 0, (hipStream_t)stream, *d);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }

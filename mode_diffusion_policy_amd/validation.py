@@ -5,10 +5,15 @@ held-out windows and measure the error between the sampled chunk and the demonst
 path ``ChunkedRolloutPolicy.denoise_actions`` takes (one hipGraph replay for the fused samplers), and ``mode_action_error`` (csrc/data_stream.hip;
 formulas and summation order: include/mode_hip.h) adds the batch's masked squared and absolute errors into fp64 accumulators on the device.  The
 caller's ``float(result["mse"])`` is the only host sync of a validation pass.
+
+``LevelValidator`` is the other held-out signal: the denoising (score-matching) loss itself, per noise level.  ``mode_val_noise_levels`` gives every
+swept window a level of a fixed sigma table and its noised input, one denoiser evaluation per batch predicts the clean chunk, and ``mode_level_error``
+adds the masked squared error into fp64 accumulators per level - the same summation body as ``mode_action_error``, the same no-read-back loop.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Callable, Optional
 
 import torch
@@ -102,10 +107,9 @@ class Validator:
     ``step_goals`` validates the image-goal modality (a future step's stored embedding as the goal; ``"last"``: the episode's final step), the
     default sweep the episode's own goal.  Nothing here changes for it.
 
-    Not here: a held-out score-matching loss per noise level (``GCDenoiser.loss`` on ``WindowSweep`` batches gives one), encoding goal frames (the
-    sweep gathers stored embeddings; ``batch["goal_index"]`` names the frame for an encoder of the caller's), disk formats, and gathering results
-    across ranks - rank ``r`` of ``n`` may run the batches ``r, r + n, ...`` itself and sum the returned accumulators
-    (``ValidationResult.from_sums``)."""
+    The held-out score-matching loss per noise level is ``LevelValidator``'s, below.  Not here: encoding goal frames (the sweep gathers stored
+    embeddings; ``batch["goal_index"]`` names the frame for an encoder of the caller's), disk formats, and gathering results across ranks - rank
+    ``r`` of ``n`` may run the batches ``r, r + n, ...`` itself and sum the returned accumulators (``ValidationResult.from_sums``)."""
 
     def __init__(self, denoiser, sweep: WindowSweep, embed: Callable[[dict], dict], num_sampling_steps: int = 10, sigma_min: float = 0.001,
                  sigma_max: float = 80.0, noise_scheduler: str = "exponential", sampler_type: str = "ddim", raw_units: bool = True):
@@ -156,3 +160,235 @@ class Validator:
             for m, was in modes:
                 m.training = was
         return ValidationResult.from_sums(sq, ab, cnt)
+
+
+# ------------------------------------------------------------------------------------------------ held-out denoising loss per noise level
+MAX_LEVELS = 256           # the kernels' limit (include/mode_hip.h)
+
+
+def _same(name: str, who: str, t, shape, dt, dev) -> None:
+    if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous {dt} {shape} tensor on {dev}, got "
+                         f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
+
+
+def noise_levels(actions: torch.Tensor, noise: torch.Tensor, window: torch.Tensor, sigmas: torch.Tensor, draw: int = 0):
+    """``mode_val_noise_levels`` on the current stream -> ``(level [B] int32, sigma [B] fp32, noised [B, W, A] fp32)``:
+
+        level[j] = (window[j] + draw) mod 2^32 mod K,   sigma[j] = sigmas[level[j]],   noised[j] = actions[j] + noise[j] * sigma[j]
+
+    (one fp32 product and one fp32 sum per element, unfused).  ``actions``, ``noise`` [B, W, A] fp32, ``window`` [B] int32, ``sigmas`` [K] fp32,
+    ``K <= 256``, all contiguous on one ROCm device.  A row depends on its window number, the draw and the table only."""
+    from . import _lib as L
+    from .engine import _stream
+    if not torch.is_tensor(actions) or actions.dim() != 3 or actions.device.type != "cuda":
+        raise ValueError(f"noise_levels: actions must be a [B, W, A] tensor on a ROCm device, got {tuple(getattr(actions, 'shape', ()))}")
+    if isinstance(draw, bool) or not isinstance(draw, int) or not 0 <= draw < 2 ** 32:
+        raise ValueError(f"draw must be an int in 0..2^32 - 1, got {draw!r}")
+    B, W, A = actions.shape
+    K = sigmas.shape[0] if torch.is_tensor(sigmas) and sigmas.dim() == 1 else 0
+    if not 1 <= B <= MAX_BATCH or W < 1 or A < 1 or W * A > MAX_WINDOW_FLOATS or not 1 <= K <= MAX_LEVELS:
+        raise ValueError(f"noise_levels: needs 1 <= B <= {MAX_BATCH}, 1 <= W * A <= {MAX_WINDOW_FLOATS} and 1 <= K <= {MAX_LEVELS}, got {(B, W, A)}, K = {K}")
+    dev = actions.device
+    for name, t, shape, dt in (("actions", actions, (B, W, A), torch.float32), ("noise", noise, (B, W, A), torch.float32),
+                               ("window", window, (B,), torch.int32), ("sigmas", sigmas, (K,), torch.float32)):
+        _same(name, "noise_levels", t, shape, dt, dev)
+    level = torch.empty(B, dtype=torch.int32, device=dev)
+    sigma = torch.empty(B, dtype=torch.float32, device=dev)
+    x = torch.empty(B, W, A, dtype=torch.float32, device=dev)
+    d = L.ModeValLevelsDesc(actions=actions.data_ptr(), noise=noise.data_ptr(), window=window.data_ptr(), sigmas=sigmas.data_ptr(), B=B, W=W, A=A, K=K,
+                            draw=draw, level=level.data_ptr(), sigma=sigma.data_ptr(), x=x.data_ptr())
+    with torch.cuda.device(dev):
+        L.check(L.load().mode_val_noise_levels(C.byref(d), _stream()), "val_noise_levels")
+    return level, sigma, x
+
+
+def level_error(pred: torch.Tensor, target: torch.Tensor, level: torch.Tensor, sq: torch.Tensor, cnt: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                weight: Optional[torch.Tensor] = None, accumulate: bool = True) -> None:
+    """``mode_level_error`` on the current stream: ``action_error`` without ``unit`` and ``ab``, binned by ``level`` [B] int32 -
+
+        sq[k, w * A + a] (+)= sum over {b: level[b] == k} of c e^2,   cnt[k, w] (+)= sum over {b: level[b] == k} of c
+
+    with ``sq`` [K, W * A] and ``cnt`` [K, W] fp64, ``K <= 256``.  A row whose level is outside ``0..K-1`` counts nowhere; rows of another level and
+    terms with ``c == 0`` are skipped, so ``pred`` may hold anything there.  Level ``k``'s slice has the bits ``action_error`` gives with the weight
+    zeroed on every other level's rows."""
+    from . import _lib as L
+    from .engine import _stream
+    if not torch.is_tensor(pred) or pred.dim() != 3 or pred.device.type != "cuda":
+        raise ValueError(f"level_error: pred must be a [B, W, A] tensor on a ROCm device, got {tuple(getattr(pred, 'shape', ()))}")
+    B, W, A = pred.shape
+    K = cnt.shape[0] if torch.is_tensor(cnt) and cnt.dim() == 2 else 0
+    if not 1 <= B <= MAX_BATCH or W < 1 or A < 1 or W * A > MAX_WINDOW_FLOATS or not 1 <= K <= MAX_LEVELS:
+        raise ValueError(f"level_error: needs 1 <= B <= {MAX_BATCH}, 1 <= W * A <= {MAX_WINDOW_FLOATS} and cnt [K, W] with 1 <= K <= {MAX_LEVELS}, "
+                         f"got {(B, W, A)}, cnt {tuple(getattr(cnt, 'shape', ()))}")
+    for name, t, shape, dt in (("pred", pred, (B, W, A), torch.float32), ("target", target, (B, W, A), torch.float32), ("mask", mask, (B, W), torch.float32),
+                               ("weight", weight, (B,), torch.float32), ("level", level, (B,), torch.int32), ("sq", sq, (K, W * A), torch.float64),
+                               ("cnt", cnt, (K, W), torch.float64)):
+        if t is None and name in ("mask", "weight"):
+            continue
+        _same(name, "level_error", t, shape, dt, pred.device)
+    p = lambda t: None if t is None else t.data_ptr()
+    d = L.ModeLevelErrorDesc(pred=p(pred), target=p(target), mask=p(mask), weight=p(weight), level=p(level), sq=p(sq), cnt=p(cnt), B=B, W=W, A=A, K=K,
+                             accumulate=1 if accumulate else 0)
+    with torch.cuda.device(pred.device):
+        L.check(L.load().mode_level_error(C.byref(d), _stream()), "level_error")
+
+
+def level_table(levels="density", num_levels: int = 16, sigma_min: float = 0.001, sigma_max: float = 80.0, num_sampling_steps: int = 10,
+                sigma_data: float = 0.5) -> torch.Tensor:
+    """The noise levels of a ``LevelValidator`` as a 1-d CPU tensor (fp64 for ``"density"``, else as given), before the cast to fp32:
+
+        "density"   the K = num_levels quantiles u_k = (k + 0.5) / K of the shipped training density - ``utils.rand_log_logistic(u=)`` with
+                    loc = ln(sigma_data), scale = 0.5, truncated to [sigma_min, sigma_max], in its fp64 arithmetic.  Each level stands for 1 / K of the
+                    density's mass, so the equal-weight mean over the levels estimates the training loss's expectation over sigma.
+        "schedule"  ``get_sigmas_exponential(num_sampling_steps, sigma_min, sigma_max)`` without its trailing 0: the levels the sampler visits.
+        a sequence  or 1-d tensor of finite positive values, taken as it is."""
+    from .gc_sampling import get_sigmas_exponential
+    from .utils import rand_log_logistic
+    if isinstance(levels, str):
+        if levels == "density":
+            K = num_levels
+            if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= MAX_LEVELS:
+                raise ValueError(f"num_levels must be an int in 1..{MAX_LEVELS}, got {K!r}")
+            if not (0 < sigma_min < sigma_max and math.isfinite(sigma_max) and sigma_data > 0):
+                raise ValueError(f"needs 0 < sigma_min < sigma_max < inf and sigma_data > 0, got {sigma_min!r}, {sigma_max!r}, {sigma_data!r}")
+            u = (torch.arange(K, dtype=torch.float64) + 0.5) / K
+            table = rand_log_logistic((K,), loc=math.log(sigma_data), scale=0.5, min_value=sigma_min, max_value=sigma_max, dtype=torch.float64, u=u)
+        elif levels == "schedule":
+            n = num_sampling_steps
+            if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+                raise ValueError(f"num_sampling_steps must be an int >= 1, got {n!r}")
+            table = get_sigmas_exponential(n, sigma_min, sigma_max)[:n].clone()
+        else:
+            raise ValueError(f"levels must be 'density', 'schedule' or a sequence of noise levels, got {levels!r}")
+    else:
+        try:
+            table = torch.as_tensor(levels).detach().cpu()
+        except (TypeError, ValueError, RuntimeError) as e:
+            raise ValueError(f"levels must be 'density', 'schedule' or a sequence of noise levels, got {type(levels).__name__}") from e
+        if table.dim() != 1 or table.dtype == torch.bool or table.is_complex():
+            raise ValueError(f"levels must be a 1-d sequence of numbers, got shape {tuple(table.shape)}, {table.dtype}")
+        if not table.is_floating_point():
+            table = table.to(torch.float64)
+    if not 1 <= table.numel() <= MAX_LEVELS:
+        raise ValueError(f"the level table needs 1..{MAX_LEVELS} entries, got {table.numel()}")
+    as32 = table.to(torch.float32)
+    if not bool((torch.isfinite(as32) & (as32 > 0)).all()):
+        raise ValueError("every noise level must be finite and positive as an fp32 value")
+    return table
+
+
+class LevelResult(dict):
+    """What ``LevelValidator.run`` returns: device tensors, nothing read back.
+
+        sigmas [K] fp32; the accumulators sq [K, W, A] and cnt [K, W] (fp64, the model's normalised units); count_per_level [K];
+        mse_per_level [K], mse_per_level_step [K, W], mse_per_level_dim [K, A]: means of |D - a|^2 over the real steps (and action dimensions) of a
+            level - with ``unit`` [A] fp64 in raw action units, ``unit[a]^2`` applied per dimension in fp64 here;
+        loss_per_level [K] = lambda(sigma_k) * sum_{w, a} sq[k] / (A * sum_w cnt[k]), lambda = (sigma^2 + sigma_data^2) / (sigma sigma_data)^2 =
+            1 / c_out^2 in fp64 from the fp32 level: ``GCDenoiser.loss``'s masked mean at that level (F - target = (D - a) / c_out), always in the
+            model's own units;
+        loss: the mean of loss_per_level over the levels with a positive count.
+
+    A mean over nothing is 0.  Accumulators of several ranks (or passes) over the same table add: ``LevelResult.from_sums(sq, cnt, sigmas,
+    sigma_data, unit)`` derives the means of the sums."""
+
+    @classmethod
+    def from_sums(cls, sq: torch.Tensor, cnt: torch.Tensor, sigmas: torch.Tensor, sigma_data: float, unit: Optional[torch.Tensor] = None) -> "LevelResult":
+        K, W = cnt.shape
+        sq = sq.reshape(K, W, -1)
+        A = sq.shape[2]
+        mean = lambda num, den: torch.where(den > 0, num / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(den))
+        count = cnt.sum(1)
+        raw = sq if unit is None else sq * (unit.to(sq) * unit.to(sq))
+        s = sigmas.to(sq)
+        lam = (s * s + sigma_data ** 2) / (s * sigma_data) ** 2
+        loss_k = lam * mean(sq.sum((1, 2)), A * count)
+        live = (count > 0).to(sq)
+        return cls(sigmas=sigmas, sq=sq, cnt=cnt, count_per_level=count, mse_per_level=mean(raw.sum((1, 2)), A * count),
+                   mse_per_level_step=mean(raw.sum(2), A * cnt), mse_per_level_dim=mean(raw.sum(1), count[:, None].expand(K, A)),
+                   loss_per_level=loss_k, loss=mean((loss_k * live).sum(), live.sum()))
+
+
+class LevelValidator:
+    """The held-out denoising (score-matching) loss resolved by noise level: the training objective itself on held-out windows, one denoiser
+    evaluation per window instead of a sampler run, accumulated on the device per level of a fixed sigma table.
+
+    ``levels`` / ``num_levels`` / ``sigma_min`` / ``sigma_max`` / ``num_sampling_steps``: the table, see ``level_table`` (``"density"``, the default:
+    quantiles of the training density, whose equal-weight mean - ``result["loss"]`` - estimates the training loss; ``"schedule"``: the levels the
+    sampler visits; or explicit values).  It is cast to fp32 once and lives on the device; at most 256 levels.
+
+    ``batch(i, draw=0)``: the sweep's batch with unit-normal noise (``noise_scale=1.0``) plus ``level`` [B] int32, ``sigma`` [B] fp32 and
+    ``noised`` [B, W, A] from one ``mode_val_noise_levels`` launch: window g meets level ``(g + draw) mod K`` with the noise of (g, draw), whatever
+    the batch size - two checkpoints are compared on the same draws, and draws ``0..K-1`` give every window every level exactly once.
+
+    ``predict(batch) -> [B, W, A]``: ``denoiser(embed(batch), batch["noised"], batch["latent_goal"], batch["sigma"])`` under ``no_grad`` in eval
+    mode - ``MoDeDiT.denoise`` on the HIP chain with one sigma per row.  ``denoiser.guidance_scale`` is left as the caller set it; the training loss
+    corresponds to ``None``.
+
+    ``run(draws=None, ema=None) -> LevelResult``: ``draws`` defaults to K, the full window x level cross.  Eval mode, the EMA swap and the restore
+    in a ``finally`` are ``Validator.run``'s.  Per batch: one sweep launch (two with cameras; one more with hindsight goals), the prep launch,
+    ``embed``, one denoiser evaluation and one ``mode_level_error`` launch weighted by ``valid * action_mask``; nothing is read back.
+    ``raw_units`` as in ``Validator``: the ``mse_*`` entries in the store's raw action units, a constant dimension contributing nothing;
+    ``loss_per_level`` and ``loss`` stay in the model's units.
+
+    Not here: continuous or jittered sigma inside a bin, per-level expert-utilisation statistics, pre-cached routing per level, capturing the
+    per-batch chain as one graph, and gathering across ranks (the accumulators add: ``LevelResult.from_sums``)."""
+
+    def __init__(self, denoiser, sweep: WindowSweep, embed: Callable[[dict], dict], levels="density", num_levels: int = 16, sigma_min: float = 0.001,
+                 sigma_max: float = 80.0, num_sampling_steps: int = 10, raw_units: bool = True):
+        if not isinstance(sweep, WindowSweep):
+            raise ValueError(f"LevelValidator needs a data.WindowSweep, got {type(sweep).__name__}")
+        if not callable(embed):
+            raise ValueError("embed must be a function batch -> {'state_images': [B, n_img_tokens, obs_dim]}")
+        st = sweep.store
+        self.denoiser, self.sweep, self.embed = denoiser, sweep, embed
+        self.sigma_data = float(denoiser.sigma_data)
+        table = level_table(levels, num_levels, sigma_min, sigma_max, num_sampling_steps, self.sigma_data)
+        self.sigmas = table.to(torch.float32).to(st.device).contiguous()
+        self.unit = None
+        if raw_units and st.scale is not None:
+            s = st.scale.to(torch.float64)
+            self.unit = torch.where(s != 0, 1.0 / torch.where(s != 0, s, torch.ones_like(s)), torch.zeros_like(s)).contiguous()
+
+    def __len__(self) -> int:
+        return len(self.sweep)
+
+    @property
+    def num_levels(self) -> int:
+        return self.sigmas.shape[0]
+
+    def batch(self, i: int, draw: int = 0) -> dict:
+        b = self.sweep.batch(i, draw, noise_scale=1.0)
+        b["level"], b["sigma"], b["noised"] = noise_levels(b["actions"], b["noise"], b["window"], self.sigmas, int(draw))
+        return b
+
+    @torch.no_grad()
+    def predict(self, batch: dict) -> torch.Tensor:
+        self.denoiser.eval()
+        return self.denoiser(self.embed(batch), batch["noised"], batch["latent_goal"], batch["sigma"])
+
+    @torch.no_grad()
+    def run(self, draws: Optional[int] = None, ema=None) -> LevelResult:
+        K = self.num_levels
+        draws = K if draws is None else draws
+        if isinstance(draws, bool) or not isinstance(draws, int) or draws < 1:
+            raise ValueError(f"draws must be an int >= 1, got {draws!r}")
+        den, sw = self.denoiser, self.sweep
+        W, A, dev = sw.window, sw.store.action_dim, sw.store.device
+        modes = [(m, m.training) for m in den.modules()]
+        sq = torch.zeros(K, W * A, dtype=torch.float64, device=dev)
+        cnt = torch.zeros(K, W, dtype=torch.float64, device=dev)
+        if ema is not None:
+            ema.swap()
+        try:
+            den.eval()
+            for draw in range(draws):
+                for i in range(len(sw)):
+                    b = self.batch(i, draw)
+                    level_error(self.predict(b).to(torch.float32).contiguous(), b["actions"], b["level"], sq, cnt, mask=b["action_mask"], weight=b["valid"])
+        finally:
+            if ema is not None:
+                ema.swap()
+            for m, was in modes:
+                m.training = was
+        return LevelResult.from_sums(sq, cnt, self.sigmas, self.sigma_data, self.unit)
