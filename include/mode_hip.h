@@ -1467,6 +1467,61 @@ typedef struct ModeDataGoalDesc {
 int mode_data_relabel_goals(const ModeDataGoalDesc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Ordered draws of the training batch stream: epoch permutations and weighted episode mixtures (csrc/data_stream.hip;
+ * data.WindowStream(order="epoch") / data.WindowStream(episode_weights=)).  An addition to ABI 13: a new struct and export, nothing existing
+ * changes - ModeDataStreamDesc keeps its layout and mode_data_sample_windows its launch and its bits (the i.i.d. kernel and the ordered one call ONE
+ * device function for the located-window row and ONE for the noise / u / shifts that follow it).
+ *
+ * The descriptor embeds a ModeDataStreamDesc `s`: the store, the tables, (seed, step) and the outputs of mode_data_sample_windows, with the same
+ * meaning.  Only how row j's window (e, p) - step p of episode e - is located differs; index[j] = ep_begin[e] + p, episode[j], last, the rows r_w,
+ * action_mask, actions, latent_goal, noise, u and shifts are then exactly those of mode_data_sample_windows: noise, u and shifts stay keyed by
+ * (seed, step, j) in every mode.  n = s.n_total, n_e = starts[e + 1] - starts[e], every product and sum of the keys in uint32 arithmetic modulo 2^32.
+ *
+ * mode = MODE_ORDER_EPOCH: every window exactly once per epoch.
+ *   P  = (uint64) step * B + j                     the row's global position (step < 2^32, B <= 65535: no overflow)
+ *   ep = P / n,  q = P % n                         epoch[j] = ep, position[j] = q  (int64)
+ *   g  = perm(seed, ep, n)(q),  e = the largest index with starts[e] <= g (the binary search of mode_data_sample_windows),  p = g - starts[e]
+ * perm(seed, ep, n) is a bijection of [0, n): the n consecutive positions of an epoch visit every window once, whatever B is - a batch that
+ * straddles an epoch boundary continues in the next epoch's permutation.  It is a balanced Feistel network with cycle walking:
+ *   bits = the smallest even number >= max(2, bit length of n - 1),  h = bits / 2 (1 <= h <= 16),  mask = 2^h - 1
+ *   ke   = mode_stream_seed(seed + 6 + ep_hi * 0x9E3779B9, ep_lo),  ep_lo / ep_hi the low / high 32 bits of ep
+ *   F(v): L = v >> h, R = v & mask;  for r = 0 .. MODE_PERM_ROUNDS - 1:  (L, R) <- (R, L ^ (lowbias32(ke ^ (R | (r << 16))) & mask));  F(v) = (L << h) | R
+ *   v = F(q);  while v >= n: v = F(v);  perm(q) = v
+ * F is a bijection of [0, 2^bits) for any round function, so a walk that starts inside [0, n) returns there, after < 4 applications on average
+ * (2^bits < 4 n for n >= 2).  The kernel bounds the walk by 2^bits applications - the longest cycle the domain can hold, which no q < n reaches -
+ * and clamps the result into [0, n).  MODE_PERM_ROUNDS = 10: with lowbias32 as the round function 4 rounds are visibly biased at small n and 6
+ * still sit 2.5 - 3.4 standard deviations high in the place-occupancy chi-square at n = 6; 10 rounds put every statistic of
+ * tests/test_order_references.py within 1.1 standard deviations of a uniform permutation's.
+ *
+ * mode = MODE_ORDER_WEIGHTED: episode e with probability proportional to its mass, then a start uniform within it; i.i.d., with replacement.
+ *   cut [E + 1] int64, built by the caller: mass_e = w_e >= 0 where n_e > 0, else 0;  C_0 = 0, C_{e + 1} = C_e + mass_e in fp64, in episode order;
+ *                       cut[e] = floor(2^32 * (C_e / C_E)),  cut[E] = 2^32   (monotone; cut[e + 1] == cut[e] exactly for an episode of mass 0)
+ *   r1 = lowbias32(mode_stream_seed(seed, step) ^ j)             (the word mode_data_sample_windows scales to g)
+ *   e  = the largest index in [0, E) with cut[e] <= r1 - the same binary search, on the int64 table: ties skip the episodes of mass 0 at the
+ *        front, in the middle and at the end (a trailing one has cut[e] = 2^32 > r1)
+ *   r2 = lowbias32(mode_stream_seed(seed + 7, step) ^ j),  p = ((uint64) r2 * n_e) >> 32
+ * epoch and position are not written.  The caller refuses a positive mass whose interval is empty (cut[e + 1] == cut[e]).
+ *
+ * Clamps, before anything becomes an address: q and perm's result into [0, n), e into [0, E), n_e to >= 1 and p into [0, n_e), and those of
+ * mode_data_sample_windows behind them.  One launch, B workgroups of 256 threads, every thread runs the (uniform) locate itself; plain vector
+ * stores, no LDS, no atomics.  Row j is a function of (seed, step, j, B) and the tables in MODE_ORDER_EPOCH - B enters through P only - and of
+ * (seed, step, j) and the tables in MODE_ORDER_WEIGHTED.
+ *
+ * Before any launch, outputs untouched: MODE_ERR_BAD_ARG for a NULL descriptor, a mode other than the two, MODE_ORDER_EPOCH without epoch or
+ * position, MODE_ORDER_WEIGHTED without cut; then the refusals of mode_data_sample_windows on `s`.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define MODE_ORDER_EPOCH 1
+#define MODE_ORDER_WEIGHTED 2
+#define MODE_PERM_ROUNDS 10
+typedef struct ModeDataOrderDesc {
+  ModeDataStreamDesc s;                  /* as for mode_data_sample_windows */
+  int32_t mode;                          /* MODE_ORDER_EPOCH | MODE_ORDER_WEIGHTED */
+  const int64_t* cut;                    /* [E + 1], MODE_ORDER_WEIGHTED; else unused */
+  int64_t* epoch; int64_t* position;     /* [B] each, MODE_ORDER_EPOCH; else unused */
+} ModeDataOrderDesc;
+int mode_data_sample_windows_ordered(const ModeDataOrderDesc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Held-out denoising error per noise level (csrc/data_stream.hip; validation.LevelValidator).  An addition to ABI 13: two new structs and exports,
  * nothing existing changes - no struct keeps another layout and mode_action_error keeps its bits (the two error kernels share ONE device function
  * for the lane's terms and the butterfly).

@@ -9,11 +9,11 @@ from .perceptual_encoders import (FiLMResNet18Policy, FiLMResNet34Policy, FiLMRe
 from .lora import LoraAdapter  # noqa: F401
 from .camera import CLIP_MEAN, CLIP_STD, CameraTransform, preprocess_cameras  # noqa: F401
 from . import data  # noqa: F401
-from .data import EpisodeStore, WindowStream, WindowSweep, split_episodes  # noqa: F401
+from .data import EpisodeStore, WindowStream, WindowSweep, mixture_weights, split_episodes  # noqa: F401
 from . import validation  # noqa: F401
 from .validation import LevelResult, LevelValidator, Validator  # noqa: F401
 
 __all__ = ["MoDeDiT", "NoiseBlockMoE", "GCDenoiser", "sample_ddim", "get_sigmas_exponential", "diffusion_loss", "training_step", "AdvancedLangEmbeddingBuffer",
            "FiLMResNet18Policy", "FiLMResNet34Policy", "FiLMResNet50Policy", "ResNetEncoderWithFiLM", "embed_visual_obs",
            "CameraTransform", "preprocess_cameras", "CLIP_MEAN", "CLIP_STD", "LoraAdapter", "data", "EpisodeStore", "WindowStream", "WindowSweep",
-           "split_episodes", "validation", "Validator", "LevelValidator", "LevelResult"]
+           "split_episodes", "mixture_weights", "validation", "Validator", "LevelValidator", "LevelResult"]

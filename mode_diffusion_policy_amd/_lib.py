@@ -224,6 +224,15 @@ class ModeDataStreamDesc(C.Structure):
                 ("shift_pad", c_i32 * 2)]
 
 
+MODE_ORDER_EPOCH, MODE_ORDER_WEIGHTED = 1, 2
+
+
+class ModeDataOrderDesc(C.Structure):
+    """mode_data_sample_windows_ordered (include/mode_hip.h, an addition to ABI 13): a ModeDataStreamDesc, the mode, the int64 cut table of a weighted
+    mixture and the int64 epoch / position outputs of an epoch order."""
+    _fields_ = [("s", ModeDataStreamDesc), ("mode", c_i32), ("cut", c_vp), ("epoch", c_vp), ("position", c_vp)]
+
+
 class ModeDataSweepDesc(C.Structure):
     """mode_data_sweep_windows (include/mode_hip.h, an addition to ABI 13): the store's tables, the enumeration's (stride, first), the noise's
     (seed, draw, noise_scale) and the batch's outputs."""
@@ -409,6 +418,7 @@ PROTOTYPES = {
     "mode_dit_forward_guided": (C.c_int, [P(ModeDims), P(ModeModelWeights), P(ModeGuidedArgs), c_vp, c_sz, c_vp]),
     "mode_frames_preprocess": (C.c_int, [P(ModeFramePrepDesc), c_vp]),
     "mode_data_sample_windows": (C.c_int, [P(ModeDataStreamDesc), c_vp]),
+    "mode_data_sample_windows_ordered": (C.c_int, [P(ModeDataOrderDesc), c_vp]),
     "mode_data_sweep_windows": (C.c_int, [P(ModeDataSweepDesc), c_vp]),
     "mode_action_error": (C.c_int, [P(ModeActionErrorDesc), c_vp]),
     "mode_data_relabel_goals": (C.c_int, [P(ModeDataGoalDesc), c_vp]),

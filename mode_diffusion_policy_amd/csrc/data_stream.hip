@@ -17,6 +17,10 @@
 //
 // Hindsight goals (include/mode_hip.h: mode_data_relabel_goals): a second launch behind either sampling kernel replaces a drawn share of the rows'
 // episode goals by the stored embedding of a step a drawn number of steps ahead in the same episode.
+//
+// Ordered draws (include/mode_hip.h: mode_data_sample_windows_ordered; data.WindowStream(order="epoch") / (episode_weights=)): a third sampling kernel
+// that locates row j's window another way - by a keyed permutation of the epoch's positions, or by an episode drawn from a table of weights - and then
+// runs the same located-window row body and the same noise / u / shifts tail as the i.i.d. kernel: ONE definition of each.
 #include "mode_common.h"
 
 namespace mode {
@@ -40,12 +44,14 @@ __device__ __forceinline__ WindowTables window_tables(const Desc& d) {
   return {d.actions, d.ep_begin, d.goals, d.lo, d.scale, d.S, d.E, d.A, d.G, d.W, d.out_actions, d.action_mask, d.latent_goal, d.index, d.episode};
 }
 
-// The episode of window number g: the largest e with starts[e] <= g (the header's binary search), clamped into [0, E).
-__device__ __forceinline__ int locate_episode(const int32_t* starts, int E, uint32_t g) {
+// The episode of window number g: the largest e with starts[e] <= g (the header's binary search), clamped into [0, E).  The table's elements are
+// int32 window numbers (starts) or int64 cuts of [0, 2^32] (mode_data_sample_windows_ordered's cut): never negative, compared unsigned in their width.
+template <class T>
+__device__ __forceinline__ int locate_episode(const T* starts, int E, uint32_t g) {
   int lo = 0, hi = E;
   while (hi - lo > 1) {
     const int mid = (lo + hi) >> 1;
-    if ((uint32_t)starts[mid] <= g) lo = mid; else hi = mid;
+    if ((typename std::make_unsigned<T>::type)starts[mid] <= g) lo = mid; else hi = mid;
   }
   return min(max(lo, 0), E - 1);
 }
@@ -78,15 +84,10 @@ __device__ __forceinline__ void window_row(const WindowTables& t, int j, int e, 
   }
 }
 
-__global__ __launch_bounds__(256) void data_sample_windows_kernel(ModeDataStreamDesc d) {
-  const int j = blockIdx.x, tid = threadIdx.x;
+// What follows the located window in row j of a training batch - the noise row, the sigma uniform and the cameras' shifts, keyed by (seed, step, j)
+// whatever located the window.  ONE body for the i.i.d. and the ordered kernel.
+__device__ __forceinline__ void stream_row_tail(const ModeDataStreamDesc& d, int j, int tid) {
   const uint32_t uj = (uint32_t)j;
-  const uint32_t k = mode_stream_seed(d.seed, d.step);
-  uint32_t g = (uint32_t)(((uint64_t)hash_u32(k ^ uj) * (uint64_t)(uint32_t)d.n_total) >> 32);
-  g = min(g, (uint32_t)d.n_total - 1u);
-  const int e = locate_episode(d.starts, d.E, g);
-  window_row(window_tables(d), j, e, (long)g - (long)d.starts[e], true, tid);
-
   const int WA = d.W * d.A;
   if (d.noise) {
     const uint32_t kn = mode_stream_seed(d.seed + 1u + uj * 0x9E3779B9u, d.step);
@@ -106,6 +107,74 @@ __global__ __launch_bounds__(256) void data_sample_windows_kernel(ModeDataStream
       sh[2 * (long)j + c] = (int32_t)(((uint64_t)hash_u32(k3 ^ (4u * uj + 2u * (uint32_t)q + (uint32_t)c)) * (uint64_t)(2 * pad + 1)) >> 32);
     }
   }
+}
+
+__global__ __launch_bounds__(256) void data_sample_windows_kernel(ModeDataStreamDesc d) {
+  const int j = blockIdx.x, tid = threadIdx.x;
+  const uint32_t uj = (uint32_t)j;
+  const uint32_t k = mode_stream_seed(d.seed, d.step);
+  uint32_t g = (uint32_t)(((uint64_t)hash_u32(k ^ uj) * (uint64_t)(uint32_t)d.n_total) >> 32);
+  g = min(g, (uint32_t)d.n_total - 1u);
+  const int e = locate_episode(d.starts, d.E, g);
+  window_row(window_tables(d), j, e, (long)g - (long)d.starts[e], true, tid);
+  stream_row_tail(d, j, tid);
+}
+
+// The epoch permutation (include/mode_hip.h states it bit for bit): a balanced Feistel network on the smallest even number of bits that holds n - 1,
+// MODE_PERM_ROUNDS rounds keyed by the epoch, applied again while the result is >= n (cycle walking: a walk that starts inside [0, n) returns there,
+// and the map it induces on [0, n) is a bijection).  The domain is < 4 n, so a walk takes 4 applications on average at worst.  The bound of 2^bits
+// applications is the length of the longest cycle the domain can hold: no value inside [0, n) reaches it, it only keeps a coding error from hanging
+// the device, and the clamp behind it keeps the result an index.  Every thread of the workgroup walks the same q: the trip count is uniform.
+__device__ __forceinline__ uint32_t epoch_perm(uint32_t ke, uint32_t n, uint32_t q) {
+  const int nb = 32 - __clz((int)max(n - 1u, 1u));                         // bit length of n - 1, at least 1
+  const int h = max(1, (nb + 1) >> 1);                                     // bits = 2 h: the smallest even number >= max(2, nb); h <= 16
+  const uint32_t mask = (1u << h) - 1u;
+  const uint64_t cap = 1ull << (2 * h);
+  uint32_t v = min(q, n - 1u);
+  for (uint64_t it = 0; it < cap; ++it) {
+    uint32_t L = v >> h, R = v & mask;
+#pragma unroll
+    for (uint32_t r = 0; r < (uint32_t)MODE_PERM_ROUNDS; ++r) {
+      const uint32_t t = L ^ (hash_u32(ke ^ (R | (r << 16))) & mask);
+      L = R;
+      R = t;
+    }
+    v = (L << h) | R;
+    if (v < n) break;
+  }
+  return min(v, n - 1u);
+}
+
+// Row j of an ordered batch (include/mode_hip.h: mode_data_sample_windows_ordered).  The same grid as the kernel above; every thread locates the row's
+// window itself (uniform over the workgroup): MODE_ORDER_EPOCH walks the permutation of the row's epoch and searches `starts`, MODE_ORDER_WEIGHTED
+// searches `cut` for the episode (<= 31 dependent 8-byte loads of an L2-resident table) and draws the start within it.  No LDS, no atomics.
+__global__ __launch_bounds__(256) void data_sample_windows_ordered_kernel(ModeDataOrderDesc o) {
+  const ModeDataStreamDesc& d = o.s;
+  const int j = blockIdx.x, tid = threadIdx.x;
+  const uint32_t uj = (uint32_t)j, n = (uint32_t)d.n_total;
+  int e;
+  long p;
+  if (o.mode == MODE_ORDER_EPOCH) {
+    const uint64_t P = (uint64_t)d.step * (uint64_t)(uint32_t)d.B + (uint64_t)uj;
+    const uint64_t ep = P / n;
+    const uint32_t q = (uint32_t)(P - ep * n);
+    const uint32_t ke = mode_stream_seed(d.seed + 6u + (uint32_t)(ep >> 32) * 0x9E3779B9u, (uint32_t)ep);
+    const uint32_t g = epoch_perm(ke, n, q);
+    e = locate_episode(d.starts, d.E, g);
+    p = (long)g - (long)d.starts[e];
+    if (tid == 0) {
+      o.epoch[j] = (int64_t)ep;
+      o.position[j] = (int64_t)q;
+    }
+  } else {
+    const uint32_t r1 = hash_u32(mode_stream_seed(d.seed, d.step) ^ uj);
+    const uint32_t r2 = hash_u32(mode_stream_seed(d.seed + 7u, d.step) ^ uj);
+    e = locate_episode(o.cut, d.E, r1);
+    const long n_e = max((long)d.starts[e + 1] - (long)d.starts[e], 1l);
+    p = min((long)(((uint64_t)r2 * (uint64_t)n_e) >> 32), n_e - 1);
+  }
+  window_row(window_tables(d), j, e, p, true, tid);
+  stream_row_tail(d, j, tid);
 }
 
 // The sweep (include/mode_hip.h: mode_data_sweep_windows; data.WindowSweep): row j is window first + j of the fixed enumeration instead of a
@@ -271,7 +340,8 @@ __global__ __launch_bounds__(256) void level_error_kernel(ModeLevelErrorDesc d) 
 
 using namespace mode;
 
-extern "C" int mode_data_sample_windows(const ModeDataStreamDesc* d, void* stream) {
+// The refusals of mode_data_sample_windows, shared with the ordered entry point (whose descriptor embeds the same struct).
+static int check_stream_desc(const ModeDataStreamDesc* d) {
   if (!d || !d->actions || !d->ep_begin || !d->starts || !d->goals || !d->out_actions || !d->action_mask || !d->latent_goal || !d->index || !d->episode)
     return MODE_ERR_BAD_ARG;
   if ((d->lo == nullptr) != (d->scale == nullptr)) return MODE_ERR_BAD_ARG;
@@ -279,7 +349,25 @@ extern "C" int mode_data_sample_windows(const ModeDataStreamDesc* d, void* strea
   for (int q = 0; q < 2; ++q)
     if (d->shift_pad[q] < 0 || d->shift_pad[q] > 16384 || (d->shifts[q] && d->shift_pad[q] == 0)) return MODE_ERR_BAD_ARG;
   if (d->B > 65535 || (long)d->W * d->A > 4096 || d->G > 4096) return MODE_ERR_UNSUPPORTED;
+  return MODE_OK;
+}
+
+extern "C" int mode_data_sample_windows(const ModeDataStreamDesc* d, void* stream) {
+  const int rc = check_stream_desc(d);
+  if (rc != MODE_OK) return rc;
   hipLaunchKernelGGL(data_sample_windows_kernel, dim3(d->B), dim3(256), 0, (hipStream_t)stream, *d);
+  MODE_LAUNCH_CHECK();
+  return MODE_OK;
+}
+
+extern "C" int mode_data_sample_windows_ordered(const ModeDataOrderDesc* o, void* stream) {
+  if (!o) return MODE_ERR_BAD_ARG;
+  if (o->mode != MODE_ORDER_EPOCH && o->mode != MODE_ORDER_WEIGHTED) return MODE_ERR_BAD_ARG;
+  if (o->mode == MODE_ORDER_EPOCH && (!o->epoch || !o->position)) return MODE_ERR_BAD_ARG;
+  if (o->mode == MODE_ORDER_WEIGHTED && !o->cut) return MODE_ERR_BAD_ARG;
+  const int rc = check_stream_desc(&o->s);
+  if (rc != MODE_OK) return rc;
+  hipLaunchKernelGGL(data_sample_windows_ordered_kernel, dim3(o->s.B), dim3(256), 0, (hipStream_t)stream, *o);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
 }

@@ -107,6 +107,7 @@ extern "C" size_t mode_hip_sizeof(const char* n) {
   MODE_SZ(ModeFramePrepCam) MODE_SZ(ModeFramePrepDesc) MODE_SZ(ModeEnvSelectDesc) MODE_SZ(ModeEnvBidDesc) MODE_SZ(ModeGradChunk) MODE_SZ(ModeGradClipState)
   MODE_SZ(ModeLoraDesc) MODE_SZ(ModeLoraFactDesc) MODE_SZ(ModeLoraTrain) MODE_SZ(ModeDataStreamDesc)
   MODE_SZ(ModeDataSweepDesc) MODE_SZ(ModeActionErrorDesc) MODE_SZ(ModeDataGoalDesc) MODE_SZ(ModeValLevelsDesc) MODE_SZ(ModeLevelErrorDesc)
+  MODE_SZ(ModeDataOrderDesc)
 #undef MODE_SZ
   return 0;
 }

@@ -6,9 +6,12 @@ HIP launch (csrc/data_stream.hip; the expressions, bit for bit, are the comment 
 ``mode_frames_preprocess`` launch that reads the drawn frames straight out of the store when it holds cameras.  There is no host work per step,
 no host sync and no state: a run resumed at step ``t`` with the same seed and store sees the same windows, noise, sigma uniforms and shifts.
 
-Windows are drawn i.i.d. uniformly over all window starts, WITH replacement - this is not an epoch permutation: within any stretch of steps
-some starts repeat and others are not seen.  Reading CALVIN / LIBERO files and sharding the store across ranks are not part of this module (rank
-``r`` of a data-parallel run may simply use ``seed + 16 * r``: the stream's keys use ``seed .. seed + 5``).
+By default windows are drawn i.i.d. uniformly over all window starts, WITH replacement: within any stretch of steps some starts repeat and
+others are not seen.  ``WindowStream(order="epoch")`` visits every start exactly once per epoch instead - a keyed permutation the kernel evaluates
+per row, so there is still no stored shuffle and nothing to checkpoint but the step counter - and ``WindowStream(episode_weights=w)`` draws the
+episode from a weighted mixture (``mixture_weights`` builds ``w`` for datasets or tasks of unequal size) and the start uniformly within it; both
+run ``mode_data_sample_windows_ordered``, one launch in place of the default's.  Reading CALVIN / LIBERO files and sharding the store across
+ranks are not part of this module (rank ``r`` of a data-parallel run may simply use ``seed + 16 * r``: the stream's keys use ``seed .. seed + 7``).
 
 Goal images (hindsight relabelling): a store that also holds one goal-space embedding per step (``add_episode(step_goals=[L, G])``, typically the
 image-goal encoder's output for that step's frame, computed offline) lets ``WindowStream`` / ``WindowSweep(goal="hindsight", goal_horizon=(lo,
@@ -16,7 +19,8 @@ hi))`` replace a row's episode goal by the embedding of a step ``lo .. hi`` step
 that passes its end - in ONE further launch (``mode_data_relabel_goals``) with counter-based draws: no host work, no sync, the same bits when
 step ``t`` is asked for again.  ``hindsight_prob`` mixes both kinds of goal row by row.  Not provided: encoding goal FRAMES inside the stream
 (``goal_index`` lets a caller gather ``store.frames_static[goal_index]`` and run an encoder of their own), fusing the relabel into the sampling
-launches, geometric or otherwise non-uniform horizon densities, disk formats, epoch permutations and a sharded store.
+launches, geometric or otherwise non-uniform horizon densities, disk formats, epoch order with weights (weighted sampling without replacement),
+per-epoch curricula and a sharded store.
 
 Holding episodes out: ``split_episodes`` names a training and a validation set of episode ids, ``WindowStream(episodes=train_ids)`` draws from
 the first only, and ``WindowSweep(episodes=val_ids)`` enumerates every window of the second exactly once, a batch per launch
@@ -27,6 +31,7 @@ avoids that.
 from __future__ import annotations
 
 import ctypes as C
+from fractions import Fraction
 from typing import Optional, Sequence
 
 import numpy as np
@@ -333,6 +338,83 @@ def _relabel_goals(store: EpisodeStore, out: dict, ids: Optional[torch.Tensor], 
         L.check(L.load().mode_data_relabel_goals(C.byref(d), _stream()), "data_relabel_goals")
 
 
+_ORDERS = ("iid", "epoch")
+
+
+def _cut_table(episode_weights, n_e: np.ndarray) -> np.ndarray:
+    """The int64 ``cut`` table of ``mode_data_sample_windows_ordered`` (include/mode_hip.h) for the weights ``w`` [E] and the start counts ``n_e``
+    (0 for an episode that is not listed or that no window fits): mass ``w_e`` where ``n_e > 0`` else 0, ``C`` its fp64 running sum in episode
+    order, ``cut[e] = floor(2^32 * (C_e / C_E))``, ``cut[E] = 2^32``.  ValueError for weights that are not E finite non-negative numbers, a total
+    mass of 0 (or one that overflows fp64), or a positive mass whose interval comes out empty."""
+    E = len(n_e)
+    try:
+        w = np.asarray(_host(episode_weights, "episode_weights") if torch.is_tensor(episode_weights) else episode_weights)
+        if w.dtype == np.bool_ or not (np.issubdtype(w.dtype, np.floating) or np.issubdtype(w.dtype, np.integer)):
+            raise TypeError
+        w = w.astype(np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("episode_weights must be a sequence of numbers, one per episode") from None
+    if w.shape != (E,):
+        raise ValueError(f"episode_weights must hold one number per episode of the store ({E}), got shape {w.shape}")
+    if not np.isfinite(w).all() or (w < 0).any():
+        raise ValueError("episode_weights must be finite and non-negative")
+    mass = np.where(np.asarray(n_e) > 0, w, 0.0)
+    with np.errstate(over="ignore"):
+        run = np.concatenate([[0.0], np.cumsum(mass)])
+    if not run[-1] > 0.0 or not np.isfinite(run[-1]):
+        raise ValueError("episode_weights leave no mass on an episode with a window start (or their sum overflows): nothing to draw")
+    cut = np.floor(2.0 ** 32 * (run / run[-1])).astype(np.int64)
+    cut[-1] = 2 ** 32
+    empty = (mass > 0) & (cut[1:] == cut[:-1])
+    if empty.any():
+        e = int(np.argmax(empty))
+        raise ValueError(f"episode_weights[{e}] = {w[e]!r} is positive but below 2^-32 of the total mass: it rounds to an empty interval (give 0 "
+                         f"to leave the episode out)")
+    return cut
+
+
+def mixture_weights(store: EpisodeStore, groups, group_weights, episodes=None, window: Optional[int] = None, pad: str = "hold") -> np.ndarray:
+    """Per-episode weights (fp64 numpy [E]) for ``WindowStream(episode_weights=)`` under which a batch row comes from group ``d`` with probability
+    ``group_weights[d] / sum(group_weights)`` and, within the group, from each of its window starts with equal probability:
+
+        w_e = p_d * n_e / N_d,   d = groups[e],  p_d = group_weights[d] / sum(group_weights),  N_d = the sum of n_e over the group
+
+    ``groups`` [E] holds every episode's group number in ``0 .. len(group_weights) - 1`` (a dataset of a pre-training mixture, a task of a suite).
+    ``n_e`` counts the starts the stream will see: ``L_e`` for ``pad="hold"`` (the default; ``window`` is not needed), ``max(0, L_e - window + 1)``
+    for ``pad="none"``, and 0 for an episode that ``episodes=`` (the stream's own keyword; None = all) does not list - pass the stream the same
+    ``window``, ``pad`` and ``episodes``.  ValueError for a ``groups`` of another size or with a number out of range, group weights that are not
+    finite, non-negative and of positive sum, and a group of positive weight without a start.
+
+    Per-START weights need no helper: a start of episode ``e`` is drawn with probability proportional to ``s_e`` under
+    ``episode_weights = s * n_e`` (``s = 1``: the uniform draw over the starts that the stream makes without weights)."""
+    if not isinstance(store, EpisodeStore) or not store.finalized:
+        raise ValueError("mixture_weights needs a finalized EpisodeStore")
+    if pad not in _PADS:
+        raise ValueError(f"pad must be one of {_PADS}, got {pad!r}")
+    E = store.num_episodes
+    if pad == "none":
+        if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1:
+            raise ValueError(f"pad='none' needs window, an int >= 1, got {window!r}")
+        n_e = np.maximum(0, store.lengths - int(window) + 1)
+    else:
+        n_e = store.lengths
+    n_e = np.diff(_start_table(n_e, episodes, "no window fits any selected episode: nothing to weigh")[0])
+    try:
+        p = np.asarray(group_weights, dtype=np.float64)
+        g = np.asarray(_host(groups, "groups") if torch.is_tensor(groups) else groups)
+    except (TypeError, ValueError):
+        raise ValueError("groups must be a sequence of ints and group_weights a sequence of numbers") from None
+    if p.ndim != 1 or p.size == 0 or not np.isfinite(p).all() or (p < 0).any() or not p.sum() > 0 or not np.isfinite(p.sum()):
+        raise ValueError("group_weights must be a non-empty 1-d sequence of finite non-negative numbers with a positive sum")
+    if g.shape != (E,) or g.dtype == np.bool_ or not np.issubdtype(g.dtype, np.integer) or g.min() < 0 or g.max() >= p.size:
+        raise ValueError(f"groups must hold one int in 0..{p.size - 1} per episode of the store ({E})")
+    N = np.bincount(g, weights=n_e.astype(np.float64), minlength=p.size)
+    if ((p > 0) & (N == 0)).any():
+        raise ValueError(f"group {int(np.argmax((p > 0) & (N == 0)))} has a positive weight but no window start")
+    p = p / p.sum()
+    return np.where(n_e > 0, p[g] * n_e / np.where(N[g] > 0, N[g], 1.0), 0.0)
+
+
 def _frames_of(store: EpisodeStore, tr, shifts, index: torch.Tensor, B: int, frame_dtype) -> dict:
     """``rgb_obs`` of a batch: one ``mode_frames_preprocess`` launch that reads the store rows ``index`` (``shifts[q]`` None: no shift)."""
     from . import camera
@@ -352,8 +434,8 @@ class WindowStream:
         shifts {"rgb_static", "rgb_gripper"} int32 [B, 2] (None for a transform with ``shift_pad == 0``)
 
     ``pad="none"`` draws only windows that lie inside an episode (episodes shorter than ``window`` are never drawn); ``pad="hold"`` lets a window
-    start at every step, holds the episode's last action past its end and marks those rows with ``action_mask = 0``.  Draws are i.i.d. uniform
-    over the starts, with replacement (not an epoch permutation).  Row ``j`` of step ``t`` depends on ``(seed, t, j)`` and the store only:
+    start at every step, holds the episode's last action past its end and marks those rows with ``action_mask = 0``.  By default draws are i.i.d. uniform
+    over the starts, with replacement (``order`` and ``episode_weights`` below change that).  Row ``j`` of step ``t`` depends on ``(seed, t, j)`` and the store only:
     ``noise[j] == rollout.env_noise([(seed + 1 + j * 0x9E3779B9) % 2**32], [t], W, A, 1.0)[0]``.
 
     ``episodes=ids`` (``split_episodes``) draws from the listed episodes only: an episode that is not listed gets no starts, and the kernel's search
@@ -366,20 +448,57 @@ class WindowStream:
     ``latent_goal[j] = store.step_goals[goal_index[j]]`` with ``goal_index = min(index + offset, the episode's last row)``; a row that is not
     chosen keeps its episode's goal - both modalities mixed row by row in one forward.  The batch gains ``goal_index``, ``goal_offset`` (int32
     [B], written for every row) and ``goal_kind`` (fp32 [B], 1 = relabelled).  The draws use the keys ``seed + 4`` and ``seed + 5`` and depend on
-    ``(seed, t, j)`` only.  ``goal="episode"``, the default, is the stream without any of this: the same launches, keys and bits."""
+    ``(seed, t, j)`` only.  ``goal="episode"``, the default, is the stream without any of this: the same launches, keys and bits.
+
+    ``order="epoch"``: every window exactly once per epoch, still without host work, state or a stored shuffle (``mode_data_sample_windows_ordered``
+    in include/mode_hip.h states it bit for bit).  With ``n = n_total`` row ``j`` of step ``t`` has the global position ``P = t * B + j`` (64 bits),
+    the epoch ``P // n`` and the place ``q = P % n`` in it, and draws window number ``perm(seed, epoch, n)(q)`` - a keyed bijection of ``[0, n)``
+    (a balanced Feistel network of 10 rounds with cycle walking, key ``seed + 6``) that the kernel evaluates per row.  The ``n`` consecutive
+    positions of an epoch visit every window start once; ``B`` need not divide ``n``: a batch that straddles an epoch boundary continues in the next
+    epoch's permutation, nothing is dropped and nothing repeats within an epoch.  The batch gains ``epoch`` and ``position`` (int64 [B]; select
+    ``epoch == k`` to cut at the boundary).  ``epoch_of(step)`` is the epoch of the step's first row and ``steps_per_epoch`` the exact
+    ``fractions.Fraction(n, B)``: "train 30 epochs" is ``range(ceil(30 * steps_per_epoch))``.  Rows depend on ``(seed, t, j, B)``: resuming needs the
+    same batch size.
+
+    ``episode_weights=w`` (``E`` finite non-negative numbers; ``order="iid"`` only): episode ``e`` is drawn with probability proportional to ``w_e``
+    over the episodes that ``episodes=`` lists and that have a start, then a start uniformly among that episode's - i.i.d., with replacement, in
+    integer arithmetic (an int64 table of cuts of ``[0, 2^32]``, the start from key ``seed + 7``).  ``mixture_weights`` builds ``w`` for a weighted
+    mixture of datasets or tasks; re-weighting is a new stream on the same store.  A weight of 0 leaves an episode out; a positive weight below
+    ``2^-32`` of the total is refused, as are negative or non-finite weights, a wrong size and a total of 0 - ``ValueError`` before anything is
+    allocated.  ``index`` and ``episode`` differ from the unweighted stream's; noise, ``u``, shifts and the hindsight draws stay keyed by
+    ``(seed, t, j)`` in every mode.  Without either keyword the stream issues exactly the launches it always did.  Not provided: epoch order WITH
+    weights (weighted sampling without replacement), per-epoch curricula, a sharded store, disk formats."""
 
     def __init__(self, store: EpisodeStore, batch_size: int, window: int, seed: int = 0, pad: str = "hold",
                  camera_transforms: Optional[Sequence[CameraTransform]] = None, noise: bool = True, frame_dtype=torch.float32, episodes=None,
-                 goal: str = "episode", goal_horizon=None, hindsight_prob: float = 1.0):
+                 goal: str = "episode", goal_horizon=None, hindsight_prob: float = 1.0, order: str = "iid", episode_weights=None):
         camera_transforms = _check_window_args(store, batch_size, window, seed, pad, camera_transforms, frame_dtype, "WindowStream")
         self.goal, self._goal_plan = goal, _check_goal_args(store, goal, goal_horizon, hindsight_prob, "WindowStream", sweep=False)
+        if not isinstance(order, str) or order not in _ORDERS:
+            raise ValueError(f"order must be one of {_ORDERS}, got {order!r}")
+        if order == "epoch" and episode_weights is not None:
+            raise ValueError("episode_weights needs order='iid': an epoch order with weights (weighted sampling without replacement) is not provided")
         n_e = store.lengths if pad == "hold" else np.maximum(0, store.lengths - window + 1)
         starts, n_total = _start_table(n_e, episodes, f"no window of {window} steps fits any "
                                        f"{'episode' if episodes is None else 'selected episode'} (pad={pad!r}): nothing to draw")
+        cut = None if episode_weights is None else _cut_table(episode_weights, np.diff(starts))
         self.store, self.batch_size, self.window, self.seed, self.pad, self.noise = store, int(batch_size), int(window), int(seed), pad, bool(noise)
         self.camera_transforms, self.frame_dtype = camera_transforms, frame_dtype
+        self.order = order
         self.n_total = n_total
         self.starts = torch.from_numpy(starts.astype(np.int32)).to(store.device)            # the device table the kernel searches
+        self.cut = None if cut is None else torch.from_numpy(cut).to(store.device)          # int64 [E + 1], a weighted mixture's table
+
+    @property
+    def steps_per_epoch(self) -> Fraction:
+        """``n_total / batch_size`` as an exact ``fractions.Fraction`` (``float()`` it for a plot, ``math.ceil`` it for a step count)."""
+        return Fraction(self.n_total, self.batch_size)
+
+    def epoch_of(self, step: int) -> int:
+        """The epoch of row 0 of step ``step`` under ``order="epoch"``: ``(step * B) // n_total``.  The step's last row is in the same epoch or the next."""
+        if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or not 0 <= step < 2 ** 32:
+            raise ValueError(f"step must be an int in 0..2^32 - 1, got {step!r}")
+        return (int(step) * self.batch_size) // self.n_total
 
     def batch(self, step: int) -> dict:
         from . import _lib as L
@@ -405,8 +524,17 @@ class WindowStream:
         for q in range(2):
             d.shifts[q] = p(shifts[q])
             d.shift_pad[q] = tr[q].shift_pad if tr is not None else 0
-        with torch.cuda.device(dev):
-            L.check(L.load().mode_data_sample_windows(C.byref(d), _stream()), "data_sample_windows")
+        if self.order == "iid" and self.cut is None:
+            with torch.cuda.device(dev):
+                L.check(L.load().mode_data_sample_windows(C.byref(d), _stream()), "data_sample_windows")
+        else:
+            epoch = self.order == "epoch"
+            if epoch:
+                out["epoch"], out["position"] = (torch.empty(B, dtype=torch.int64, device=dev) for _ in range(2))
+            o = L.ModeDataOrderDesc(s=d, mode=L.MODE_ORDER_EPOCH if epoch else L.MODE_ORDER_WEIGHTED, cut=p(self.cut), epoch=p(out.get("epoch")),
+                                    position=p(out.get("position")))
+            with torch.cuda.device(dev):
+                L.check(L.load().mode_data_sample_windows_ordered(C.byref(o), _stream()), "data_sample_windows_ordered")
         if self._goal_plan is not None:
             _relabel_goals(st, out, None, self.seed, int(step), self._goal_plan)
         if tr is not None:
