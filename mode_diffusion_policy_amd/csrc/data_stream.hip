@@ -340,16 +340,24 @@ __global__ __launch_bounds__(256) void level_error_kernel(ModeLevelErrorDesc d) 
 
 using namespace mode;
 
+// The MODE_ERR_BAD_ARG refusals over the fields that ModeDataStreamDesc and ModeDataSweepDesc share: the required pointers, lo / scale given together,
+// positive sizes, n_total <= S and E <= S.  An entry point tests what is its own after this and the limits last: every BAD_ARG before any UNSUPPORTED.
+template <class Desc>
+static bool window_desc_ok(const Desc* d) {
+  return d && d->actions && d->ep_begin && d->starts && d->goals && d->out_actions && d->action_mask && d->latent_goal && d->index && d->episode &&
+         (d->lo == nullptr) == (d->scale == nullptr) && d->S > 0 && d->E > 0 && d->A > 0 && d->G > 0 && d->W > 0 && d->B > 0 && d->n_total > 0 &&
+         d->n_total <= d->S && d->E <= d->S;
+}
+
+// The kernels' limits (include/mode_hip.h), MODE_ERR_UNSUPPORTED beyond them; 0 for a size that an entry point does not have.
+static bool within_limits(int B, long WA, int G, int K) { return B <= 65535 && WA <= 4096 && G <= 4096 && K <= 256; }
+
 // The refusals of mode_data_sample_windows, shared with the ordered entry point (whose descriptor embeds the same struct).
 static int check_stream_desc(const ModeDataStreamDesc* d) {
-  if (!d || !d->actions || !d->ep_begin || !d->starts || !d->goals || !d->out_actions || !d->action_mask || !d->latent_goal || !d->index || !d->episode)
-    return MODE_ERR_BAD_ARG;
-  if ((d->lo == nullptr) != (d->scale == nullptr)) return MODE_ERR_BAD_ARG;
-  if (d->S <= 0 || d->E <= 0 || d->A <= 0 || d->G <= 0 || d->W <= 0 || d->B <= 0 || d->n_total <= 0 || d->n_total > d->S || d->E > d->S) return MODE_ERR_BAD_ARG;
+  if (!window_desc_ok(d)) return MODE_ERR_BAD_ARG;
   for (int q = 0; q < 2; ++q)
     if (d->shift_pad[q] < 0 || d->shift_pad[q] > 16384 || (d->shifts[q] && d->shift_pad[q] == 0)) return MODE_ERR_BAD_ARG;
-  if (d->B > 65535 || (long)d->W * d->A > 4096 || d->G > 4096) return MODE_ERR_UNSUPPORTED;
-  return MODE_OK;
+  return within_limits(d->B, (long)d->W * d->A, d->G, 0) ? MODE_OK : MODE_ERR_UNSUPPORTED;
 }
 
 extern "C" int mode_data_sample_windows(const ModeDataStreamDesc* d, void* stream) {
@@ -373,13 +381,8 @@ extern "C" int mode_data_sample_windows_ordered(const ModeDataOrderDesc* o, void
 }
 
 extern "C" int mode_data_sweep_windows(const ModeDataSweepDesc* d, void* stream) {
-  if (!d || !d->actions || !d->ep_begin || !d->starts || !d->goals || !d->out_actions || !d->action_mask || !d->latent_goal || !d->index || !d->episode ||
-      !d->valid || !d->window)
-    return MODE_ERR_BAD_ARG;
-  if ((d->lo == nullptr) != (d->scale == nullptr)) return MODE_ERR_BAD_ARG;
-  if (d->S <= 0 || d->E <= 0 || d->A <= 0 || d->G <= 0 || d->W <= 0 || d->B <= 0 || d->n_total <= 0 || d->n_total > d->S || d->E > d->S) return MODE_ERR_BAD_ARG;
-  if (d->stride < 1 || d->first < 0 || d->first >= d->n_total) return MODE_ERR_BAD_ARG;
-  if (d->B > 65535 || (long)d->W * d->A > 4096 || d->G > 4096) return MODE_ERR_UNSUPPORTED;
+  if (!window_desc_ok(d) || !d->valid || !d->window || d->stride < 1 || d->first < 0 || d->first >= d->n_total) return MODE_ERR_BAD_ARG;
+  if (!within_limits(d->B, (long)d->W * d->A, d->G, 0)) return MODE_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(data_sweep_windows_kernel, dim3(d->B), dim3(256), 0, (hipStream_t)stream, *d);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
@@ -390,7 +393,7 @@ extern "C" int mode_data_relabel_goals(const ModeDataGoalDesc* d, void* stream) 
   if (d->S <= 0 || d->E <= 0 || d->G <= 0 || d->B <= 0 || d->E > d->S) return MODE_ERR_BAD_ARG;
   if (d->lo < 0 || d->hi < d->lo || d->thresh > (1ull << 32)) return MODE_ERR_BAD_ARG;
   if (d->goal_dtype != MODE_F32 && d->goal_dtype != MODE_BF16) return MODE_ERR_BAD_ARG;
-  if (d->B > 65535 || d->G > 4096) return MODE_ERR_UNSUPPORTED;
+  if (!within_limits(d->B, 0, d->G, 0)) return MODE_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(data_relabel_goals_kernel, dim3(d->B), dim3(256), 0, (hipStream_t)stream, *d);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
@@ -399,7 +402,7 @@ extern "C" int mode_data_relabel_goals(const ModeDataGoalDesc* d, void* stream) 
 extern "C" int mode_action_error(const ModeActionErrorDesc* d, void* stream) {
   if (!d || !d->pred || !d->target || !d->sq || !d->ab || !d->cnt) return MODE_ERR_BAD_ARG;
   if (d->B <= 0 || d->W <= 0 || d->A <= 0) return MODE_ERR_BAD_ARG;
-  if (d->B > 65535 || (long)d->W * d->A > 4096) return MODE_ERR_UNSUPPORTED;
+  if (!within_limits(d->B, (long)d->W * d->A, 0, 0)) return MODE_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(action_error_kernel, dim3((unsigned)((d->W * d->A + 3) / 4)), dim3(256), 0, (hipStream_t)stream, *d);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
@@ -408,7 +411,7 @@ extern "C" int mode_action_error(const ModeActionErrorDesc* d, void* stream) {
 extern "C" int mode_val_noise_levels(const ModeValLevelsDesc* d, void* stream) {
   if (!d || !d->actions || !d->noise || !d->window || !d->sigmas || !d->level || !d->sigma || !d->x) return MODE_ERR_BAD_ARG;
   if (d->B <= 0 || d->W <= 0 || d->A <= 0 || d->K <= 0) return MODE_ERR_BAD_ARG;
-  if (d->B > 65535 || (long)d->W * d->A > 4096 || d->K > 256) return MODE_ERR_UNSUPPORTED;
+  if (!within_limits(d->B, (long)d->W * d->A, 0, d->K)) return MODE_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(val_noise_levels_kernel, dim3(d->B), dim3(256), 0, (hipStream_t)stream, *d);
   MODE_LAUNCH_CHECK();
   return MODE_OK;
@@ -417,7 +420,7 @@ extern "C" int mode_val_noise_levels(const ModeValLevelsDesc* d, void* stream) {
 extern "C" int mode_level_error(const ModeLevelErrorDesc* d, void* stream) {
   if (!d || !d->pred || !d->target || !d->level || !d->sq || !d->cnt) return MODE_ERR_BAD_ARG;
   if (d->B <= 0 || d->W <= 0 || d->A <= 0 || d->K <= 0) return MODE_ERR_BAD_ARG;
-  if (d->B > 65535 || (long)d->W * d->A > 4096 || d->K > 256) return MODE_ERR_UNSUPPORTED;
+  if (!within_limits(d->B, (long)d->W * d->A, 0, d->K)) return MODE_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(level_error_kernel, dim3((unsigned)((d->K * d->W * d->A + 3) / 4)), dim3(256), 0, (hipStream_t)stream, *d);
   MODE_LAUNCH_CHECK();
   return MODE_OK;

@@ -30,14 +30,16 @@ avoids that.
 """
 from __future__ import annotations
 
-import ctypes as C
 from fractions import Fraction
 from typing import Optional, Sequence
 
 import numpy as np
 import torch
 
+from . import _lib
+from ._checks import _checked_float, _checked_int
 from .camera import CameraTransform
+from .engine import _launch, _ptr
 
 MAX_BATCH = 65535          # the kernels' limits (include/mode_hip.h)
 MAX_WINDOW_FLOATS = 4096
@@ -52,6 +54,15 @@ def _host(x, name: str) -> np.ndarray:
     if isinstance(x, np.ndarray):
         return x
     raise ValueError(f"{name} must be a numpy array or a torch tensor, got {type(x).__name__}")
+
+
+def _as_numpy(x, name: str, dtype=None) -> np.ndarray:
+    """A numpy array from a tensor or a sequence: ``np.asarray`` with its own TypeError / ValueError for what it does not take."""
+    return np.asarray(_host(x, name) if torch.is_tensor(x) else x, dtype=dtype)
+
+
+def _checked_u32(v, name: str) -> int:
+    return _checked_int(v, 0, 2 ** 32 - 1, f"{name} must be an int in 0..2^32 - 1, got {v!r}")
 
 
 class EpisodeStore:
@@ -70,8 +81,7 @@ class EpisodeStore:
 
     def __init__(self, action_dim: int, goal_dim: int, device="cuda", step_goal_dtype=torch.float32):
         for name, v in (("action_dim", action_dim), ("goal_dim", goal_dim)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v <= 0:
-                raise ValueError(f"{name} must be a positive int, got {v!r}")
+            _checked_int(v, 1, None, f"{name} must be a positive int, got {v!r}")
         if step_goal_dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"step_goal_dtype must be torch.float32 or torch.bfloat16, got {step_goal_dtype}")
         self.action_dim, self.goal_dim, self.device, self.step_goal_dtype = int(action_dim), int(goal_dim), torch.device(device), step_goal_dtype
@@ -151,7 +161,7 @@ class EpisodeStore:
             hi = np.max([e[0].max(axis=0) for e in self._episodes], axis=0)
         else:
             try:
-                lo, hi = (np.asarray(_host(v, "bound") if torch.is_tensor(v) else v, dtype=np.float32) for v in normalize)
+                lo, hi = (_as_numpy(v, "bound", np.float32) for v in normalize)
             except (TypeError, ValueError):
                 raise ValueError(f"normalize must be 'minmax', None or (lo, hi), got {normalize!r}") from None
             if lo.shape != (A,) or hi.shape != (A,) or not (np.isfinite(lo).all() and np.isfinite(hi).all()) or (hi < lo).any():
@@ -210,12 +220,7 @@ def split_episodes(store: EpisodeStore, val_fraction: Optional[float] = None, va
     if (val_fraction is None) == (val_episodes is None):
         raise ValueError("give exactly one of val_fraction and val_episodes")
     if val_fraction is not None:
-        try:
-            f = float(val_fraction)
-        except (TypeError, ValueError):
-            f = float("nan")
-        if isinstance(val_fraction, bool) or not 0.0 < f < 1.0:
-            raise ValueError(f"val_fraction must lie strictly inside (0, 1), got {val_fraction!r}")
+        f = _checked_float(val_fraction, 0.0, 1.0, f"val_fraction must lie strictly inside (0, 1), got {val_fraction!r}", lo_open=True, hi_open=True)
         val = np.random.default_rng(seed).permutation(E)[: max(1, int(round(f * E)))]
     else:
         val = _episode_ids(val_episodes, E, "val_episodes")
@@ -229,7 +234,7 @@ def split_episodes(store: EpisodeStore, val_fraction: Optional[float] = None, va
 def _episode_ids(ids, E: int, name: str) -> np.ndarray:
     """``ids`` as a sorted int64 array of distinct episode numbers in [0, E); ValueError otherwise."""
     try:
-        arr = np.asarray(_host(ids, name) if torch.is_tensor(ids) else ids)
+        arr = _as_numpy(ids, name)
     except (TypeError, ValueError):
         raise ValueError(f"{name} must be a sequence of episode ids") from None
     if arr.ndim != 1 or (arr.size and (arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer))):
@@ -240,6 +245,12 @@ def _episode_ids(ids, E: int, name: str) -> np.ndarray:
     if len(np.unique(arr)) != len(arr):
         raise ValueError(f"{name} repeats an id")
     return np.sort(arr)
+
+
+def _start_counts(lengths: np.ndarray, window: int, pad: str, stride: int = 1) -> np.ndarray:
+    """How many windows start in each episode, ``stride`` steps apart: ``pad="hold"`` starts one at every stride-th step, ``ceil(L / stride)``;
+    ``pad="none"`` only where the whole window fits, ``(L - W) // stride + 1`` when ``L >= W``, else none."""
+    return -(-lengths // stride) if pad == "hold" else np.where(lengths >= window, (lengths - window) // stride + 1, 0)
 
 
 def _start_table(n_e: np.ndarray, episodes, what: str):
@@ -260,9 +271,8 @@ def _check_window_args(store, batch_size, window, seed, pad, camera_transforms, 
     """The constructor checks WindowStream and WindowSweep share; returns the transforms as a tuple (or None)."""
     if not isinstance(store, EpisodeStore) or not store.finalized:
         raise ValueError(f"{who} needs a finalized EpisodeStore")
-    for name, v, hi in (("batch_size", batch_size, MAX_BATCH), ("window", window, MAX_WINDOW_FLOATS), ("seed", seed, 2 ** 32 - 1)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < (0 if name == "seed" else 1) or v > hi:
-            raise ValueError(f"{name} must be an int in {0 if name == 'seed' else 1}..{hi}, got {v!r}")
+    for name, v, lo, hi in (("batch_size", batch_size, 1, MAX_BATCH), ("window", window, 1, MAX_WINDOW_FLOATS), ("seed", seed, 0, 2 ** 32 - 1)):
+        _checked_int(v, lo, hi, f"{name} must be an int in {lo}..{hi}, got {v!r}")
     if window * store.action_dim > MAX_WINDOW_FLOATS:
         raise ValueError(f"window * action_dim must be at most {MAX_WINDOW_FLOATS}, got {window} * {store.action_dim}")
     if store.goal_dim > MAX_GOAL_DIM:
@@ -291,12 +301,7 @@ def _check_goal_args(store: EpisodeStore, goal, goal_horizon, hindsight_prob, wh
     ``mode_data_relabel_goals``.  A sweep's horizon may also be an int ``d`` (lo = hi = d) or ``"last"`` (the episode's final step)."""
     if not isinstance(goal, str) or goal not in _GOALS:
         raise ValueError(f"goal must be one of {_GOALS}, got {goal!r}")
-    try:
-        prob = float(hindsight_prob)
-    except (TypeError, ValueError):
-        prob = float("nan")
-    if isinstance(hindsight_prob, bool) or not 0.0 <= prob <= 1.0:
-        raise ValueError(f"hindsight_prob must lie in [0, 1], got {hindsight_prob!r}")
+    prob = _checked_float(hindsight_prob, 0.0, 1.0, f"hindsight_prob must lie in [0, 1], got {hindsight_prob!r}")
     if goal == "episode":
         if goal_horizon is not None:
             raise ValueError(f"goal_horizon={goal_horizon!r} needs goal='hindsight': goal='episode' draws no goal step")
@@ -322,20 +327,17 @@ def _check_goal_args(store: EpisodeStore, goal, goal_horizon, hindsight_prob, wh
 def _relabel_goals(store: EpisodeStore, out: dict, ids: Optional[torch.Tensor], seed: int, step: int, plan) -> None:
     """One ``mode_data_relabel_goals`` launch behind the sampling launch that filled ``out``: ``latent_goal`` updated in place, ``goal_index`` /
     ``goal_offset`` / ``goal_kind`` added.  ``ids`` None: a row's draws are keyed by its place; a sweep passes its ``window``."""
-    from . import _lib as L
-    from .engine import _stream
     lo, hi, thresh = plan
     B, dev = out["index"].shape[0], store.device
     out["goal_index"], out["goal_offset"] = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(2))
     out["goal_kind"] = torch.empty(B, dtype=torch.float32, device=dev)
-    d = L.ModeDataGoalDesc(step_goals=store.step_goals.data_ptr(), ep_begin=store.ep_begin.data_ptr(), index=out["index"].data_ptr(),
-                           episode=out["episode"].data_ptr(), ids=None if ids is None else ids.data_ptr(), thresh=thresh,
-                           goal_dtype=L.MODE_BF16 if store.step_goals.dtype == torch.bfloat16 else L.MODE_F32, S=store.step_goals.shape[0],
-                           E=store.goals.shape[0], G=store.goal_dim, B=B, seed=seed, step=step, lo=lo, hi=hi,
-                           latent_goal=out["latent_goal"].data_ptr(), goal_index=out["goal_index"].data_ptr(),
-                           goal_offset=out["goal_offset"].data_ptr(), goal_kind=out["goal_kind"].data_ptr())
-    with torch.cuda.device(dev):
-        L.check(L.load().mode_data_relabel_goals(C.byref(d), _stream()), "data_relabel_goals")
+    d = _lib.ModeDataGoalDesc(step_goals=store.step_goals.data_ptr(), ep_begin=store.ep_begin.data_ptr(), index=out["index"].data_ptr(),
+                              episode=out["episode"].data_ptr(), ids=None if ids is None else ids.data_ptr(), thresh=thresh,
+                              goal_dtype=_lib.MODE_BF16 if store.step_goals.dtype == torch.bfloat16 else _lib.MODE_F32, S=store.step_goals.shape[0],
+                              E=store.goals.shape[0], G=store.goal_dim, B=B, seed=seed, step=step, lo=lo, hi=hi,
+                              latent_goal=out["latent_goal"].data_ptr(), goal_index=out["goal_index"].data_ptr(),
+                              goal_offset=out["goal_offset"].data_ptr(), goal_kind=out["goal_kind"].data_ptr())
+    _launch(_lib.load().mode_data_relabel_goals, d, dev)
 
 
 _ORDERS = ("iid", "epoch")
@@ -348,7 +350,7 @@ def _cut_table(episode_weights, n_e: np.ndarray) -> np.ndarray:
     mass of 0 (or one that overflows fp64), or a positive mass whose interval comes out empty."""
     E = len(n_e)
     try:
-        w = np.asarray(_host(episode_weights, "episode_weights") if torch.is_tensor(episode_weights) else episode_weights)
+        w = _as_numpy(episode_weights, "episode_weights")
         if w.dtype == np.bool_ or not (np.issubdtype(w.dtype, np.floating) or np.issubdtype(w.dtype, np.integer)):
             raise TypeError
         w = w.astype(np.float64)
@@ -393,15 +395,11 @@ def mixture_weights(store: EpisodeStore, groups, group_weights, episodes=None, w
         raise ValueError(f"pad must be one of {_PADS}, got {pad!r}")
     E = store.num_episodes
     if pad == "none":
-        if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1:
-            raise ValueError(f"pad='none' needs window, an int >= 1, got {window!r}")
-        n_e = np.maximum(0, store.lengths - int(window) + 1)
-    else:
-        n_e = store.lengths
-    n_e = np.diff(_start_table(n_e, episodes, "no window fits any selected episode: nothing to weigh")[0])
+        window = _checked_int(window, 1, None, f"pad='none' needs window, an int >= 1, got {window!r}")
+    n_e = np.diff(_start_table(_start_counts(store.lengths, window, pad), episodes, "no window fits any selected episode: nothing to weigh")[0])
     try:
         p = np.asarray(group_weights, dtype=np.float64)
-        g = np.asarray(_host(groups, "groups") if torch.is_tensor(groups) else groups)
+        g = _as_numpy(groups, "groups")
     except (TypeError, ValueError):
         raise ValueError("groups must be a sequence of ints and group_weights a sequence of numbers") from None
     if p.ndim != 1 or p.size == 0 or not np.isfinite(p).all() or (p < 0).any() or not p.sum() > 0 or not np.isfinite(p.sum()):
@@ -422,6 +420,22 @@ def _frames_of(store: EpisodeStore, tr, shifts, index: torch.Tensor, B: int, fra
     dst = [torch.empty(tr[q].out_shape((B,) + tuple(frames[q].shape[1:])), dtype=frame_dtype, device=store.device) for q in range(2)]
     camera.launch([(tr[q], frames[q], dst[q], shifts[q]) for q in range(2)], index.data_ptr(), B, frames[0].shape[0])
     return {"rgb_static": dst[0], "rgb_gripper": dst[1]}
+
+
+def _window_outputs(src, who: str):
+    """What ``WindowStream.batch`` and ``WindowSweep.batch`` (``src``; ``who`` names it in the refusal) share: the device check, the five outputs
+    of a located window and the descriptor fields that ModeDataStreamDesc and ModeDataSweepDesc have in common, as keyword arguments."""
+    st, B, W = src.store, src.batch_size, src.window
+    A, G, dev = st.action_dim, st.goal_dim, st.device
+    if dev.type != "cuda":
+        raise ValueError(f"{who}.batch: the store must be on a ROCm device (there is no CPU path), got {dev}")
+    f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
+    out = {"actions": f32(B, W, A), "action_mask": f32(B, W), "latent_goal": f32(B, G), "index": i32(B), "episode": i32(B)}
+    return out, dict(actions=_ptr(st.actions), ep_begin=_ptr(st.ep_begin), starts=_ptr(src.starts), goals=_ptr(st.goals), lo=_ptr(st.lo),
+                     scale=_ptr(st.scale), S=st.actions.shape[0], E=st.goals.shape[0], A=A, G=G, W=W, B=B, n_total=src.n_total, seed=src.seed,
+                     out_actions=_ptr(out["actions"]), action_mask=_ptr(out["action_mask"]), latent_goal=_ptr(out["latent_goal"]),
+                     index=_ptr(out["index"]), episode=_ptr(out["episode"]))
 
 
 class WindowStream:
@@ -478,8 +492,7 @@ class WindowStream:
             raise ValueError(f"order must be one of {_ORDERS}, got {order!r}")
         if order == "epoch" and episode_weights is not None:
             raise ValueError("episode_weights needs order='iid': an epoch order with weights (weighted sampling without replacement) is not provided")
-        n_e = store.lengths if pad == "hold" else np.maximum(0, store.lengths - window + 1)
-        starts, n_total = _start_table(n_e, episodes, f"no window of {window} steps fits any "
+        starts, n_total = _start_table(_start_counts(store.lengths, window, pad), episodes, f"no window of {window} steps fits any "
                                        f"{'episode' if episodes is None else 'selected episode'} (pad={pad!r}): nothing to draw")
         cut = None if episode_weights is None else _cut_table(episode_weights, np.diff(starts))
         self.store, self.batch_size, self.window, self.seed, self.pad, self.noise = store, int(batch_size), int(window), int(seed), pad, bool(noise)
@@ -496,47 +509,32 @@ class WindowStream:
 
     def epoch_of(self, step: int) -> int:
         """The epoch of row 0 of step ``step`` under ``order="epoch"``: ``(step * B) // n_total``.  The step's last row is in the same epoch or the next."""
-        if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or not 0 <= step < 2 ** 32:
-            raise ValueError(f"step must be an int in 0..2^32 - 1, got {step!r}")
-        return (int(step) * self.batch_size) // self.n_total
+        return (_checked_u32(step, "step") * self.batch_size) // self.n_total
 
     def batch(self, step: int) -> dict:
-        from . import _lib as L
-        from .engine import _stream
-        if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or not 0 <= step < 2 ** 32:
-            raise ValueError(f"step must be an int in 0..2^32 - 1, got {step!r}")
-        st, B, W = self.store, self.batch_size, self.window
-        A, G, dev = st.action_dim, st.goal_dim, st.device
-        if dev.type != "cuda":
-            raise ValueError(f"WindowStream.batch: the store must be on a ROCm device (there is no CPU path), got {dev}")
-        f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-        i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
-        out = {"actions": f32(B, W, A), "action_mask": f32(B, W), "latent_goal": f32(B, G), "index": i32(B), "episode": i32(B)}
+        step = _checked_u32(step, "step")
+        out, common = _window_outputs(self, "WindowStream")
+        st, B, W, dev = self.store, self.batch_size, self.window, self.store.device
         if self.noise:
-            out["noise"], out["u"] = f32(B, W, A), torch.empty(B, dtype=torch.float64, device=dev)
+            out["noise"] = torch.empty(B, W, st.action_dim, dtype=torch.float32, device=dev)
+            out["u"] = torch.empty(B, dtype=torch.float64, device=dev)
         tr = self.camera_transforms
-        shifts = [i32(B, 2) if tr is not None and tr[q].shift_pad > 0 else None for q in range(2)]
-        p = lambda t: None if t is None else t.data_ptr()
-        d = L.ModeDataStreamDesc(actions=p(st.actions), ep_begin=p(st.ep_begin), starts=p(self.starts), goals=p(st.goals), lo=p(st.lo), scale=p(st.scale),
-                                 S=st.actions.shape[0], E=st.goals.shape[0], A=A, G=G, W=W, B=B, n_total=self.n_total, seed=self.seed, step=int(step),
-                                 out_actions=p(out["actions"]), action_mask=p(out["action_mask"]), latent_goal=p(out["latent_goal"]),
-                                 index=p(out["index"]), episode=p(out["episode"]), noise=p(out.get("noise")), u=p(out.get("u")))
+        shifts = [torch.empty(B, 2, dtype=torch.int32, device=dev) if tr is not None and tr[q].shift_pad > 0 else None for q in range(2)]
+        d = _lib.ModeDataStreamDesc(**common, step=step, noise=_ptr(out.get("noise")), u=_ptr(out.get("u")))
         for q in range(2):
-            d.shifts[q] = p(shifts[q])
+            d.shifts[q] = _ptr(shifts[q])
             d.shift_pad[q] = tr[q].shift_pad if tr is not None else 0
         if self.order == "iid" and self.cut is None:
-            with torch.cuda.device(dev):
-                L.check(L.load().mode_data_sample_windows(C.byref(d), _stream()), "data_sample_windows")
+            _launch(_lib.load().mode_data_sample_windows, d, dev)
         else:
             epoch = self.order == "epoch"
             if epoch:
                 out["epoch"], out["position"] = (torch.empty(B, dtype=torch.int64, device=dev) for _ in range(2))
-            o = L.ModeDataOrderDesc(s=d, mode=L.MODE_ORDER_EPOCH if epoch else L.MODE_ORDER_WEIGHTED, cut=p(self.cut), epoch=p(out.get("epoch")),
-                                    position=p(out.get("position")))
-            with torch.cuda.device(dev):
-                L.check(L.load().mode_data_sample_windows_ordered(C.byref(o), _stream()), "data_sample_windows_ordered")
+            o = _lib.ModeDataOrderDesc(s=d, mode=_lib.MODE_ORDER_EPOCH if epoch else _lib.MODE_ORDER_WEIGHTED, cut=_ptr(self.cut), epoch=_ptr(out.get("epoch")),
+                                       position=_ptr(out.get("position")))
+            _launch(_lib.load().mode_data_sample_windows_ordered, o, dev)
         if self._goal_plan is not None:
-            _relabel_goals(st, out, None, self.seed, int(step), self._goal_plan)
+            _relabel_goals(st, out, None, self.seed, step, self._goal_plan)
         if tr is not None:
             out["rgb_obs"] = _frames_of(st, tr, shifts, out["index"], B, self.frame_dtype)
             out["shifts"] = {"rgb_static": shifts[0], "rgb_gripper": shifts[1]}
@@ -573,15 +571,12 @@ class WindowSweep:
                  goal: str = "episode", goal_horizon=None, hindsight_prob: float = 1.0):
         camera_transforms = _check_window_args(store, batch_size, window, seed, pad, camera_transforms, frame_dtype, "WindowSweep")
         self.goal, self._goal_plan = goal, _check_goal_args(store, goal, goal_horizon, hindsight_prob, "WindowSweep", sweep=True)
-        if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
-            raise ValueError(f"stride must be an int >= 1, got {stride!r}")
+        stride = _checked_int(stride, 1, None, f"stride must be an int >= 1, got {stride!r}")
         if isinstance(noise_scale, bool) or not np.isfinite(float(noise_scale)):
             raise ValueError(f"noise_scale must be a finite number, got {noise_scale!r}")
-        L_e = store.lengths
-        n_e = -(-L_e // stride) if pad == "hold" else np.where(L_e >= window, (L_e - window) // stride + 1, 0)
-        starts, n_total = _start_table(n_e, episodes, f"no window of {window} steps fits any "
+        starts, n_total = _start_table(_start_counts(store.lengths, window, pad, stride), episodes, f"no window of {window} steps fits any "
                                        f"{'episode' if episodes is None else 'selected episode'} (pad={pad!r}): nothing to sweep")
-        self.store, self.batch_size, self.window, self.stride, self.pad, self.seed = store, int(batch_size), int(window), int(stride), pad, int(seed)
+        self.store, self.batch_size, self.window, self.stride, self.pad, self.seed = store, int(batch_size), int(window), stride, pad, int(seed)
         self.camera_transforms, self.frame_dtype, self.noise_scale = camera_transforms, frame_dtype, float(noise_scale)
         self.n_total = n_total
         self.starts = torch.from_numpy(starts.astype(np.int32)).to(store.device)            # the device table the kernel searches
@@ -591,33 +586,20 @@ class WindowSweep:
 
     def batch(self, i: int, draw: int = 0, noise_scale: Optional[float] = None) -> dict:
         """``noise_scale``: this batch's factor in place of the sweep's own (``validation.Validator`` asks for its ``sigma_max``)."""
-        from . import _lib as L
-        from .engine import _stream
         scale = self.noise_scale if noise_scale is None else float(noise_scale)
         if not np.isfinite(scale):
             raise ValueError(f"noise_scale must be a finite number, got {noise_scale!r}")
-        if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 0 <= i < len(self):
-            raise ValueError(f"batch index must be an int in 0..{len(self) - 1}, got {i!r}")
-        if isinstance(draw, bool) or not isinstance(draw, (int, np.integer)) or not 0 <= draw < 2 ** 32:
-            raise ValueError(f"draw must be an int in 0..2^32 - 1, got {draw!r}")
-        st, B, W = self.store, self.batch_size, self.window
-        A, G, dev = st.action_dim, st.goal_dim, st.device
-        if dev.type != "cuda":
-            raise ValueError(f"WindowSweep.batch: the store must be on a ROCm device (there is no CPU path), got {dev}")
-        f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-        i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
-        out = {"actions": f32(B, W, A), "action_mask": f32(B, W), "latent_goal": f32(B, G), "index": i32(B), "episode": i32(B), "valid": f32(B),
-               "window": i32(B), "noise": f32(B, W, A)}
-        p = lambda t: None if t is None else t.data_ptr()
-        d = L.ModeDataSweepDesc(actions=p(st.actions), ep_begin=p(st.ep_begin), starts=p(self.starts), goals=p(st.goals), lo=p(st.lo), scale=p(st.scale),
-                                S=st.actions.shape[0], E=st.goals.shape[0], A=A, G=G, W=W, B=B, n_total=self.n_total, stride=self.stride,
-                                first=int(i) * B, seed=self.seed, draw=int(draw), noise_scale=scale, out_actions=p(out["actions"]),
-                                action_mask=p(out["action_mask"]), latent_goal=p(out["latent_goal"]), index=p(out["index"]), episode=p(out["episode"]),
-                                valid=p(out["valid"]), window=p(out["window"]), noise=p(out["noise"]))
-        with torch.cuda.device(dev):
-            L.check(L.load().mode_data_sweep_windows(C.byref(d), _stream()), "data_sweep_windows")
+        i = _checked_int(i, 0, len(self) - 1, f"batch index must be an int in 0..{len(self) - 1}, got {i!r}")
+        draw = _checked_u32(draw, "draw")
+        out, common = _window_outputs(self, "WindowSweep")
+        st, B, dev = self.store, self.batch_size, self.store.device
+        out["valid"], out["window"] = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
+        out["noise"] = torch.empty(B, self.window, st.action_dim, dtype=torch.float32, device=dev)
+        d = _lib.ModeDataSweepDesc(**common, stride=self.stride, first=i * B, draw=draw, noise_scale=scale, valid=_ptr(out["valid"]),
+                                   window=_ptr(out["window"]), noise=_ptr(out["noise"]))
+        _launch(_lib.load().mode_data_sweep_windows, d, dev)
         if self._goal_plan is not None:
-            _relabel_goals(st, out, out["window"], self.seed, int(draw), self._goal_plan)
+            _relabel_goals(st, out, out["window"], self.seed, draw, self._goal_plan)
         if self.camera_transforms is not None:
             out["rgb_obs"] = _frames_of(st, self.camera_transforms, (None, None), out["index"], B, self.frame_dtype)
         return out

@@ -36,6 +36,18 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def _ptr(t: Optional[torch.Tensor]):
+    """A tensor's address for a descriptor field; None (NULL) for an absent one."""
+    return None if t is None else t.data_ptr()
+
+
+def _launch(fn, desc, dev) -> None:
+    """``fn(&desc, the current stream)`` with ``dev`` current, for an entry point ``fn = L.load().mode_<what>`` that takes a descriptor; a status other
+    than MODE_OK raises (``L.check``, which names ``<what>``: ctypes gives a library's function pointer the symbol's name as ``__name__``)."""
+    with torch.cuda.device(dev):
+        L.check(fn(C.byref(desc), _stream()), fn.__name__[len("mode_"):])
+
+
 def graphs_enabled() -> bool:
     """The hipGraph switch: MODE_HIP_GRAPH=0 sends every graphed path (denoiser, samplers, rollout chunks, perceptual encoders) down its step-by-step
     launch chain.  Read at every call, so it can be flipped mid-process."""

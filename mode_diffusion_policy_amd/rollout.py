@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import gc_sampling as gs
+from ._checks import _checked_float, _checked_int
 from .engine import graphs_enabled
 
 
@@ -305,25 +306,6 @@ def coherence_weights(rho: float, length: int) -> np.ndarray:
     """The weight table of candidate selection (``VectorEnvPolicy(candidates=N, coherence_decay=rho)``), ``w_i = rho ** i`` for the i-th coming
     step: the fp64 power rounded to fp32, ``length`` entries.  The kernel reads this table and evaluates no transcendental itself."""
     return (float(rho) ** np.arange(length, dtype=np.float64)).astype(np.float32)
-
-
-def _checked_int(value, lo: int, hi: Optional[int], message: str) -> int:
-    """``value`` as an int when it is one (no bool) in [lo, hi] (``hi`` None: no upper bound); ValueError(message) otherwise."""
-    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or int(value) < lo or (hi is not None and int(value) > hi):
-        raise ValueError(message)
-    return int(value)
-
-
-def _checked_float(value, lo: float, hi: float, message: str, lo_open: bool = False) -> float:
-    """``float(value)`` when it is finite and in [lo, hi] ((lo, hi] with ``lo_open``); ValueError(message) otherwise, also for a bool and for
-    what float() does not take."""
-    try:
-        x = float(value)
-    except (TypeError, ValueError):
-        x = float("nan")
-    if isinstance(value, bool) or not (np.isfinite(x) and lo <= x <= hi and not (lo_open and x == lo)):
-        raise ValueError(message)
-    return x
 
 
 def _env_latents(what: str, seeds, draws, dev, shape, *tail) -> torch.Tensor:

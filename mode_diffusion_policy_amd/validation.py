@@ -12,14 +12,65 @@ adds the masked squared error into fp64 accumulators per level - the same summat
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Callable, Optional
 
 import torch
 
+from . import _lib
 from .data import MAX_BATCH, MAX_WINDOW_FLOATS, WindowSweep
+from .engine import _launch, _ptr
 from .rollout import ChunkedRolloutPolicy
+
+
+def _same(name: str, who: str, t, shape, dt, dev) -> None:
+    if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous {dt} {shape} tensor on {dev}, got "
+                         f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
+
+
+def _mean(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
+    """``num / den`` where ``den > 0``, else 0: a mean over nothing is 0."""
+    return torch.where(den > 0, num / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(den))
+
+
+def _raw_unit(store, raw_units: bool) -> Optional[torch.Tensor]:
+    """``unit[a] = 1 / (double) scale[a]``, 0 where ``scale[a] == 0``; None without ``raw_units`` or for a store without normalisation."""
+    if not raw_units or store.scale is None:
+        return None
+    s = store.scale.to(torch.float64)
+    return torch.where(s != 0, 1.0 / torch.where(s != 0, s, torch.ones_like(s)), torch.zeros_like(s)).contiguous()
+
+
+def _check_validator_args(who: str, sweep, embed) -> None:
+    if not isinstance(sweep, WindowSweep):
+        raise ValueError(f"{who} needs a data.WindowSweep, got {type(sweep).__name__}")
+    if not callable(embed):
+        raise ValueError("embed must be a function batch -> {'state_images': [B, n_img_tokens, obs_dim]}")
+
+
+def _check_draws(draws) -> None:
+    if isinstance(draws, bool) or not isinstance(draws, int) or draws < 1:
+        raise ValueError(f"draws must be an int >= 1, got {draws!r}")
+
+
+def _held_out_pass(val, denoiser, draws, ema, add: Callable[[dict], None]) -> None:
+    """The pass both validators run (``val``: the ``Validator`` or ``LevelValidator``): ``add(val.batch(i, draw))`` for every batch of every draw with
+    ``denoiser`` in eval mode and, with ``ema``, the averaged weights swapped in; in a ``finally`` the live weights are swapped back and every
+    submodule gets the ``training`` flag it had."""
+    modes = [(m, m.training) for m in denoiser.modules()]
+    if ema is not None:
+        ema.swap()
+    try:
+        denoiser.eval()
+        for draw in range(draws):
+            for i in range(len(val)):
+                add(val.batch(i, draw))
+    finally:
+        if ema is not None:
+            ema.swap()
+        for m, was in modes:
+            m.training = was
 
 
 def action_error(pred: torch.Tensor, target: torch.Tensor, sq: torch.Tensor, ab: torch.Tensor, cnt: torch.Tensor, mask: Optional[torch.Tensor] = None,
@@ -32,8 +83,6 @@ def action_error(pred: torch.Tensor, target: torch.Tensor, sq: torch.Tensor, ab:
     ``pred``, ``target`` [B, W, A] fp32, ``mask`` [B, W] fp32, ``weight`` [B] fp32, ``unit`` [A] fp64, ``sq`` / ``ab`` [W * A] and ``cnt`` [W] fp64, all
     contiguous on one ROCm device.  Terms with ``c == 0`` are skipped, so ``pred`` may hold anything there.  No atomics: the result's bits depend on
     the shapes and the order of the calls only.  ``accumulate=False`` stores instead of adding."""
-    from . import _lib as L
-    from .engine import _stream
     if not torch.is_tensor(pred) or pred.dim() != 3 or pred.device.type != "cuda":
         raise ValueError(f"action_error: pred must be a [B, W, A] tensor on a ROCm device, got {tuple(getattr(pred, 'shape', ()))}")
     B, W, A = pred.shape
@@ -44,14 +93,10 @@ def action_error(pred: torch.Tensor, target: torch.Tensor, sq: torch.Tensor, ab:
                                ("ab", ab, (W * A,), torch.float64), ("cnt", cnt, (W,), torch.float64)):
         if t is None and name in ("mask", "weight", "unit"):
             continue
-        if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or t.device != pred.device or not t.is_contiguous():
-            raise ValueError(f"action_error: {name} must be a contiguous {dt} {shape} tensor on {pred.device}, got "
-                             f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
-    p = lambda t: None if t is None else t.data_ptr()
-    d = L.ModeActionErrorDesc(pred=p(pred), target=p(target), mask=p(mask), weight=p(weight), unit=p(unit), sq=p(sq), ab=p(ab), cnt=p(cnt), B=B, W=W, A=A,
-                              accumulate=1 if accumulate else 0)
-    with torch.cuda.device(pred.device):
-        L.check(L.load().mode_action_error(C.byref(d), _stream()), "action_error")
+        _same(name, "action_error", t, shape, dt, pred.device)
+    d = _lib.ModeActionErrorDesc(pred=_ptr(pred), target=_ptr(target), mask=_ptr(mask), weight=_ptr(weight), unit=_ptr(unit), sq=_ptr(sq), ab=_ptr(ab),
+                                 cnt=_ptr(cnt), B=B, W=W, A=A, accumulate=1 if accumulate else 0)
+    _launch(_lib.load().mode_action_error, d, pred.device)
 
 
 class ValidationResult(dict):
@@ -69,16 +114,14 @@ class ValidationResult(dict):
         sq, ab = sq.reshape(W, -1), ab.reshape(W, -1)
         A = sq.shape[1]
         count = cnt.sum()
-        mean = lambda num, den: torch.where(den > 0, num / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(den))
-        return cls(sq=sq, ab=ab, cnt=cnt, count=count, mse=mean(sq.sum(), A * count), mae=mean(ab.sum(), A * count),
-                   mse_per_step=mean(sq.sum(1), A * cnt), mse_per_dim=mean(sq.sum(0), count.expand(A)))
+        return cls(sq=sq, ab=ab, cnt=cnt, count=count, mse=_mean(sq.sum(), A * count), mae=_mean(ab.sum(), A * count),
+                   mse_per_step=_mean(sq.sum(1), A * cnt), mse_per_dim=_mean(sq.sum(0), count.expand(A)))
 
     def mse_executed(self, multistep: int) -> torch.Tensor:
         W, A = self["sq"].shape
         if isinstance(multistep, bool) or not isinstance(multistep, int) or not 1 <= multistep <= W:
             raise ValueError(f"multistep must be an int in 1..{W}, got {multistep!r}")
-        num, den = self["sq"][:multistep].sum(), A * self["cnt"][:multistep].sum()
-        return torch.where(den > 0, num / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(den))
+        return _mean(self["sq"][:multistep].sum(), A * self["cnt"][:multistep].sum())
 
 
 class Validator:
@@ -113,19 +156,13 @@ class Validator:
 
     def __init__(self, denoiser, sweep: WindowSweep, embed: Callable[[dict], dict], num_sampling_steps: int = 10, sigma_min: float = 0.001,
                  sigma_max: float = 80.0, noise_scheduler: str = "exponential", sampler_type: str = "ddim", raw_units: bool = True):
-        if not isinstance(sweep, WindowSweep):
-            raise ValueError(f"Validator needs a data.WindowSweep, got {type(sweep).__name__}")
-        if not callable(embed):
-            raise ValueError("embed must be a function batch -> {'state_images': [B, n_img_tokens, obs_dim]}")
+        _check_validator_args("Validator", sweep, embed)
         st = sweep.store
         self.sweep, self.embed, self.sigma_max = sweep, embed, float(sigma_max)
         self.policy = ChunkedRolloutPolicy(denoiser, num_sampling_steps=num_sampling_steps, sigma_min=sigma_min, sigma_max=sigma_max,
                                            noise_scheduler=noise_scheduler, sampler_type=sampler_type, act_window_size=sweep.window,
                                            multistep=sweep.window, action_dim=st.action_dim)
-        self.unit = None
-        if raw_units and st.scale is not None:
-            s = st.scale.to(torch.float64)
-            self.unit = torch.where(s != 0, 1.0 / torch.where(s != 0, s, torch.ones_like(s)), torch.zeros_like(s)).contiguous()
+        self.unit = _raw_unit(st, raw_units)
 
     def __len__(self) -> int:
         return len(self.sweep)
@@ -139,37 +176,17 @@ class Validator:
 
     @torch.no_grad()
     def run(self, draws: int = 1, ema=None) -> ValidationResult:
-        if isinstance(draws, bool) or not isinstance(draws, int) or draws < 1:
-            raise ValueError(f"draws must be an int >= 1, got {draws!r}")
-        den, sw = self.policy.model, self.sweep
-        W, A, dev = sw.window, sw.store.action_dim, sw.store.device
-        modes = [(m, m.training) for m in den.modules()]
+        _check_draws(draws)
+        W, A, dev = self.sweep.window, self.sweep.store.action_dim, self.sweep.store.device
         sq, ab = (torch.zeros(W * A, dtype=torch.float64, device=dev) for _ in range(2))
         cnt = torch.zeros(W, dtype=torch.float64, device=dev)
-        if ema is not None:
-            ema.swap()
-        try:
-            den.eval()
-            for draw in range(draws):
-                for i in range(len(sw)):
-                    b = self.batch(i, draw)
-                    action_error(self.predict(b).to(torch.float32).contiguous(), b["actions"], sq, ab, cnt,mask=b["action_mask"], weight=b["valid"], unit=self.unit)
-        finally:
-            if ema is not None:
-                ema.swap()
-            for m, was in modes:
-                m.training = was
+        _held_out_pass(self, self.policy.model, draws, ema, lambda b: action_error(
+            self.predict(b).to(torch.float32).contiguous(), b["actions"], sq, ab, cnt, mask=b["action_mask"], weight=b["valid"], unit=self.unit))
         return ValidationResult.from_sums(sq, ab, cnt)
 
 
 # ------------------------------------------------------------------------------------------------ held-out denoising loss per noise level
 MAX_LEVELS = 256           # the kernels' limit (include/mode_hip.h)
-
-
-def _same(name: str, who: str, t, shape, dt, dev) -> None:
-    if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
-        raise ValueError(f"{who}: {name} must be a contiguous {dt} {shape} tensor on {dev}, got "
-                         f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
 
 
 def noise_levels(actions: torch.Tensor, noise: torch.Tensor, window: torch.Tensor, sigmas: torch.Tensor, draw: int = 0):
@@ -179,8 +196,6 @@ def noise_levels(actions: torch.Tensor, noise: torch.Tensor, window: torch.Tenso
 
     (one fp32 product and one fp32 sum per element, unfused).  ``actions``, ``noise`` [B, W, A] fp32, ``window`` [B] int32, ``sigmas`` [K] fp32,
     ``K <= 256``, all contiguous on one ROCm device.  A row depends on its window number, the draw and the table only."""
-    from . import _lib as L
-    from .engine import _stream
     if not torch.is_tensor(actions) or actions.dim() != 3 or actions.device.type != "cuda":
         raise ValueError(f"noise_levels: actions must be a [B, W, A] tensor on a ROCm device, got {tuple(getattr(actions, 'shape', ()))}")
     if isinstance(draw, bool) or not isinstance(draw, int) or not 0 <= draw < 2 ** 32:
@@ -196,10 +211,9 @@ def noise_levels(actions: torch.Tensor, noise: torch.Tensor, window: torch.Tenso
     level = torch.empty(B, dtype=torch.int32, device=dev)
     sigma = torch.empty(B, dtype=torch.float32, device=dev)
     x = torch.empty(B, W, A, dtype=torch.float32, device=dev)
-    d = L.ModeValLevelsDesc(actions=actions.data_ptr(), noise=noise.data_ptr(), window=window.data_ptr(), sigmas=sigmas.data_ptr(), B=B, W=W, A=A, K=K,
-                            draw=draw, level=level.data_ptr(), sigma=sigma.data_ptr(), x=x.data_ptr())
-    with torch.cuda.device(dev):
-        L.check(L.load().mode_val_noise_levels(C.byref(d), _stream()), "val_noise_levels")
+    d = _lib.ModeValLevelsDesc(actions=actions.data_ptr(), noise=noise.data_ptr(), window=window.data_ptr(), sigmas=sigmas.data_ptr(), B=B, W=W, A=A, K=K,
+                               draw=draw, level=level.data_ptr(), sigma=sigma.data_ptr(), x=x.data_ptr())
+    _launch(_lib.load().mode_val_noise_levels, d, dev)
     return level, sigma, x
 
 
@@ -212,8 +226,6 @@ def level_error(pred: torch.Tensor, target: torch.Tensor, level: torch.Tensor, s
     with ``sq`` [K, W * A] and ``cnt`` [K, W] fp64, ``K <= 256``.  A row whose level is outside ``0..K-1`` counts nowhere; rows of another level and
     terms with ``c == 0`` are skipped, so ``pred`` may hold anything there.  Level ``k``'s slice has the bits ``action_error`` gives with the weight
     zeroed on every other level's rows."""
-    from . import _lib as L
-    from .engine import _stream
     if not torch.is_tensor(pred) or pred.dim() != 3 or pred.device.type != "cuda":
         raise ValueError(f"level_error: pred must be a [B, W, A] tensor on a ROCm device, got {tuple(getattr(pred, 'shape', ()))}")
     B, W, A = pred.shape
@@ -227,11 +239,9 @@ def level_error(pred: torch.Tensor, target: torch.Tensor, level: torch.Tensor, s
         if t is None and name in ("mask", "weight"):
             continue
         _same(name, "level_error", t, shape, dt, pred.device)
-    p = lambda t: None if t is None else t.data_ptr()
-    d = L.ModeLevelErrorDesc(pred=p(pred), target=p(target), mask=p(mask), weight=p(weight), level=p(level), sq=p(sq), cnt=p(cnt), B=B, W=W, A=A, K=K,
-                             accumulate=1 if accumulate else 0)
-    with torch.cuda.device(pred.device):
-        L.check(L.load().mode_level_error(C.byref(d), _stream()), "level_error")
+    d = _lib.ModeLevelErrorDesc(pred=_ptr(pred), target=_ptr(target), mask=_ptr(mask), weight=_ptr(weight), level=_ptr(level), sq=_ptr(sq),
+                                cnt=_ptr(cnt), B=B, W=W, A=A, K=K, accumulate=1 if accumulate else 0)
+    _launch(_lib.load().mode_level_error, d, pred.device)
 
 
 def level_table(levels="density", num_levels: int = 16, sigma_min: float = 0.001, sigma_max: float = 80.0, num_sampling_steps: int = 10,
@@ -297,16 +307,15 @@ class LevelResult(dict):
         K, W = cnt.shape
         sq = sq.reshape(K, W, -1)
         A = sq.shape[2]
-        mean = lambda num, den: torch.where(den > 0, num / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(den))
         count = cnt.sum(1)
         raw = sq if unit is None else sq * (unit.to(sq) * unit.to(sq))
         s = sigmas.to(sq)
         lam = (s * s + sigma_data ** 2) / (s * sigma_data) ** 2
-        loss_k = lam * mean(sq.sum((1, 2)), A * count)
+        loss_k = lam * _mean(sq.sum((1, 2)), A * count)
         live = (count > 0).to(sq)
-        return cls(sigmas=sigmas, sq=sq, cnt=cnt, count_per_level=count, mse_per_level=mean(raw.sum((1, 2)), A * count),
-                   mse_per_level_step=mean(raw.sum(2), A * cnt), mse_per_level_dim=mean(raw.sum(1), count[:, None].expand(K, A)),
-                   loss_per_level=loss_k, loss=mean((loss_k * live).sum(), live.sum()))
+        return cls(sigmas=sigmas, sq=sq, cnt=cnt, count_per_level=count, mse_per_level=_mean(raw.sum((1, 2)), A * count),
+                   mse_per_level_step=_mean(raw.sum(2), A * cnt), mse_per_level_dim=_mean(raw.sum(1), count[:, None].expand(K, A)),
+                   loss_per_level=loss_k, loss=_mean((loss_k * live).sum(), live.sum()))
 
 
 class LevelValidator:
@@ -336,19 +345,13 @@ class LevelValidator:
 
     def __init__(self, denoiser, sweep: WindowSweep, embed: Callable[[dict], dict], levels="density", num_levels: int = 16, sigma_min: float = 0.001,
                  sigma_max: float = 80.0, num_sampling_steps: int = 10, raw_units: bool = True):
-        if not isinstance(sweep, WindowSweep):
-            raise ValueError(f"LevelValidator needs a data.WindowSweep, got {type(sweep).__name__}")
-        if not callable(embed):
-            raise ValueError("embed must be a function batch -> {'state_images': [B, n_img_tokens, obs_dim]}")
+        _check_validator_args("LevelValidator", sweep, embed)
         st = sweep.store
         self.denoiser, self.sweep, self.embed = denoiser, sweep, embed
         self.sigma_data = float(denoiser.sigma_data)
         table = level_table(levels, num_levels, sigma_min, sigma_max, num_sampling_steps, self.sigma_data)
         self.sigmas = table.to(torch.float32).to(st.device).contiguous()
-        self.unit = None
-        if raw_units and st.scale is not None:
-            s = st.scale.to(torch.float64)
-            self.unit = torch.where(s != 0, 1.0 / torch.where(s != 0, s, torch.ones_like(s)), torch.zeros_like(s)).contiguous()
+        self.unit = _raw_unit(st, raw_units)
 
     def __len__(self) -> int:
         return len(self.sweep)
@@ -369,26 +372,11 @@ class LevelValidator:
 
     @torch.no_grad()
     def run(self, draws: Optional[int] = None, ema=None) -> LevelResult:
-        K = self.num_levels
+        K, W, A, dev = self.num_levels, self.sweep.window, self.sweep.store.action_dim, self.sweep.store.device
         draws = K if draws is None else draws
-        if isinstance(draws, bool) or not isinstance(draws, int) or draws < 1:
-            raise ValueError(f"draws must be an int >= 1, got {draws!r}")
-        den, sw = self.denoiser, self.sweep
-        W, A, dev = sw.window, sw.store.action_dim, sw.store.device
-        modes = [(m, m.training) for m in den.modules()]
+        _check_draws(draws)
         sq = torch.zeros(K, W * A, dtype=torch.float64, device=dev)
         cnt = torch.zeros(K, W, dtype=torch.float64, device=dev)
-        if ema is not None:
-            ema.swap()
-        try:
-            den.eval()
-            for draw in range(draws):
-                for i in range(len(sw)):
-                    b = self.batch(i, draw)
-                    level_error(self.predict(b).to(torch.float32).contiguous(), b["actions"], b["level"], sq, cnt, mask=b["action_mask"], weight=b["valid"])
-        finally:
-            if ema is not None:
-                ema.swap()
-            for m, was in modes:
-                m.training = was
+        _held_out_pass(self, self.denoiser, draws, ema, lambda b: level_error(
+            self.predict(b).to(torch.float32).contiguous(), b["actions"], b["level"], sq, cnt, mask=b["action_mask"], weight=b["valid"]))
         return LevelResult.from_sums(sq, cnt, self.sigmas, self.sigma_data, self.unit)

@@ -175,3 +175,9 @@ def masked_loss(F, action, noise, sigma, sigma_data, mask=None, weight=None):
     b_per = k * np.where(Mb > 0, e_S / np.where(Mb > 0, A * Mb, 1.0) + (math.ceil(W / 64) + 9) * U24 * per, 0.0)
     b_loss = k * ((wt * e_S).sum() / den + (math.ceil(B / 16) + 18 + n_c) * U24 * loss) if den > 0 else 0.0
     return dict(loss=loss, dF=dF, per_sample=per, b_loss=float(b_loss), b_dF=b_dF, b_per_sample=b_per)
+
+
+def same_bits(a, b) -> bool:
+    """Two arrays of one shape and dtype with the same bytes: NaN payloads and the sign of zero count."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()

@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from mode_diffusion_policy_amd import _lib as L
@@ -192,3 +193,12 @@ def combine_norm(u, Y, pos, posw, k, g, cond, rows_per_cond, eps=1e-6, h_dtype=t
     L.check(lib.mode_moe_combine_norm_fwd(p(u), p(Y), dt_of(Y), 1, 0, p(pos), p(posw), N, D, k, p(g), p(cond), rows_per_cond, eps, p(xn), p(h),
                                           L.MODE_BF16 if h_dtype == torch.bfloat16 else L.MODE_F32, stream()), "combine_norm")
     return xn, h
+
+
+def dev_store(eps, norm):
+    """The episode store's device tables, as data.EpisodeStore.finalize() lays them out, built by hand for the ctypes path."""
+    lengths = [e[0].shape[0] for e in eps]
+    t = dict(actions=torch.from_numpy(np.concatenate([e[0] for e in eps])).cuda(), goals=torch.from_numpy(np.stack([e[1] for e in eps])).cuda(),
+             ep_begin=torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)).cuda(), lengths=lengths)
+    t["lo"], t["scale"] = (None, None) if norm is None else (torch.from_numpy(norm[0]).cuda(), torch.from_numpy(norm[1]).cuda())
+    return t

@@ -63,11 +63,6 @@ def factors(B, W, A, kind, rng):
     return mask, weight
 
 
-def same_bits(got, want, what):
-    for g, w, name in zip(got, want, ("sq", "ab", "cnt")):
-        assert np.array_equal(g.view(np.uint64), w.view(np.uint64)), (what, name, float(np.abs(g - w).max()))
-
-
 @pytest.mark.parametrize("unit_kind", ["absent", "present"])
 @pytest.mark.parametrize("B,W,A", SHAPES)
 def test_sums_match_the_ordered_reference_bit_for_bit(B, W, A, unit_kind):
@@ -87,7 +82,7 @@ def test_sums_match_the_ordered_reference_bit_for_bit(B, W, A, unit_kind):
             torch.cuda.synchronize()
             ref = V.action_error(pred, target, mask, weight, unit)
             assert acc.intact()
-            same_bits(acc.host(), ref, (mk, wk))
+            V.same_sums(acc.host(), ref, (mk, wk))
             live = bool((V._terms(pred, target, mask, weight, None)[0] > 0).any())
             assert live == (ref[2].sum() > 0) and (live or all((r == 0).all() for r in ref)) and not (live and "zero" in (mk, wk))
             if live and (unit is None or A > 1):
@@ -112,17 +107,17 @@ def test_accumulation_over_calls_and_dirt_under_the_mask(B, W, A):
     torch.cuda.synchronize()
     first = V.action_error(p1, t1, mask, weight, unit)
     assert all(np.isfinite(h).all() for h in acc.host())
-    same_bits(acc.host(), first, "first call, dirty pred")
+    V.same_sums(acc.host(), first, "first call, dirty pred")
     assert launch(acc, dev(p2), dev(t2), None, dev(weight), None, accumulate=1) == 0
     torch.cuda.synchronize()
     both = V.action_error(p2, t2, None, weight, None, into=first)
-    same_bits(acc.host(), both, "two calls")
+    V.same_sums(acc.host(), both, "two calls")
     assert acc.intact() and (both[0] > first[0]).all()
     # the Python entry: the same launch, accumulate by default
     sq, ab, cnt = (torch.zeros(n, dtype=torch.float64, device="cuda") for n in (W * A, W * A, W))
     validation.action_error(dev(p1d), dev(t1), sq, ab, cnt, mask=dev(mask), weight=dev(weight), unit=dev(unit, torch.float64))
     validation.action_error(dev(p2), dev(t2), sq, ab, cnt, weight=dev(weight))
-    same_bits([v.cpu().numpy() for v in (sq, ab, cnt)], both, "validation.action_error")
+    V.same_sums([v.cpu().numpy() for v in (sq, ab, cnt)], both, "validation.action_error")
     res = validation.ValidationResult.from_sums(sq, ab, cnt)
     assert abs(float(res["mse"]) - both[0].sum() / (A * both[2].sum())) < 1e-12 * float(res["mse"]) and float(res["count"]) == both[2].sum()
     assert res["mse_per_step"].shape == (W,) and res["mse_per_dim"].shape == (A,) and float(res.mse_executed(1)) == float(res["mse_per_step"][0])

@@ -18,15 +18,6 @@ BAD_ARG, UNSUPPORTED = -1, -2
 BATCHES = (1, 7, 64, 300)
 
 
-def dev_store(eps, norm):
-    """The store's device tables, as EpisodeStore.finalize() lays them out, built by hand for the ctypes path."""
-    lengths = [e[0].shape[0] for e in eps]
-    t = dict(actions=torch.from_numpy(np.concatenate([e[0] for e in eps])).cuda(), goals=torch.from_numpy(np.stack([e[1] for e in eps])).cuda(),
-             ep_begin=torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)).cuda(), lengths=lengths)
-    t["lo"], t["scale"] = (None, None) if norm is None else (torch.from_numpy(norm[0]).cuda(), torch.from_numpy(norm[1]).cuda())
-    return t
-
-
 class Outs:
     """Guarded outputs of one launch (int32 / fp64 tables as raw canary-framed buffers of their own dtype)."""
 
@@ -86,7 +77,7 @@ def check_batch(got, ref, W, A, seed, step, what):
 def test_batches_match_the_reference_bit_for_bit(W, A, G, pad, norm):
     eps = R.make_store(W, A, G, seed=W)
     lo, hi, scale = R.minmax(eps)
-    t = dev_store(eps, (lo, scale) if norm else None)
+    t = H.dev_store(eps, (lo, scale) if norm else None)
     starts_h = R.start_table(t["lengths"], W, pad)
     starts = torch.from_numpy(starts_h.astype(np.int32)).cuda()
     st = data.EpisodeStore(A, G)
@@ -163,7 +154,7 @@ def test_bad_descriptors_are_refused_before_any_launch():
     W, A, G, B = 4, 3, 5, 7
     eps = R.make_store(W, A, G)
     lo, hi, scale = R.minmax(eps)
-    t = dev_store(eps, (lo, scale))
+    t = H.dev_store(eps, (lo, scale))
     starts_h = R.start_table(t["lengths"], W, "hold")
     starts = torch.from_numpy(starts_h.astype(np.int32)).cuda()
     lib = L.load()

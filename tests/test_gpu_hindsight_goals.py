@@ -112,19 +112,15 @@ class Case:
         return rc, got, ok, ref
 
 
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.int32), np.ascontiguousarray(b).view(np.int32))
-
-
 def check(got, ref, what, skip=None):
     for k in ("goal_index", "goal_offset", "goal_kind"):
         if k == skip:
             assert (got[k] == SENTINEL).all(), (what, k)                                  # an absent output is not written
         else:
-            assert same_bits(got[k], ref[k]), (what, k)
-    assert same_bits(got["latent_goal"], ref["latent_goal"]), (what, "latent_goal")
+            assert R.same_bits(got[k], ref[k]), (what, k)
+    assert R.same_bits(got["latent_goal"], ref["latent_goal"]), (what, "latent_goal")
     off = ref["goal_kind"] == 0
-    assert same_bits(got["latent_goal"][off], ref["pre"][off]), (what, "rows that keep their episode goal")
+    assert R.same_bits(got["latent_goal"][off], ref["pre"][off]), (what, "rows that keep their episode goal")
 
 
 @pytest.mark.parametrize("bf16", [False, True], ids=["fp32", "bf16"])
@@ -176,7 +172,7 @@ def test_a_row_is_a_function_of_seed_step_and_id():
     _, g7, _, _ = c.launch(7, 0, 6, 2 ** 31, False)
     _, g130, _, _ = c.launch(130, 0, 6, 2 ** 31, False)
     for k in g7:
-        assert same_bits(g7[k], g130[k][:7]), k                                        # rows [:7] of B = 130 == the B = 7 launch
+        assert R.same_bits(g7[k], g130[k][:7]), k                                        # rows [:7] of B = 130 == the B = 7 launch
     _, other, _, ref = c.launch(130, 0, 6, 2 ** 31, False, step=STEP + 1)
     assert not np.array_equal(other["goal_offset"], g130["goal_offset"]) and not np.array_equal(other["goal_kind"], g130["goal_kind"])
     check(other, ref, "step + 1")
@@ -217,9 +213,9 @@ def test_bad_descriptors_are_refused_before_any_launch():
     for over, want in cases:
         rc, got, ok, ref = c.launch(7, 0, 6, 2 ** 32, True, over=over)
         assert rc == want and ok, over
-        assert same_bits(got["latent_goal"], ref["pre"]) and all((got[k] == SENTINEL).all() for k in ("goal_index", "goal_offset", "goal_kind")), over
+        assert R.same_bits(got["latent_goal"], ref["pre"]) and all((got[k] == SENTINEL).all() for k in ("goal_index", "goal_offset", "goal_kind")), over
     rc, got, ok, ref = c.launch(7, 0, 6, 2 ** 32, True)                               # the descriptor these were derived from is a good one
-    assert rc == 0 and ok and not same_bits(got["latent_goal"], ref["pre"])
+    assert rc == 0 and ok and not R.same_bits(got["latent_goal"], ref["pre"])
 
 
 # ---------------------------------------------------------------------------------------------------------------- data.py, end to end
@@ -258,9 +254,9 @@ def test_hindsight_stream_batch_equals_the_reference(dtype):
     for k in ("index", "episode", "action_mask"):
         assert np.array_equal(b[k].cpu().numpy(), base[k]), k
     for k in ("goal_index", "goal_offset", "goal_kind"):
-        assert b[k].shape == (BE,) and same_bits(b[k].cpu().numpy(), ref[k]), k
+        assert b[k].shape == (BE,) and R.same_bits(b[k].cpu().numpy(), ref[k]), k
     assert b["goal_index"].dtype == torch.int32 and b["goal_offset"].dtype == torch.int32 and b["goal_kind"].dtype == torch.float32
-    assert same_bits(b["latent_goal"].cpu().numpy(), GR.relabelled_goals(base["latent_goal"], sg, ref))
+    assert R.same_bits(b["latent_goal"].cpu().numpy(), GR.relabelled_goals(base["latent_goal"], sg, ref))
     on = b["goal_kind"] == 1
     assert torch.equal(b["latent_goal"][on], st.step_goals[b["goal_index"][on].long()].float())
     assert torch.equal(b["latent_goal"][~on], st.goals[b["episode"][~on].long()])

@@ -65,11 +65,6 @@ def action_error_slices(pred, target, level, K, mask, weight):
     return sq.cpu().numpy(), cnt.cpu().numpy()
 
 
-def same_bits(got, want, what):
-    for g, w, name in zip(got, want, ("sq", "cnt")):
-        assert g.shape == w.shape and np.array_equal(g.view(np.uint64), w.view(np.uint64)), (what, name)
-
-
 def inputs(B, W, A, K, seed):
     """pred, target, mask, weight, level with every reachable level live: round-robin levels, the first row of each level fully unmasked."""
     rng = np.random.default_rng(seed)
@@ -103,8 +98,8 @@ def test_sums_match_the_replay_and_the_action_error_bit_for_bit(B, W, A, K):
         torch.cuda.synchronize()
         ref = LR.level_error(pred, target, level, K, m, wt)
         assert out.intact()
-        same_bits(out.host(), ref, kind)
-        same_bits(out.host(), action_error_slices(dp, dtg, dl, K, dev(m), dev(wt)), kind + ": mode_action_error per level")
+        V.same_sums(out.host(), ref, kind)
+        V.same_sums(out.host(), action_error_slices(dp, dtg, dl, K, dev(m), dev(wt)), kind + ": mode_action_error per level")
         for k in range(K):
             if k < min(B, K):
                 assert ref[1][k].sum() > 0 and ref[0][k].sum() > 0
@@ -125,7 +120,7 @@ def test_empty_levels_masked_rows_and_levels_out_of_range(B, W, A, K):
     assert launch(out, dev(pred), dtg, dev(lv, torch.int32), K, dev(mask), dev(weight)) == 0
     torch.cuda.synchronize()
     got = out.host()
-    same_bits(got, LR.level_error(pred, target, lv, K, mask, weight), "a level without rows")
+    V.same_sums(got, LR.level_error(pred, target, lv, K, mask, weight), "a level without rows")
     assert out.intact() and not got[0][gone].view(np.uint64).any() and not got[1][gone].view(np.uint64).any()       # +0.0, not -0.0 or NaN
     # every row masked: every sum is +0.0
     out = Out(K, W, A)
@@ -147,9 +142,9 @@ def test_empty_levels_masked_rows_and_levels_out_of_range(B, W, A, K):
     got = out.host()
     clean = LR.level_error(pred, target, np.where(inside, lv, 0), K, mask, weight * inside)      # the rows out of range weighted 0 instead
     assert out.intact() and all(np.isfinite(h).all() for h in got)
-    same_bits(got, LR.level_error(dirty, target, lv, K, mask, weight), "dirty pred, levels out of range")
-    same_bits(got, clean, "out of range = weight 0")
-    same_bits(got, action_error_slices(dev(dirty), dtg, dev(lv, torch.int32), K, dev(mask), dev(weight)), "mode_action_error per level")
+    V.same_sums(got, LR.level_error(dirty, target, lv, K, mask, weight), "dirty pred, levels out of range")
+    V.same_sums(got, clean, "out of range = weight 0")
+    V.same_sums(got, action_error_slices(dev(dirty), dtg, dev(lv, torch.int32), K, dev(mask), dev(weight)), "mode_action_error per level")
 
 
 @pytest.mark.parametrize("K", LEVELS)
@@ -163,13 +158,13 @@ def test_two_calls_accumulate(B, W, A, K):
     torch.cuda.synchronize()
     first = LR.level_error(p1, t1, l1, K, mask, weight)
     both = LR.level_error(p2, t2, l2, K, None, weight, into=first)
-    same_bits(out.host(), both, "two calls")
+    V.same_sums(out.host(), both, "two calls")
     assert out.intact() and (both[1] >= first[1]).all() and (both[1] > first[1]).any()
     # the Python entry: the same launches, accumulate by default
     sq, cnt = torch.zeros(K, W * A, dtype=torch.float64, device="cuda"), torch.zeros(K, W, dtype=torch.float64, device="cuda")
     validation.level_error(dev(p1), dev(t1), dev(l1, torch.int32), sq, cnt, mask=dev(mask), weight=dev(weight))
     validation.level_error(dev(p2), dev(t2), dev(l2, torch.int32), sq, cnt, weight=dev(weight))
-    same_bits((sq.cpu().numpy(), cnt.cpu().numpy()), both, "validation.level_error")
+    V.same_sums((sq.cpu().numpy(), cnt.cpu().numpy()), both, "validation.level_error")
     for bad in (dict(mask=dev(mask)[:, :1]), dict(weight=dev(weight).double()), dict(level=dev(l2, torch.int64))):
         kw = {**dict(level=dev(l2, torch.int32)), **bad}
         with pytest.raises(ValueError):

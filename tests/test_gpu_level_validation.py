@@ -16,14 +16,12 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import data_refs as R  # noqa: E402
-import goal_refs as GR  # noqa: E402
 import level_refs as LR  # noqa: E402
 import tolerances as T  # noqa: E402
 import val_refs as V  # noqa: E402
 import mode_diffusion_policy_amd as M  # noqa: E402
 from mode_diffusion_policy_amd import data, rollout  # noqa: E402
 from mode_diffusion_policy_amd.optim import ArenaEMA  # noqa: E402
-from test_gpu_train import build_train  # noqa: E402
 
 W, A, SEED, K = 10, 7, 5, 3
 SIGMAS = [0.02, 0.6, 30.0]
@@ -32,18 +30,7 @@ REAL_STEPS = sum(min(W, L - p) for L in LENGTHS for p in range(L))
 
 
 def setup(dtype, B=8, levels=SIGMAS, step_goals=False, sweep_kw=None, **kw):
-    """Denoiser (training mode), the store of data_refs.make_store with features stored per step, the sweep and its LevelValidator."""
-    cfg, sd, m = build_train("c1e4", 210, dtype)
-    den = M.GCDenoiser(m, 0.5).train()
-    eps = R.make_store(W, A, cfg.goal_dim, seed=3)
-    sg = GR.step_goal_table(eps, cfg.goal_dim) if step_goals else [None] * len(eps)
-    st = data.EpisodeStore(A, cfg.goal_dim)
-    for e, s in zip(eps, sg):
-        st.add_episode(e[0], e[1], step_goals=s)
-    st.finalize("minmax")
-    feats = torch.randn(st.num_steps, cfg.n_img_tokens, cfg.obs_dim, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
-    embed = lambda b: {"state_images": feats[b["index"].long()]}
-    sweep = data.WindowSweep(st, B, W, seed=SEED, **(sweep_kw or {}))
+    den, m, st, sweep, embed = V.held_out_setup(dtype, W, A, B, SEED, step_goals, sweep_kw)
     return den, m, st, sweep, embed, M.LevelValidator(den, sweep, embed, levels=levels, **kw)
 
 
@@ -63,14 +50,6 @@ def replay(val, draws):
     return acc, calls
 
 
-def bits(t):
-    return t.detach().cpu().numpy().reshape(-1).view(np.uint64 if t.dtype == torch.float64 else np.uint32)
-
-
-def same(res, acc):
-    return all(np.array_equal(bits(res[k]), a.reshape(-1).view(np.uint64)) for k, a in zip(("sq", "cnt"), acc))
-
-
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_predict_is_the_denoiser_on_the_hand_built_noised_input(dtype):
     den, m, st, sweep, embed, val = setup(dtype)
@@ -82,7 +61,7 @@ def test_predict_is_the_denoiser_on_the_hand_built_noised_input(dtype):
         assert torch.equal(b["noise"], z)                                        # the sweep's unit-normal noise of (window, draw)
         level, sigma, noised = LR.noise_levels(*host(b, "actions", "noise", "window"), table, draw)
         assert np.array_equal(host(b, "level")[0], level) and level.tolist() == [(g + draw) % K for g in b["window"].tolist()]
-        assert np.array_equal(bits(b["sigma"]), sigma.view(np.uint32)) and np.array_equal(bits(b["noised"]), noised.reshape(-1).view(np.uint32))
+        assert np.array_equal(V.bits(b["sigma"]), sigma.view(np.uint32)) and np.array_equal(V.bits(b["noised"]), noised.reshape(-1).view(np.uint32))
         got = val.predict(b)
         assert not den.training
         with torch.no_grad():
@@ -97,7 +76,7 @@ def test_run_accumulates_what_the_replay_gives_for_the_same_predictions(dtype):
     den, m, st, sweep, embed, val = setup(dtype)
     acc, calls = replay(val, K)
     res = val.run()                                                              # draws = K by default
-    assert same(res, acc) and calls == K * 5
+    assert V.same(res, acc) and calls == K * 5
     assert res["count_per_level"].tolist() == [float(REAL_STEPS)] * K            # the full cross: every window at every level once
     assert all(v.is_cuda for v in res.values()) and res["sq"].shape == (K, W, A) and res["cnt"].shape == (K, W)
     assert torch.equal(res["sigmas"], val.sigmas) and bool((res["loss_per_level"] > 0).all()) and float(res["loss"]) > 0
@@ -115,10 +94,10 @@ def test_run_accumulates_what_the_replay_gives_for_the_same_predictions(dtype):
     # one draw: every window once, at one level each
     acc1, _ = replay(val, 1)
     res1 = val.run(draws=1)
-    assert same(res1, acc1) and float(res1["count_per_level"].sum()) == REAL_STEPS and bool((res1["count_per_level"] > 0).all())
+    assert V.same(res1, acc1) and float(res1["count_per_level"].sum()) == REAL_STEPS and bool((res1["count_per_level"] > 0).all())
     # normalised units: the same sums, other means
     resn = M.LevelValidator(den, sweep, embed, levels=SIGMAS, raw_units=False).run()
-    assert same(resn, acc) and close(resn["mse_per_level"], sq.sum((1, 2)) / (A * cnt.sum(1))) and torch.equal(resn["loss_per_level"], res["loss_per_level"])
+    assert V.same(resn, acc) and close(resn["mse_per_level"], sq.sum((1, 2)) / (A * cnt.sum(1))) and torch.equal(resn["loss_per_level"], res["loss_per_level"])
     for kw in (dict(draws=0), dict(draws=1.5), dict(draws=True)):
         with pytest.raises(ValueError):
             val.run(**kw)

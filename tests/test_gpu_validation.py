@@ -14,23 +14,12 @@ import val_refs as V  # noqa: E402
 import mode_diffusion_policy_amd as M  # noqa: E402
 from mode_diffusion_policy_amd import data, rollout  # noqa: E402
 from mode_diffusion_policy_amd.optim import ArenaEMA  # noqa: E402
-from test_gpu_train import build_train  # noqa: E402
 
 W, A, SEED = 10, 7, 5
 
 
 def setup(dtype, B=8, **kw):
-    """Denoiser (training mode), the store of data_refs.make_store (episodes of 1, 9, 10 and 13 steps: 33 windows), features stored per step."""
-    cfg, sd, m = build_train("c1e4", 210, dtype)
-    den = M.GCDenoiser(m, 0.5).train()
-    eps = R.make_store(W, A, cfg.goal_dim, seed=3)
-    st = data.EpisodeStore(A, cfg.goal_dim)
-    for e in eps:
-        st.add_episode(e[0], e[1])
-    st.finalize("minmax")
-    feats = torch.randn(st.num_steps, cfg.n_img_tokens, cfg.obs_dim, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
-    embed = lambda b: {"state_images": feats[b["index"].long()]}
-    sweep = data.WindowSweep(st, B, W, seed=SEED)
+    den, m, st, sweep, embed = V.held_out_setup(dtype, W, A, B, SEED)
     return den, m, st, sweep, embed, M.Validator(den, sweep, embed, **kw)
 
 
@@ -49,14 +38,6 @@ def reference(val, unit, draws=1):
             acc = V.action_error(p.cpu().numpy(), b["actions"].cpu().numpy(), b["action_mask"].cpu().numpy(), b["valid"].cpu().numpy(), unit, into=acc)
             steps += int((b["action_mask"] * b["valid"][:, None]).sum())
     return acc, steps
-
-
-def bits(t):
-    return t.detach().cpu().numpy().reshape(-1).view(np.uint64 if t.dtype == torch.float64 else np.uint32)
-
-
-def same(res, acc):
-    return all(np.array_equal(bits(res[k]), a.view(np.uint64)) for k, a in zip(("sq", "ab", "cnt"), acc))
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
@@ -82,7 +63,7 @@ def test_run_accumulates_what_the_reference_gives_for_the_same_predictions(dtype
     acc, steps = reference(val, unit_of(st))
     assert steps == real_steps
     res = val.run()
-    assert same(res, acc)
+    assert V.same(res, acc)
     assert float(res["count"]) == real_steps                                     # the partial last batch's padding rows count nothing
     sq, cnt = acc[0].reshape(W, A), acc[2]
     close = lambda t, want: np.allclose(t.cpu().numpy(), want, rtol=1e-12, atol=0)
@@ -93,13 +74,13 @@ def test_run_accumulates_what_the_reference_gives_for_the_same_predictions(dtype
     # two draws: twice the steps, other noise on the second pass
     acc2, _ = reference(val, unit_of(st), draws=2)
     res2 = val.run(draws=2)
-    assert same(res2, acc2) and float(res2["count"]) == 2 * real_steps and not np.array_equal(acc2[0], 2 * acc[0])
+    assert V.same(res2, acc2) and float(res2["count"]) == 2 * real_steps and not np.array_equal(acc2[0], 2 * acc[0])
     # normalised units
     valn = M.Validator(den, sweep, embed, raw_units=False)
     assert valn.unit is None
     accn, _ = reference(valn, None)
     resn = valn.run()
-    assert same(resn, accn) and not np.array_equal(accn[0], acc[0]) and np.array_equal(accn[2], acc[2])
+    assert V.same(resn, accn) and not np.array_equal(accn[0], acc[0]) and np.array_equal(accn[2], acc[2])
     # another batch size sweeps the same windows: the same number of real steps (15 padding rows in its last batch)
     res16 = M.Validator(den, data.WindowSweep(st, 16, W, seed=SEED), embed).run()
     assert float(res16["count"]) == real_steps and torch.isfinite(res16["mse"])

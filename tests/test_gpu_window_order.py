@@ -65,25 +65,20 @@ def straddle_step(n, B):
     return t
 
 
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
 def check_batch(got, ref, seed, step, what, shifts=False):
     B, Wn, A = ref["actions"].shape
     for k in ("index", "episode", "action_mask", "actions", "latent_goal", "u"):
-        assert same_bits(got[k].cpu().numpy(), ref[k]), (what, k)
+        assert R.same_bits(got[k].cpu().numpy(), ref[k]), (what, k)
     for k in ("epoch", "position"):
         if k in ref:
-            assert got[k].dtype == torch.int64 and same_bits(got[k].cpu().numpy(), ref[k]), (what, k)
+            assert got[k].dtype == torch.int64 and R.same_bits(got[k].cpu().numpy(), ref[k]), (what, k)
         else:
             assert k not in got, (what, k)
     z = rollout.env_noise(R.noise_seeds(seed, B), [step] * B, Wn, A, 1.0, "cuda")
     assert torch.equal(got["noise"], z), (what, "noise")
     if shifts:
         for q, name in enumerate(("rgb_static", "rgb_gripper")):
-            assert same_bits(got["shifts"][name].cpu().numpy(), ref["shifts"][q]), (what, "shifts", name)
+            assert R.same_bits(got["shifts"][name].cpu().numpy(), ref["shifts"][q]), (what, "shifts", name)
 
 
 def all_starts(st, stream):
@@ -218,8 +213,8 @@ def test_epoch_order_composes_with_hindsight_goals():
         check_batch({k: v for k, v in b.items() if k != "latent_goal"} | {"latent_goal": torch.from_numpy(base["latent_goal"])}, base, seed, step, f"step={step}")
         ref = GR.relabel(begin, base["index"], base["episode"], seed, step, 0, 3, 2 ** 31)
         for k in ("goal_index", "goal_offset", "goal_kind"):
-            assert same_bits(b[k].cpu().numpy(), ref[k]), (step, k)
-        assert same_bits(b["latent_goal"].cpu().numpy(), GR.relabelled_goals(base["latent_goal"], np.concatenate(sg), ref)), step
+            assert R.same_bits(b[k].cpu().numpy(), ref[k]), (step, k)
+        assert R.same_bits(b["latent_goal"].cpu().numpy(), GR.relabelled_goals(base["latent_goal"], np.concatenate(sg), ref)), step
         kinds |= set(ref["goal_kind"].tolist())
     assert kinds == {0.0, 1.0}
 

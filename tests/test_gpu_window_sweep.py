@@ -19,14 +19,6 @@ BAD_ARG, UNSUPPORTED = -1, -2
 KEYS = ("actions", "action_mask", "latent_goal", "index", "episode", "valid", "window", "noise")
 
 
-def dev_store(eps, norm):
-    lengths = [e[0].shape[0] for e in eps]
-    t = dict(actions=torch.from_numpy(np.concatenate([e[0] for e in eps])).cuda(), goals=torch.from_numpy(np.stack([e[1] for e in eps])).cuda(),
-             ep_begin=torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)).cuda(), lengths=lengths)
-    t["lo"], t["scale"] = (None, None) if norm is None else (torch.from_numpy(norm[0]).cuda(), torch.from_numpy(norm[1]).cuda())
-    return t
-
-
 def py_store(eps, normalize, cams=False):
     st = data.EpisodeStore(eps[0][0].shape[1], eps[0][1].shape[0])
     for e in eps:
@@ -87,7 +79,7 @@ def test_sweep_matches_the_reference_bit_for_bit(W, A, G, pad, stride, norm):
     eps = R.make_store(W, A, G, seed=W)
     lo, hi, scale = R.minmax(eps)
     nrm = (lo, scale) if norm else None
-    t = dev_store(eps, nrm)
+    t = H.dev_store(eps, nrm)
     starts_h = V.sweep_table(t["lengths"], W, stride, pad)
     n_total = int(starts_h[-1])
     starts = torch.from_numpy(starts_h.astype(np.int32)).cuda()
@@ -178,7 +170,7 @@ def test_bad_descriptors_are_refused_before_any_launch():
     W, A, G, B = 4, 3, 5, 7
     eps = R.make_store(W, A, G)
     lo, hi, scale = R.minmax(eps)
-    t = dev_store(eps, (lo, scale))
+    t = H.dev_store(eps, (lo, scale))
     starts_h = V.sweep_table(t["lengths"], W, 1, "hold")
     n_total = int(starts_h[-1])
     starts = torch.from_numpy(starts_h.astype(np.int32)).cuda()

@@ -120,3 +120,43 @@ def action_error_plain(pred, target, mask=None, weight=None, unit=None):
         t2 = np.where(live, c[:, :, None] * e * e, 0.0)
         t1 = np.where(live, c[:, :, None] * np.abs(e), 0.0)
     return t2.sum(axis=0).reshape(W * A), t1.sum(axis=0).reshape(W * A), c.sum(axis=0)
+
+
+_SUMS = {3: ("sq", "ab", "cnt"), 2: ("sq", "cnt")}                              # mode_action_error's accumulators | mode_level_error's
+
+
+def same_sums(got, want, what) -> None:
+    """Asserts that the accumulators ``got`` carry the bits of ``want`` (tuples of numpy arrays)."""
+    for g, w, name in zip(got, want, _SUMS[len(want)]):
+        assert R.same_bits(g, w), (what, name, float(np.abs(g - w).max()) if g.shape == w.shape else (g.shape, w.shape))
+
+
+def bits(t):
+    """A device tensor's elements as a flat array of unsigned words (fp64: 64 bits, else 32)."""
+    return t.detach().cpu().numpy().reshape(-1).view(np.uint64 if t.element_size() == 8 else np.uint32)
+
+
+def same(res, acc) -> bool:
+    """A validator's result ``res`` holds the bits of the reference accumulators ``acc``."""
+    return all(np.array_equal(bits(res[k]), a.reshape(-1).view(np.uint64)) for k, a in zip(_SUMS[len(acc)], acc))
+
+
+def held_out_setup(dtype, W: int, A: int, B: int, seed: int, step_goals: bool = False, sweep_kw=None):
+    """GPU: the tiny c1e4 denoiser (training mode), the store of data_refs.make_store (episodes of 1, 9, 10 and 13 steps at W = 10: 33 windows) with
+    features stored per step, and its sweep -> (den, m, store, sweep, embed)."""
+    import torch
+    import goal_refs as GR
+    import mode_diffusion_policy_amd as M
+    from mode_diffusion_policy_amd import data
+    from test_gpu_train import build_train
+    cfg, sd, m = build_train("c1e4", 210, dtype)
+    den = M.GCDenoiser(m, 0.5).train()
+    eps = R.make_store(W, A, cfg.goal_dim, seed=3)
+    sg = GR.step_goal_table(eps, cfg.goal_dim) if step_goals else [None] * len(eps)
+    st = data.EpisodeStore(A, cfg.goal_dim)
+    for e, s in zip(eps, sg):
+        st.add_episode(e[0], e[1], step_goals=s)
+    st.finalize("minmax")
+    feats = torch.randn(st.num_steps, cfg.n_img_tokens, cfg.obs_dim, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
+    embed = lambda b: {"state_images": feats[b["index"].long()]}
+    return den, m, st, data.WindowSweep(st, B, W, seed=seed, **(sweep_kw or {})), embed
